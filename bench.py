@@ -14,6 +14,12 @@ Workload at N=1 = BASELINE.json configs[1]: 12L/768d/ffn3072/12 heads, S=1024, B
 seed 1234). N>1 (configs[2], weak scaling): ONE global batch of N x 32 sequences from the same seed, dealt to the ranks by
 sequence length exactly as the pre-training loop's BalancedDistributedSampler deals its global batches (rank_share below).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (value = tokens/s, ms_per_step = wall milliseconds of one
+timed step). --full adds, after the timed region, everything else the line used to carry: the in-step per-kernel probe and the
+rooflines, the padded / real-mix / data-parallel / decode legs, the exact-f32, split-bf16 and configs[4] steps and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -116,7 +122,7 @@ def cpu_baseline_child(cfgkw, S):
 
 
 def cpu_baseline(cfgkw, S, timeout=170):
-    """Bounded: the child is killed after `timeout` seconds so the default bench run always finishes within minutes."""
+    """Bounded: the child is killed after `timeout` seconds so the --full bench run always finishes within minutes."""
     import subprocess
     try:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), '--cpu-baseline-child', json.dumps(cfgkw), str(S)],
@@ -253,6 +259,28 @@ def isolated_fc1(ops, eng, args, code, Tiso, dev):
     return e0.elapsed_time(e1) / nrep, host_ms
 
 
+DUMP_SAMPLE = 1 << 21          # elements of each flat f32 buffer --dump-outputs writes (8 MB per file)
+
+
+def dump_outputs(path, eng, sums):
+    """--dump-outputs: what the last timed step hands its caller, as .npy files in `path`:
+      loss_sums.npy    (24,) float64: per Octuple head the masked CE sum, the mask count and the correct-argmax count (loss_and_grads)
+      grad_sample.npy  float32: the step's gradients (the flat f32 gradient buffer, before clipping)
+      param_sample.npy float32: the parameters after the step's clip + AdamW update
+    The two flat buffers are written whole up to DUMP_SAMPLE elements, else at a fixed sample of positions (numpy seed 0, the same
+    for every run of the same model shape)."""
+    import numpy as np
+    eng.finish_updates()
+    torch.cuda.synchronize()
+    n = eng.P32.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE))
+    idx = torch.from_numpy(idx).to(eng.P32.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss_sums.npy'), sums.double().cpu().numpy())
+    np.save(os.path.join(path, 'grad_sample.npy'), eng.G32.index_select(0, idx).cpu().numpy())
+    np.save(os.path.join(path, 'param_sample.npy'), eng.P32.index_select(0, idx).cpu().numpy())
+
+
 def decode_bench(args, model, eng, dev, rank):
     """BASELINE configs[3]: prompt (1,S,8) with L_enc ~ S/2 then EOS + PAD, KV-cached decode; special tokens are made
     unsamplable so that every run generates `--steps` positions (random-init weights would stop at once)."""
@@ -275,6 +303,9 @@ def decode_bench(args, model, eng, dev, rank):
     out = eng.generate(enc, emask, model.sample_row, max_new=nsteps, sampler=sampler)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                                 # the generated Octuple rows (1, S, 8), PAD after the last one
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'tokens.npy'), out.double().cpu().numpy())
     if rank == 0:
         print(json.dumps({"metric": "generate tokens/s (KV-cached decode, B=1, S=%d)" % S, "value": nsteps / dt, "unit": "tokens/s", "n_gpus": 1,
                           "steps": nsteps, "warmup": 1, "ms_per_step": dt / nsteps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -651,6 +682,9 @@ def main():
     ap.add_argument('--no-probe', action='store_true', help='skip the per-family in-step timing that follows the timed region')
     ap.add_argument('--force-reducer', action='store_true', help='install the RCCL gradient reducer even at world size 1 (test)')
     ap.add_argument('--mode', default='pretrain', choices=['pretrain', 'decode'], help='decode = BASELINE configs[3]: KV-cached generate, B=1')
+    ap.add_argument('--full', action='store_true', help='after the timed region also run the probe, rooflines, the other legs and shapes and '
+                                                        'the CPU baseline (each still subject to --no-probe / --no-cpu-baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:               # plain `python bench.py --gpus N`: start the N ranks as a child job
@@ -724,6 +758,9 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    sums = sums.clone()                                              # the last timed step's sums: the --full legs below run more steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, sums)
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     if os.environ.get('PB_LONG_RUN_DUMP') and rank == 0:             # developer aid (tools/long_run.py): the step times in order
         with open(os.environ['PB_LONG_RUN_DUMP'], 'w') as fh:
@@ -751,10 +788,10 @@ def main():
     step_tflops_per_gpu = live_flops / (ms_per_step * 1e-3) / 1e12              # the rows and (query, key) pairs the step computes
 
     # ---- roofline of the dominant kernel AS LAUNCHED BY THE STEP (fc1: NT T x ffn x d + bias + GELU + derivative out), and the
-    # per-family shares, from HIP events on the launch stream (one-stream schedule; after the timed region, rank 0 at N=1 only)
+    # per-family shares, from HIP events on the launch stream (one-stream schedule; after the timed region, --full, rank 0 at N=1 only)
     families = table = None
     fc1_ms = fc1_n = None
-    if world == 1 and not args.no_probe:
+    if args.full and world == 1 and not args.no_probe:
         from pianobart_amd import engine as E
         saved = E._WGRAD_STREAM
         E._WGRAD_STREAM = 0
@@ -785,14 +822,14 @@ def main():
     # neighbour kernel in between.
     code = ops.dtype_code(eng.xdt)
     iso_ms, iso_host_ms, Tiso = None, None, (Te if fc1_ms else T)
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         iso_ms, iso_host_ms = isolated_fc1(ops, eng, args, code, Tiso, dev)
     gemm_ms = fc1_ms if fc1_ms else iso_ms
     gemm_tflops = ((fc1_flops if fc1_ms else 2.0 * Tiso * args.ffn * args.hs) / (gemm_ms * 1e-3) / 1e12) if gemm_ms else None
 
-    # ---- numbers the driver's default line would otherwise never see: each a few seconds, all after the timed region
+    # ---- numbers the headline never shows: each a few seconds, all after the timed region, --full only
     extras = {}
-    if world == 1 and not args.no_probe:
+    if args.full and world == 1 and not args.no_probe:
         extras = extra_measurements(args, model, eng, ops, step, peak, dev)
         extras.update(other_instantiations(args, cfgkw, dev))
     # the largest single row of the committed kernel trace is not the GEMM but the one-pass attention backward: a second roofline entry
@@ -808,7 +845,6 @@ def main():
                          "how": "HIP events around the %d calls of the probe steps; FLOPs = 2.5 x 4 x H x hd x (query, key) pairs covered" % n_}
 
     if rank == 0:
-        traffic, traffic_src = pmc_traffic(sorted({Te, Td}), args.ffn, args.hs)
         s = sums.double().cpu()
         w8 = torch.tensor([262, 134, 262, 134, 38, 135, 55, 260], dtype=torch.double)
         loss = float(((s[0:8] / s[8:16]) * w8).sum() / w8.sum())
@@ -833,21 +869,23 @@ def main():
                        "flops_per_token_train": fpt,
                        "flops_note": "flops_per_token_train: algorithmic FLOPs of the reference graph (SURVEY 8d), full S^2 attention (causal at "
                                      "1/2), every padded row; step_tflops_per_gpu uses the same graph restricted to the rows / pairs the step computes"},
-            "roofline": {"bound": "mfma", "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s", "frac": (gemm_tflops / peak) if gemm_tflops else None,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "gemm3_kernel<%s,NT> (256x256 ping-pong) fc1 M=%s N=%d K=%d + bias + GELU + derivative out" %
-                                   (args.precision, T if Te == T else '%d (encoder layers) / %d (decoder layers)' % (Te, Td), args.ffn, args.hs),
-                         "avg_launch_ms": gemm_ms,
-                         "how": ("HIP events around each of the %.0f fc1 launches of a step, inside the step (one-stream schedule)" % fc1_n) if fc1_ms
-                                else "isolated back-to-back launches (probe disabled)",
-                         "isolated_back_to_back_ms": iso_ms, "isolated_rows": Tiso, "isolated_host_enqueue_ms_per_launch": iso_host_ms,
-                         "families_in_step": families, "top_ops_in_step": table},
         }
+        if args.full:
+            traffic, traffic_src = pmc_traffic(sorted({Te, Td}), args.ffn, args.hs)
+            rec["roofline"] = {"bound": "mfma", "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s", "frac": (gemm_tflops / peak) if gemm_tflops else None,
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": "gemm3_kernel<%s,NT> (256x256 ping-pong) fc1 M=%s N=%d K=%d + bias + GELU + derivative out" %
+                                         (args.precision, T if Te == T else '%d (encoder layers) / %d (decoder layers)' % (Te, Td), args.ffn, args.hs),
+                               "avg_launch_ms": gemm_ms,
+                               "how": ("HIP events around each of the %.0f fc1 launches of a step, inside the step (one-stream schedule)" % fc1_n) if fc1_ms
+                                      else "isolated back-to-back launches (probe disabled)",
+                               "isolated_back_to_back_ms": iso_ms, "isolated_rows": Tiso, "isolated_host_enqueue_ms_per_launch": iso_host_ms,
+                               "families_in_step": families, "top_ops_in_step": table}
         if roofline2 is not None:
             rec["roofline_secondary"] = roofline2
         rec.update(extras)
         rec["rows"]["loss_rows_fraction"] = Ts / float(Td)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(cfgkw, S)
         print(json.dumps(rec), flush=True)
     if world > 1 or args.force_reducer:

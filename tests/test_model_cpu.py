@@ -139,7 +139,7 @@ def test_module_prefixed_checkpoint_loads(capsys):
     res = m.load_state_dict(checkpoint_state_dict(wrapped, m), strict=False)
     assert not res.missing_keys and not res.unexpected_keys
     for (k1, v1), (k2, v2) in zip(o.state_dict().items(), m.state_dict().items()):
-        assert k1 == k2 and torch.equal(v1, v2)
+        assert k1 == k2 and torch.equal(v1.cpu(), v2)                            # DataParallel moves `o` to cuda:0 where a GPU is visible
     assert "stripping the 'module.' prefix" in capsys.readouterr().out
     plain = o.state_dict()
     assert checkpoint_state_dict(plain, m) is plain and capsys.readouterr().out == ''

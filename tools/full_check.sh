@@ -4,7 +4,7 @@
 TAG=${1:-check}; O=gpurun_out/$TAG; mkdir -p $O
 timeout 2400 python -m pytest tests -x -q -m gpu > $O/full_tests.log 2>&1; tail -4 $O/full_tests.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-python bench.py > $O/full_bench.json 2> $O/full_bench.err; O=$O python - <<'PY'
+python bench.py --full > $O/full_bench.json 2> $O/full_bench.err; O=$O python - <<'PY'
 import json, os
 lines = open(os.environ['O'] + '/full_bench.json').read().strip().splitlines()
 d = json.loads(lines[-1])

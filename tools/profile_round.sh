@@ -10,7 +10,7 @@
 TAG=${1:-r05}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R; O=gpurun_out/${TAG}prof; mkdir -p $O; rm -rf $O/prof_* $O/pmc_* $O/p[1-4]
-python bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/${TAG}_bench_default.json; echo
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/${TAG}_bench_default.json; echo
 ROWS=$(python - <<PY
 import json
 d=json.loads([l for l in open('$O/${TAG}_bench_default.json').read().splitlines() if l.startswith('{')][-1])
