@@ -430,6 +430,40 @@ int pb_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok8);
 int pb_decoder_wait(void* dec, int32_t ticket);
 int pb_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows);
 int pb_decoder_seek(void* dec, int32_t pos, const int16_t* tok8);
+/* Batched device-sampled decode (additive to ABI 8): up to PB_DECODE_BATCH_MAX prompts decoded in the same launches, so each weight byte of
+ * a step is read once for all rows. The same launches per step as the batch-1 decoder (6 n_layers + 3 with the sampler); each row's
+ * arithmetic is the batch-1 kernels' arithmetic (same K partition, FMA order, reduction trees and split-record merge), so the logged
+ * logits rows are bit-identical to pb_decoder_*'s for the same prompt and the same fed tokens. Per row in device memory: the position,
+ * a done flag (set by the sampler on a special id, by the embedding kernel at the position limit, or by the host), the uniform draws.
+ * pb_decode_batch.plan holds the shapes and weights as for pb_decoder_create, with B-row scratch: x, y1, yc, y2, a (B, d), g (B, ffn),
+ * logits (B, vocab) f32, attn_part (B, H, PB_DECODE_MAX_SPLITS, hd + 4) f32, enc_mask (B, S) f32 or NULL, tok16 unused, and
+ * layers[l].kv_self / kv_cross (B, S, 2d). s_enc[b] = row b's visible encoder extent (its cross-attention split geometry).
+ *   pb_batch_decoder_create         0 = created, 1 = shape not covered (same rule as pb_decoder_create; 1 <= B <= 16), < 0 = error.
+ *   pb_batch_decoder_reset          every row at position -1 and live, ordered behind `caller_stream`.
+ *   pb_batch_decoder_sampler_init   the 8 heads' constants as pb_decoder_sampler_init, pad8 = the ids from which a sampled id is special,
+ *                                   u = (B, S, 8) f64 draws (copied), limit = positions per row (<= S); fault_row / fault_period > 0
+ *                                   corrupt head 0's id of that row at every fault_period-th position (tests of the rewind path only).
+ *   pb_batch_decoder_launch         enqueue ntok batched steps (first_tok, (B, 8) host ids or NULL); ticket >= 0 for pb_batch_decoder_wait.
+ *   pb_batch_decoder_logs           pinned logs: (B, S, vocab) f32 logits rows, (B, S, 8) int16 device-sampled ids.
+ *   pb_batch_decoder_seek           tok8 != NULL: drain, then row's last decoded position = pos, its next input = tok8, live again (the
+ *                                   other rows are untouched); tok8 == NULL: the row is done from the next enqueued step on (no drain). */
+#define PB_DECODE_BATCH_MAX 16
+typedef struct pb_decode_batch {
+    pb_decode_plan plan;
+    int32_t B; int32_t _pad;
+    int32_t s_enc[PB_DECODE_BATCH_MAX];
+} pb_decode_batch;
+int pb_batch_decoder_create(const pb_decode_batch* plan, void** dec);
+int pb_batch_decoder_destroy(void* dec);
+int pb_batch_decoder_reset(void* dec, void* caller_stream, int32_t use_graph);
+int pb_batch_decoder_sampler_init(void* dec, const float* temps8, const float* p8, const int32_t* n8, const int32_t* off8, const int32_t* pad8,
+                                  const double* u, int64_t n_u, int32_t limit, int32_t fault_row, int32_t fault_period);
+int pb_batch_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok);
+int pb_batch_decoder_wait(void* dec, int32_t ticket);
+int pb_batch_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows);
+int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const int16_t* tok8);
+int pb_batch_decoder_launches(void* dec);
+int pb_batch_decoder_graph(void* dec);
 
 /* ---- fused attention of the "bf16x3" parity instantiation (round 6, ABI 8): f32 q / k / v / o, every product a split-bf16 triple on the
  * bf16 matrix cores (see PB_F32X3), softmax in f32 -- instead of the unfused QK^T -> softmax -> PV chain of the exact-f32 path

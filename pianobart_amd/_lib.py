@@ -46,6 +46,11 @@ class DecodePlan(ctypes.Structure):
                [('layers', DecodeLayer * 48)]
 
 
+class DecodeBatch(ctypes.Structure):
+    """pb_decode_batch: the plan of the batched decoder (B-row scratch, (B, S, 2d) caches) and each row's visible encoder extent."""
+    _fields_ = [('plan', DecodePlan), ('B', ctypes.c_int32), ('_pad', ctypes.c_int32), ('s_enc', ctypes.c_int32 * 16)]
+
+
 _SCALARS = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64,
             'uint32_t': ctypes.c_uint32, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int': ctypes.c_int}
 

@@ -1509,6 +1509,222 @@ class Engine:
                                 tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, s_enc=s_enc, device_sampler=True, rewinds=rewinds,
                                 tokens_per_graph_replay=K)
 
+    # ---- batched generation ----------------------------------------------------------------------------------------------------
+    BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
+
+    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None):
+        """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
+        prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
+        contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
+        (None = the global stream); it is called for different rows from a small thread pool, one generator per row. enc_ids (B, S, 8),
+        emask (B, S) or None; returns (B, S, 8) with PAD after each prompt's stop.
+        Where the fused decode kernels cover the shape (bf16, head_dim 64 / 128, d a multiple of 256 up to 1024) and `sampler` names
+        the constants, up to BATCH_MAX prompts share one batched device-sampled decoder (pb_batch_decoder_*); every other case runs
+        the per-prompt loop over `generate` (_generate_batch_loop)."""
+        B = int(enc_ids.shape[0])
+        if len(rngs) != B:
+            raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
+        self._await_updates(2)
+        if B == 0:
+            return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
+        if not self._batch_decoder_covers(sampler):
+            return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler)
+        outs = []
+        for c0 in range(0, B, self.BATCH_MAX):
+            c1 = min(B, c0 + self.BATCH_MAX)
+            outs.append(self._generate_batch_chunk(enc_ids[c0:c1], emask[c0:c1] if emask is not None else None, sample_row, rngs[c0:c1],
+                                                   max_new, sampler))
+        return torch.cat(outs, 0)
+
+    def _batch_decoder_covers(self, sampler):
+        return (sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0 and _DECODE_SPLIT and self.code == PB_BF16 and self.hd in (64, 128)
+                and self.d % 256 == 0 and self.d <= 1024 and self.fd % 8 == 0 and self.fd <= 8192)
+
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
+        """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
+        caller's global state is restored afterwards."""
+        saved = np.random.get_state()
+        outs = []
+        try:
+            for b in range(int(enc_ids.shape[0])):
+                np.random.set_state(rngs[b].get_state())
+                outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
+                                          max_new=max_new, sampler=sampler))
+                rngs[b].set_state(np.random.get_state())
+        finally:
+            np.random.set_state(saved)
+        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
+        return torch.cat(outs, 0)
+
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
+        """<= BATCH_MAX prompts through one batched decoder. Encoder pass and cross K/V projections run per prompt, exactly as
+        `generate` runs them, into that row's slice of the (B, S, 2d) caches; then the device-ahead / host-behind loop of
+        `_generate_device_sampled` with per-row draws, per-row verification and per-row rewinds (pb_batch_decoder_seek touches one row)."""
+        import ctypes
+        from ._lib import DecodeBatch
+        pb, d, X, ND = self.pb, self.d, self.xdt, self.ND
+        self.bind(enc_ids.device)
+        B, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
+        pad_cpu = torch.from_numpy(pb.pad_word_np)
+        em = emask.to(torch.float32).contiguous() if emask is not None else None
+        enc16 = ops.ids_to_i16(enc_ids)
+        self.note_ids(enc16); self.check_ids(collective=False)
+        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
+        with torch.no_grad():
+            wf, ff = self.wf, self.fd
+            kvc = [e(B, S, 2 * d) for _ in range(ND)]
+            s_enc = []
+            km = torch.empty(1, dtype=torch.int32, device=dev)
+            for b in range(B):                                             # the batch-1 encoder pass of each prompt, into its cache row
+                emb = em[b:b + 1] if em is not None else None
+                _, enc_out = self.forward_hidden(enc16[b:b + 1], None, emb, None, False, 0)
+                for l in range(ND):
+                    self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, kvc[l][b], S, 2 * d, d)
+                se = S
+                if emb is not None:
+                    ops.key_extent(emb, km)
+                    se = max(1, min(S, int(km.item())))
+                s_enc.append(se)
+            kvs = [torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(ND)]
+            rows = {n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}
+            rows['g'] = e(B, ff)
+            stat = torch.empty(8, dtype=torch.float32, device=dev)
+            logits = torch.empty(B, ops.VOCAB, dtype=torch.float32, device=dev)
+            tok16 = torch.tensor(pb.sos_word_np, dtype=torch.int16, device=dev)
+            attn_part = torch.empty(B * self.H * 16 * (self.hd + 4), dtype=torch.float32, device=dev)
+            bp = DecodeBatch()
+            plan = bp.plan
+            plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), ND, ops.VOCAB
+            for k in range(9):
+                plan.tab_off[k] = ops.TAB_OFF[k]
+            P = lambda t: t.data_ptr()
+            plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(tok16), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
+            plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
+            for n, t in rows.items():
+                setattr(plan, n, P(t))
+            plan.stat, plan.logits, plan.head_w, plan.head_b = P(stat), P(logits), P(self.w['head.w']), P(wf['head.b'])
+            plan.attn_part = P(attn_part)
+            for l in range(ND):
+                pf, L = 'dec.%d.' % l, plan.layers[l]
+                L.wqkv, L.bqkv, L.wo, L.bo = P(self.w[pf + 'wqkv']), P(wf[pf + 'bqkv']), P(self.w[pf + 'wo']), P(wf[pf + 'bo'])
+                L.ln1_w, L.ln1_b = P(wf[pf + 'ln1.w']), P(wf[pf + 'ln1.b'])
+                L.wq_c, L.bq_c, L.wo_c, L.bo_c = P(self.w[pf + 'wq_c']), P(wf[pf + 'bq_c']), P(self.w[pf + 'wo_c']), P(wf[pf + 'bo_c'])
+                L.lnc_w, L.lnc_b = P(wf[pf + 'lnc.w']), P(wf[pf + 'lnc.b'])
+                L.w1, L.b1, L.w2, L.b2 = P(self.w[pf + 'w1']), P(wf[pf + 'b1']), P(self.w[pf + 'w2']), P(wf[pf + 'b2'])
+                L.ln2_w, L.ln2_b = P(wf[pf + 'ln2.w']), P(wf[pf + 'ln2.b'])
+                L.kv_self, L.kv_cross = P(kvs[l]), P(kvc[l])
+            bp.B = B
+            for b in range(B):
+                bp.s_enc[b] = s_enc[b]
+            dec = ctypes.c_void_p()
+            rc = int(LIB.query('pb_batch_decoder_create', ctypes.byref(bp), ctypes.byref(dec)))
+            if rc < 0:
+                raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
+            if rc == 1:                                                    # not covered: the per-prompt loop
+                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler)
+            res_cpu = pad_cpu.repeat(B, S, 1)
+            try:
+                LIB.call('pb_batch_decoder_reset', dec, ops._stream(), _DECODE_GRAPH)
+                torch.cuda.current_stream().synchronize()
+                self._batch_device_sampled(dec, B, S, sample_row, rngs, sampler, res_cpu, pad_cpu, max_new)
+            finally:
+                LIB.call('pb_batch_decoder_destroy', dec)
+            self.last_decode['s_enc'] = s_enc
+            return res_cpu.to(dev)
+
+    def _batch_device_sampled(self, dec, B, S, sample_row, rngs, sampler, res_cpu, pad_cpu, max_new):
+        """The loop of `_generate_device_sampled` over B rows. Draws: row b's (S, 8) uniforms from a COPY of rngs[b]. The device runs
+        ahead, K batched steps per graph replay, two runs in flight; the host follows one run behind and replays every row position
+        through `sample_row(logged row, rngs[b])` -- the reference code path, consuming rngs[b] as the batch-1 loop consumes the global
+        stream. A row whose device choice differs is rewound alone (pb_batch_decoder_seek drains, then moves that row only); a row whose
+        host token is special stops there (the device stops it from the next step on)."""
+        import ctypes
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        K, vocab = 8, ops.VOCAB
+        limit = S if max_new is None else max(0, min(S, int(max_new)))
+        U = np.empty((B, S * 8), dtype=np.float64)
+        for b in range(B):
+            ahead = np.random.RandomState()
+            ahead.set_state(rngs[b].get_state())
+            U[b] = ahead.random_sample(S * 8)
+        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
+        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
+        pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
+        t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
+        fault_row, fault_period = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
+        LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
+                 U.ctypes.data, B * S * 8, limit, int(fault_row), int(fault_period))
+        lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
+        LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
+        log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
+        log_tok = np.ctypeslib.as_array((ctypes.c_int16 * (B * S * 8)).from_address(tp.value)).reshape(B, S, 8)
+        first = np.ascontiguousarray(np.tile(np.asarray(self.pb.sos_word_np, dtype=np.int16), (B, 1)))
+        nxt = [0] * B                              # next position the enqueued work decodes, per row
+        live = [limit > 0] * B                     # the host has not stopped the row
+        tokens, rewinds = [0] * B, [0] * B
+        runs = deque()
+        steps, host_s = 0, 0.0
+
+        def launch(tok=None):
+            nonlocal steps
+            cnt = min(K, max(limit - nxt[b] for b in range(B) if live[b]))
+            tk = int(LIB.query('pb_batch_decoder_launch', dec, cnt, None if tok is None else tok.ctypes.data))
+            if tk < 0:
+                raise PBError('pb_batch_decoder_launch failed (%d): %s' % (tk, LIB.load().pb_last_error().decode()))
+            spans = []
+            for b in range(B):
+                s = nxt[b]
+                e = min(limit, s + cnt) if live[b] else s
+                spans.append([s, e])
+                nxt[b] = e
+            runs.append((tk, spans))
+            steps += cnt
+
+        def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
+            for i in range(s, e):
+                tok = sample_row(log_logits[b, i], rngs[b])
+                tokens[b] += 1
+                if (tok >= pad_cpu).any():
+                    return ('stop', i)
+                res_cpu[b, i] = tok
+                t16 = tok.numpy().astype(np.int16)
+                if not np.array_equal(t16, log_tok[b, i]):
+                    return ('seek', i, t16)
+            return None
+
+        pending = lambda: any(live[b] and nxt[b] < limit for b in range(B))
+        t_loop = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=min(B, 8)) as pool:
+            if pending():
+                launch(first)
+            while runs or pending():
+                while len(runs) < 2 and pending():
+                    launch()
+                tk, spans = runs.popleft()
+                LIB.call('pb_batch_decoder_wait', dec, tk)
+                t_h = time.perf_counter()
+                todo = [b for b in range(B) if live[b] and spans[b][1] > spans[b][0]]
+                outcome = dict(zip(todo, pool.map(lambda b: verify(b, *spans[b]), todo)))
+                host_s += time.perf_counter() - t_h
+                for b in todo:
+                    r = outcome[b]
+                    if r is None:
+                        continue
+                    if r[0] == 'stop':
+                        live[b] = False
+                        LIB.call('pb_batch_decoder_seek', dec, b, r[1], None)
+                    else:                                                  # drain, move row b back; its spans in the queued runs are void
+                        i = r[1]
+                        rewinds[b] += 1
+                        LIB.call('pb_batch_decoder_seek', dec, b, i, r[2].ctypes.data)
+                        nxt[b] = i + 1
+                        for _, sp in runs:
+                            sp[b][0] = sp[b][1] = i + 1
+        self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
+                                tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
+                                device_sampler=True, batched=True, batch=B, tokens_per_graph_replay=K)
+
     def _generate_pyloop(self, enc_ids, emask, sample_row):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path."""

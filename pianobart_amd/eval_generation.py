@@ -1,0 +1,123 @@
+"""Generate a whole test set into one .npy: the reference's eval_generation.py on the HIP path (python -m pianobart_amd.eval_generation).
+
+Same flags as the reference (--dict_file --ckpt --dataset_path --dataset_name --output --num_workers --batch_size --max_seq_len --hs
+--layers --ffn_dims --heads --nopretrain --cpu --cuda_devices) plus --precision and --seed, and the same order of work as demo.py:
+vocabulary, model from the flags, checkpoint through checkpoint_state_dict with strict=False, encoder mask = bar column != PAD,
+generation, one device. The output is float32 (N, max_seq_len, 8), one row per prompt, PAD after each prompt's stop.
+
+RNG rules:
+  * without --seed: --batch_size 1 is the reference's loop, every prompt drawing from the one global np.random stream in turn
+    (PianoBartLM.forward(generate=True)); --batch_size > 1 is refused (the reference's model exits with ERROR for B != 1).
+  * with --seed s: prompt i draws from its own RandomState(s + i) (PianoBartLM.generate_batch: up to 16 prompts per batched decode
+    step), so the file is identical for every --batch_size.
+The prompts are sliced from the loaded array in order; --num_workers is accepted for the reference's command lines and not needed.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from ._lib import PBError
+from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_VOCAB = os.path.join(_HERE, 'data', 'octuple_vocab.json')
+
+
+def get_args(argv=None):
+    ap = argparse.ArgumentParser(description='')
+    ap.add_argument('--dict_file', type=str, default=_VOCAB)
+    ap.add_argument('--ckpt', type=str, default='result/pretrain/pianobart/model_best.ckpt')
+    ap.add_argument('--dataset_path', type=str, default='./Data/output_generate/GiantMIDI1k/gen_method')
+    ap.add_argument('--dataset_name', type=str, default='GiantMIDI1k_test.npy')
+    ap.add_argument('--output', type=str, default='./output.npy')
+    ap.add_argument('--num_workers', type=int, default=5)
+    ap.add_argument('--batch_size', type=int, default=1)
+    ap.add_argument('--max_seq_len', type=int, default=1024, help='all sequences are padded to `max_seq_len`')
+    ap.add_argument('--hs', type=int, default=1024)
+    ap.add_argument('--layers', type=int, default=8)
+    ap.add_argument('--ffn_dims', type=int, default=2048)
+    ap.add_argument('--heads', type=int, default=8)
+    ap.add_argument('--nopretrain', action='store_true', default=False)
+    ap.add_argument('--cpu', action='store_true')
+    ap.add_argument('--cuda_devices', type=int, nargs='+', default=[0], help='HIP device id (one)')
+    ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
+    ap.add_argument('--seed', type=int, default=None, help='prompt i samples from RandomState(seed + i): the output is the same for every --batch_size')
+    return ap.parse_args(argv)
+
+
+def check_args(args):
+    """The argument rules that need no device; raises PBError."""
+    if args.batch_size < 1:
+        raise PBError('--batch_size must be >= 1 (got %d)' % args.batch_size)
+    if args.seed is None and args.batch_size > 1:
+        raise PBError('--batch_size %d needs --seed: without it every prompt draws from the one global RNG stream in turn, which only the '
+                      'batch-1 loop reproduces (the reference exits with ERROR for batches); with --seed s prompt i uses RandomState(s + i) '
+                      'and the output does not depend on --batch_size' % args.batch_size)
+    if args.cuda_devices is not None and len(args.cuda_devices) > 1:
+        raise PBError('eval_generation runs on ONE device: give one id to --cuda_devices')
+    if args.cpu:
+        raise PBError('pianobart_amd has no CPU execution path: eval_generation needs an MI355X')
+
+
+def build_model(args, e2w, w2e):
+    """demo.py's model from the flags (+ the checkpoint unless --nopretrain)."""
+    shape = dict(max_position_embeddings=args.max_seq_len, d_model=args.hs)
+    for side in ('encoder', 'decoder'):
+        shape.update({side + '_layers': args.layers, side + '_ffn_dim': args.ffn_dims, side + '_attention_heads': args.heads})
+    pianobart = PianoBart(bartConfig=BartConfig(**shape), e2w=e2w, w2e=w2e, precision=args.precision)
+    model = PianoBartLM(pianobart)
+    if not args.nopretrain:
+        print("   Loading pre-trained model from", args.ckpt.split('/')[-1])
+        sd = torch.load(args.ckpt, map_location='cpu', weights_only=False)['state_dict']
+        model.load_state_dict(checkpoint_state_dict(sd, model), strict=False)
+    return model
+
+
+def load_data(dataset_path, dataset_name):
+    return np.load(os.path.join(dataset_path, dataset_name), allow_pickle=True)
+
+
+def eval_generation(args=None):
+    """Returns the (N, max_seq_len, 8) float32 array it saved to args.output."""
+    if args is None:
+        args = get_args()
+    check_args(args)
+    if not torch.cuda.is_available():
+        raise PBError('pianobart_amd has no CPU execution path: eval_generation needs an MI355X')
+    from .pretrain import _load_vocab
+    print("Loading Dictionary")
+    e2w, w2e = _load_vocab(args.dict_file)
+    print("\nBuilding BART model")
+    model = build_model(args, e2w, w2e)
+    print("\nLoading Dataset", args.dataset_name)
+    data = load_data(args.dataset_path, args.dataset_name)
+    N = len(data)
+    print("   len of dataset", N)
+    if N and tuple(np.shape(data[0])) != (args.max_seq_len, 8):
+        raise PBError('prompts of shape %s: expected (%d, 8) (--max_seq_len)' % (tuple(np.shape(data[0])), args.max_seq_len))
+    device_num = args.cuda_devices[0] if args.cuda_devices else 0
+    device = torch.device('cuda', device_num)
+    print("Use GPU", device)
+    model = model.to(device).eval()
+    bar_pad = model.pianobart.bar_pad_word
+    output = np.zeros((N, args.max_seq_len, 8), dtype=np.float32)
+    print("\nEval Start")
+    with torch.no_grad():
+        for c0 in range(0, N, args.batch_size):
+            c1 = min(N, c0 + args.batch_size)
+            x = torch.as_tensor(np.asarray(data[c0:c1])).long().to(device)
+            attn_encoder = (x[:, :, 0] != bar_pad).float()
+            if args.seed is None:
+                y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num)
+            else:
+                y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num)
+            output[c0:c1] = y.float().cpu().numpy()
+    np.save(args.output, output)
+    print("Saved", output.shape, "to", args.output)
+    return output
+
+
+if __name__ == '__main__':
+    eval_generation()

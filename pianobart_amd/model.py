@@ -8,6 +8,7 @@ CPU execution path: calling forward with CPU tensors raises.
 """
 import math
 import random
+import threading
 from types import SimpleNamespace
 
 import numpy as np
@@ -268,19 +269,22 @@ def nucleus(probs, p):
     return word
 
 
-_SAMPLE_TAB = {}
+_SAMPLE_TLS = threading.local()
 
 
 def _sample_tables():
-    """Constants and scratch of PianoBartLM.sample_row: per-element temperatures, the (8, 272) probability rows, the native call's arrays."""
-    if not _SAMPLE_TAB:
+    """Constants and scratch of PianoBartLM.sample_row: per-element temperatures, the (8, 272) probability rows, the native call's arrays.
+    One set per thread: Engine.generate_batch verifies the rows of a batch on a small thread pool."""
+    tab = getattr(_SAMPLE_TLS, 'tab', None)
+    if tab is None:
+        tab = _SAMPLE_TLS.tab = {}
         n = [ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)]
         width = (max(n) + 15) // 16 * 16
         n_a, p_a = np.asarray(n, dtype=np.int32), np.asarray(PianoBartLM.SAMPLE_P, dtype=np.float32)
-        _SAMPLE_TAB.update(n_a=n_a, p_a=p_a, n_p=n_a.ctypes.data, p_p=p_a.ctypes.data, out=np.zeros(8, dtype=np.int32), tie=np.zeros(1, dtype=np.int32))
-        _SAMPLE_TAB.update(n=n, probs=torch.zeros(8, width, dtype=torch.float32),
-                           tvec=torch.cat([torch.full((n[j],), float(PianoBartLM.SAMPLE_T[j]), dtype=torch.float32) for j in range(8)]))
-    return _SAMPLE_TAB
+        tab.update(n_a=n_a, p_a=p_a, n_p=n_a.ctypes.data, p_p=p_a.ctypes.data, out=np.zeros(8, dtype=np.int32), tie=np.zeros(1, dtype=np.int32))
+        tab.update(n=n, probs=torch.zeros(8, width, dtype=torch.float32),
+                   tvec=torch.cat([torch.full((n[j],), float(PianoBartLM.SAMPLE_T[j]), dtype=torch.float32) for j in range(8)]))
+    return tab
 
 
 def _nucleus_with_draw(probs, p, u):
@@ -353,24 +357,43 @@ class PianoBartLM(nn.Module):
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
+    def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1):
+        """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
+        numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
+        result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
+        np.random stream is not touched. Placed like forward(generate=True): CPU for device_num == -1, else cuda:device_num."""
+        B = int(input_ids_encoder.shape[0])
+        if (rngs is None) == (seeds is None):
+            raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
+        if rngs is None:
+            rngs = [np.random.RandomState(int(s)) for s in seeds]
+        rngs = list(rngs)
+        if len(rngs) != B:
+            raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
+        eng = self._get_engine()
+        out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
+                                 sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P))
+        return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
+
     # model.py:68-78 -- temperatures / nucleus thresholds per head
     SAMPLE_T = [1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
-    def sample_row(self, row_logits):
+    def sample_row(self, row_logits, rng=None):
         """row_logits: (1280,) f32 CPU tensor of one position; returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
         on the host row -- the division by the temperature (one call with a per-element temperature vector: the same quotients) and a
         1-D softmax per head -- then nucleus() for all 8 heads in one native call (pb_nucleus_rows: numpy's arithmetic order and
         precision; ties among candidates go back to the numpy code), fed the 8 uniform draws np.random.choice would have made. Checked
         draw for draw and RNG state for RNG state against sampling() in tests/test_model_cpu.py. 0.31 -> 0.1 ms of host time per
-        generated position, which sits in series with the GPU's ~0.3 ms."""
+        generated position, which sits in series with the GPU's ~0.3 ms. rng: a numpy RandomState to draw the 8 uniforms from instead of
+        the global stream (generate_batch: one generator per prompt)."""
         tab = _sample_tables()
         y = row_logits / tab['tvec']
         probs = tab['probs']
         for j in range(8):                                           # 1-D calls: a 2-D softmax would open an OpenMP region per position
             torch.softmax(y[ops.SEG_OFF[j]:ops.SEG_OFF[j + 1]], dim=-1, out=probs[j, :tab['n'][j]])
         # the 8 draws np.random.choice would make, in head order (RandomState fills a request sequentially: the same stream as 8 calls)
-        u = np.random.random_sample(8)
+        u = np.random.random_sample(8) if rng is None else rng.random_sample(8)
         out, tie = tab['out'], tab['tie']
         LIB.call('pb_nucleus_rows', probs.data_ptr(), probs.shape[1], tab['n_p'], tab['p_p'], u.ctypes.data, 8, out.ctypes.data, tie.ctypes.data)
         if tie[0]:                                                   # equal probabilities among a head's candidates: numpy's own order decides

@@ -1,0 +1,94 @@
+"""Batched KV-cached generation throughput (Engine.generate_batch) at BASELINE configs[3]'s model: 12 layers, d 768, 12 heads, ffn 3072,
+S = 1024, prompts with ~S/2 visible encoder rows, special ids made unsamplable as in bench.py's decode_bench (every row generates --steps
+positions). Prints ONE JSON line: per B in --batches, aggregate tokens/s, ms per batched step, launches per step, rewinds, host
+verification ms per step and an HBM-bytes estimate per step (decoder + LM-head weights once, plus each row's cross K/V over its visible
+encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
+
+    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--seq', type=int, default=1024)
+    ap.add_argument('--layers', type=int, default=12)
+    ap.add_argument('--hs', type=int, default=768)
+    ap.add_argument('--ffn', type=int, default=3072)
+    ap.add_argument('--heads', type=int, default=12)
+    ap.add_argument('--steps', type=int, default=256, help='generated positions per row')
+    ap.add_argument('--batches', type=int, nargs='+', default=[1, 4, 8, 16])
+    args = ap.parse_args(argv)
+
+    import numpy as np
+    import torch
+    from pianobart_amd.model import BartConfig, PianoBart, PianoBartLM
+    from tests.golden_util import load_vocab, synth_octuple_batch
+    dev = torch.device('cuda', 0)
+    e2w, w2e = load_vocab()
+    S, d, L, f = args.seq, args.hs, args.layers, args.ffn
+    cfg = BartConfig(max_position_embeddings=S, d_model=d, encoder_layers=L, decoder_layers=L, encoder_ffn_dim=f, decoder_ffn_dim=f,
+                     encoder_attention_heads=args.heads, decoder_attention_heads=args.heads, dropout=0.0)
+    torch.manual_seed(0)
+    model = PianoBartLM(PianoBart(cfg, e2w, w2e, precision='bf16')).to(dev).eval()
+    with torch.no_grad():
+        for i, p0 in enumerate([256, 128, 129, 256, 128, 32, 254, 49]):
+            model.mask_lm.proj[i].bias[p0:] = -30.0
+    eng = model._get_engine()
+    eng.bind(dev)
+    sampler = dict(T=model.SAMPLE_T, P=model.SAMPLE_P)
+    Bmax = max(args.batches)
+    enc = synth_octuple_batch(Bmax, S, seed=7, min_len=S // 2)[5].to(dev)     # S/2 .. S visible rows, as bench.py's decode prompt
+    emask = (enc[:, :, 0] != 256).float()
+    steps = min(args.steps, S)
+    vis = [int(v) for v in emask.sum(1).tolist()]
+
+    # weight bytes a step streams once (bf16): per layer q|k|v, out, q_c, out_c, fc1, fc2; the LM head
+    w_layer = (3 * d * d + d * d + d * d + d * d + 2 * d * f) * 2
+    w_bytes = L * w_layer + 1280 * d * 2
+
+    def kv_bytes(rows):                                     # cross K/V over the visible rows + self K/V at the mean position
+        return sum(L * (vis[b] + steps / 2) * 2 * d * 2 for b in range(rows))
+
+    # batch 1 through Engine.generate (the device-sampled batch-1 decoder), same process
+    np.random.seed(0)
+    eng.generate(enc[:1], emask[:1], model.sample_row, max_new=16, sampler=sampler)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.generate(enc[:1], emask[:1], model.sample_row, max_new=steps, sampler=sampler)
+    torch.cuda.synchronize()
+    b1 = steps / (time.perf_counter() - t0)
+    b1_info = dict(eng.last_decode)
+
+    res = {}
+    for B in args.batches:
+        rngs = [np.random.RandomState(b) for b in range(B)]
+        eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=16, sampler=sampler)     # warm-up (capture, pinned logs)
+        torch.cuda.synchronize()
+        rngs = [np.random.RandomState(b) for b in range(B)]
+        t0 = time.perf_counter()
+        eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=steps, sampler=sampler)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        info = eng.last_decode
+        ntok = sum(info['tokens'])
+        res[str(B)] = dict(tokens_per_s=ntok / dt, ms_per_step=info['loop_ms'] / max(1, info['steps']), wall_ms=dt * 1e3,
+                           loop_ms=info['loop_ms'], launches_per_step=info['launches_per_token'], graph=info['graph'],
+                           rewinds=sum(info['rewinds']), host_ms_per_step=info['host_ms'] / max(1, info['steps']), steps=info['steps'],
+                           tokens=ntok, hbm_bytes_per_step=w_bytes + kv_bytes(B))
+    best = max(res.values(), key=lambda r: r['tokens_per_s'])['tokens_per_s']
+    print(json.dumps({"metric": "batched generate tokens/s (KV-cached decode, %dL/%dd, S=%d, %d positions per row)" % (L, d, S, steps),
+                      "batch1_generate_tokens_per_s": b1, "batch1_info": b1_info, "by_batch": res,
+                      "speedup_best_vs_batch1": best / b1, "visible_encoder_rows": vis[:Bmax]}), flush=True)
+
+
+if __name__ == '__main__':
+    main()
