@@ -23,7 +23,7 @@ extern "C" {
                         bf16 matrix cores with f32 accumulation (~2^-16 relative per product): the parity-grade instantiation that is not bound by
                         the f32-input MFMA rate (precision="bf16x3"); every other op of that instantiation runs its PB_F32 form */
 
-#define PB_ABI_VERSION 8   /* 8 (round 6): + pb_decoder_sampler_init / launch / wait / logs / seek (device-sampled decode), dtype PB_F32X3 in pb_gemm, pb_flash_*_x3, pb_gemm_reserve_cus; 7 (round 5): + PB_GEMM_ROWDOT / rowdot_out in pb_gemm_desc, delta_rows in pb_flash_bwd1*; 6 (round 5): + pb_flash_bwd1_supported; 5 (round 4): + pb_flash_bwd1*, bh_order in the packed attention calls; 4 (round 3): + pb_decoder_*, pb_nucleus_rows, pb_ids_check */
+#define PB_ABI_VERSION 9   /* 9: one fused decoder for every B (pb_batch_decoder_*, + pb_batch_decoder_step; pb_decoder_* removed); 8 (round 6): + pb_decoder_sampler_init / launch / wait / logs / seek (device-sampled decode), dtype PB_F32X3 in pb_gemm, pb_flash_*_x3, pb_gemm_reserve_cus; 7 (round 5): + PB_GEMM_ROWDOT / rowdot_out in pb_gemm_desc, delta_rows in pb_flash_bwd1*; 6 (round 5): + pb_flash_bwd1_supported; 5 (round 4): + pb_flash_bwd1*, bh_order in the packed attention calls; 4 (round 3): + pb_decoder_*, pb_nucleus_rows, pb_ids_check */
 int pb_abi_version(void);
 const char* pb_last_error(void);
 
@@ -386,64 +386,47 @@ typedef struct pb_decode_plan {
 } pb_decode_plan;
 int pb_decode_step(const pb_decode_plan* plan, int32_t i, void* stream);
 
-/* Decode as ONE hipGraph replay per token (round 3; replaces the per-position host loop of model.py:42-65 around pb_decode_step for the
- * shapes it covers: bf16, head_dim 64 / 128, d a multiple of 256 up to 1024). The position lives in device memory, so the launches of a
- * token (embed, per layer {self-attention with the q|k|v projections and the pending post-LN fused in, out-projection, cross-attention
- * with its q projection, out-projection, fc1 + GELU, fc2}, LM heads: 6 n_layers + 2) carry no position-dependent argument; the token ids
- * go up and the logits row comes down through copy nodes of the same graph.
- *   pb_decoder_create   0 = created (*dec), 1 = this plan's shape is not covered (keep pb_decode_step), < 0 = error. The plan is copied;
- *                       its buffers (weights, K/V caches, scratch rows, attn_part) must stay alive until pb_decoder_destroy.
- *   pb_decoder_reset    start of a prompt: position -1, ordered behind everything enqueued on `caller_stream` so far (encoder pass, cross
- *                       K/V projections); use_graph = 0 issues every token's launches directly (A/B, debugging).
- *   pb_decoder_step     one token: tok8 (8 ids, host) in, the (vocab) f32 logits row of its position out (host); returns when it landed.
- *   pb_decoder_launches kernels per token; pb_decoder_graph 1 when tokens are graph replays. */
 /* Host-side nucleus sampling of one position (model.py:84-98 for the 8 heads): probs (heads, width) f32 softmax rows of lengths n[h],
  * thresholds p[h], u[h] = the uniform draw np.random.choice would consume. out[h] = sampled id; bit h of *tie_mask set (out[h] = -1)
  * when the result would depend on numpy's order of equal probabilities: the caller runs its numpy code for that head. No device work. */
 int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const float* p, const double* u, int32_t heads, int32_t* out,
                     int32_t* tie_mask);
-int pb_decoder_create(const pb_decode_plan* plan, void** dec);
-int pb_decoder_destroy(void* dec);
-int pb_decoder_reset(void* dec, void* caller_stream, int32_t use_graph);
-int pb_decoder_step(void* dec, const int16_t* tok8, float* logits_out);
-int pb_decoder_launches(void* dec);
-int pb_decoder_graph(void* dec);
-/* Device-sampled decode (round 6; ABI 8): the per-token host round trip of model.py:42-65 (logits row down, sampling(), token up) leaves
- * the critical path. np.random.choice's uniform draws do not depend on the logits (model.py:97), so the host draws the (S, 8) of a whole
- * prompt ahead and uploads them once; a one-workgroup kernel behind the LM-head GEMV then does model.py:68-107 for the 8 heads (y = logit
- * / T, softmax, nucleus with the threshold p and the draw of that position: pb_nucleus_rows' arithmetic order) and writes the next decoder
- * input on the device, so tokens are enqueued back to back, 8 per hipGraph replay. The kernel also writes the raw logits row and its 8 ids
- * to pinned host logs indexed by position: the HOST stays the authority -- it replays each position from the logged row through the
- * reference code path (CPU softmax + nucleus, consuming the global RNG stream exactly as before) and, on the rare position where the
- * device's softmax rounding made another choice, rewinds the decoder (pb_decoder_seek) and continues from its own token. Results are
- * therefore bit-identical to the per-token loop (tests/test_model_gpu.py) whatever the device sampled.
- *   pb_decoder_sampler_init  temperatures, thresholds, class counts and logits offsets of the 8 heads, u = (S, 8) f64 draws (host; copied),
- *                            fault_period > 0 corrupts head 0's id at every fault_period-th position (tests of the rewind path only).
- *   pb_decoder_launch        enqueue the next ntok tokens (first_tok8, 8 host ids or NULL, is copied up as the first decoder input);
- *                            returns a ticket >= 0 for pb_decoder_wait, or < 0.
- *   pb_decoder_wait          block until that run's tokens are decoded and logged.
- *   pb_decoder_logs          the pinned logs: (S, vocab) f32 logits rows, (S, 8) int16 device-sampled ids.
- *   pb_decoder_seek          drain, then: last decoded position = pos, decoder input of position pos + 1 = tok8. */
-int pb_decoder_sampler_init(void* dec, const float* temps8, const float* p8, const int32_t* n8, const int32_t* off8, const double* u,
-                            int64_t n_u, int32_t fault_period);
-int pb_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok8);
-int pb_decoder_wait(void* dec, int32_t ticket);
-int pb_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows);
-int pb_decoder_seek(void* dec, int32_t pos, const int16_t* tok8);
-/* Batched device-sampled decode (additive to ABI 8): up to PB_DECODE_BATCH_MAX prompts decoded in the same launches, so each weight byte of
- * a step is read once for all rows. The same launches per step as the batch-1 decoder (6 n_layers + 3 with the sampler); each row's
- * arithmetic is the batch-1 kernels' arithmetic (same K partition, FMA order, reduction trees and split-record merge), so the logged
- * logits rows are bit-identical to pb_decoder_*'s for the same prompt and the same fed tokens. Per row in device memory: the position,
- * a done flag (set by the sampler on a special id, by the embedding kernel at the position limit, or by the host), the uniform draws.
- * pb_decode_batch.plan holds the shapes and weights as for pb_decoder_create, with B-row scratch: x, y1, yc, y2, a (B, d), g (B, ffn),
+/* The fused decoder (round 3, rows and one decoder for every B in ABI 9): one step of 1 <= B <= PB_DECODE_BATCH_MAX prompts = ONE hipGraph
+ * replay, for the shapes it covers (bf16, head_dim 64 / 128, d a multiple of 256 up to 1024; anything else keeps pb_decode_step or the
+ * per-prompt loop). The positions live in device memory, so the launches of a step (embed, per layer {self-attention with the q|k|v
+ * projections and the pending post-LN fused in, out-projection, cross-attention with its q projection, out-projection, fc1 + GELU, fc2},
+ * LM heads: 6 n_layers + 2, + 1 with the device sampler) carry no position-dependent argument, and each weight byte of a step is read once
+ * for all rows. B == 1 runs the single-row kernels (every load up front, no per-row flags); B > 1 their row forms, whose per-row
+ * arithmetic is the same source, so a row's logits do not depend on B (tests/test_generate_batch_gpu.py). Per row in device memory: the
+ * position, a done flag (B > 1: set by the sampler on a special id, by the embedding kernel at the position limit, or by the host), the
+ * uniform draws.
+ * pb_decode_batch.plan holds the shapes and weights as for pb_decode_step, with B-row scratch: x, y1, yc, y2, a (B, d), g (B, ffn),
  * logits (B, vocab) f32, attn_part (B, H, PB_DECODE_MAX_SPLITS, hd + 4) f32, enc_mask (B, S) f32 or NULL, tok16 unused, and
  * layers[l].kv_self / kv_cross (B, S, 2d). s_enc[b] = row b's visible encoder extent (its cross-attention split geometry).
- *   pb_batch_decoder_create         0 = created, 1 = shape not covered (same rule as pb_decoder_create; 1 <= B <= 16), < 0 = error.
- *   pb_batch_decoder_reset          every row at position -1 and live, ordered behind `caller_stream`.
- *   pb_batch_decoder_sampler_init   the 8 heads' constants as pb_decoder_sampler_init, pad8 = the ids from which a sampled id is special,
- *                                   u = (B, S, 8) f64 draws (copied), limit = positions per row (<= S); fault_row / fault_period > 0
- *                                   corrupt head 0's id of that row at every fault_period-th position (tests of the rewind path only).
- *   pb_batch_decoder_launch         enqueue ntok batched steps (first_tok, (B, 8) host ids or NULL); ticket >= 0 for pb_batch_decoder_wait.
+ *   pb_batch_decoder_create     0 = created (*dec), 1 = shape not covered (return 1 is not an error), < 0 = error. The plan is copied;
+ *                               its buffers (weights, K/V caches, scratch rows, attn_part) must stay alive until pb_batch_decoder_destroy.
+ *   pb_batch_decoder_reset      every row at position -1 and live, ordered behind everything enqueued on `caller_stream` so far (encoder
+ *                               passes, cross K/V projections); use_graph = 0 issues every step's launches directly (A/B, debugging).
+ *   pb_batch_decoder_step       B == 1, host-sampled: tok8 (8 ids, host) in, the (vocab) f32 logits row of its position out (host);
+ *                               returns when it landed (the token ids go up and the logits row comes down through copy nodes of the graph).
+ *   pb_batch_decoder_launches   kernels per step; pb_batch_decoder_graph 1 when steps are graph replays.
+ * Device-sampled decode (round 6): the per-token host round trip of model.py:42-65 (logits row down, sampling(), token up) leaves the
+ * critical path. np.random.choice's uniform draws do not depend on the logits (model.py:97), so the host draws each row's (S, 8) ahead and
+ * uploads them once; a one-workgroup-per-row kernel behind the LM-head GEMV then does model.py:68-107 for the 8 heads (y = logit / T,
+ * softmax, nucleus with the threshold p and the draw of that position: pb_nucleus_rows' arithmetic order) and writes the next decoder
+ * input on the device, so steps are enqueued back to back, 8 per hipGraph replay. The kernel also writes the raw logits row and its 8 ids
+ * to pinned host logs indexed by row and position: the HOST stays the authority -- it replays each position from the logged row through
+ * the reference code path (CPU softmax + nucleus, consuming the row's RNG stream exactly as the per-token loop) and, on the rare position
+ * where the device's softmax rounding made another choice, rewinds that row (pb_batch_decoder_seek) and continues from its own token.
+ * Results are therefore bit-identical to the per-token loop (tests/test_model_gpu.py) whatever the device sampled.
+ *   pb_batch_decoder_sampler_init   temperatures, thresholds, class counts and logits offsets of the 8 heads, pad8 = the ids from which a
+ *                                   sampled id is special, u = (B, S, 8) f64 draws (copied), limit = positions per row (<= S);
+ *                                   fault_row / fault_period > 0 corrupt head 0's id of that row at every fault_period-th position
+ *                                   (tests of the rewind path only; B == 1: row 0).
+ *   pb_batch_decoder_launch         enqueue ntok steps (first_tok, (B, 8) host ids or NULL, is copied up as the rows' decoder inputs);
+ *                                   ticket >= 0 for pb_batch_decoder_wait, or < 0. B > 1: a row stops by itself at the limit; B == 1:
+ *                                   the steps must stay within it.
+ *   pb_batch_decoder_wait           block until that run's steps are decoded and logged.
  *   pb_batch_decoder_logs           pinned logs: (B, S, vocab) f32 logits rows, (B, S, 8) int16 device-sampled ids.
  *   pb_batch_decoder_seek           tok8 != NULL: drain, then row's last decoded position = pos, its next input = tok8, live again (the
  *                                   other rows are untouched); tok8 == NULL: the row is done from the next enqueued step on (no drain). */
@@ -456,6 +439,7 @@ typedef struct pb_decode_batch {
 int pb_batch_decoder_create(const pb_decode_batch* plan, void** dec);
 int pb_batch_decoder_destroy(void* dec);
 int pb_batch_decoder_reset(void* dec, void* caller_stream, int32_t use_graph);
+int pb_batch_decoder_step(void* dec, const int16_t* tok8, float* logits_out);
 int pb_batch_decoder_sampler_init(void* dec, const float* temps8, const float* p8, const int32_t* n8, const int32_t* off8, const int32_t* pad8,
                                   const double* u, int64_t n_u, int32_t limit, int32_t fault_row, int32_t fault_period);
 int pb_batch_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok);

@@ -97,8 +97,8 @@ class _Lib:
                 fn.restype = restype
                 fn.argtypes = argtypes
             ver = dll.pb_abi_version()
-            if ver != 8:
-                raise PBError('ABI version mismatch: library %d, binding 8' % ver)
+            if ver != 9:
+                raise PBError('ABI version mismatch: library %d, binding 9' % ver)
             self._dll = dll
         return self._dll
 

@@ -34,7 +34,8 @@ __device__ __forceinline__ float block_sum4(float v, float* red, int lane, int w
 // part[h][s] = {m, l, -, -, o[hd]} (f32): every workgroup merges the splits of the heads its K range touches on the fly
 // (ctx = sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M), rounded to T like the stored context of the one-kernel form), so the
 // split needs neither a merge launch nor any inter-workgroup hand-off inside the attention kernel.
-struct MergeIn { const float* part; int nsplit, hd, stride; };       // stride = floats per (head, split) record
+struct MergeIn { const float* part; int nsplit, hd, stride; long row_stride; };    // stride = floats per (head, split) record;
+                                                                                    // row form: row b's records at part + b row_stride
 
 // NCH = chunks of EPV elements a thread owns along K (K <= NCH * 256 * EPV). Everything a thread will ever read -- its weight chunks
 // of both rows, x, the residual, gamma / beta, the split records' maxima -- is requested up front, so the kernel is ONE memory round
@@ -43,11 +44,24 @@ template <typename T> struct VecOf;
 template <> struct VecOf<bf16_t> { typedef bf16x8 type; };
 template <> struct VecOf<float> { typedef f32x4 type; };
 
-template <typename T, typename TO, int NCH, bool MERGE>
+// Device state of the fused decoder (pb_batch_decoder_*, below): one allocation.
+constexpr int BMAX = PB_DECODE_BATCH_MAX;
+struct BState {
+    int pos[BMAX];                         // last decoded position of each row (-1 at reset)
+    int done[BMAX];                        // row form: 0 = live; 1 = special id sampled / stopped by the host; 2 = position limit reached
+    int limit;                             // row form: positions per row
+};
+
+// ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
+// (and gamma / beta) in registers and runs the per-row part below for each row that is not done, requesting the row's input, residual
+// and split records after the barrier behind the previous row's reductions: only the shared operands are loaded once. The arithmetic of a
+// row is the single-row kernel's (no MFMA: its rounding would differ from the FMA chain).
+template <typename T, typename TO, int NCH, bool MERGE, bool ROWS>
 __global__ __launch_bounds__(256) void gemv_kernel(const T* __restrict__ W, const T* __restrict__ x, const float* __restrict__ bias,
                                                    TO* __restrict__ y, TO* __restrict__ y2, int n_split, int N, int K, int gelu,
                                                    const T* __restrict__ res, const float* __restrict__ gamma,
-                                                   const float* __restrict__ beta, T* __restrict__ ln_out, float eps, const MergeIn mg) {
+                                                   const float* __restrict__ beta, T* __restrict__ ln_out, float eps, const MergeIn mg,
+                                                   const BState* __restrict__ st, int B) {
     constexpr int EPV = 16 / sizeof(T);
     __shared__ float red[4][2];
     __shared__ float red1[4];
@@ -67,96 +81,115 @@ __global__ __launch_bounds__(256) void gemv_kernel(const T* __restrict__ W, cons
         const bool in = c < K;
         u0[i] = in ? *reinterpret_cast<const V*>(w0 + c) : zero4;
         u1[i] = in ? *reinterpret_cast<const V*>(w1 + c) : zero4;
-        xr[i] = (in && !MERGE) ? *reinterpret_cast<const V*>(x + c) : zero4;
-        rr[i] = (in && res) ? *reinterpret_cast<const V*>(res + c) : zero4;
+        if constexpr (!ROWS) {
+            xr[i] = (in && !MERGE) ? *reinterpret_cast<const V*>(x + c) : zero4;
+            rr[i] = (in && res) ? *reinterpret_cast<const V*>(res + c) : zero4;
+        }
 #pragma unroll
         for (int v4 = 0; v4 < EPV / 4; ++v4) {
             gm[i][v4] = (in && res) ? *reinterpret_cast<const f32x4*>(gamma + c + 4 * v4) : f32x4{0.f, 0.f, 0.f, 0.f};
             bt[i][v4] = (in && res) ? *reinterpret_cast<const f32x4*>(beta + c + 4 * v4) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    float xf[NCH][EPV];
+    for (int b = 0; !ROWS || b < B; ++b) {                                  // rows b = 0 .. B - 1 (one row: no loop at all)
+        const T* rb = ROWS && res ? res + (long)b * K : res;
+        if constexpr (ROWS) {
+            if (st->done[b]) continue;                                      // block-uniform
+            __syncthreads();                                                // red / red1 of the previous row are read
+            const T* xb = MERGE ? nullptr : x + (long)b * K;
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int c = (threadIdx.x + 256 * i) * EPV;
-        if (MERGE && c < K) {
-            const int h = c / mg.hd, off = c % mg.hd;                      // EPV columns of one head (hd is a multiple of EPV)
-            const float* rec = mg.part + (size_t)h * mg.nsplit * mg.stride;
-            // all loads of the <= PB_DECODE_MAX_SPLITS records are issued before the first use: one L2 round trip, not one per split
-            float ms[PB_DECODE_MAX_SPLITS], ls[PB_DECODE_MAX_SPLITS];
-            f32x4 oa[PB_DECODE_MAX_SPLITS][EPV / 4];
-#pragma unroll
-            for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) {
-                const float* r = rec + (size_t)(sp < mg.nsplit ? sp : 0) * mg.stride;
-                ms[sp] = sp < mg.nsplit ? r[0] : -INFINITY;
-                ls[sp] = r[1];
-#pragma unroll
-                for (int v4 = 0; v4 < EPV / 4; ++v4) oa[sp][v4] = *reinterpret_cast<const f32x4*>(r + 4 + off + 4 * v4);
+            for (int i = 0; i < NCH; ++i) {
+                const int c = (threadIdx.x + 256 * i) * EPV;
+                const bool in = c < K;
+                xr[i] = (in && !MERGE) ? *reinterpret_cast<const V*>(xb + c) : zero4;
+                rr[i] = (in && rb) ? *reinterpret_cast<const V*>(rb + c) : zero4;
             }
-            float M = -INFINITY;
-#pragma unroll
-            for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) M = fmaxf(M, ms[sp]);
-            float L = 0.f, o[EPV];
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) o[j] = 0.f;
-#pragma unroll
-            for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) {
-                const float wgt = (M == -INFINITY || ms[sp] == -INFINITY) ? 0.f : __expf(ms[sp] - M);   // no visible key in the split (or at all): weight 0
-                L = fmaf(ls[sp], wgt, L);
-#pragma unroll
-                for (int j = 0; j < EPV; ++j) o[j] = fmaf(oa[sp][j >> 2][j & 3], wgt, o[j]);
-            }
-            const float inv = L > 0.f ? 1.0f / L : 0.f;                    // nothing visible -> zero row (oracle header)
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) xf[i][j] = to_f(from_f<T>(o[j] * inv));     // rounded to T like the stored context of the one-kernel form
-        } else {
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) xf[i][j] = to_f(xr[i][j]);
         }
-    }
-    if (res) {
-        // x' = LayerNorm(res + x) * gamma + beta, two-pass statistics from the registers
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) { xf[i][j] += to_f(rr[i][j]); s += xf[i][j]; }       // lanes beyond K hold zeros
-        }
-        const float mean = block_sum4(s, red1, lane, wave) / (float)K;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const bool in = (threadIdx.x + 256 * i) * EPV < K;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) { const float z = xf[i][j] - mean; q = in ? fmaf(z, z, q) : q; }
-        }
-        const float rstd = rsqrtf(block_sum4(q, red1, lane, wave) / (float)K + eps);
+        float xf[NCH][EPV];
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = (threadIdx.x + 256 * i) * EPV;
-            V xo;
+            if (MERGE && c < K) {
+                const int h = c / mg.hd, off = c % mg.hd;                  // EPV columns of one head (hd is a multiple of EPV)
+                const float* rec = mg.part + (size_t)b * mg.row_stride + (size_t)h * mg.nsplit * mg.stride;
+                // all loads of the <= PB_DECODE_MAX_SPLITS records are issued before the first use: one L2 round trip, not one per split
+                float ms[PB_DECODE_MAX_SPLITS], ls[PB_DECODE_MAX_SPLITS];
+                f32x4 oa[PB_DECODE_MAX_SPLITS][EPV / 4];
 #pragma unroll
-            for (int j = 0; j < EPV; ++j) {       // rounded to T exactly like the stored LayerNorm output the unfused path would read back
-                xo[j] = from_f<T>((xf[i][j] - mean) * rstd * gm[i][j >> 2][j & 3] + bt[i][j >> 2][j & 3]);
-                xf[i][j] = to_f(xo[j]);
+                for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) {
+                    const float* r = rec + (size_t)(sp < mg.nsplit ? sp : 0) * mg.stride;
+                    ms[sp] = sp < mg.nsplit ? r[0] : -INFINITY;
+                    ls[sp] = r[1];
+#pragma unroll
+                    for (int v4 = 0; v4 < EPV / 4; ++v4) oa[sp][v4] = *reinterpret_cast<const f32x4*>(r + 4 + off + 4 * v4);
+                }
+                float M = -INFINITY;
+#pragma unroll
+                for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) M = fmaxf(M, ms[sp]);
+                float L = 0.f, o[EPV];
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) o[j] = 0.f;
+#pragma unroll
+                for (int sp = 0; sp < PB_DECODE_MAX_SPLITS; ++sp) {
+                    const float wgt = (M == -INFINITY || ms[sp] == -INFINITY) ? 0.f : __expf(ms[sp] - M);   // no visible key in the split (or at all): weight 0
+                    L = fmaf(ls[sp], wgt, L);
+#pragma unroll
+                    for (int j = 0; j < EPV; ++j) o[j] = fmaf(oa[sp][j >> 2][j & 3], wgt, o[j]);
+                }
+                const float inv = L > 0.f ? 1.0f / L : 0.f;                // nothing visible -> zero row (oracle header)
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) xf[i][j] = to_f(from_f<T>(o[j] * inv));     // rounded to T like the stored context of the one-kernel form
+            } else {
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) xf[i][j] = to_f(xr[i][j]);
             }
-            if (blockIdx.x == 0 && c < K) *reinterpret_cast<V*>(ln_out + c) = xo;
         }
-    }
-    float a0 = 0.f, a1 = 0.f;
+        if (rb) {
+            // x' = LayerNorm(res + x) * gamma + beta, two-pass statistics from the registers
+            float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
+            for (int i = 0; i < NCH; ++i) {
 #pragma unroll
-        for (int j = 0; j < EPV; ++j) { a0 = fmaf(to_f(u0[i][j]), xf[i][j], a0); a1 = fmaf(to_f(u1[i][j]), xf[i][j], a1); }    // weights beyond K are zeros
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1);
-    if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; }
-    __syncthreads();
-    if (threadIdx.x < 2 && (threadIdx.x == 0 || two)) {
-        const int n = n0 + threadIdx.x;
-        float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] + bias_v;
-        if (gelu) v = gelu_f(v);
-        if (n < n_split) y[n] = from_f<TO>(v); else y2[n - n_split] = from_f<TO>(v);
+                for (int j = 0; j < EPV; ++j) { xf[i][j] += to_f(rr[i][j]); s += xf[i][j]; }       // lanes beyond K hold zeros
+            }
+            const float mean = block_sum4(s, red1, lane, wave) / (float)K;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const bool in = (threadIdx.x + 256 * i) * EPV < K;
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) { const float z = xf[i][j] - mean; q = in ? fmaf(z, z, q) : q; }
+            }
+            const float rstd = rsqrtf(block_sum4(q, red1, lane, wave) / (float)K + eps);
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const int c = (threadIdx.x + 256 * i) * EPV;
+                V xo;
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) {       // rounded to T exactly like the stored LayerNorm output the unfused path would read back
+                    xo[j] = from_f<T>((xf[i][j] - mean) * rstd * gm[i][j >> 2][j & 3] + bt[i][j >> 2][j & 3]);
+                    xf[i][j] = to_f(xo[j]);
+                }
+                if (blockIdx.x == 0 && c < K) *reinterpret_cast<V*>(ln_out + (long)b * K + c) = xo;
+            }
+        }
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+#pragma unroll
+            for (int j = 0; j < EPV; ++j) { a0 = fmaf(to_f(u0[i][j]), xf[i][j], a0); a1 = fmaf(to_f(u1[i][j]), xf[i][j], a1); }    // weights beyond K are zeros
+        }
+        a0 = wave_sum(a0); a1 = wave_sum(a1);
+        if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; }
+        __syncthreads();
+        if (threadIdx.x < 2 && (threadIdx.x == 0 || two)) {
+            const int n = n0 + threadIdx.x;
+            float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] + bias_v;
+            if (gelu) v = gelu_f(v);
+            if (ROWS) y[(long)b * N + n] = from_f<TO>(v);
+            else if (n < n_split) y[n] = from_f<TO>(v); else y2[n - n_split] = from_f<TO>(v);
+        }
+        if (!ROWS) break;
     }
 }
 
@@ -398,29 +431,34 @@ __global__ __launch_bounds__(AS_WAVES * 64) void attn_split_kernel(const T* __re
 
 struct LnIn { const void* res; const float* gamma; const float* beta; void* out; };
 
+// st / B > 1: the fused decoder's row form (bf16; y, ln_out and the split records of row b at + b N, + b K, + b mg.row_stride)
 static int gemv_launch(const void* W, const void* x, const float* bias, void* y, void* y2, int n_split, int N, int K, int dtype, int y_f32,
-                       int gelu, hipStream_t stream, LnIn ln = LnIn{nullptr, nullptr, nullptr, nullptr}, MergeIn mg = MergeIn{nullptr, 0, 0, 0}) {
+                       int gelu, hipStream_t stream, LnIn ln = LnIn{nullptr, nullptr, nullptr, nullptr}, MergeIn mg = MergeIn{nullptr, 0, 0, 0, 0},
+                       const BState* st = nullptr, int B = 1) {
     const int epv = dtype == PB_BF16 ? 8 : 4;
     PB_REQUIRE(N > 0 && K > 0 && K % epv == 0, "pb_gemv: K=%d must be a multiple of %d", K, epv);
     PB_REQUIRE(((uintptr_t)W % 16 == 0) && ((uintptr_t)x % 16 == 0), "pb_gemv: operands must be 16-byte aligned");
+    PB_REQUIRE(B == 1 || (dtype == PB_BF16 && st), "pb_gemv: rows need bf16 and the decoder state");
     dim3 grid((N + 1) / 2), block(256);
     const float eps = 1e-5f;
     const int nch = (K + 256 * epv - 1) / (256 * epv);
     PB_REQUIRE(nch <= 4, "pb_gemv: K=%d exceeds %d", K, 4 * 256 * epv);
-#define PB_GEMV_GO(TT, TO, NCH_, MG_)                                                                                                      \
-    hipLaunchKernelGGL((gemv_kernel<TT, TO, NCH_, MG_>), grid, block, 0, stream, (const TT*)W, (const TT*)x, bias, (TO*)y, (TO*)y2, n_split, N, K, \
-                       gelu, (const TT*)ln.res, ln.gamma, ln.beta, (TT*)ln.out, eps, mg)
-#define PB_GEMV_NCH(TT, TO)                                                                                   \
+#define PB_GEMV_GO(TT, TO, NCH_, MG_, ROWS_)                                                                                               \
+    hipLaunchKernelGGL((gemv_kernel<TT, TO, NCH_, MG_, ROWS_>), grid, block, 0, stream, (const TT*)W, (const TT*)x, bias, (TO*)y, (TO*)y2, n_split, \
+                       N, K, gelu, (const TT*)ln.res, ln.gamma, ln.beta, (TT*)ln.out, eps, mg, st, B)
+#define PB_GEMV_NCH(TT, TO, ROWS_)                                                                            \
     do {                                                                                                      \
-        if (mg.part) { PB_REQUIRE(nch <= 1, "pb_gemv: the split-merge prologue needs K <= %d", 256 * epv); PB_GEMV_GO(TT, TO, 1, true); } \
-        else if (nch <= 1) PB_GEMV_GO(TT, TO, 1, false);                                                      \
-        else if (nch == 2) PB_GEMV_GO(TT, TO, 2, false);                                                      \
-        else PB_GEMV_GO(TT, TO, 4, false);                                                                    \
+        if (mg.part) { PB_REQUIRE(nch <= 1, "pb_gemv: the split-merge prologue needs K <= %d", 256 * epv); PB_GEMV_GO(TT, TO, 1, true, ROWS_); } \
+        else if (nch <= 1) PB_GEMV_GO(TT, TO, 1, false, ROWS_);                                               \
+        else if (nch == 2) PB_GEMV_GO(TT, TO, 2, false, ROWS_);                                               \
+        else PB_GEMV_GO(TT, TO, 4, false, ROWS_);                                                             \
     } while (0)
-    if (dtype == PB_BF16) {
-        if (y_f32) PB_GEMV_NCH(bf16_t, float); else PB_GEMV_NCH(bf16_t, bf16_t);
+    if (dtype == PB_BF16 && B > 1) {
+        if (y_f32) PB_GEMV_NCH(bf16_t, float, true); else PB_GEMV_NCH(bf16_t, bf16_t, true);
+    } else if (dtype == PB_BF16) {
+        if (y_f32) PB_GEMV_NCH(bf16_t, float, false); else PB_GEMV_NCH(bf16_t, bf16_t, false);
     } else {
-        PB_GEMV_NCH(float, float);
+        PB_GEMV_NCH(float, float, false);
     }
 #undef PB_GEMV_NCH
 #undef PB_GEMV_GO
@@ -543,13 +581,13 @@ extern "C" int pb_decode_step(const pb_decode_plan* p, int32_t i, void* stream) 
     return gemv_launch(p->head_w, p->a, p->head_b, p->logits, nullptr, p->vocab, p->vocab, d, dt, 1, 0, st, ln);
 }
 
+
 // =====================================================================================================================
-// Decode, second form (round 3): one token = ONE hipGraph replay of 6 launches per decoder layer (+ embed + heads).
-// What changed against pb_decode_step above:
-//   * the position i lives in DEVICE memory (incremented by the first kernel of a step), so the launches of a step have no
+// Decode, second form: the fused decoder (pb_batch_decoder_*). One step = ONE hipGraph replay of 6 launches per decoder layer
+// (+ embed + heads, + the device sampler). What changed against pb_decode_step above:
+//   * the positions live in DEVICE memory (advanced by the first kernel of a step), so the launches of a step have no
 //     position-dependent argument or grid and one captured graph serves every position: the host's ~3.5 us of enqueue per launch
-//     (host-bound with kernels this short) become one hipGraphLaunch per token; the token ids go up and the logits row comes down
-//     through two copy nodes of the same graph (pinned host buffers owned by the decoder);
+//     (host-bound with kernels this short) become one hipGraphLaunch per token;
 //   * the q projection is fused into the single-query attention (dec_attn_kernel): a (head, key split) workgroup needs q of ITS
 //     head only (hd rows of W_q, 98 KB at cfg 2: re-read by the <= 16 splits of a head from L2), so it applies the pending post-LN
 //     itself, projects q_h, and goes on to its keys -- the q|k|v GEMV launch and its all-to-all seam are gone. For the self-attention
@@ -559,6 +597,15 @@ extern "C" int pb_decode_step(const pb_decode_plan* p, int32_t i, void* stream) 
 //     out_c (merge) -> fc1 (+LNc, GELU) -> fc2. Every remaining boundary is a real all-to-all seam (each output needs the whole
 //     input vector, produced by all workgroups of the launch before): cdna_hip_programming.md 5.6 prices a grid barrier above a
 //     kernel boundary, so they stay launches.
+// Rows: 1 <= B <= PB_DECODE_BATCH_MAX prompts go through the same launches, so a step reads each weight byte once for all of them. Each
+// kernel is one template with a ROWS switch. The single-row instance (ROWS = false, launched at B == 1) has the row fixed at 0, no done /
+// limit checks and every load issued up front: the batch-1 token is pure latency. The row instance takes its row from the grid (embedding,
+// attention, sampler) or loops over the rows (bgemv_kernel), addresses row b's slice of the scratch rows, caches and split records, and
+// skips rows that are done. The arithmetic of a row is the same source in both, so a row's logits do not depend on B
+// (tests/test_generate_batch_gpu.py).
+// Per-row state in device memory (BState): pos[b], and for the row form done[b] (the sampler's special id, the position limit, or the
+// host) and the limit, so rows advance, stop and rewind independently; a done row writes nothing, never a row past S - 1. At B == 1 the
+// host keeps the count of enqueued positions instead.
 // bf16, head_dim 64 or 128, d a multiple of 256 up to 1024; anything else keeps pb_decode_step.
 namespace {
 
@@ -571,42 +618,66 @@ __device__ __forceinline__ float half_sum(float v) {            // sum over the 
     return __uint_as_float(a[0]) + __uint_as_float(a[1]);
 }
 
-struct DecAttnArgs {
+// ---------------------------------------------------------------- single-query attention with the q projection, (head, key split, row) workgroups
+// The arguments of the two forms share their first fields; each form's member order is its kernarg layout.
+struct DecAttnCommon {
     const bf16_t* x_in;                                          // the input vector (d) when res == NULL
     const bf16_t* res; const bf16_t* add; const float* gamma; const float* beta; bf16_t* ln_out;   // x' = LN(res + add) gamma + beta
     const bf16_t* Wq; const float* bq;                           // q projection rows [d][d] (+ bias); head h owns rows h HD ..
     const bf16_t* Wk; const float* bk; const bf16_t* Wv; const float* bv;      // SELF: the new token's k / v rows
     bf16_t* kc; bf16_t* vc; long kv_ss;                          // cached rows: kc + j kv_ss + h HD
+};
+template <bool ROWS> struct DecAttnArgs;
+template <> struct DecAttnArgs<false> : DecAttnCommon {
     const float* key_mask;                                       // cross: [Sk] (0 = masked) or NULL
-    int* pos; int Sk_fixed;                                      // SELF: keys cached so far = *pos, row *pos is written; cross: Sk_fixed keys
+    BState* st;                                                  // SELF: keys cached so far = pos[0], row pos[0] is written
+    int Sk_fixed;                                                // cross: Sk_fixed keys
     int d, nreg, ck_fixed;                                       // regular key splits; cross: keys per split
     float scale, eps;
     float* part;                                                 // [H][gridDim.y][HD + 4] records {m, l, -, -, o[HD]}
+    static constexpr long kv_rs = 0, mask_rs = 0, part_rs = 0;
+    __device__ int s_enc(int) const { return Sk_fixed; }
+    __device__ int ck(int) const { return ck_fixed; }
+};
+template <> struct DecAttnArgs<true> : DecAttnCommon {           // x_in, res, add, ln_out: (B, d) rows
+    long kv_rs;                                                  // row b's cached rows at kc / vc + b kv_rs
+    const float* key_mask; long mask_rs;                         // cross: row b's (Sk) mask at key_mask + b mask_rs, or NULL
+    BState* st;
+    int d, nreg;
+    float scale, eps;
+    float* part; long part_rs;                                   // row b's records at part + b part_rs
+    int s_enc_[BMAX], ck_[BMAX];                                 // cross: keys and keys per split of each row
+    __device__ int s_enc(int b) const { return s_enc_[b]; }
+    __device__ int ck(int b) const { return ck_[b]; }
 };
 
 // Threads: 256; the self-attention form launches 768 so that the new token's workgroup projects q, k and v side by side (wave
 // groups 0 / 1 / 2, every weight load of a group in flight at once: ONE memory round trip instead of six dependent ones -- these
 // kernels are pure latency); in the other workgroups of that launch waves 4 .. 11 leave at once.
-template <int NC, int HD, bool SELF>
-__global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAttnArgs a) {
+template <int NC, int HD, bool SELF, bool ROWS>
+__global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAttnArgs<ROWS> a) {
     constexpr int CPR = HD / 8, KPW = 64 / CPR, STEP = 4 * KPW, UR = 4, RPW = HD / 4, NP = RPW / 2;
     constexpr int PBATCH = (NC <= 3 && !SELF) || NC <= 2 ? (NP < 8 ? NP : 8) : 4;       // passes of weight rows in flight per lane (registers)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* qs = reinterpret_cast<float*>(smem);                  // [HD] q of this head, rounded to bf16 like a stored q row, times the softmax scale
     float* red = qs + HD;                                        // [4 HD] reductions / per-wave partial outputs (new-token workgroup: k | v)
     float* sc = red + 4 * HD;                                    // [keys per split] scores -> probabilities
-    const int h = blockIdx.x, sp = blockIdx.y, nrec = gridDim.y;
+    const int h = blockIdx.x, sp = blockIdx.y, nrec = gridDim.y, b = ROWS ? (int)blockIdx.z : 0;
+    if (ROWS && a.st->done[b]) return;                           // block-uniform: a done row writes no K/V row and no record
     const int t = threadIdx.x, lane = t & 63, l32 = lane & 31, half = lane >> 5;
     const int wgrp = SELF ? (int)(t >> 8) : 0;                   // 0: q (and the attention), 1: k, 2: v of the new token
     const int wave = (t >> 6) & 3;
     const int d = a.d;
-    const int Sk = SELF ? *a.pos : a.Sk_fixed;
+    const int Sk = SELF ? a.st->pos[b] : a.s_enc(b);
     const bool is_new = SELF && sp == a.nreg;
     if (SELF && wgrp > 0 && !is_new) return;                     // only the new token's workgroup uses the other two wave groups
-    int ck = a.ck_fixed;
+    bf16_t* const kc = a.kc + (long)b * a.kv_rs;
+    bf16_t* const vc = a.vc + (long)b * a.kv_rs;
+    const float* const key_mask = a.key_mask ? a.key_mask + (long)b * a.mask_rs : nullptr;
+    int ck = SELF ? 0 : a.ck(b);
     if (SELF) { ck = (Sk + a.nreg - 1) / a.nreg; ck = ck < 64 ? 64 : (ck + 15) & ~15; }
     const int j0 = sp * ck, j1 = min(Sk, j0 + ck);
-    float* rec = a.part + ((size_t)h * nrec + sp) * (HD + 4);
+    float* rec = a.part + (long)b * a.part_rs + ((size_t)h * nrec + sp) * (HD + 4);
     if (!is_new && j0 >= Sk) {                                   // no key in this split: a record of weight zero
         if (t == 0) { rec[0] = -INFINITY; rec[1] = 0.f; }
         if (t < HD) rec[4 + t] = 0.f;
@@ -622,18 +693,20 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
         const int j = jfirst + r * STEP + grp;
         kpre[r] = uint4{0u, 0u, 0u, 0u}; vpre[r] = uint4{0u, 0u, 0u, 0u};
         if (!is_new && j < j1) {
-            kpre[r] = *reinterpret_cast<const uint4*>(a.kc + (long)j * a.kv_ss + h * HD + sub * 8);
-            vpre[r] = *reinterpret_cast<const uint4*>(a.vc + (long)j * a.kv_ss + h * HD + sub * 8);
+            kpre[r] = *reinterpret_cast<const uint4*>(kc + (long)j * a.kv_ss + h * HD + sub * 8);
+            vpre[r] = *reinterpret_cast<const uint4*>(vc + (long)j * a.kv_ss + h * HD + sub * 8);
         }
     }
     // the input vector, whole, in every half-wave: lane l32 holds the 8 elements of chunks l32 + 32 c
     float xf[NC][8];
     if (a.res) {
+        const bf16_t* resb = a.res + (long)b * d;
+        const bf16_t* addb = a.add + (long)b * d;
         bf16x8 rr[NC], aa[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            rr[c] = *reinterpret_cast<const bf16x8*>(a.res + (l32 + 32 * c) * 8);
-            aa[c] = *reinterpret_cast<const bf16x8*>(a.add + (l32 + 32 * c) * 8);
+            rr[c] = *reinterpret_cast<const bf16x8*>(resb + (l32 + 32 * c) * 8);
+            aa[c] = *reinterpret_cast<const bf16x8*>(addb + (l32 + 32 * c) * 8);
         }
         float s = 0.f;
 #pragma unroll
@@ -659,12 +732,13 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
                 xo[j] = (bf16_t)((xf[c][j] - mean) * rstd * (j < 4 ? g0[j & 3] : g1[j & 3]) + (j < 4 ? b0[j & 3] : b1[j & 3]));
                 xf[c][j] = (float)xo[j];
             }
-            if (store_ln) *reinterpret_cast<bf16x8*>(a.ln_out + e0) = xo;
+            if (store_ln) *reinterpret_cast<bf16x8*>(a.ln_out + (long)b * d + e0) = xo;
         }
     } else {
+        const bf16_t* xb = a.x_in + (long)b * d;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const bf16x8 xv = *reinterpret_cast<const bf16x8*>(a.x_in + (l32 + 32 * c) * 8);
+            const bf16x8 xv = *reinterpret_cast<const bf16x8*>(xb + (l32 + 32 * c) * 8);
 #pragma unroll
             for (int j = 0; j < 8; ++j) xf[c][j] = (float)xv[j];
         }
@@ -701,8 +775,8 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
         else project(a.Wv, a.bv, vs, 1.f);
         __syncthreads();
         if (t < HD) {
-            a.kc[(long)Sk * a.kv_ss + h * HD + t] = (bf16_t)ks[t];
-            a.vc[(long)Sk * a.kv_ss + h * HD + t] = (bf16_t)vs[t];
+            kc[(long)Sk * a.kv_ss + h * HD + t] = (bf16_t)ks[t];         // Sk < S (row form: < limit, the embedding kernel's guard)
+            vc[(long)Sk * a.kv_ss + h * HD + t] = (bf16_t)vs[t];
             rec[4 + t] = vs[t];
         }
         if (t < 64) {
@@ -728,7 +802,7 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
             kraw[r] = kpre[r];
             if (jb != jfirst) {
                 kraw[r] = uint4{0u, 0u, 0u, 0u};
-                if (j < j1) kraw[r] = *reinterpret_cast<const uint4*>(a.kc + (long)j * a.kv_ss + h * HD + sub * 8);
+                if (j < j1) kraw[r] = *reinterpret_cast<const uint4*>(kc + (long)j * a.kv_ss + h * HD + sub * 8);
             }
         }
 #pragma unroll
@@ -743,7 +817,7 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
 #pragma unroll
             for (int o = 1; o < CPR; o <<= 1) s += __shfl_xor(s, o, 64);
             if (j < j1) {
-                const float sv = (!a.key_mask || a.key_mask[j] != 0.f) ? s : -INFINITY;
+                const float sv = (!key_mask || key_mask[j] != 0.f) ? s : -INFINITY;
                 if (sub == 0) sc[j - j0] = sv;
                 mx = fmaxf(mx, sv);
             }
@@ -774,7 +848,7 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
                 vraw[r] = vpre[r];
                 if (jb != jfirst) {
                     vraw[r] = uint4{0u, 0u, 0u, 0u};
-                    if (j < j1) vraw[r] = *reinterpret_cast<const uint4*>(a.vc + (long)j * a.kv_ss + h * HD + sub * 8);
+                    if (j < j1) vraw[r] = *reinterpret_cast<const uint4*>(vc + (long)j * a.kv_ss + h * HD + sub * 8);
                 }
             }
 #pragma unroll
@@ -800,16 +874,26 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
     if (t < HD) rec[4 + t] = (red[t] + red[HD + t]) + (red[2 * HD + t] + red[3 * HD + t]);
 }
 
-// token embedding + learned position + LayerNorm of ONE decoder token at the position kept in device memory: i = ++*pos
+// token embedding + learned position + LayerNorm of ONE decoder token per row at the position kept in device memory: i = ++pos[b]
 // (PianoBart.py:60-71 through the projected table, modeling_bart.py positions offset 2; same sums as embed_ln_fwd_kernel)
 struct SegOff9 { int off[9]; };
+template <bool ROWS>
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restrict__ tok16, const float* __restrict__ P, const SegOff9 so,
                                                         const float* __restrict__ lin_b, const float* __restrict__ pos_tab,
-                                                        const float* __restrict__ w, const float* __restrict__ b, bf16_t* __restrict__ y,
-                                                        int* __restrict__ pos, int d, float eps) {
+                                                        const float* __restrict__ w, const float* __restrict__ bb, bf16_t* __restrict__ y,
+                                                        BState* __restrict__ st, int d, float eps) {
     __shared__ float red1[4];
+    const int b = ROWS ? (int)blockIdx.x : 0;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, d4 = d >> 2;
-    const int i = *pos + 1;
+    if (ROWS && st->done[b]) return;                             // block-uniform
+    const int i = st->pos[b] + 1;
+    if (ROWS && i >= st->limit) {                                // the row's last position is decoded: it stops here (no row past limit - 1 <= S - 1)
+        __syncthreads();                                         // every thread has read done[b] before it changes
+        if (t == 0) st->done[b] = 2;
+        return;
+    }
+    tok16 += b * 8;
+    y += (long)b * d;
     const uint4 raw = *reinterpret_cast<const uint4*>(tok16);
     int id[8];
     id[0] = (int)(raw.x & 0xffff); id[1] = (int)(raw.x >> 16); id[2] = (int)(raw.y & 0xffff); id[3] = (int)(raw.y >> 16);
@@ -828,11 +912,11 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
         for (int j = 0; j < 4; ++j) { const float c = v[j] - mean; q += c * c; }
     }
     const float rstd = rsqrtf(block_sum4(q, red1, lane, wave) / (float)d + eps);
-    if (in) store4(y + 4 * t, (v - mean) * rstd * load4(w + 4 * t) + load4(b + 4 * t));
-    if (t == 0) *pos = i;                                        // every thread has read *pos (two barriers ago); later launches see i
+    if (in) store4(y + 4 * t, (v - mean) * rstd * load4(w + 4 * t) + load4(bb + 4 * t));
+    if (t == 0) st->pos[b] = i;                                  // every thread has read pos[b] (two barriers ago); later launches see i
 }
 
-// ---------------------------------------------------------------- device-side nucleus sampling (round 6)
+// ---------------------------------------------------------------- device-side nucleus sampling (round 6), one workgroup per row
 // model.py:68-107 for the 8 heads of ONE position, on the device: logits row -> y = logit / T[h] -> softmax -> nucleus(p[h]) with
 // the uniform draw u[pos][h] the host drew AHEAD for this position (the draws do not depend on the logits, model.py:97 /
 // np.random.choice) -> the 8 ids of the next decoder input, written to tok_dev for the next step's embedding kernel, and -- with the
@@ -840,19 +924,29 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // 1e-5), descending order with ties by index, candidates up to the first cumsum > p, q = cand / sum(cand), f64 cdf / cdf[-1] > u) with
 // wave-parallel prefix sums in place of numpy's left-to-right ones (33.6 -> 19.3 us per token under the profiler); it cannot reproduce the host path bit
 // for bit anyway (torch's vectorised CPU exp and its summation order are 1 ulp apart), so the HOST remains the authority: it replays every position
-// from the logged logits row with the reference code path and rolls the decoder back on the (rare) position where the device chose
-// differently (Engine.generate). The device result is a PREDICTION that lets the next token start without a host round trip.
+// from the logged logits row with the reference code path and rolls the row back on the (rare) position where the device chose
+// differently (Engine._decode_device_sampled). The device result is a PREDICTION that lets the next token start without a host round trip.
 // One workgroup of 512 threads: wave h = head h for the softmax and the scans; the rank counting of the heads with p < 1 uses one
-// thread per (head, class). fault_period > 0 (tests only) corrupts head 0's id at every fault_period-th position.
-struct SampleArgs {
-    const float* logits;                  // (vocab) f32 row of the position just decoded
-    const double* u;                      // (S, 8) uniform draws, device
-    const int* pos;                       // device: the position the row belongs to
-    int16_t* tok_dev;                     // (8) next decoder input
-    float* log_logits;                    // pinned host (S, vocab)
-    int16_t* log_tok;                     // pinned host (S, 8)
+// thread per (head, class). fault_period > 0 (tests only) corrupts head 0's id of row fault_row (the single row: row 0) at every
+// fault_period-th position. Row form: a special id (>= pad[h] for any head) marks the row done.
+struct SampleCommon {
+    const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
+    const double* u;                      // (B, S, 8) uniform draws, device
+    BState* st;                           // the positions the rows belong to
+    int16_t* tok_dev;                     // (B, 8) next decoder inputs
+    float* log_logits;                    // pinned host (B, S, vocab)
+    int16_t* log_tok;                     // pinned host (B, S, 8)
+};
+template <bool ROWS> struct SampleArgs;   // each form's member order is its kernarg layout
+template <> struct SampleArgs<false> : SampleCommon {
     int vocab, fault_period;
     int off[8], n[8];
+    float temp[8], p[8];
+    static constexpr int S = 0, fault_row = 0;
+};
+template <> struct SampleArgs<true> : SampleCommon {
+    int vocab, S, fault_row, fault_period;   // S: the rows' stride in u and the logs
+    int off[8], n[8], pad[8];             // pad: the first special id of each head
     float temp[8], p[8];
 };
 constexpr int SMP_W = 272;                // >= the largest head (262), multiple of 16
@@ -862,16 +956,21 @@ __device__ __forceinline__ float wave_scan_f(float v, int lane) {
     for (int o = 1; o < 64; o <<= 1) { const float u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
     return v;
 }
-__global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs a) {
+template <bool ROWS>
+__global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs<ROWS> a) {
     __shared__ __attribute__((aligned(16))) float pn[8][SMP_W];     // normalised probabilities, class order
     __shared__ float sp[8][SMP_W + 64];   // ... in descending order (heads with p < 1), zero tail
     __shared__ int si[8][SMP_W];          // class of each sorted entry
     __shared__ int htok[8];
+    const int b = ROWS ? (int)blockIdx.x : 0;
+    if (ROWS && a.st->done[b]) return;                           // block-uniform
     const int t = threadIdx.x, lane = t & 63, h = t >> 6;
-    const int pos = *a.pos;
+    const int pos = a.st->pos[b];
+    const float* logits = a.logits + (size_t)b * a.vocab;
+    float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
     const int n = a.n[h], off = a.off[h];
     const float T = a.temp[h];
-    const double u_draw = a.u[(size_t)pos * 8 + h];            // requested now: a load that depends on *pos would otherwise sit at the end of the chain
+    const double u_draw = a.u[((size_t)b * a.S + pos) * 8 + h];  // requested now: a load that depends on pos would otherwise sit at the end of the chain
     // softmax(logit / T) of head h (torch.softmax(logit / t, dim=-1), model.py:103-104), then probs /= (sum(probs) + 1e-5) (model.py:85).
     // The sums here are wave reductions, not numpy's left-to-right ones: a common divisor that differs in its last bit moves every
     // probability alike, so the order and (but for a 1e-7 neighbourhood of a threshold) the choice stay -- the host checks every position.
@@ -881,8 +980,8 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs a) {
     for (int k = 0; k < 5; ++k) {
         const int c = lane + 64 * k;
         const bool in = c < n;
-        const float lg = in ? a.logits[off + c] : 0.f;
-        if (in) a.log_logits[(size_t)pos * a.vocab + off + c] = lg;
+        const float lg = in ? logits[off + c] : 0.f;
+        if (in) ROWS ? log_logits[off + c] = lg : a.log_logits[(size_t)pos * a.vocab + off + c] = lg;
         y[k] = in ? lg / T : -INFINITY;
         mx = fmaxf(mx, y[k]);
     }
@@ -967,157 +1066,220 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs a) {
     __syncthreads();
     if (t < 8) {
         int id = htok[t];
-        if (a.fault_period > 0 && t == 0 && (pos % a.fault_period) == a.fault_period - 1) id = (id + 1) % a.n[0];
-        a.tok_dev[t] = (int16_t)id;
-        a.log_tok[(size_t)pos * 8 + t] = (int16_t)id;
+        if (a.fault_period > 0 && (!ROWS || b == a.fault_row) && t == 0 && (pos % a.fault_period) == a.fault_period - 1) id = (id + 1) % a.n[0];
+        a.tok_dev[b * 8 + t] = (int16_t)id;
+        a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)id;
+        if constexpr (ROWS) { if (id >= a.pad[t]) a.st->done[b] = 1; }    // the device stops the row here; the host confirms or rewinds it
     }
 }
 
-constexpr int SPEC_K = 8;                  // tokens per graph replay of the device-sampled decode
+constexpr int SPEC_K = 8;                  // steps per graph replay of the device-sampled decode
 constexpr int SPEC_EVENTS = 8;
+enum { G_STEP, G_ONE, G_RUN, N_GRAPHS };   // captured graphs: one host-sampled step; 1 and SPEC_K device-sampled steps
 
 struct Decoder {
-    pb_decode_plan plan;
+    pb_decode_batch bp;
+    int B = 0;
     hipStream_t stream = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    // device-sampled ("speculative") decode, pb_decoder_sampler_init .. pb_decoder_seek
-    bool sampler = false;
-    SampleArgs sa{};
+    BState* st = nullptr;                  // device
+    int16_t* tok_dev = nullptr;            // device (B, 8): the rows' current decoder inputs
+    int16_t* tok_host = nullptr;           // pinned (B, 8)
+    float* logits_host = nullptr;          // pinned (vocab): the host-sampled step's row
     double* u_dev = nullptr;
-    float* log_logits = nullptr;           // pinned (S, vocab)
-    int16_t* log_tok = nullptr;            // pinned (S, 8)
-    hipGraph_t graph1 = nullptr, graphK = nullptr;
-    hipGraphExec_t exec1 = nullptr, execK = nullptr;
+    float* log_logits = nullptr;           // pinned (B, S, vocab)
+    int16_t* log_tok = nullptr;            // pinned (B, S, 8)
+    SampleArgs<true> sa{};                 // the sampler constants (the single-row kernel takes its subset)
+    bool sampler = false;
+    hipGraph_t graph[N_GRAPHS] = {};
+    hipGraphExec_t exec[N_GRAPHS] = {};
+    hipEvent_t ev = nullptr;
     hipEvent_t evs[SPEC_EVENTS] = {};
     int next_ev = 0;
-    int* pos = nullptr;                    // device: position of the token being decoded
-    int16_t* tok_dev = nullptr;            // device copy of the current token (8 ids)
-    int16_t* tok_host = nullptr;           // pinned
-    float* logits_host = nullptr;          // pinned
-    hipEvent_t ev = nullptr;
-    int launches = 0, use_graph = 1, ck_cross = 0, nsplit_cross = 0;
-    int ns_self = PB_DECODE_MAX_SPLITS, ns_cross = PB_DECODE_MAX_SPLITS;    // workgroups per head of the two attention launches (records per head)
-    int steps = 0;                         // tokens decoded since the last reset: the device position must stay inside the caches (plan.S rows)
+    int launches = 0, use_graph = 1, ns_self = PB_DECODE_MAX_SPLITS, ns_cross = PB_DECODE_MAX_SPLITS;   // workgroups per head of the two attention launches
+    int ck_cross[BMAX] = {};
+    int steps = 0, limit = 0;              // B == 1: positions enqueued since the reset and their bound (the single-row kernels do not check)
     size_t lds_attn = 0;
 };
 
-template <int NC, int HD>
-static void dec_attn_go(const DecAttnArgs& a, bool self, int H, int nrec, size_t lds, hipStream_t st) {
-    if (self) hipLaunchKernelGGL((dec_attn_kernel<NC, HD, true>), dim3(H, nrec), dim3(768), lds, st, a);
-    else hipLaunchKernelGGL((dec_attn_kernel<NC, HD, false>), dim3(H, nrec), dim3(256), lds, st, a);
+template <int NC, int HD, bool ROWS>
+static void dec_attn_go(const DecAttnArgs<ROWS>& a, bool self, int H, int nrec, int B, size_t lds, hipStream_t st) {
+    if (self) hipLaunchKernelGGL((dec_attn_kernel<NC, HD, true, ROWS>), dim3(H, nrec, B), dim3(768), lds, st, a);
+    else hipLaunchKernelGGL((dec_attn_kernel<NC, HD, false, ROWS>), dim3(H, nrec, B), dim3(256), lds, st, a);
 }
-static int dec_attn_launch(const DecAttnArgs& a, bool self, int H, int hd, int nrec, size_t lds, hipStream_t st) {
+template <bool ROWS>
+static int dec_attn_launch(const DecAttnArgs<ROWS>& a, bool self, int H, int hd, int nrec, int B, size_t lds, hipStream_t st) {
     const int nc = a.d / 256;
-#define PB_DA(NC_) do { if (hd == 64) dec_attn_go<NC_, 64>(a, self, H, nrec, lds, st); else dec_attn_go<NC_, 128>(a, self, H, nrec, lds, st); } while (0)
+#define PB_DA(NC_) do { if (hd == 64) dec_attn_go<NC_, 64>(a, self, H, nrec, B, lds, st); else dec_attn_go<NC_, 128>(a, self, H, nrec, B, lds, st); } while (0)
     if (nc == 1) PB_DA(1); else if (nc == 2) PB_DA(2); else if (nc == 3) PB_DA(3); else PB_DA(4);
 #undef PB_DA
     PB_LAUNCH_CHECK();
     return 0;
 }
 
-// the launches of one token on `st` (captured once, or issued directly when capture is unavailable); returns their number in *count
-static int decoder_issue(Decoder* D, hipStream_t st, int* count) {
-    const pb_decode_plan* p = &D->plan;
-    const int d = p->d, H = p->H, hd = d / H, f = p->ffn, dt = p->dtype;
+// the launches of one step on D->stream (the single-row instances when ROWS is false, B == 1), the sampler last when `sample`;
+// D->launches = their number
+template <bool ROWS>
+static int step_issue(Decoder* D, bool sample) {
+    const pb_decode_plan* p = &D->bp.plan;
+    const int d = p->d, H = p->H, hd = d / H, f = p->ffn, B = D->B;
     const float scale = 1.0f / sqrtf((float)hd);
+    const long part_rs = (long)H * PB_DECODE_MAX_SPLITS * (hd + 4);
+    const LnIn none{nullptr, nullptr, nullptr, nullptr};
+    const MergeIn none_mg{nullptr, 0, 0, 0, 0};
+    hipStream_t st = D->stream;
     int n = 0;
     SegOff9 so;
     for (int k = 0; k < 9; ++k) so.off[k] = p->tab_off[k];
-    hipLaunchKernelGGL(dec_embed_kernel, dim3(1), dim3(256), 0, st, D->tok_dev, p->ptab, so, p->lin_b, p->pos, p->lne_w, p->lne_b, (bf16_t*)p->x, D->pos, d, 1e-5f);
+    hipLaunchKernelGGL(dec_embed_kernel<ROWS>, dim3(B), dim3(256), 0, st, D->tok_dev, p->ptab, so, p->lin_b,
+                       p->pos, p->lne_w, p->lne_b, (bf16_t*)p->x, D->st, d, 1e-5f);
     PB_LAUNCH_CHECK(); ++n;
     char* x = (char*)p->x; char* alt = (char*)p->y2;
     char* h = x;
-    LnIn ln{nullptr, nullptr, nullptr, nullptr};
-    const MergeIn mg_self{p->attn_part, D->ns_self, hd, hd + 4}, mg_cross{p->attn_part, D->ns_cross, hd, hd + 4};
+    LnIn ln = none;                                      // pending post-LN of the previous layer, applied by the next attention (or the heads)
+    const MergeIn mg_self{p->attn_part, D->ns_self, hd, hd + 4, part_rs}, mg_cross{p->attn_part, D->ns_cross, hd, hd + 4, part_rs};
+    DecAttnArgs<ROWS> a{};
+    a.d = d; a.scale = scale; a.eps = 1e-5f; a.part = p->attn_part; a.st = D->st; a.kv_ss = 2 * d;
+    if constexpr (ROWS) {
+        a.kv_rs = (long)p->S * 2 * d; a.mask_rs = p->S; a.part_rs = part_rs;
+        for (int b = 0; b < B; ++b) { a.s_enc_[b] = D->bp.s_enc[b]; a.ck_[b] = D->ck_cross[b]; }
+    }
     for (int l = 0; l < p->n_layers; ++l) {
         const pb_decode_layer& L = p->layers[l];
-        DecAttnArgs a{};
-        a.d = d; a.scale = scale; a.eps = 1e-5f; a.part = p->attn_part; a.pos = D->pos; a.kv_ss = 2 * d;
         // self-attention: LN2 of the layer below (or the embedding row), q|k|v of this token, keys 0 .. i
         a.x_in = (const bf16_t*)h; a.res = (const bf16_t*)ln.res; a.add = (const bf16_t*)p->a; a.gamma = ln.gamma; a.beta = ln.beta; a.ln_out = (bf16_t*)ln.out;
         a.Wq = (const bf16_t*)L.wqkv; a.bq = L.bqkv;
         a.Wk = a.Wq + (size_t)d * d; a.bk = L.bqkv + d; a.Wv = a.Wq + (size_t)2 * d * d; a.bv = L.bqkv + 2 * d;
-        a.kc = (bf16_t*)L.kv_self; a.vc = a.kc + d; a.key_mask = nullptr; a.nreg = D->ns_self - 1; a.ck_fixed = 0; a.Sk_fixed = 0;
-        if (dec_attn_launch(a, true, H, hd, D->ns_self, D->lds_attn, st)) return -1;
+        a.kc = (bf16_t*)L.kv_self; a.vc = a.kc + d; a.key_mask = nullptr; a.nreg = D->ns_self - 1;
+        if (dec_attn_launch(a, true, H, hd, D->ns_self, B, D->lds_attn, st)) return -1;
         ++n;
         if (ln.res) h = alt;
-        if (gemv_launch(L.wo, p->ctx, L.bo, p->a, nullptr, d, d, d, dt, 0, 0, st, LnIn{nullptr, nullptr, nullptr, nullptr}, mg_self)) return -1;
+        if (gemv_launch(L.wo, nullptr, L.bo, p->a, nullptr, d, d, d, PB_BF16, 0, 0, st, none, mg_self, D->st, B)) return -1;
         ++n;
         // cross-attention: LN1(h + a) -> y1, q_c, the cached encoder keys
-        DecAttnArgs c{};
-        c.d = d; c.scale = scale; c.eps = 1e-5f; c.part = p->attn_part; c.pos = D->pos; c.kv_ss = 2 * d;
-        c.x_in = nullptr; c.res = (const bf16_t*)h; c.add = (const bf16_t*)p->a; c.gamma = L.ln1_w; c.beta = L.ln1_b; c.ln_out = (bf16_t*)p->y1;
-        c.Wq = (const bf16_t*)L.wq_c; c.bq = L.bq_c;
-        c.kc = (bf16_t*)const_cast<void*>(L.kv_cross); c.vc = c.kc + d; c.key_mask = p->enc_mask; c.nreg = D->nsplit_cross; c.ck_fixed = D->ck_cross; c.Sk_fixed = p->S_enc;
-        if (dec_attn_launch(c, false, H, hd, D->ns_cross, D->lds_attn, st)) return -1;
+        a.x_in = nullptr; a.res = (const bf16_t*)h; a.add = (const bf16_t*)p->a; a.gamma = L.ln1_w; a.beta = L.ln1_b; a.ln_out = (bf16_t*)p->y1;
+        a.Wq = (const bf16_t*)L.wq_c; a.bq = L.bq_c; a.Wk = nullptr; a.bk = nullptr; a.Wv = nullptr; a.bv = nullptr;
+        a.kc = (bf16_t*)const_cast<void*>(L.kv_cross); a.vc = a.kc + d; a.key_mask = p->enc_mask; a.nreg = D->ns_cross;
+        if constexpr (!ROWS) { a.ck_fixed = D->ck_cross[0]; a.Sk_fixed = D->bp.s_enc[0]; }
+        if (dec_attn_launch(a, false, H, hd, D->ns_cross, B, D->lds_attn, st)) return -1;
         ++n;
-        if (gemv_launch(L.wo_c, p->ctx, L.bo_c, p->a, nullptr, d, d, d, dt, 0, 0, st, LnIn{nullptr, nullptr, nullptr, nullptr}, mg_cross)) return -1;
+        if (gemv_launch(L.wo_c, nullptr, L.bo_c, p->a, nullptr, d, d, d, PB_BF16, 0, 0, st, none, mg_cross, D->st, B)) return -1;
         ++n;
         // FFN: fc1 applies LNc(y1 + a) -> yc
-        if (gemv_launch(L.w1, p->a, L.b1, p->g, nullptr, f, f, d, dt, 0, 1, st, LnIn{p->y1, L.lnc_w, L.lnc_b, p->yc})) return -1;
+        if (gemv_launch(L.w1, p->a, L.b1, p->g, nullptr, f, f, d, PB_BF16, 0, 1, st, LnIn{p->y1, L.lnc_w, L.lnc_b, p->yc}, none_mg, D->st, B)) return -1;
         ++n;
-        if (gemv_launch(L.w2, p->g, L.b2, p->a, nullptr, d, d, f, dt, 0, 0, st)) return -1;
+        if (gemv_launch(L.w2, p->g, L.b2, p->a, nullptr, d, d, f, PB_BF16, 0, 0, st, none, none_mg, D->st, B)) return -1;
         ++n;
         ln = LnIn{p->yc, L.ln2_w, L.ln2_b, alt};
     }
-    if (gemv_launch(p->head_w, p->a, p->head_b, p->logits, nullptr, p->vocab, p->vocab, d, dt, 1, 0, st, ln)) return -1;
+    if (gemv_launch(p->head_w, p->a, p->head_b, p->logits, nullptr, p->vocab, p->vocab, d, PB_BF16, 1, 0, st, ln, none_mg, D->st, B)) return -1;
     ++n;
-    *count = n;
+    if (sample) {
+        if constexpr (ROWS) {
+            hipLaunchKernelGGL(dec_sample_kernel<true>, dim3(B), dim3(512), 0, st, D->sa);
+        } else {
+            SampleArgs<false> s1{};
+            static_cast<SampleCommon&>(s1) = D->sa;
+            s1.vocab = D->sa.vocab; s1.fault_period = D->sa.fault_period;
+            for (int k = 0; k < 8; ++k) { s1.off[k] = D->sa.off[k]; s1.n[k] = D->sa.n[k]; s1.temp[k] = D->sa.temp[k]; s1.p[k] = D->sa.p[k]; }
+            hipLaunchKernelGGL(dec_sample_kernel<false>, dim3(1), dim3(512), 0, st, s1);
+        }
+        PB_LAUNCH_CHECK(); ++n;
+    }
+    D->launches = n;
     return 0;
+}
+
+// ntok == 0: one host-sampled step (B == 1: tok_host goes up, the logits row comes down to logits_host); ntok > 0: ntok device-sampled steps
+static int issue(Decoder* D, int ntok) {
+    if (ntok == 0) PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16, hipMemcpyHostToDevice, D->stream));
+    for (int k = 0; k < (ntok ? ntok : 1); ++k)
+        if (D->B == 1 ? step_issue<false>(D, ntok > 0) : step_issue<true>(D, ntok > 0)) return -1;
+    if (ntok == 0)
+        PB_CHECK_HIP(hipMemcpyAsync(D->logits_host, D->bp.plan.logits, sizeof(float) * (size_t)D->bp.plan.vocab, hipMemcpyDeviceToHost, D->stream));
+    return 0;
+}
+
+// issue(D, ntok) captured as graph g (a single linear stream of kernels and copies: no parallel branches); false = capture unavailable
+static bool capture(Decoder* D, int g, int ntok) {
+    if (hipStreamSynchronize(D->stream) != hipSuccess || hipStreamBeginCapture(D->stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const int rc = issue(D, ntok);
+    const hipError_t e = hipStreamEndCapture(D->stream, &D->graph[g]);
+    if (rc || e != hipSuccess || !D->graph[g] || hipGraphInstantiate(&D->exec[g], D->graph[g], nullptr, nullptr, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (D->graph[g]) { (void)hipGraphDestroy(D->graph[g]); D->graph[g] = nullptr; }
+        D->exec[g] = nullptr;
+        return false;
+    }
+    return true;
+}
+
+static void drop_graphs(Decoder* D) {
+    for (int g = 0; g < N_GRAPHS; ++g) {
+        if (D->exec[g]) (void)hipGraphExecDestroy(D->exec[g]);
+        if (D->graph[g]) (void)hipGraphDestroy(D->graph[g]);
+        D->exec[g] = nullptr; D->graph[g] = nullptr;
+    }
 }
 
 }  // namespace
 
-extern "C" int pb_decoder_create(const pb_decode_plan* plan, void** out) {
-    PB_REQUIRE(plan && out, "pb_decoder_create: null argument");
+extern "C" int pb_batch_decoder_create(const pb_decode_batch* bp, void** out) {
+    PB_REQUIRE(bp && out, "pb_batch_decoder_create: null argument");
     *out = nullptr;
+    const pb_decode_plan* plan = &bp->plan;
     const int d = plan->d, H = plan->H, hd = H > 0 ? d / H : 0;
-    // shapes the fused kernels cover; anything else keeps pb_decode_step (return 1 = declined, not an error)
+    // the shapes the fused kernels cover (return 1 = declined, not an error: pb_decode_step or the per-prompt loop), 1 <= B <= 16, every
+    // row with a visible encoder extent
     if (plan->dtype != PB_BF16 || H <= 0 || d % H != 0 || (hd != 64 && hd != 128) || d % 256 != 0 || d > 1024 || !plan->attn_part ||
-        plan->n_layers <= 0 || plan->n_layers > PB_DECODE_MAX_LAYERS || plan->ffn % 8 != 0 || plan->ffn > 8192 || plan->S_enc <= 0) return 1;
+        plan->n_layers <= 0 || plan->n_layers > PB_DECODE_MAX_LAYERS || plan->ffn % 8 != 0 || plan->ffn > 8192 || plan->S <= 0 ||
+        bp->B < 1 || bp->B > BMAX) return 1;
+    for (int b = 0; b < bp->B; ++b)
+        if (bp->s_enc[b] <= 0 || bp->s_enc[b] > plan->S) return 1;
     Decoder* D = new Decoder();
-    D->plan = *plan;
+    D->bp = *bp;
+    D->B = bp->B;
     if (hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&D->ev, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&D->pos, 64) != hipSuccess || hipMalloc(&D->tok_dev, 64) != hipSuccess ||
-        hipHostMalloc(&D->tok_host, 64, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(&D->st, sizeof(BState)) != hipSuccess || hipMalloc(&D->tok_dev, 16 * BMAX) != hipSuccess ||
+        hipHostMalloc(&D->tok_host, 16 * BMAX, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&D->logits_host, sizeof(float) * (size_t)plan->vocab, hipHostMallocDefault) != hipSuccess) {
-        pb_set_error("pb_decoder_create: allocation failed: %s", hipGetErrorString(hipGetLastError()));
-        pb_decoder_destroy(D);
+        pb_set_error("pb_batch_decoder_create: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        pb_batch_decoder_destroy(D);
         return -1;
     }
-    // cross-attention: <= 16 splits of >= 64 keys over the visible encoder positions (fixed for the prompt)
     // Every (head, split) workgroup projects q of its head itself (hd rows of W_q: 98 KB at cfg 2), so the split count trades K / V rows
-    // per workgroup against re-reads of W_q: PB_DECODE_SPLITS_SELF / _CROSS (2 .. 16; developer A/B, profiles/r06_decode_splits_ab.txt)
+    // per workgroup against re-reads of W_q: PB_DECODE_SPLITS_SELF / _CROSS (2 .. 16; developer A/B, profiles/r06_decode_splits_ab.txt).
+    // Cross-attention: splits of >= 64 keys over each row's visible encoder positions (fixed for the prompt).
     auto env_splits = [](const char* name, int dflt) { const char* e = getenv(name); int v = e ? atoi(e) : dflt; return v < 2 ? 2 : (v > PB_DECODE_MAX_SPLITS ? PB_DECODE_MAX_SPLITS : v); };
     D->ns_self = env_splits("PB_DECODE_SPLITS_SELF", PB_DECODE_MAX_SPLITS);
     D->ns_cross = env_splits("PB_DECODE_SPLITS_CROSS", PB_DECODE_MAX_SPLITS);
-    int ck = (plan->S_enc + D->ns_cross - 1) / D->ns_cross;
-    ck = ck < 64 ? 64 : (ck + 15) & ~15;
-    D->ck_cross = ck; D->nsplit_cross = D->ns_cross;
+    int ck_max = 0;
+    for (int b = 0; b < D->B; ++b) {
+        int ck = (bp->s_enc[b] + D->ns_cross - 1) / D->ns_cross;
+        ck = ck < 64 ? 64 : (ck + 15) & ~15;
+        D->ck_cross[b] = ck;
+        ck_max = ck > ck_max ? ck : ck_max;
+    }
     int ck_self = (plan->S + D->ns_self - 2) / (D->ns_self - 1);
     ck_self = ck_self < 64 ? 64 : (ck_self + 15) & ~15;
-    D->lds_attn = sizeof(float) * (size_t)(5 * hd + (ck > ck_self ? ck : ck_self) + 16);
+    D->lds_attn = sizeof(float) * (size_t)(5 * hd + (ck_max > ck_self ? ck_max : ck_self) + 16);
     *out = D;
     return 0;
 }
 
-extern "C" int pb_decoder_destroy(void* dec) {
+extern "C" int pb_batch_decoder_destroy(void* dec) {
     Decoder* D = (Decoder*)dec;
     if (!D) return 0;
     if (D->stream) (void)hipStreamSynchronize(D->stream);
-    if (D->exec) (void)hipGraphExecDestroy(D->exec);
-    if (D->graph) (void)hipGraphDestroy(D->graph);
-    if (D->exec1) (void)hipGraphExecDestroy(D->exec1);
-    if (D->graph1) (void)hipGraphDestroy(D->graph1);
-    if (D->execK) (void)hipGraphExecDestroy(D->execK);
-    if (D->graphK) (void)hipGraphDestroy(D->graphK);
+    drop_graphs(D);
     for (int i = 0; i < SPEC_EVENTS; ++i) if (D->evs[i]) (void)hipEventDestroy(D->evs[i]);
     if (D->u_dev) (void)hipFree(D->u_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
     if (D->ev) (void)hipEventDestroy(D->ev);
-    if (D->pos) (void)hipFree(D->pos);
+    if (D->st) (void)hipFree(D->st);
     if (D->tok_dev) (void)hipFree(D->tok_dev);
     if (D->tok_host) (void)hipHostFree(D->tok_host);
     if (D->logits_host) (void)hipHostFree(D->logits_host);
@@ -1126,143 +1288,95 @@ extern "C" int pb_decoder_destroy(void* dec) {
     return 0;
 }
 
-// Start of a prompt: the decoder's stream waits for everything already enqueued on the caller's stream (encoder pass, cross K/V
-// projections), the position counter goes to -1. use_graph = 0 issues the launches of every token directly (A/B, debugging).
-extern "C" int pb_decoder_reset(void* dec, void* caller_stream, int32_t use_graph) {
+// Start of a prompt / batch: every row at position -1 and live (pos = -1: 0xff bytes, done = 0), ordered behind everything enqueued on the
+// caller's stream (encoder passes, cross K/V projections). use_graph = 0 issues the launches of every step directly (A/B, debugging).
+extern "C" int pb_batch_decoder_reset(void* dec, void* caller_stream, int32_t use_graph) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D, "pb_decoder_reset: null decoder");
+    PB_REQUIRE(D, "pb_batch_decoder_reset: null decoder");
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
-    PB_CHECK_HIP(hipMemsetAsync(D->pos, 0xff, 4, D->stream));           // -1
+    PB_CHECK_HIP(hipMemsetAsync(D->st->pos, 0xff, sizeof(int) * BMAX, D->stream));
+    PB_CHECK_HIP(hipMemsetAsync(D->st->done, 0, sizeof(int) * BMAX, D->stream));
     D->steps = 0;
     D->use_graph = use_graph;
-    if (use_graph && !D->exec) {
-        PB_CHECK_HIP(hipStreamSynchronize(D->stream));
-        int n = 0;
-        hipError_t e = hipStreamBeginCapture(D->stream, hipStreamCaptureModeRelaxed);
-        if (e == hipSuccess) {
-            int rc = 0;
-            if (hipMemcpyAsync(D->tok_dev, D->tok_host, 16, hipMemcpyHostToDevice, D->stream) != hipSuccess) rc = -1;
-            if (!rc) rc = decoder_issue(D, D->stream, &n);
-            if (!rc && hipMemcpyAsync(D->logits_host, D->plan.logits, sizeof(float) * (size_t)D->plan.vocab, hipMemcpyDeviceToHost, D->stream) != hipSuccess) rc = -1;
-            e = hipStreamEndCapture(D->stream, &D->graph);
-            if (rc || e != hipSuccess || !D->graph || hipGraphInstantiate(&D->exec, D->graph, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                if (D->graph) { (void)hipGraphDestroy(D->graph); D->graph = nullptr; }
-                D->exec = nullptr;
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-        if (!D->exec) D->use_graph = 0;                                  // capture unavailable: direct launches
-        else D->launches = n;
-    }
     return 0;
 }
 
-// One token: tok8 (the decoder input of this position, 8 ids) goes up, the (vocab) f32 logits row of the position comes back into
-// logits_out (host memory). Blocks until the row has landed.
-extern "C" int pb_decoder_step(void* dec, const int16_t* tok8, float* logits_out) {
+// One host-sampled step (B == 1): tok8 (the decoder input of this position, 8 ids) goes up, the (vocab) f32 logits row of the position
+// comes back into logits_out (host memory). Blocks until the row has landed.
+extern "C" int pb_batch_decoder_step(void* dec, const int16_t* tok8, float* logits_out) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && tok8 && logits_out, "pb_decoder_step: null argument");
-    PB_REQUIRE(D->steps < D->plan.S, "pb_decoder_step: position %d is outside the K/V caches and the position table (S = %d): call pb_decoder_reset for a new prompt",
-               D->steps, D->plan.S);
+    PB_REQUIRE(D && D->B == 1 && tok8 && logits_out, "pb_batch_decoder_step: null argument or B > 1");
+    PB_REQUIRE(D->steps < D->bp.plan.S, "pb_batch_decoder_step: position %d is outside the K/V caches and the position table (S = %d): call "
+               "pb_batch_decoder_reset for a new prompt", D->steps, D->bp.plan.S);
     ++D->steps;
     for (int k = 0; k < 8; ++k) D->tok_host[k] = tok8[k];
-    if (D->use_graph && D->exec) {
-        PB_CHECK_HIP(hipGraphLaunch(D->exec, D->stream));
-    } else {
-        PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16, hipMemcpyHostToDevice, D->stream));
-        int n = 0;
-        if (decoder_issue(D, D->stream, &n)) return -1;
-        D->launches = n;
-        PB_CHECK_HIP(hipMemcpyAsync(D->logits_host, D->plan.logits, sizeof(float) * (size_t)D->plan.vocab, hipMemcpyDeviceToHost, D->stream));
-    }
+    if (D->use_graph && !D->exec[G_STEP] && !capture(D, G_STEP, 0)) D->use_graph = 0;     // capture unavailable: direct launches
+    if (D->use_graph) PB_CHECK_HIP(hipGraphLaunch(D->exec[G_STEP], D->stream));
+    else if (issue(D, 0)) return -1;
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));
-    for (int k = 0; k < D->plan.vocab; ++k) logits_out[k] = D->logits_host[k];
+    for (int k = 0; k < D->bp.plan.vocab; ++k) logits_out[k] = D->logits_host[k];
     return 0;
 }
 
-// ---- device-sampled decode: the sampler's constants and the uniform draws of the whole prompt go up once; tokens are then enqueued in
-// runs (pb_decoder_launch: SPEC_K tokens = one graph replay) without waiting for the host; the host follows behind through the pinned
-// logs (pb_decoder_wait + pb_decoder_logs), and pb_decoder_seek rewinds after a position where it disagrees with the device's choice.
-extern "C" int pb_decoder_sampler_init(void* dec, const float* temps8, const float* p8, const int32_t* n8, const int32_t* off8,
-                                       const double* u, int64_t n_u, int32_t fault_period) {
+// ---- device-sampled decode: the sampler's constants and the uniform draws of the whole batch go up once; steps are then enqueued in
+// runs (pb_batch_decoder_launch: SPEC_K steps = one graph replay) without waiting for the host; the host follows behind through the pinned
+// logs (pb_batch_decoder_wait + pb_batch_decoder_logs), and pb_batch_decoder_seek rewinds a row after a position where it disagrees with
+// the device's choice.
+extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, const float* p8, const int32_t* n8, const int32_t* off8, const int32_t* pad8,
+                                             const double* u, int64_t n_u, int32_t limit, int32_t fault_row, int32_t fault_period) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && temps8 && p8 && n8 && off8 && u, "pb_decoder_sampler_init: null argument");
-    PB_REQUIRE(n_u >= (int64_t)D->plan.S * 8, "pb_decoder_sampler_init: %lld draws for %d positions x 8 heads", (long long)n_u, D->plan.S);
+    PB_REQUIRE(D && temps8 && p8 && n8 && off8 && pad8 && u, "pb_batch_decoder_sampler_init: null argument");
+    const size_t S = (size_t)D->bp.plan.S, B = (size_t)D->B, vocab = (size_t)D->bp.plan.vocab;
+    PB_REQUIRE(n_u >= (int64_t)(B * S * 8), "pb_batch_decoder_sampler_init: %lld draws for %d rows x %d positions x 8 heads", (long long)n_u, D->B, (int)S);
+    PB_REQUIRE(limit >= 0 && limit <= (int)S, "pb_batch_decoder_sampler_init: limit %d outside 0..%d", limit, (int)S);
     for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(n8[h] > 0 && n8[h] <= SMP_W && n8[h] <= 320 && off8[h] >= 0 && off8[h] + n8[h] <= D->plan.vocab && temps8[h] > 0.f,
-                   "pb_decoder_sampler_init: head %d (n %d, offset %d, temperature %g)", h, n8[h], off8[h], (double)temps8[h]);
-        D->sa.n[h] = n8[h]; D->sa.off[h] = off8[h]; D->sa.temp[h] = temps8[h]; D->sa.p[h] = p8[h];
+        PB_REQUIRE(n8[h] > 0 && n8[h] <= SMP_W && n8[h] <= 320 && off8[h] >= 0 && off8[h] + n8[h] <= (int)vocab && temps8[h] > 0.f,
+                   "pb_batch_decoder_sampler_init: head %d (n %d, offset %d, temperature %g)", h, n8[h], off8[h], (double)temps8[h]);
+        D->sa.n[h] = n8[h]; D->sa.off[h] = off8[h]; D->sa.temp[h] = temps8[h]; D->sa.p[h] = p8[h]; D->sa.pad[h] = pad8[h];
     }
     int sorted = 0;
     for (int h = 0; h < 8; ++h) if (p8[h] < 1.0f) sorted += n8[h];
-    PB_REQUIRE(sorted <= 512, "pb_decoder_sampler_init: %d classes under heads with p < 1 (one thread each, 512 threads)", sorted);
-    const size_t S = (size_t)D->plan.S;
+    PB_REQUIRE(sorted <= 512, "pb_batch_decoder_sampler_init: %d classes under heads with p < 1 (one thread each, 512 threads)", sorted);
     if (!D->u_dev) {
-        if (hipMalloc(&D->u_dev, sizeof(double) * S * 8) != hipSuccess ||
-            hipHostMalloc(&D->log_logits, sizeof(float) * S * (size_t)D->plan.vocab, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&D->log_tok, sizeof(int16_t) * S * 8, hipHostMallocDefault) != hipSuccess) {
-            pb_set_error("pb_decoder_sampler_init: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        if (hipMalloc(&D->u_dev, sizeof(double) * B * S * 8) != hipSuccess ||
+            hipHostMalloc(&D->log_logits, sizeof(float) * B * S * vocab, hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc(&D->log_tok, sizeof(int16_t) * B * S * 8, hipHostMallocDefault) != hipSuccess) {
+            pb_set_error("pb_batch_decoder_sampler_init: allocation failed: %s", hipGetErrorString(hipGetLastError()));
             return -1;
         }
         for (int i = 0; i < SPEC_EVENTS; ++i) PB_CHECK_HIP(hipEventCreateWithFlags(&D->evs[i], hipEventDisableTiming));
     }
-    PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * S * 8, hipMemcpyHostToDevice, D->stream));
+    PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->limit, limit, 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
-    D->sa.logits = D->plan.logits; D->sa.u = D->u_dev; D->sa.pos = D->pos; D->sa.tok_dev = D->tok_dev;
-    D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = D->plan.vocab; D->sa.fault_period = fault_period;
+    D->limit = limit;
+    D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
+    D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
+    D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
+    drop_graphs(D);                                                     // captured with the previous constants
     D->sampler = true;
     return 0;
 }
 
-static int spec_issue(Decoder* D, hipStream_t st, int ntok, int* count) {
-    int n = 0;
-    for (int k = 0; k < ntok; ++k) {
-        if (decoder_issue(D, st, &n)) return -1;
-        hipLaunchKernelGGL(dec_sample_kernel, dim3(1), dim3(512), 0, st, D->sa);
-        PB_LAUNCH_CHECK();
-    }
-    *count = n + 1;
-    return 0;
-}
-
-static bool spec_capture(Decoder* D, int ntok, hipGraph_t* g, hipGraphExec_t* x) {
-    int n = 0;
-    if (hipStreamBeginCapture(D->stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const int rc = spec_issue(D, D->stream, ntok, &n);
-    const hipError_t e = hipStreamEndCapture(D->stream, g);
-    if (rc || e != hipSuccess || !*g || hipGraphInstantiate(x, *g, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        if (*g) { (void)hipGraphDestroy(*g); *g = nullptr; }
-        *x = nullptr;
-        return false;
-    }
-    D->launches = n;
-    return true;
-}
-
-// Enqueue the next `ntok` tokens (decoder input of the first = tok_dev as the previous step's sampler, pb_decoder_seek or `first_tok8`
-// left it). Returns a ticket >= 0 for pb_decoder_wait, < 0 on error. first_tok8 (8 ids, may be NULL) is copied up in front of the run.
-extern "C" int pb_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok8) {
+// Enqueue `ntok` steps; first_tok ((B, 8) host ids, may be NULL) is copied up in front as the rows' decoder inputs. Row form: a row stops
+// by itself at the limit; B == 1: the steps must stay within it. Returns a ticket >= 0 for pb_batch_decoder_wait, < 0 on error.
+extern "C" int pb_batch_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && D->sampler, "pb_decoder_launch: pb_decoder_sampler_init first");
-    PB_REQUIRE(ntok > 0 && D->steps + ntok <= D->plan.S, "pb_decoder_launch: %d tokens from position %d leave the K/V caches (S = %d)", ntok, D->steps, D->plan.S);
-    if (first_tok8) {
+    PB_REQUIRE(D && D->sampler, "pb_batch_decoder_launch: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(ntok > 0, "pb_batch_decoder_launch: %d steps", ntok);
+    PB_REQUIRE(D->B > 1 || D->steps + ntok <= D->limit, "pb_batch_decoder_launch: %d steps from position %d pass the limit %d", ntok, D->steps, D->limit);
+    if (first_tok) {
         PB_CHECK_HIP(hipStreamSynchronize(D->stream));                 // tok_host is about to be rewritten: no copy of it may be in flight
-        for (int k = 0; k < 8; ++k) D->tok_host[k] = first_tok8[k];
-        PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16, hipMemcpyHostToDevice, D->stream));
+        for (int k = 0; k < 8 * D->B; ++k) D->tok_host[k] = first_tok[k];
+        PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16 * (size_t)D->B, hipMemcpyHostToDevice, D->stream));
     }
-    if (D->use_graph && !D->exec1) {
-        PB_CHECK_HIP(hipStreamSynchronize(D->stream));
-        if (!spec_capture(D, 1, &D->graph1, &D->exec1) || !spec_capture(D, SPEC_K, &D->graphK, &D->execK)) D->use_graph = 0;
-    }
+    if (D->use_graph && !D->exec[G_ONE] && (!capture(D, G_ONE, 1) || !capture(D, G_RUN, SPEC_K))) D->use_graph = 0;
     int left = ntok;
     while (left > 0) {
-        if (D->use_graph && left >= SPEC_K) { PB_CHECK_HIP(hipGraphLaunch(D->execK, D->stream)); left -= SPEC_K; }
-        else if (D->use_graph) { PB_CHECK_HIP(hipGraphLaunch(D->exec1, D->stream)); left -= 1; }
-        else { int n = 0; if (spec_issue(D, D->stream, 1, &n)) return -1; D->launches = n; left -= 1; }
+        if (D->use_graph && left >= SPEC_K) { PB_CHECK_HIP(hipGraphLaunch(D->exec[G_RUN], D->stream)); left -= SPEC_K; }
+        else if (D->use_graph) { PB_CHECK_HIP(hipGraphLaunch(D->exec[G_ONE], D->stream)); left -= 1; }
+        else { if (issue(D, 1)) return -1; left -= 1; }
     }
     D->steps += ntok;
     const int tk = D->next_ev;
@@ -1270,30 +1384,40 @@ extern "C" int pb_decoder_launch(void* dec, int32_t ntok, const int16_t* first_t
     PB_CHECK_HIP(hipEventRecord(D->evs[tk], D->stream));
     return tk;
 }
-extern "C" int pb_decoder_wait(void* dec, int32_t ticket) {
+extern "C" int pb_batch_decoder_wait(void* dec, int32_t ticket) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && D->sampler && ticket >= 0 && ticket < SPEC_EVENTS, "pb_decoder_wait: bad ticket %d", ticket);
+    PB_REQUIRE(D && D->sampler && ticket >= 0 && ticket < SPEC_EVENTS, "pb_batch_decoder_wait: bad ticket %d", ticket);
     PB_CHECK_HIP(hipEventSynchronize(D->evs[ticket]));
     return 0;
 }
-extern "C" int pb_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows) {
+extern "C" int pb_batch_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && D->sampler && logits_rows && tok_rows, "pb_decoder_logs: no sampler");
+    PB_REQUIRE(D && D->sampler && logits_rows && tok_rows, "pb_batch_decoder_logs: no sampler");
     *logits_rows = D->log_logits; *tok_rows = D->log_tok;
     return 0;
 }
-// Rewind: drain what is enqueued, make `pos` the last decoded position and tok8 the decoder input of position pos + 1.
-extern "C" int pb_decoder_seek(void* dec, int32_t pos, const int16_t* tok8) {
+// Rewind one row (tok8 != NULL): drain what is enqueued, then row's last decoded position = pos, its next input = tok8, live again. The
+// other rows keep their positions, inputs and flags. tok8 == NULL: the row is done from the next enqueued step on (no drain).
+extern "C" int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const int16_t* tok8) {
     Decoder* D = (Decoder*)dec;
-    PB_REQUIRE(D && tok8 && pos >= -1 && pos < D->plan.S, "pb_decoder_seek: position %d", pos);
+    PB_REQUIRE(D && row >= 0 && row < D->B, "pb_batch_decoder_seek: row %d", row);
+    if (!tok8) {
+        PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->done[row], 1, 1, D->stream));
+        return 0;
+    }
+    PB_REQUIRE(pos >= -1 && pos < D->bp.plan.S, "pb_batch_decoder_seek: position %d", pos);
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));
-    for (int k = 0; k < 8; ++k) D->tok_host[k] = tok8[k];
-    PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16, hipMemcpyHostToDevice, D->stream));
-    PB_CHECK_HIP(hipMemcpyAsync(D->pos, &pos, 4, hipMemcpyHostToDevice, D->stream));
+    for (int k = 0; k < 8; ++k) D->tok_host[row * 8 + k] = tok8[k];
+    PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev + row * 8, D->tok_host + row * 8, 16, hipMemcpyHostToDevice, D->stream));
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->pos[row], pos, 1, D->stream));
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->done[row], 0, 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));
     D->steps = pos + 1;
     return 0;
 }
 
-extern "C" int pb_decoder_launches(void* dec) { return dec ? ((Decoder*)dec)->launches : 0; }
-extern "C" int pb_decoder_graph(void* dec) { return dec ? (((Decoder*)dec)->use_graph && ((Decoder*)dec)->exec ? 1 : 0) : 0; }
+extern "C" int pb_batch_decoder_launches(void* dec) { return dec ? ((Decoder*)dec)->launches : 0; }
+extern "C" int pb_batch_decoder_graph(void* dec) {
+    const Decoder* D = (const Decoder*)dec;
+    return D && D->use_graph && (D->exec[G_STEP] || D->exec[G_RUN]) ? 1 : 0;
+}

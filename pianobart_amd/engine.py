@@ -32,7 +32,7 @@ _X3_ONEHOT = int(os.environ.get('PB_X3_ONEHOT', '1'))                        # b
 _DP_RESERVE_CUS = int(os.environ.get('PB_DP_RESERVE_CUS', '0'))                 # data parallel: 0 = backward GEMMs as ordinary grids (default: +0.45 ms at world 1, profiles/r06_dp_mode_ab.txt); n > 0 = persistent grids that leave n CUs to RCCL's kernels (+1.0 / +1.4 ms for 8 / 16)
 _SIDE_PRIORITY = int(os.environ.get('PB_SIDE_PRIORITY', '0'))                      # HIP priority of the second stream (1 = low, -1 = high; developer A/B)
 _X3_FLASH = int(os.environ.get('PB_X3_FLASH', '1'))                            # bf16x3: 1 = fused split-bf16 attention (pb_flash_*_x3), 0 = the unfused QK^T / softmax / PV chain of the exact-f32 path
-_DECODE_SPEC = int(os.environ.get('PB_DECODE_SPEC', '1'))                       # 1 = device-side sampling ahead of the host where the caller names the sampler (Engine._generate_device_sampled), 0 = one host round trip per token
+_DECODE_SPEC = int(os.environ.get('PB_DECODE_SPEC', '1'))                       # 1 = device-side sampling ahead of the host where the caller names the sampler (Engine._decode_device_sampled), 0 = one host round trip per token
 _DECODE_GRAPH = int(os.environ.get('PB_DECODE_GRAPH', '1'))                     # 1 = one hipGraph replay per token (6 launches per layer), 0 = the same launches issued directly, -1 = the round-2 per-launch loop (the persistent-kernel forms of round 4, measured slower, left the library in round 5: profiles/r04_decode_persistent.txt)
 _NO_FUSED_BIAS = False             # settled (round 2): True takes the bias gradients out of the GEMM / attention epilogues
 
@@ -1331,183 +1331,138 @@ class Engine:
         only depend on decoder inputs <= i (causal), so the tokens are identical (tests/test_model_gpu.py).
         max_new: stop after that many positions (None = the window). sampler = dict(T=[8 temperatures], P=[8 thresholds]): the caller
         states that `sample_row` IS model.py:68-107 with these constants, drawing np.random.random_sample(8) per position; the decoder may
-        then sample on the device ahead of the host (`_generate_device_sampled`) -- `sample_row` still decides every token."""
+        then sample on the device ahead of the host (`_decode_device_sampled`) -- `sample_row` still decides every token."""
         self._await_updates(2)
         if not use_cache:
             return self._generate_nocache(enc_ids, emask, sample_row)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
             return self._generate_pyloop(enc_ids, emask, sample_row)
         import ctypes
-        from ._lib import DecodePlan
-        pb, d, X = self.pb, self.d, self.xdt
+        pb = self.pb
         self.bind(enc_ids.device)
         S, dev = enc_ids.shape[1], enc_ids.device
-        pad = torch.from_numpy(pb.pad_word_np).to(dev)
         pad_cpu = torch.from_numpy(pb.pad_word_np)
-        result = pad.repeat(1, S, 1)
         em = emask.to(torch.float32).contiguous() if emask is not None else None
         enc16 = ops.ids_to_i16(enc_ids)
         self.note_ids(enc16); self.check_ids(collective=False)
-        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
         with torch.no_grad():
+            s_enc = self._key_extent(em, S)
+            bp, bufs = self._decode_plan(1, S, [s_enc], em, dev)
             _, enc_out = self.forward_hidden(enc16, None, em, None, False, 0)
-            wf, ff = self.wf, self.fd
-            kvc = [e(S, 2 * d) for _ in range(self.ND)]
             for l in range(self.ND):
-                self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, kvc[l], S, 2 * d, d)
-            kvs = [torch.zeros(S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)]
-            rows = {n: e(1, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}
-            rows['g'] = e(1, ff)
-            stat = torch.empty(8, dtype=torch.float32, device=dev)
-            logits = torch.empty(1, ops.VOCAB, dtype=torch.float32, device=dev)
-            tok16 = torch.tensor(pb.sos_word_np, dtype=torch.int16, device=dev)
-            plan = DecodePlan()
-            s_enc = S
-            if em is not None:                                               # keys behind the last visible encoder position are masked for every query: stop there
-                km = torch.empty(1, dtype=torch.int32, device=dev)
-                ops.key_extent(em, km)
-                s_enc = max(1, min(S, int(km.item())))
-            plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, s_enc, self.ND, ops.VOCAB
-            for k in range(9):
-                plan.tab_off[k] = ops.TAB_OFF[k]
-            P = lambda t: t.data_ptr()
-            plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(tok16), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
-            plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
-            for n, t in rows.items():
-                setattr(plan, n, P(t))
-            plan.stat, plan.logits, plan.head_w, plan.head_b = P(stat), P(logits), P(self.w['head.w']), P(wf['head.b'])
-            attn_part = torch.empty(self.H * 16 * (self.hd + 4), dtype=torch.float32, device=dev)      # PB_DECODE_MAX_SPLITS records per head
-            # the split records are merged in the out-projection GEMV's prologue, which holds K = d in one chunk per thread (256 threads x
-            # 16 bytes): wider models keep the one-workgroup-per-head attention
-            epv = 8 if self.code == PB_BF16 else 4
-            plan.attn_part = P(attn_part) if (_DECODE_SPLIT and d <= 256 * epv) else None
-            for l in range(self.ND):
-                pf, L = 'dec.%d.' % l, plan.layers[l]
-                L.wqkv, L.bqkv, L.wo, L.bo = P(self.w[pf + 'wqkv']), P(wf[pf + 'bqkv']), P(self.w[pf + 'wo']), P(wf[pf + 'bo'])
-                L.ln1_w, L.ln1_b = P(wf[pf + 'ln1.w']), P(wf[pf + 'ln1.b'])
-                L.wq_c, L.bq_c, L.wo_c, L.bo_c = P(self.w[pf + 'wq_c']), P(wf[pf + 'bq_c']), P(self.w[pf + 'wo_c']), P(wf[pf + 'bo_c'])
-                L.lnc_w, L.lnc_b = P(wf[pf + 'lnc.w']), P(wf[pf + 'lnc.b'])
-                L.w1, L.b1, L.w2, L.b2 = P(self.w[pf + 'w1']), P(wf[pf + 'b1']), P(self.w[pf + 'w2']), P(wf[pf + 'b2'])
-                L.ln2_w, L.ln2_b = P(wf[pf + 'ln2.w']), P(wf[pf + 'ln2.b'])
-                L.kv_self, L.kv_cross = P(kvs[l]), P(kvc[l])
-            pref = ctypes.byref(plan)
+                self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][0], S, 2 * self.d, self.d)
             stream = ops._stream()
-            res_cpu = pad_cpu.repeat(S, 1)
-            # One hipGraph replay per token where the fused decode kernels cover the shape (bf16, head_dim 64 / 128, d a multiple of
-            # 256 up to 1024): pb_decoder_* keeps the position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly,
-            # PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
-            dec = ctypes.c_void_p()
+            res_cpu = pad_cpu.repeat(1, S, 1)
+            # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
+            # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
             self.last_decode = None
-            rc_dec = int(LIB.query('pb_decoder_create', pref, ctypes.byref(dec))) if (_DECODE_GRAPH >= 0 and _DECODE_SPLIT) else 1
-            if rc_dec < 0:                                              # 1 = the fused kernels do not cover this shape (the loop below does); < 0 is an error
-                raise PBError('pb_decoder_create failed (%d): %s' % (rc_dec, LIB.load().pb_last_error().decode()))
-            if rc_dec == 0 and sampler is not None and _DECODE_SPEC:
+            dec = self._decoder_create(bp) if _DECODE_GRAPH >= 0 else None
+            if dec is not None:
                 try:
-                    LIB.call('pb_decoder_reset', dec, stream, _DECODE_GRAPH)
-                    torch.cuda.current_stream().synchronize()
-                    self._generate_device_sampled(dec, sample_row, sampler, S, s_enc, res_cpu, pad_cpu, max_new)
-                finally:
-                    LIB.call('pb_decoder_destroy', dec)
-                return res_cpu.to(dev).unsqueeze(0)
-            if rc_dec == 0:
-                try:
-                    LIB.call('pb_decoder_reset', dec, stream, _DECODE_GRAPH)
-                    tok_np = np.asarray(pb.sos_word_np, dtype=np.int16).copy()
-                    logit_cpu = torch.empty(ops.VOCAB, dtype=torch.float32)
-                    tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
-                    n = 0
+                    LIB.call('pb_batch_decoder_reset', dec, stream, _DECODE_GRAPH)
                     torch.cuda.current_stream().synchronize()           # the prompt's encoder pass: not part of the per-token time below
-                    t_loop = time.perf_counter()
-                    for i in range(S if max_new is None else min(S, max_new)):
-                        LIB.call('pb_decoder_step', dec, tok_p, log_p)
-                        n += 1
-                        tok = sample_row(logit_cpu)
-                        if (tok >= pad_cpu).any():
-                            break
-                        res_cpu[i] = tok
-                        tok_np[:] = tok.numpy()
-                    self.last_decode = dict(launches_per_token=int(LIB.query('pb_decoder_launches', dec)), graph=bool(LIB.query('pb_decoder_graph', dec)),
-                                            tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, s_enc=s_enc)
+                    if sampler is not None and _DECODE_SPEC:
+                        fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
+                        info = self._decode_device_sampled(dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
+                                                           res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True)
+                        info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0])
+                    else:
+                        info = self._decode_host_sampled(dec, S, sample_row, res_cpu, pad_cpu, max_new)
+                    self.last_decode = dict(info, s_enc=s_enc)
                 finally:
-                    LIB.call('pb_decoder_destroy', dec)
-                return res_cpu.to(dev).unsqueeze(0)
+                    LIB.call('pb_batch_decoder_destroy', dec)
+                return res_cpu.to(dev)
+            pref = ctypes.byref(bp.plan)
+            tok16 = bufs['tok16']
             tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
             logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
             for i in range(S):
                 LIB.call('pb_decode_step', pref, i, stream)
-                logit_pin.copy_(logits[0])                                  # D2H on the current stream, returns when the row has landed
+                logit_pin.copy_(bufs['logits'][0])                          # D2H on the current stream, returns when the row has landed
                 tok = sample_row(logit_pin)
                 if (tok >= pad_cpu).any():
                     break
-                res_cpu[i] = tok
+                res_cpu[0, i] = tok
                 tok_pin.copy_(tok)
                 tok16.copy_(tok_pin, non_blocking=True)                     # stream-ordered before the next step's kernels
-            result = res_cpu.to(dev).unsqueeze(0)
-        return result
+            return res_cpu.to(dev)
 
-    def _generate_device_sampled(self, dec, sample_row, sampler, S, s_enc, res_cpu, pad_cpu, max_new):
-        """The decode loop without a host round trip per token (round 6). The 8 uniform draws of a position do not depend on its logits
-        (np.random.choice inside nucleus(), model.py:97), so all S x 8 are drawn AHEAD from a copy of the global RNG state and uploaded;
-        the device then samples each position itself (pb_decoder_sampler_init: model.py:68-107 in pb_nucleus_rows' arithmetic order) and
-        runs on, 8 tokens per hipGraph replay, two runs in flight. The host follows one run behind: for every position it calls
-        `sample_row` on the logged logits row -- the reference code path, consuming the GLOBAL RNG exactly as the per-token loop did, so
-        np.random.get_state() ends where the reference's does -- and compares with the ids the device chose. They differ only where the
-        device's softmax rounding (1 ulp against torch's CPU softmax) crosses a threshold or a tie; then the decoder is rewound to that
-        position with the host's token and everything decoded behind it is discarded. The result is the host's, token for token."""
+    def _key_extent(self, em, S):
+        """Encoder positions a decoder query can see: keys behind the last visible one are masked for every query, so the decode stops there."""
+        if em is None:
+            return S
+        km = torch.empty(1, dtype=torch.int32, device=em.device)
+        ops.key_extent(em, km)
+        return max(1, min(S, int(km.item())))
+
+    def _decode_plan(self, B, S, s_enc, em, dev):
+        """The pb_decode_batch of B prompts (pb_decode_step reads its plan at B = 1) and the buffers it points into: per decoder layer the
+        (B, S, 2d) cross K|V cache (filled by the caller from each prompt's encoder pass) and self K|V cache, the (B, d) / (B, ffn)
+        scratch rows, (B, vocab) logits and the split records."""
+        from ._lib import DecodeBatch
+        d, X, ff, wf = self.d, self.xdt, self.fd, self.wf
+        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
+        bufs = dict(kvc=[e(B, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
+                    rows={n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}, g=e(B, ff), stat=e(8, dt=torch.float32),
+                    logits=e(B, ops.VOCAB, dt=torch.float32), tok16=torch.tensor(self.pb.sos_word_np, dtype=torch.int16, device=dev),
+                    attn_part=e(B * self.H * 16 * (self.hd + 4), dt=torch.float32))      # PB_DECODE_MAX_SPLITS records per (row, head)
+        bp = DecodeBatch()
+        plan = bp.plan
+        plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), self.ND, ops.VOCAB
+        for k in range(9):
+            plan.tab_off[k] = ops.TAB_OFF[k]
+        P = lambda t: t.data_ptr()
+        plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(bufs['tok16']), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
+        plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
+        for n, t in bufs['rows'].items():
+            setattr(plan, n, P(t))
+        plan.g, plan.stat, plan.logits, plan.head_w, plan.head_b = P(bufs['g']), P(bufs['stat']), P(bufs['logits']), P(self.w['head.w']), P(wf['head.b'])
+        # the split records are merged in the out-projection GEMV's prologue, which holds K = d in one chunk per thread (256 threads x
+        # 16 bytes): wider models keep the one-workgroup-per-head attention
+        epv = 8 if self.code == PB_BF16 else 4
+        plan.attn_part = P(bufs['attn_part']) if (_DECODE_SPLIT and d <= 256 * epv) else None
+        for l in range(self.ND):
+            pf, L = 'dec.%d.' % l, plan.layers[l]
+            L.wqkv, L.bqkv, L.wo, L.bo = P(self.w[pf + 'wqkv']), P(wf[pf + 'bqkv']), P(self.w[pf + 'wo']), P(wf[pf + 'bo'])
+            L.ln1_w, L.ln1_b = P(wf[pf + 'ln1.w']), P(wf[pf + 'ln1.b'])
+            L.wq_c, L.bq_c, L.wo_c, L.bo_c = P(self.w[pf + 'wq_c']), P(wf[pf + 'bq_c']), P(self.w[pf + 'wo_c']), P(wf[pf + 'bo_c'])
+            L.lnc_w, L.lnc_b = P(wf[pf + 'lnc.w']), P(wf[pf + 'lnc.b'])
+            L.w1, L.b1, L.w2, L.b2 = P(self.w[pf + 'w1']), P(wf[pf + 'b1']), P(self.w[pf + 'w2']), P(wf[pf + 'b2'])
+            L.ln2_w, L.ln2_b = P(wf[pf + 'ln2.w']), P(wf[pf + 'ln2.b'])
+            L.kv_self, L.kv_cross = P(bufs['kvs'][l]), P(bufs['kvc'][l])
+        bp.B = B
+        for b in range(B):
+            bp.s_enc[b] = s_enc[b]
+        return bp, bufs
+
+    @staticmethod
+    def _decoder_create(bp):
+        """The fused decoder of `bp`, or None where it does not cover the shape (pb_batch_decoder_create holds the one rule)."""
         import ctypes
-        from collections import deque
-        K, vocab = 8, ops.VOCAB
-        limit = S if max_new is None else max(0, min(S, int(max_new)))
-        state = np.random.get_state()
-        ahead = np.random.RandomState()
-        ahead.set_state(state)
-        U = np.ascontiguousarray(ahead.random_sample(S * 8))
-        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
-        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
-        t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
-        fault = int(getattr(self, 'decode_fault_period', 0) or 0)                # tests: the device's choice is corrupted at every fault-th position
-        LIB.call('pb_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, U.ctypes.data, S * 8, fault)
-        lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
-        LIB.call('pb_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
-        log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (S * vocab)).from_address(lp.value)).reshape(S, vocab))
-        log_tok = np.ctypeslib.as_array((ctypes.c_int16 * (S * 8)).from_address(tp.value)).reshape(S, 8)
-        first = np.asarray(self.pb.sos_word_np, dtype=np.int16).copy()
-        runs, enq, n, rewinds, stop = deque(), 0, 0, 0, False
+        dec = ctypes.c_void_p()
+        rc = int(LIB.query('pb_batch_decoder_create', ctypes.byref(bp), ctypes.byref(dec))) if _DECODE_SPLIT else 1
+        if rc < 0:
+            raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
+        return dec if rc == 0 else None
 
-        def launch(tok=None):
-            nonlocal enq
-            cnt = min(K, limit - enq)
-            tk = int(LIB.query('pb_decoder_launch', dec, cnt, None if tok is None else tok.ctypes.data))
-            if tk < 0:
-                raise PBError('pb_decoder_launch failed (%d): %s' % (tk, LIB.load().pb_last_error().decode()))
-            runs.append((tk, enq, cnt))
-            enq += cnt
-
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new):
+        """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between."""
+        import ctypes
+        tok_np = np.asarray(self.pb.sos_word_np, dtype=np.int16).copy()
+        logit_cpu = torch.empty(ops.VOCAB, dtype=torch.float32)
+        tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
+        n = 0
         t_loop = time.perf_counter()
-        if limit > 0:
-            launch(first)
-        while not stop and (runs or enq < limit):
-            while len(runs) < 2 and enq < limit:
-                launch()
-            tk, start, cnt = runs.popleft()
-            LIB.call('pb_decoder_wait', dec, tk)
-            for i in range(start, start + cnt):
-                tok = sample_row(log_logits[i])
-                n += 1
-                if (tok >= pad_cpu).any():
-                    stop = True
-                    break
-                res_cpu[i] = tok
-                t16 = tok.numpy().astype(np.int16)
-                if not np.array_equal(t16, log_tok[i]):                  # the device chose another id here: its later positions are void
-                    rewinds += 1
-                    LIB.call('pb_decoder_seek', dec, i, t16.ctypes.data)
-                    runs.clear()
-                    enq = i + 1
-                    break
-        self.last_decode = dict(launches_per_token=int(LIB.query('pb_decoder_launches', dec)), graph=bool(LIB.query('pb_decoder_graph', dec)),
-                                tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, s_enc=s_enc, device_sampler=True, rewinds=rewinds,
-                                tokens_per_graph_replay=K)
+        for i in range(S if max_new is None else min(S, max_new)):
+            LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
+            n += 1
+            tok = sample_row(logit_cpu)
+            if (tok >= pad_cpu).any():
+                break
+            res_cpu[0, i] = tok
+            tok_np[:] = tok.numpy()
+        return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
+                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3)
 
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
@@ -1537,8 +1492,8 @@ class Engine:
         return torch.cat(outs, 0)
 
     def _batch_decoder_covers(self, sampler):
-        return (sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0 and _DECODE_SPLIT and self.code == PB_BF16 and self.hd in (64, 128)
-                and self.d % 256 == 0 and self.d <= 1024 and self.fd % 8 == 0 and self.fd <= 8192)
+        """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
+        return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0 and _DECODE_SPLIT
 
     def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
@@ -1557,87 +1512,49 @@ class Engine:
         return torch.cat(outs, 0)
 
     def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
-        """<= BATCH_MAX prompts through one batched decoder. Encoder pass and cross K/V projections run per prompt, exactly as
-        `generate` runs them, into that row's slice of the (B, S, 2d) caches; then the device-ahead / host-behind loop of
-        `_generate_device_sampled` with per-row draws, per-row verification and per-row rewinds (pb_batch_decoder_seek touches one row)."""
-        import ctypes
-        from ._lib import DecodeBatch
-        pb, d, X, ND = self.pb, self.d, self.xdt, self.ND
-        self.bind(enc_ids.device)
+        """<= BATCH_MAX prompts through one fused decoder. Encoder pass and cross K/V projections run per prompt, exactly as `generate`
+        runs them, into that row's slice of the (B, S, 2d) caches; then the device-ahead / host-behind loop with per-row draws, per-row
+        verification and per-row rewinds (_decode_device_sampled)."""
         B, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
-        pad_cpu = torch.from_numpy(pb.pad_word_np)
+        self.bind(dev)
+        pad_cpu = torch.from_numpy(self.pb.pad_word_np)
         em = emask.to(torch.float32).contiguous() if emask is not None else None
         enc16 = ops.ids_to_i16(enc_ids)
         self.note_ids(enc16); self.check_ids(collective=False)
-        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
         with torch.no_grad():
-            wf, ff = self.wf, self.fd
-            kvc = [e(B, S, 2 * d) for _ in range(ND)]
-            s_enc = []
-            km = torch.empty(1, dtype=torch.int32, device=dev)
-            for b in range(B):                                             # the batch-1 encoder pass of each prompt, into its cache row
-                emb = em[b:b + 1] if em is not None else None
-                _, enc_out = self.forward_hidden(enc16[b:b + 1], None, emb, None, False, 0)
-                for l in range(ND):
-                    self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, kvc[l][b], S, 2 * d, d)
-                se = S
-                if emb is not None:
-                    ops.key_extent(emb, km)
-                    se = max(1, min(S, int(km.item())))
-                s_enc.append(se)
-            kvs = [torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(ND)]
-            rows = {n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}
-            rows['g'] = e(B, ff)
-            stat = torch.empty(8, dtype=torch.float32, device=dev)
-            logits = torch.empty(B, ops.VOCAB, dtype=torch.float32, device=dev)
-            tok16 = torch.tensor(pb.sos_word_np, dtype=torch.int16, device=dev)
-            attn_part = torch.empty(B * self.H * 16 * (self.hd + 4), dtype=torch.float32, device=dev)
-            bp = DecodeBatch()
-            plan = bp.plan
-            plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), ND, ops.VOCAB
-            for k in range(9):
-                plan.tab_off[k] = ops.TAB_OFF[k]
-            P = lambda t: t.data_ptr()
-            plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(tok16), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
-            plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
-            for n, t in rows.items():
-                setattr(plan, n, P(t))
-            plan.stat, plan.logits, plan.head_w, plan.head_b = P(stat), P(logits), P(self.w['head.w']), P(wf['head.b'])
-            plan.attn_part = P(attn_part)
-            for l in range(ND):
-                pf, L = 'dec.%d.' % l, plan.layers[l]
-                L.wqkv, L.bqkv, L.wo, L.bo = P(self.w[pf + 'wqkv']), P(wf[pf + 'bqkv']), P(self.w[pf + 'wo']), P(wf[pf + 'bo'])
-                L.ln1_w, L.ln1_b = P(wf[pf + 'ln1.w']), P(wf[pf + 'ln1.b'])
-                L.wq_c, L.bq_c, L.wo_c, L.bo_c = P(self.w[pf + 'wq_c']), P(wf[pf + 'bq_c']), P(self.w[pf + 'wo_c']), P(wf[pf + 'bo_c'])
-                L.lnc_w, L.lnc_b = P(wf[pf + 'lnc.w']), P(wf[pf + 'lnc.b'])
-                L.w1, L.b1, L.w2, L.b2 = P(self.w[pf + 'w1']), P(wf[pf + 'b1']), P(self.w[pf + 'w2']), P(wf[pf + 'b2'])
-                L.ln2_w, L.ln2_b = P(wf[pf + 'ln2.w']), P(wf[pf + 'ln2.b'])
-                L.kv_self, L.kv_cross = P(kvs[l]), P(kvc[l])
-            bp.B = B
-            for b in range(B):
-                bp.s_enc[b] = s_enc[b]
-            dec = ctypes.c_void_p()
-            rc = int(LIB.query('pb_batch_decoder_create', ctypes.byref(bp), ctypes.byref(dec)))
-            if rc < 0:
-                raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
-            if rc == 1:                                                    # not covered: the per-prompt loop
+            s_enc = [self._key_extent(em[b:b + 1] if em is not None else None, S) for b in range(B)]
+            bp, bufs = self._decode_plan(B, S, s_enc, em, dev)
+            dec = self._decoder_create(bp)
+            if dec is None:                                                # not covered: the per-prompt loop
                 return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler)
             res_cpu = pad_cpu.repeat(B, S, 1)
             try:
+                for b in range(B):                                         # the batch-1 encoder pass of each prompt, into its cache row
+                    _, enc_out = self.forward_hidden(enc16[b:b + 1], None, em[b:b + 1] if em is not None else None, None, False, 0)
+                    for l in range(self.ND):
+                        self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][b], S, 2 * self.d, self.d)
                 LIB.call('pb_batch_decoder_reset', dec, ops._stream(), _DECODE_GRAPH)
                 torch.cuda.current_stream().synchronize()
-                self._batch_device_sampled(dec, B, S, sample_row, rngs, sampler, res_cpu, pad_cpu, max_new)
+                fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
+                info = self._decode_device_sampled(dec, B, S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
+                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
-            self.last_decode['s_enc'] = s_enc
+            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B)
             return res_cpu.to(dev)
 
-    def _batch_device_sampled(self, dec, B, S, sample_row, rngs, sampler, res_cpu, pad_cpu, max_new):
-        """The loop of `_generate_device_sampled` over B rows. Draws: row b's (S, 8) uniforms from a COPY of rngs[b]. The device runs
-        ahead, K batched steps per graph replay, two runs in flight; the host follows one run behind and replays every row position
-        through `sample_row(logged row, rngs[b])` -- the reference code path, consuming rngs[b] as the batch-1 loop consumes the global
-        stream. A row whose device choice differs is rewound alone (pb_batch_decoder_seek drains, then moves that row only); a row whose
-        host token is special stops there (the device stops it from the next step on)."""
+    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify):
+        """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
+        logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
+        (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
+        itself (pb_batch_decoder_sampler_init: model.py:68-107 in pb_nucleus_rows' arithmetic order) and runs on, K steps per hipGraph
+        replay, two runs in flight. The host follows one run behind: for every row position it calls sample(b, logged row) -- the
+        reference code path, consuming that row's generator exactly as the per-token loop does, so its state ends where the reference's
+        does -- and compares with the ids the device chose. They differ only where the device's softmax rounding (1 ulp against torch's CPU
+        softmax) crosses a threshold or a tie; then that row alone is rewound to the position with the host's token (pb_batch_decoder_seek
+        drains, then moves that row only) and everything it decoded behind it is discarded. A row whose host token is special stops there.
+        The result is the host's, token for token. inline_verify: the rows are replayed in this thread (B = 1) instead of a small pool."""
+        import contextlib
         import ctypes
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
@@ -1646,15 +1563,14 @@ class Engine:
         U = np.empty((B, S * 8), dtype=np.float64)
         for b in range(B):
             ahead = np.random.RandomState()
-            ahead.set_state(rngs[b].get_state())
+            ahead.set_state(states[b])
             U[b] = ahead.random_sample(S * 8)
         n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
         off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
         pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
         t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
-        fault_row, fault_period = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
         LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
-                 U.ctypes.data, B * S * 8, limit, int(fault_row), int(fault_period))
+                 U.ctypes.data, B * S * 8, limit, int(fault[0]), int(fault[1]))
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
@@ -1683,7 +1599,7 @@ class Engine:
 
         def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(s, e):
-                tok = sample_row(log_logits[b, i], rngs[b])
+                tok = sample(b, log_logits[b, i])
                 tokens[b] += 1
                 if (tok >= pad_cpu).any():
                     return ('stop', i)
@@ -1695,7 +1611,7 @@ class Engine:
 
         pending = lambda: any(live[b] and nxt[b] < limit for b in range(B))
         t_loop = time.perf_counter()
-        with ThreadPoolExecutor(max_workers=min(B, 8)) as pool:
+        with (contextlib.nullcontext() if inline_verify else ThreadPoolExecutor(max_workers=min(B, 8))) as pool:
             if pending():
                 launch(first)
             while runs or pending():
@@ -1705,7 +1621,7 @@ class Engine:
                 LIB.call('pb_batch_decoder_wait', dec, tk)
                 t_h = time.perf_counter()
                 todo = [b for b in range(B) if live[b] and spans[b][1] > spans[b][0]]
-                outcome = dict(zip(todo, pool.map(lambda b: verify(b, *spans[b]), todo)))
+                outcome = dict(zip(todo, (pool.map if pool else map)(lambda b: verify(b, *spans[b]), todo)))
                 host_s += time.perf_counter() - t_h
                 for b in todo:
                     r = outcome[b]
@@ -1721,9 +1637,9 @@ class Engine:
                         nxt[b] = i + 1
                         for _, sp in runs:
                             sp[b][0] = sp[b][1] = i + 1
-        self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
-                                tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
-                                device_sampler=True, batched=True, batch=B, tokens_per_graph_replay=K)
+        return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
+                    tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
+                    device_sampler=True, tokens_per_graph_replay=K)
 
     def _generate_pyloop(self, enc_ids, emask, sample_row):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
