@@ -429,7 +429,12 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *   pb_batch_decoder_wait           block until that run's steps are decoded and logged.
  *   pb_batch_decoder_logs           pinned logs: (B, S, vocab) f32 logits rows, (B, S, 8) int16 device-sampled ids.
  *   pb_batch_decoder_seek           tok8 != NULL: drain, then row's last decoded position = pos, its next input = tok8, live again (the
- *                                   other rows are untouched); tok8 == NULL: the row is done from the next enqueued step on (no drain). */
+ *                                   other rows are untouched); tok8 == NULL: the row is done from the next enqueued step on (no drain).
+ *   pb_batch_decoder_start          primed generation, after reset (and sampler_init): row b's last decoded position = last_pos[b]
+ *                                   (-1 .. S - 1; its self-attention cache rows 0 .. last_pos[b] filled by the caller), its next input =
+ *                                   next_tok[b] ((B, 8) host ids), the position it stops before = limit[b] ((B) or NULL = the sampler's
+ *                                   limit, S without one); every row live. One upload for all rows; B == 1: the steps the host may
+ *                                   enqueue follow (last_pos[0] + 1 .. limit[0]). */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -446,6 +451,7 @@ int pb_batch_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok);
 int pb_batch_decoder_wait(void* dec, int32_t ticket);
 int pb_batch_decoder_logs(void* dec, float** logits_rows, int16_t** tok_rows);
 int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const int16_t* tok8);
+int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const int16_t* next_tok, const int32_t* limit);
 int pb_batch_decoder_launches(void* dec);
 int pb_batch_decoder_graph(void* dec);
 

@@ -49,7 +49,7 @@ constexpr int BMAX = PB_DECODE_BATCH_MAX;
 struct BState {
     int pos[BMAX];                         // last decoded position of each row (-1 at reset)
     int done[BMAX];                        // row form: 0 = live; 1 = special id sampled / stopped by the host; 2 = position limit reached
-    int limit;                             // row form: positions per row
+    int limit[BMAX];                       // row form: the row stops before this position (a primed row: its prefix + max_new)
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -887,7 +887,7 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, d4 = d >> 2;
     if (ROWS && st->done[b]) return;                             // block-uniform
     const int i = st->pos[b] + 1;
-    if (ROWS && i >= st->limit) {                                // the row's last position is decoded: it stops here (no row past limit - 1 <= S - 1)
+    if (ROWS && i >= st->limit[b]) {                             // the row's last position is decoded: it stops here (no row past limit - 1 <= S - 1)
         __syncthreads();                                         // every thread has read done[b] before it changes
         if (t == 0) st->done[b] = 2;
         return;
@@ -1348,7 +1348,7 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
         for (int i = 0; i < SPEC_EVENTS; ++i) PB_CHECK_HIP(hipEventCreateWithFlags(&D->evs[i], hipEventDisableTiming));
     }
     PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
-    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->limit, limit, 1, D->stream));
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->limit, limit, BMAX, D->stream));    // every row; pb_batch_decoder_start may set them one by one
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
     D->limit = limit;
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
@@ -1413,6 +1413,32 @@ extern "C" int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const 
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->done[row], 0, 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));
     D->steps = pos + 1;
+    return 0;
+}
+
+// Primed start (after reset, and after sampler_init where there is one): every row at its own last decoded position last_pos[b] (-1 = none,
+// up to S - 1: the prefix rows' K|V are in the self-attention cache), with next_tok[b] as its next decoder input and limit[b] (NULL: the
+// sampler's limit, S without a sampler) as the position it stops before. The whole row state goes up in one copy. B == 1: the host bound
+// of the single-row kernels follows (steps = last_pos[0] + 1, limit = limit[0]).
+extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const int16_t* next_tok, const int32_t* limit) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && last_pos && next_tok, "pb_batch_decoder_start: null argument");
+    const int S = D->bp.plan.S, B = D->B, dflt = D->sampler ? D->limit : S;
+    BState h{};
+    for (int b = 0; b < BMAX; ++b) { h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt; }
+    for (int b = 0; b < B; ++b) {
+        PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
+        PB_REQUIRE(!limit || (limit[b] >= 0 && limit[b] <= S), "pb_batch_decoder_start: row %d limit %d outside 0..%d", b, limit[b], S);
+        h.pos[b] = last_pos[b];
+        if (limit) h.limit[b] = limit[b];
+    }
+    PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // tok_host may still be read by an enqueued copy
+    for (int k = 0; k < 8 * B; ++k) D->tok_host[k] = next_tok[k];
+    PB_CHECK_HIP(hipMemcpyAsync(D->tok_dev, D->tok_host, 16 * (size_t)B, hipMemcpyHostToDevice, D->stream));
+    PB_CHECK_HIP(hipMemcpyAsync(D->st, &h, sizeof(BState), hipMemcpyHostToDevice, D->stream));
+    PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `h` lives on this stack
+    D->steps = h.pos[0] + 1;
+    D->limit = h.limit[0];
     return 0;
 }
 

@@ -23,10 +23,11 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16'):
+                 precision='bf16', prime=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
+        self.prime = prime                  # None, N or 'half': continue the piece from its first rows (eval_generation's --prime rule)
 
 
 def get_args(argv=None):
@@ -45,6 +46,8 @@ def get_args(argv=None):
     ap.add_argument('--cpu', action='store_true')
     ap.add_argument('--cuda_devices', type=int, nargs='+', default=[0], help='HIP device ids (one: generate is batch-1 sequential)')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
+    ap.add_argument('--prime', type=str, default=None, help='N or "half": keep the first k = min(N, L) (half: L // 2) rows of the piece and '
+                    'continue from there (eval_generation --prime)')
     return ap.parse_args(argv)
 
 
@@ -55,6 +58,8 @@ def demo(args=None):
         raise PBError('pianobart_amd has no CPU execution path: demo() needs an MI355X')
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
         raise PBError('generate is batch-1 sequential: give ONE device (the reference itself is single-device here, README.md:154)')
+    from .eval_generation import parse_prime, prime_inputs, prime_lengths
+    prime = parse_prime(getattr(args, 'prime', None))
     from .pretrain import _load_vocab
     print("Loading Dictionary")
     e2w, w2e = _load_vocab(args.dict_file)
@@ -73,10 +78,14 @@ def demo(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
-    octuple = octuple.long().to(device)
+    octuple, prefix = octuple.long(), None
+    if prime is not None:                    # the piece's first k rows primed, the encoder sees them only
+        ks = prime_lengths(octuple.numpy(), prime, pianobart.bar_pad_word, pianobart.pad_word_np)
+        octuple, prefix = prime_inputs(octuple, ks, pianobart.pad_word_np)
+    octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
-        y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num)
+        y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
     if Octuple2Midi(y, args.output):
         print(f"Saved to {args.output}")
     print(octuple.shape, y.shape)

@@ -80,6 +80,42 @@ def _r4(n):
     return (n + 3) // 4 * 4
 
 
+def check_prefix(prefix, prefix_len, B, S, pad):
+    """The argument rules of primed generation, on the host before any device work. prefix: (B, P, 8) Octuple ids (tensor on any device, or
+    array) whose rows 0 .. k_b - 1 prime prompt b; prefix_len: B lengths (None: P for every row). Every id of a prefix row must be an ordinary
+    event, 0 <= id < pad[head] -- the range check of a decoder input (note_ids), without the special ids a decoder input may otherwise hold.
+    Returns (k, rows): k = [k_b], rows = int64 CPU (B, max k_b, 8), or None when no row is primed. Raises PBError."""
+    if prefix is None:
+        if prefix_len is not None and any(int(v) for v in (prefix_len.tolist() if hasattr(prefix_len, 'tolist') else prefix_len)):
+            raise PBError('prefix_len given without a prefix')
+        return [0] * B, None
+    p = torch.as_tensor(prefix)
+    if p.dim() != 3 or int(p.shape[0]) != B or int(p.shape[2]) != 8:
+        raise PBError('prefix of shape %s: expected (%d, P, 8) for %d prompt(s)' % (tuple(p.shape), B, B))
+    if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
+        raise PBError('prefix ids must be integers (got %s)' % p.dtype)
+    P = int(p.shape[1])
+    if prefix_len is None:
+        k = [P] * B
+    else:
+        k = [int(v) for v in (prefix_len.tolist() if hasattr(prefix_len, 'tolist') else prefix_len)]
+        if len(k) != B:
+            raise PBError('prefix_len has %d entries for %d prompt(s)' % (len(k), B))
+    for b, kb in enumerate(k):
+        if not 0 <= kb <= min(S, P):
+            raise PBError('prefix_len[%d] = %d outside 0 .. %d (window S = %d, prefix rows P = %d)' % (b, kb, min(S, P), S, P))
+    if max(k, default=0) == 0:
+        return k, None
+    rows = p[:, :max(k)].detach().to('cpu', torch.int64)
+    lim = torch.as_tensor(np.asarray(pad), dtype=torch.int64)
+    for b, kb in enumerate(k):
+        bad = ((rows[b, :kb] < 0) | (rows[b, :kb] >= lim)).nonzero()
+        if len(bad):
+            i, h = int(bad[0, 0]), int(bad[0, 1])
+            raise PBError('prefix of prompt %d, row %d, head %d: id %d is not an ordinary event (0 <= id < %d)' % (b, i, h, int(rows[b, i, h]), int(lim[h])))
+    return k, rows
+
+
 class _Slot:
     __slots__ = ('off', 'shape', 'numel')
 
@@ -1323,7 +1359,7 @@ class Engine:
         self._await_updates(2)
 
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -1331,16 +1367,23 @@ class Engine:
         only depend on decoder inputs <= i (causal), so the tokens are identical (tests/test_model_gpu.py).
         max_new: stop after that many positions (None = the window). sampler = dict(T=[8 temperatures], P=[8 thresholds]): the caller
         states that `sample_row` IS model.py:68-107 with these constants, drawing np.random.random_sample(8) per position; the decoder may
-        then sample on the device ahead of the host (`_decode_device_sampled`) -- `sample_row` still decides every token."""
+        then sample on the device ahead of the host (`_decode_device_sampled`) -- `sample_row` still decides every token.
+        prefix (1, k, 8): primed generation -- the reference loop with decoder inputs 1 .. k and their mask set to the prefix, the loop
+        starting at position k and result[:, :k] = prefix. The forced positions draw nothing; max_new counts sampled positions
+        (the row stops at min(S, k + max_new)). The cache rows of the prefix come from one teacher-forced decoder pass (_prefill)."""
+        S = int(enc_ids.shape[1])
+        ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
+        k = ks[0]
+        pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre)
         import ctypes
         pb = self.pb
         self.bind(enc_ids.device)
-        S, dev = enc_ids.shape[1], enc_ids.device
+        dev = enc_ids.device
         pad_cpu = torch.from_numpy(pb.pad_word_np)
         em = emask.to(torch.float32).contiguous() if emask is not None else None
         enc16 = ops.ids_to_i16(enc_ids)
@@ -1351,8 +1394,11 @@ class Engine:
             _, enc_out = self.forward_hidden(enc16, None, em, None, False, 0)
             for l in range(self.ND):
                 self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][0], S, 2 * self.d, self.d)
+            timer = self._prefill(enc16, em, pre, k, [t[0] for t in bufs['kvs']])
             stream = ops._stream()
             res_cpu = pad_cpu.repeat(1, S, 1)
+            if k:
+                res_cpu[0, :k] = pre
             # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
             # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
             self.last_decode = None
@@ -1364,19 +1410,21 @@ class Engine:
                     if sampler is not None and _DECODE_SPEC:
                         fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                         info = self._decode_device_sampled(dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
-                                                           res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True)
+                                                           res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k])
                         info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0])
                     else:
-                        info = self._decode_host_sampled(dec, S, sample_row, res_cpu, pad_cpu, max_new)
-                    self.last_decode = dict(info, s_enc=s_enc)
+                        info = self._decode_host_sampled(dec, S, sample_row, res_cpu, pad_cpu, max_new, k)
+                    self.last_decode = dict(info, s_enc=s_enc, prefix=k, prefill_ms=timer())
                 finally:
                     LIB.call('pb_batch_decoder_destroy', dec)
                 return res_cpu.to(dev)
             pref = ctypes.byref(bp.plan)
             tok16 = bufs['tok16']
+            if k:
+                tok16.copy_(pre[k - 1].to(torch.int16))                     # the input of position k: the prefix's last row
             tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
             logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
-            for i in range(S):
+            for i in range(k, S):
                 LIB.call('pb_decode_step', pref, i, stream)
                 logit_pin.copy_(bufs['logits'][0])                          # D2H on the current stream, returns when the row has landed
                 tok = sample_row(logit_pin)
@@ -1386,6 +1434,33 @@ class Engine:
                 tok_pin.copy_(tok)
                 tok16.copy_(tok_pin, non_blocking=True)                     # stream-ordered before the next step's kernels
             return res_cpu.to(dev)
+
+    def _prefill(self, enc16, em, pre, k, kvs):
+        """Primed generation: rows 0 .. k-1 of the self-attention caches kvs[l] ((S, 2d) each, row j = K | V of decoder position j, the layout
+        pb_decode_step and the fused decoder's new-token workgroup write) get the K|V of the decoder inputs SOS, pre[0] .. pre[k-2]. ONE
+        teacher-forced decoder pass over them on the training kernels, against the encoder pass just run (reuse_encoder), then a row gather
+        (pb_gather_rows16: 16-byte copies, no arithmetic) out of each layer's q|k|v workspace: in d-wide blocks, cache blocks 2j, 2j + 1 <-
+        workspace blocks 3j + 1, 3j + 2. Per prompt, like the encoder pass, so that a row of generate_batch stays the batch-1 generate of its
+        prompt bit for bit. No-op unless 0 < k < S (k = S samples nothing). Returns a callable giving the pass's device milliseconds."""
+        if not 0 < k < int(enc16.shape[1]):
+            return lambda: 0.0
+        S, dev = int(enc16.shape[1]), enc16.device
+        dec = torch.from_numpy(self.pb.pad_word_np).repeat(1, S, 1)
+        dec[0, 0] = torch.from_numpy(self.pb.sos_word_np)
+        dec[0, 1:k] = pre[:k - 1]
+        dmask = torch.zeros(1, S, dtype=torch.float32)
+        dmask[0, :k] = 1
+        dec16, dmask = ops.ids_to_i16(dec.to(dev)), dmask.to(dev)
+        rows = torch.arange(k, dtype=torch.int32)
+        idx = torch.stack([3 * rows + 1, 3 * rows + 2], 1).reshape(-1).to(dev)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=True)
+        esz = 2 if self.xdt == torch.bfloat16 else 4
+        for l in range(self.ND):
+            ops.gather_rows16(self._cur_ws['dec'][l]['qkv'], idx, kvs[l], 2 * k, self.d * esz)
+        t1.record()
+        return lambda: t0.elapsed_time(t1)
 
     def _key_extent(self, em, S):
         """Encoder positions a decoder query can see: keys behind the last visible one are masked for every query, so the decode stops there."""
@@ -1445,15 +1520,19 @@ class Engine:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new):
-        """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between."""
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0):
+        """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
+        k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds."""
         import ctypes
-        tok_np = np.asarray(self.pb.sos_word_np, dtype=np.int16).copy()
+        tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
+        if k:
+            last = np.asarray([k - 1], dtype=np.int32)
+            LIB.call('pb_batch_decoder_start', dec, last.ctypes.data, tok_np.ctypes.data, None)
         logit_cpu = torch.empty(ops.VOCAB, dtype=torch.float32)
         tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
         n = 0
         t_loop = time.perf_counter()
-        for i in range(S if max_new is None else min(S, max_new)):
+        for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
             tok = sample_row(logit_cpu)
@@ -1467,7 +1546,7 @@ class Engine:
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
-    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None):
+    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -1475,43 +1554,47 @@ class Engine:
         emask (B, S) or None; returns (B, S, 8) with PAD after each prompt's stop.
         Where the fused decode kernels cover the shape (bf16, head_dim 64 / 128, d a multiple of 256 up to 1024) and `sampler` names
         the constants, up to BATCH_MAX prompts share one batched device-sampled decoder (pb_batch_decoder_*); every other case runs
-        the per-prompt loop over `generate` (_generate_batch_loop)."""
+        the per-prompt loop over `generate` (_generate_batch_loop).
+        prefix (B, P, 8) with prefix_len (B lengths, None = P each): row b is primed with prefix[b, :prefix_len[b]] as in `generate`; rows with
+        length 0 are today's unprimed rows, so one batch may mix both (check_prefix holds the argument rules)."""
         B = int(enc_ids.shape[0])
+        ks, rows = check_prefix(prefix, prefix_len, B, int(enc_ids.shape[1]), self.pb.pad_word_np)
         if len(rngs) != B:
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
         self._await_updates(2)
         if B == 0:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
-            return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler)
+            return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows)
         outs = []
         for c0 in range(0, B, self.BATCH_MAX):
             c1 = min(B, c0 + self.BATCH_MAX)
             outs.append(self._generate_batch_chunk(enc_ids[c0:c1], emask[c0:c1] if emask is not None else None, sample_row, rngs[c0:c1],
-                                                   max_new, sampler))
+                                                   max_new, sampler, ks[c0:c1], rows[c0:c1] if rows is not None else None))
         return torch.cat(outs, 0)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0 and _DECODE_SPLIT
 
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
-        caller's global state is restored afterwards."""
+        caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed)."""
         saved = np.random.get_state()
         outs = []
         try:
             for b in range(int(enc_ids.shape[0])):
                 np.random.set_state(rngs[b].get_state())
+                pre = rows[b:b + 1, :ks[b]] if rows is not None and ks[b] else None
                 outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
-                                          max_new=max_new, sampler=sampler))
+                                          max_new=max_new, sampler=sampler, prefix=pre))
                 rngs[b].set_state(np.random.get_state())
         finally:
             np.random.set_state(saved)
         self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler):
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows):
         """<= BATCH_MAX prompts through one fused decoder. Encoder pass and cross K/V projections run per prompt, exactly as `generate`
         runs them, into that row's slice of the (B, S, 2d) caches; then the device-ahead / host-behind loop with per-row draws, per-row
         verification and per-row rewinds (_decode_device_sampled)."""
@@ -1526,24 +1609,29 @@ class Engine:
             bp, bufs = self._decode_plan(B, S, s_enc, em, dev)
             dec = self._decoder_create(bp)
             if dec is None:                                                # not covered: the per-prompt loop
-                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler)
+                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows)
             res_cpu = pad_cpu.repeat(B, S, 1)
+            timers = []
             try:
-                for b in range(B):                                         # the batch-1 encoder pass of each prompt, into its cache row
-                    _, enc_out = self.forward_hidden(enc16[b:b + 1], None, em[b:b + 1] if em is not None else None, None, False, 0)
+                for b in range(B):                                         # the batch-1 encoder pass (and prefill) of each prompt, into its cache rows
+                    emb = em[b:b + 1] if em is not None else None
+                    _, enc_out = self.forward_hidden(enc16[b:b + 1], None, emb, None, False, 0)
                     for l in range(self.ND):
                         self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][b], S, 2 * self.d, self.d)
+                    if ks[b]:
+                        res_cpu[b, :ks[b]] = rows[b, :ks[b]]
+                        timers.append(self._prefill(enc16[b:b + 1], emb, rows[b], ks[b], [t[b] for t in bufs['kvs']]))
                 LIB.call('pb_batch_decoder_reset', dec, ops._stream(), _DECODE_GRAPH)
                 torch.cuda.current_stream().synchronize()
                 fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
                 info = self._decode_device_sampled(dec, B, S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
-                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False)
+                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False, starts=list(ks))
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
-            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B)
+            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B, prefix=list(ks), prefill_ms=sum(t() for t in timers))
             return res_cpu.to(dev)
 
-    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify):
+    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -1553,18 +1641,23 @@ class Engine:
         does -- and compares with the ids the device chose. They differ only where the device's softmax rounding (1 ulp against torch's CPU
         softmax) crosses a threshold or a tie; then that row alone is rewound to the position with the host's token (pb_batch_decoder_seek
         drains, then moves that row only) and everything it decoded behind it is discarded. A row whose host token is special stops there.
-        The result is the host's, token for token. inline_verify: the rows are replayed in this thread (B = 1) instead of a small pool."""
+        The result is the host's, token for token. inline_verify: the rows are replayed in this thread (B = 1) instead of a small pool.
+        starts[b] = k_b (primed rows): row b's positions 0 .. k_b - 1 are its prefix (in res_cpu, their K|V in the cache), so it starts at
+        k_b with input res_cpu[b, k_b - 1], its draws start at position k_b and it stops before min(S, k_b + max_new)
+        (pb_batch_decoder_start: per-row positions, inputs and limits in one upload)."""
         import contextlib
         import ctypes
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         K, vocab = 8, ops.VOCAB
-        limit = S if max_new is None else max(0, min(S, int(max_new)))
-        U = np.empty((B, S * 8), dtype=np.float64)
+        starts = list(starts) if starts is not None else [0] * B
+        lim = [S if max_new is None else max(0, min(S, k + int(max_new))) for k in starts]
+        limit = max(lim)
+        U = np.zeros((B, S * 8), dtype=np.float64)
         for b in range(B):
             ahead = np.random.RandomState()
             ahead.set_state(states[b])
-            U[b] = ahead.random_sample(S * 8)
+            U[b, starts[b] * 8:] = ahead.random_sample((S - starts[b]) * 8)
         n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
         off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
         pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
@@ -1576,22 +1669,27 @@ class Engine:
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
         log_tok = np.ctypeslib.as_array((ctypes.c_int16 * (B * S * 8)).from_address(tp.value)).reshape(B, S, 8)
         first = np.ascontiguousarray(np.tile(np.asarray(self.pb.sos_word_np, dtype=np.int16), (B, 1)))
-        nxt = [0] * B                              # next position the enqueued work decodes, per row
-        live = [limit > 0] * B                     # the host has not stopped the row
+        for b in range(B):
+            if starts[b]:
+                first[b] = res_cpu[b, starts[b] - 1].numpy().astype(np.int16)
+        last_pos, lim32 = np.asarray([k - 1 for k in starts], dtype=np.int32), np.asarray(lim, dtype=np.int32)
+        LIB.call('pb_batch_decoder_start', dec, last_pos.ctypes.data, first.ctypes.data, lim32.ctypes.data)
+        nxt = list(starts)                         # next position the enqueued work decodes, per row
+        live = [lim[b] > starts[b] for b in range(B)]     # the host has not stopped the row
         tokens, rewinds = [0] * B, [0] * B
         runs = deque()
         steps, host_s = 0, 0.0
 
         def launch(tok=None):
             nonlocal steps
-            cnt = min(K, max(limit - nxt[b] for b in range(B) if live[b]))
+            cnt = min(K, max(lim[b] - nxt[b] for b in range(B) if live[b]))
             tk = int(LIB.query('pb_batch_decoder_launch', dec, cnt, None if tok is None else tok.ctypes.data))
             if tk < 0:
                 raise PBError('pb_batch_decoder_launch failed (%d): %s' % (tk, LIB.load().pb_last_error().decode()))
             spans = []
             for b in range(B):
                 s = nxt[b]
-                e = min(limit, s + cnt) if live[b] else s
+                e = min(lim[b], s + cnt) if live[b] else s
                 spans.append([s, e])
                 nxt[b] = e
             runs.append((tk, spans))
@@ -1609,11 +1707,9 @@ class Engine:
                     return ('seek', i, t16)
             return None
 
-        pending = lambda: any(live[b] and nxt[b] < limit for b in range(B))
+        pending = lambda: any(live[b] and nxt[b] < lim[b] for b in range(B))
         t_loop = time.perf_counter()
         with (contextlib.nullcontext() if inline_verify else ThreadPoolExecutor(max_workers=min(B, 8))) as pool:
-            if pending():
-                launch(first)
             while runs or pending():
                 while len(runs) < 2 and pending():
                     launch()
@@ -1641,9 +1737,10 @@ class Engine:
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
                     device_sampler=True, tokens_per_graph_replay=K)
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
-        kept as a cross-check of the native pb_decode_step path."""
+        kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
+        rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         self.bind(enc_ids.device)
         S, dev = enc_ids.shape[1], enc_ids.device
@@ -1690,6 +1787,10 @@ class Engine:
                     out = y2 if h is not y2 else x
                     ops.add_ln_fwd(yc, a, wf[pf + 'ln2.w'], wf[pf + 'ln2.b'], out, mr[6:7], mr[7:8], LN_EPS, 0, 0, 0.0)
                     h = out
+                if i < k:                                                  # a forced position: its token is the prefix row, no draw
+                    result[:, i, :] = pre[i].to(dev)
+                    cur = pre[i].to(dev).reshape(1, 1, 8)
+                    continue
                 ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
                 tok = sample_row(logits[0].cpu())
                 if (tok >= pad_cpu).any():
@@ -1698,9 +1799,9 @@ class Engine:
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
-        cross-check of the cached path)."""
+        cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k."""
         pb = self.pb
         self.bind(enc_ids.device)
         S = enc_ids.shape[1]
@@ -1711,14 +1812,19 @@ class Engine:
         dmask = torch.zeros(1, S, dtype=torch.float32, device=dev)
         dec[:, 0, :] = torch.tensor(pb.sos_word_np, device=dev)
         dmask[:, 0] = 1
+        if k:
+            n = min(k, S - 1)                                              # k = S: the last prefix row is no decoder input
+            dec[0, 1:n + 1] = pre[:n].to(dev)
+            dmask[0, :n + 1] = 1
+            result[0, :k] = pre.to(dev)
         pad_cpu = torch.from_numpy(pb.pad_word_np)
         em = emask.to(torch.float32).contiguous() if emask is not None else None
         enc16 = ops.ids_to_i16(enc_ids)
         self.note_ids(enc16); self.check_ids(collective=False)
         with torch.no_grad():
-            for i in range(S):
+            for i in range(k, S):
                 dec16 = ops.ids_to_i16(dec)
-                dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > 0))
+                dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
                 logits = self.heads_forward(dec_h)
                 cur = sample_row(logits[i].float().cpu())
                 if i != S - 1:

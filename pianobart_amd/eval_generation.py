@@ -44,11 +44,48 @@ def get_args(argv=None):
     ap.add_argument('--cuda_devices', type=int, nargs='+', default=[0], help='HIP device id (one)')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
     ap.add_argument('--seed', type=int, default=None, help='prompt i samples from RandomState(seed + i): the output is the same for every --batch_size')
+    ap.add_argument('--prime', type=str, default=None, help='N or "half": continue each piece from its first k = min(N, L) (half: L // 2) rows, '
+                    'L = rows whose bar id is not PAD (Ablation.py:134); the encoder sees rows < k only')
     return ap.parse_args(argv)
+
+
+def parse_prime(value):
+    """--prime -> None, 'half' or an int N >= 0; PBError otherwise."""
+    if value is None or value == 'half':
+        return value
+    try:
+        n = int(value)
+    except ValueError:
+        n = -1
+    if n < 0:
+        raise PBError('--prime takes a number of rows >= 0 or "half" (got %r)' % value)
+    return n
+
+
+def prime_lengths(x, prime, bar_pad, pad_word):
+    """The prime length of every prompt of x (B, S, 8): k_b = min(N, L_b), or L_b // 2 for 'half', with L_b = the rows whose bar id is not
+    PAD (Ablation.py:134), capped at the number of leading rows that are ordinary events (every id < PAD of its head: a prefix row may hold
+    no special id, e.g. the EOS row)."""
+    x = np.asarray(x)
+    L = (x[:, :, 0] != bar_pad).sum(1)
+    k = L // 2 if prime == 'half' else np.minimum(int(prime), L)
+    ordinary = ((x >= 0) & (x < np.asarray(pad_word))).all(-1)
+    lead = np.where(ordinary.all(1), x.shape[1], np.argmin(ordinary, axis=1))
+    return [int(v) for v in np.minimum(k, lead)]
+
+
+def prime_inputs(x, ks, pad_word):
+    """Ablation.py:138: the encoder input with rows >= k_b of prompt b set to PAD, and the (B, max k, 8) decoder prefix (the same rows)."""
+    enc = torch.as_tensor(np.asarray(x)).long().clone()
+    prefix = enc[:, :max(ks, default=0)].clone()
+    for b, k in enumerate(ks):
+        enc[b, k:] = torch.as_tensor(np.asarray(pad_word))
+    return enc, prefix
 
 
 def check_args(args):
     """The argument rules that need no device; raises PBError."""
+    parse_prime(getattr(args, 'prime', None))
     if args.batch_size < 1:
         raise PBError('--batch_size must be >= 1 (got %d)' % args.batch_size)
     if args.seed is None and args.batch_size > 1:
@@ -102,17 +139,24 @@ def eval_generation(args=None):
     print("Use GPU", device)
     model = model.to(device).eval()
     bar_pad = model.pianobart.bar_pad_word
+    prime = parse_prime(getattr(args, 'prime', None))
     output = np.zeros((N, args.max_seq_len, 8), dtype=np.float32)
     print("\nEval Start")
     with torch.no_grad():
         for c0 in range(0, N, args.batch_size):
             c1 = min(N, c0 + args.batch_size)
-            x = torch.as_tensor(np.asarray(data[c0:c1])).long().to(device)
+            x = torch.as_tensor(np.asarray(data[c0:c1])).long()
+            prefix = ks = None
+            if prime is not None:                     # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
+                ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
+                x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
+            x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
-                y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num)
+                y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
             else:
-                y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num)
+                y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
+                                         decoder_prefix=prefix, prefix_len=ks)
             output[c0:c1] = y.float().cpu().numpy()
     np.save(args.output, output)
     print("Saved", output.shape, "to", args.output)

@@ -344,24 +344,32 @@ class PianoBartLM(nn.Module):
         return self._engine
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
-                decoder_attention_mask=None, generate=False, device_num=-1):
+                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None):
+        """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
+        position k on (Engine.generate's `prefix`)."""
         eng = self._get_engine()
         if not generate:
+            if decoder_prefix is not None:
+                raise PBError('decoder_prefix primes generation: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             return [logits[..., ops.SEG_OFF[i]:ops.SEG_OFF[i + 1]] for i in range(8)]
         if input_ids_encoder.shape[0] != 1:
             print("ERROR")
             exit(-1)
-        out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P))
+        out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
+                           prefix=decoder_prefix)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
-    def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1):
+    def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
+                       decoder_prefix=None, prefix_len=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
-        np.random stream is not touched. Placed like forward(generate=True): CPU for device_num == -1, else cuda:device_num."""
+        np.random stream is not touched. Placed like forward(generate=True): CPU for device_num == -1, else cuda:device_num.
+        decoder_prefix (B, P, 8) + prefix_len (B lengths, None = P): prompt b is primed with its first prefix_len[b] rows, as
+        forward(generate=True, decoder_prefix=...) primes one prompt; length 0 = unprimed."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -372,7 +380,7 @@ class PianoBartLM(nn.Module):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
-                                 sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P))
+                                 sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     # model.py:68-78 -- temperatures / nucleus thresholds per head

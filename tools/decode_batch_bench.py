@@ -4,7 +4,7 @@ positions). Prints ONE JSON line: per B in --batches, aggregate tokens/s, ms per
 verification ms per step and an HBM-bytes estimate per step (decoder + LM-head weights once, plus each row's cross K/V over its visible
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
-    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16]
+    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K]
 """
 import argparse
 import json
@@ -26,6 +26,7 @@ def main(argv=None):
     ap.add_argument('--heads', type=int, default=12)
     ap.add_argument('--steps', type=int, default=256, help='generated positions per row')
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4, 8, 16])
+    ap.add_argument('--prime', type=int, default=0, help='also time primed generation: K decoder rows given per prompt, --steps sampled after them')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -85,9 +86,38 @@ def main(argv=None):
                            rewinds=sum(info['rewinds']), host_ms_per_step=info['host_ms'] / max(1, info['steps']), steps=info['steps'],
                            tokens=ntok, hbm_bytes_per_step=w_bytes + kv_bytes(B))
     best = max(res.values(), key=lambda r: r['tokens_per_s'])['tokens_per_s']
-    print(json.dumps({"metric": "batched generate tokens/s (KV-cached decode, %dL/%dd, S=%d, %d positions per row)" % (L, d, S, steps),
-                      "batch1_generate_tokens_per_s": b1, "batch1_info": b1_info, "by_batch": res,
-                      "speedup_best_vs_batch1": best / b1, "visible_encoder_rows": vis[:Bmax]}), flush=True)
+    out = {"metric": "batched generate tokens/s (KV-cached decode, %dL/%dd, S=%d, %d positions per row)" % (L, d, S, steps),
+           "batch1_generate_tokens_per_s": b1, "batch1_info": b1_info, "by_batch": res,
+           "speedup_best_vs_batch1": best / b1, "visible_encoder_rows": vis[:Bmax]}
+    if args.prime:
+        # primed generation: the first K rows of each prompt's own piece given to the decoder, the encoder sees those rows only
+        # (Ablation.py:132-139); --steps positions sampled after them. prefill_ms = the teacher-forced decoder pass that fills the
+        # self-attention caches, per prompt (device time)
+        K = min(args.prime, S - steps)
+        piece = synth_octuple_batch(Bmax, S + 1, seed=9, min_len=S + 1)[5][:, :K]
+        penc = enc.clone()
+        penc[:, :K] = piece.to(dev)
+        penc[:, K:] = torch.tensor(model.pianobart.pad_word_np, device=dev)
+        pmask = (penc[:, :, 0] != 256).float()
+        primed = {}
+        for B in sorted(set([1] + [b for b in args.batches if b in (1, 16)])):
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            eng.generate_batch(penc[:B], pmask[:B], model.sample_row, rngs, max_new=16, sampler=sampler, prefix=piece[:B])   # warm-up
+            torch.cuda.synchronize()
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            t0 = time.perf_counter()
+            eng.generate_batch(penc[:B], pmask[:B], model.sample_row, rngs, max_new=steps, sampler=sampler, prefix=piece[:B])
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            info = eng.last_decode
+            ntok = sum(info['tokens'])
+            primed[str(B)] = dict(prefill_ms_per_prompt=info['prefill_ms'] / B, continuation_tokens_per_s=ntok / (info['loop_ms'] * 1e-3),
+                                  tokens_per_s_incl_encoder_and_prefill=ntok / dt, wall_ms=dt * 1e3, loop_ms=info['loop_ms'], tokens=ntok,
+                                  rewinds=sum(info['rewinds']))
+            if str(B) in res:
+                primed[str(B)]['unprimed_loop_tokens_per_s'] = res[str(B)]['tokens'] / (res[str(B)]['loop_ms'] * 1e-3)
+        out['primed'] = dict(prefix_rows=K, by_batch=primed)
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == '__main__':
