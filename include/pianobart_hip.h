@@ -434,7 +434,20 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   (-1 .. S - 1; its self-attention cache rows 0 .. last_pos[b] filled by the caller), its next input =
  *                                   next_tok[b] ((B, 8) host ids), the position it stops before = limit[b] ((B) or NULL = the sampler's
  *                                   limit, S without one); every row live. One upload for all rows; B == 1: the steps the host may
- *                                   enqueue follow (last_pos[0] + 1 .. limit[0]). */
+ *                                   enqueue follow (last_pos[0] + 1 .. limit[0]).
+ * Samples of one prompt (several rows continuing the same piece) share its encoder pass and its cross K|V:
+ *   pb_batch_decoder_share_cross    after pb_batch_decoder_create, before the first reset or launch: layers[l].kv_cross is read as
+ *                                   (n_groups, S, 2d), 1 <= n_groups <= B, and row b attends to slice kv_row[b] ((B) host ints in
+ *                                   [0, n_groups), every slice named by at least one row). Rows of one slice are rows of ONE prompt: their
+ *                                   s_enc must be equal and so must their enc_mask rows (the grouped kernel reads a slice's mask through one
+ *                                   of its rows). Everything else stays per row: kv_self, enc_mask (B, S), scratch rows, split records,
+ *                                   positions, limits, done flags, draws. A bad map, or a call after a step was issued or captured, is
+ *                                   refused (< 0, pb_last_error) and changes nothing. Without the call kv_cross is (B, S, 2d) and row b
+ *                                   reads slice b. Where rows share a slice the cross-attention launch becomes its grouped form: one
+ *                                   workgroup per (head, key split, tile of <= 4 rows of a slice) loads the K / V chunks, W_q rows and b_q
+ *                                   once for the tile; each row's arithmetic, hence its logits, is bit for bit the per-row kernel's, and the
+ *                                   launches per step do not change. PB_DECODE_CROSS_GROUPED=0 keeps the per-row kernel reading through
+ *                                   kv_row, PB_DECODE_GROUP_TILE=2|4|8 sets the tile (developer A/B switches). */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -454,6 +467,7 @@ int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const int16_t* to
 int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const int16_t* next_tok, const int32_t* limit);
 int pb_batch_decoder_launches(void* dec);
 int pb_batch_decoder_graph(void* dec);
+int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const int32_t* kv_row);
 
 /* ---- fused attention of the "bf16x3" parity instantiation (round 6, ABI 8): f32 q / k / v / o, every product a split-bf16 triple on the
  * bf16 matrix cores (see PB_F32X3), softmax in f32 -- instead of the unfused QK^T -> softmax -> PV chain of the exact-f32 path

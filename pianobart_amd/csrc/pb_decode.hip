@@ -638,6 +638,7 @@ template <> struct DecAttnArgs<false> : DecAttnCommon {
     static constexpr long kv_rs = 0, mask_rs = 0, part_rs = 0;
     __device__ int s_enc(int) const { return Sk_fixed; }
     __device__ int ck(int) const { return ck_fixed; }
+    __device__ int kv_row(int) const { return 0; }
 };
 template <> struct DecAttnArgs<true> : DecAttnCommon {           // x_in, res, add, ln_out: (B, d) rows
     long kv_rs;                                                  // row b's cached rows at kc / vc + b kv_rs
@@ -647,8 +648,16 @@ template <> struct DecAttnArgs<true> : DecAttnCommon {           // x_in, res, a
     float scale, eps;
     float* part; long part_rs;                                   // row b's records at part + b part_rs
     int s_enc_[BMAX], ck_[BMAX];                                 // cross: keys and keys per split of each row
+    int kv_row_[BMAX];                                           // cross: row b attends to slice kv_row_[b] of kc / vc (pb_batch_decoder_share_cross;
+                                                                 // b itself without it); the self-attention cache is always the row's own
     __device__ int s_enc(int b) const { return s_enc_[b]; }
     __device__ int ck(int b) const { return ck_[b]; }
+    __device__ int kv_row(int b) const { return kv_row_[b]; }
+};
+// The grouped cross-attention form (dec_attn_group_kernel): the rows ordered by their cross K|V slice and cut into tiles of <= RT rows of
+// one slice; tile t = rows_[tile_first[t] .. + tile_n[t]).
+struct DecAttnGroupArgs : DecAttnArgs<true> {
+    int rows_[BMAX], tile_first[BMAX], tile_n[BMAX];
 };
 
 // Threads: 256; the self-attention form launches 768 so that the new token's workgroup projects q, k and v side by side (wave
@@ -671,8 +680,9 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
     const int Sk = SELF ? a.st->pos[b] : a.s_enc(b);
     const bool is_new = SELF && sp == a.nreg;
     if (SELF && wgrp > 0 && !is_new) return;                     // only the new token's workgroup uses the other two wave groups
-    bf16_t* const kc = a.kc + (long)b * a.kv_rs;
-    bf16_t* const vc = a.vc + (long)b * a.kv_rs;
+    const int kvb = SELF ? b : a.kv_row(b);                      // the slice of the cache this row reads (cross: may be shared with other rows)
+    bf16_t* const kc = a.kc + (long)kvb * a.kv_rs;
+    bf16_t* const vc = a.vc + (long)kvb * a.kv_rs;
     const float* const key_mask = a.key_mask ? a.key_mask + (long)b * a.mask_rs : nullptr;
     int ck = SELF ? 0 : a.ck(b);
     if (SELF) { ck = (Sk + a.nreg - 1) / a.nreg; ck = ck < 64 ? 64 : (ck + 15) & ~15; }
@@ -872,6 +882,275 @@ __global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAtt
     __syncthreads();
     if (t == 0) { rec[0] = mx; rec[1] = sum; }
     if (t < HD) rec[4 + t] = (red[t] + red[HD + t]) + (red[2 * HD + t] + red[3 * HD + t]);
+}
+
+// ---------------------------------------------------------------- grouped cross-attention: (head, key split, row tile) workgroups
+// Rows that share one slice of the cross K|V cache (samples of one prompt, pb_batch_decoder_share_cross) go through ONE workgroup per
+// (head, key split) in tiles of <= RT rows: the 16-byte K and V chunks of the split, the head's W_q rows and b_q are loaded once and
+// applied to every live row of the tile, where the per-row form streams them once per row. What a row computes is the per-row kernel's,
+// operation for operation: LN1 in a half-wave, the projection's fma chain over (chunk, element) and its half_sum, the same lane -> key
+// mapping, fma / shuffle order of the scores, block maximum, __expf and sum order, the P V chain and the wave / block reductions -- so each
+// row's {m, l, o[HD]} record, and with the unchanged out-projection merge its logits, are bit-identical to the per-row form's
+// (tests/test_samples_per_prompt_gpu.py). Per-row state between the phases: LN1 output as bf16 in LDS (it is rounded to bf16 anyway), q,
+// scores and reduction scratch in LDS per row; maxima, sums and the RT x 8 output accumulators in registers. RT is the row tile: the
+// accumulators, the PBATCH x NC weight fragments of the projection and the K / V chunks in flight bound it (RT = 8: 64 + 96 + 32 VGPRs at
+// NC = 3), and every row of a tile runs in series behind one workgroup's loads, so a small tile also keeps more workgroups in flight.
+// The rows of a tile have one prompt: equal s_enc, hence equal split geometry, and equal mask rows (read through the tile's first live row).
+// Done rows are skipped; a tile without a live row writes nothing. ln_out is written once per row (by the head-0, split-0 workgroup).
+template <int NC, int HD, int RT>
+__global__ __launch_bounds__(256) void dec_attn_group_kernel(const DecAttnGroupArgs a) {
+    constexpr int CPR = HD / 8, KPW = 64 / CPR, STEP = 4 * KPW, UR = 4, RPW = HD / 4, NP = RPW / 2;
+    constexpr int PBATCH = NC <= 3 ? (NP < 8 ? NP : 8) : 4;      // as the per-row cross form
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int d = a.d;
+    const int h = blockIdx.x, sp = blockIdx.y, nrec = gridDim.y, tile = blockIdx.z;
+    const int first = a.tile_first[tile], nrow = a.tile_n[tile];
+    int rowb[RT];
+    bool lv[RT];
+    int b0 = -1;                                                 // first live row: the tile's geometry, cache slice and mask
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        rowb[r] = r < nrow ? a.rows_[first + r] : 0;
+        lv[r] = r < nrow && !a.st->done[rowb[r]];                // block-uniform
+        if (lv[r] && b0 < 0) b0 = rowb[r];
+    }
+    if (b0 < 0) return;
+    const int Sk = a.s_enc(b0), ck = a.ck(b0), ckp = (ck + 3) & ~3;
+    float* qs = reinterpret_cast<float*>(smem);                  // [RT][HD] q of this head per row, bf16-rounded, times the softmax scale
+    float* red = qs + RT * HD;                                   // [RT][4 HD] reductions / per-wave partial outputs
+    bf16_t* xs = reinterpret_cast<bf16_t*>(red + RT * 4 * HD);   // [RT][d] LN1 output rows
+    float* sc = reinterpret_cast<float*>(xs + (size_t)RT * d);   // [RT][ckp] scores -> probabilities
+    const int t = threadIdx.x, lane = t & 63, l32 = lane & 31, half = lane >> 5, wave = t >> 6;
+    const bf16_t* const kc = a.kc + (long)a.kv_row(b0) * a.kv_rs;
+    const bf16_t* const vc = a.vc + (long)a.kv_row(b0) * a.kv_rs;
+    const float* const key_mask = a.key_mask ? a.key_mask + (long)b0 * a.mask_rs : nullptr;
+    const int j0 = sp * ck, j1 = min(Sk, j0 + ck);
+    const size_t rec_off = ((size_t)h * nrec + sp) * (HD + 4);
+    if (j0 >= Sk) {                                              // no key in this split: a record of weight zero per live row
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (!lv[r]) continue;
+            float* rec = a.part + (long)rowb[r] * a.part_rs + rec_off;
+            if (t == 0) { rec[0] = -INFINITY; rec[1] = 0.f; }
+            if (t < HD) rec[4 + t] = 0.f;
+        }
+        return;
+    }
+    const int sub = lane % CPR, grp = lane / CPR;
+    const int jfirst = j0 + wave * KPW;
+    uint4 kpre[UR], vpre[UR];                                    // the first block of the split, requested before anything else
+#pragma unroll
+    for (int r = 0; r < UR; ++r) {
+        const int j = jfirst + r * STEP + grp;
+        kpre[r] = uint4{0u, 0u, 0u, 0u}; vpre[r] = uint4{0u, 0u, 0u, 0u};
+        if (j < j1) {
+            kpre[r] = *reinterpret_cast<const uint4*>(kc + (long)j * a.kv_ss + h * HD + sub * 8);
+            vpre[r] = *reinterpret_cast<const uint4*>(vc + (long)j * a.kv_ss + h * HD + sub * 8);
+        }
+    }
+    // LN1 of the tile's rows: wave w takes rows w, w + 4, ..; both half-waves compute the row (as every half-wave of the per-row form does)
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r] || (r & 3) != wave) continue;                 // wave-uniform
+        const int b = rowb[r];
+        const bf16_t* resb = a.res + (long)b * d;
+        const bf16_t* addb = a.add + (long)b * d;
+        float xf[NC][8];
+        bf16x8 rr[NC], aa[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            rr[c] = *reinterpret_cast<const bf16x8*>(resb + (l32 + 32 * c) * 8);
+            aa[c] = *reinterpret_cast<const bf16x8*>(addb + (l32 + 32 * c) * 8);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { xf[c][j] = (float)rr[c][j] + (float)aa[c][j]; s += xf[c][j]; }
+        const float mean = half_sum(s) / (float)d;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float z = xf[c][j] - mean; q = fmaf(z, z, q); }
+        const float rstd = rsqrtf(half_sum(q) / (float)d + a.eps);
+        const bool store_ln = h == 0 && sp == 0 && half == 0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int e0 = (l32 + 32 * c) * 8;
+            const f32x4 g0 = *reinterpret_cast<const f32x4*>(a.gamma + e0), g1 = *reinterpret_cast<const f32x4*>(a.gamma + e0 + 4);
+            const f32x4 b0v = *reinterpret_cast<const f32x4*>(a.beta + e0), b1v = *reinterpret_cast<const f32x4*>(a.beta + e0 + 4);
+            bf16x8 xo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                xo[j] = (bf16_t)((xf[c][j] - mean) * rstd * (j < 4 ? g0[j & 3] : g1[j & 3]) + (j < 4 ? b0v[j & 3] : b1v[j & 3]));
+            if (half == 0) *reinterpret_cast<bf16x8*>(xs + (size_t)r * d + e0) = xo;
+            if (store_ln) *reinterpret_cast<bf16x8*>(a.ln_out + (long)b * d + e0) = xo;
+        }
+    }
+    __syncthreads();
+    // q_h of every live row: each pass batch of W_q rows is loaded once and applied to the rows in turn
+#pragma unroll 1
+    for (int pb = 0; pb < NP; pb += PBATCH) {
+        bf16x8 w[PBATCH][NC];
+        float bv[PBATCH];
+#pragma unroll
+        for (int p = 0; p < PBATCH; ++p) {
+            const int row = h * HD + wave * RPW + 2 * (pb + p) + half;
+            bv[p] = a.bq[row];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) w[p][c] = *reinterpret_cast<const bf16x8*>(a.Wq + (size_t)row * d + (l32 + 32 * c) * 8);
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (!lv[r]) continue;
+            float xf[NC][8];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const bf16x8 xv = *reinterpret_cast<const bf16x8*>(xs + (size_t)r * d + (l32 + 32 * c) * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xf[c][j] = (float)xv[j];
+            }
+#pragma unroll
+            for (int p = 0; p < PBATCH; ++p) {
+                float acc = 0.f;
+#pragma unroll
+                for (int c = 0; c < NC; ++c)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc = fmaf((float)w[p][c][j], xf[c][j], acc);
+                acc = half_sum(acc);
+                if (l32 == 0) qs[r * HD + wave * RPW + 2 * (pb + p) + half] = (float)(bf16_t)(acc + bv[p]) * a.scale;
+            }
+        }
+    }
+    __syncthreads();
+    // scores: every K chunk of the split is loaded once and meets the q of each live row
+    float mx[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) mx[r] = -INFINITY;
+    for (int jb = jfirst; jb < j1; jb += UR * STEP) {
+        uint4 kraw[UR];
+        bool vis[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int j = jb + u * STEP + grp;
+            kraw[u] = kpre[u];
+            if (jb != jfirst) {
+                kraw[u] = uint4{0u, 0u, 0u, 0u};
+                if (j < j1) kraw[u] = *reinterpret_cast<const uint4*>(kc + (long)j * a.kv_ss + h * HD + sub * 8);
+            }
+            vis[u] = j < j1 && (!key_mask || key_mask[j] != 0.f);
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (!lv[r]) continue;
+            float qv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) qv[e] = qs[r * HD + sub * 8 + e];
+#pragma unroll
+            for (int u = 0; u < UR; ++u) {
+                const int j = jb + u * STEP + grp;
+                float s = 0.f;
+                if (j < j1) {
+                    const bf16_t* kv = reinterpret_cast<const bf16_t*>(&kraw[u]);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s = fmaf((float)kv[e], qv[e], s);
+                }
+#pragma unroll
+                for (int o = 1; o < CPR; o <<= 1) s += __shfl_xor(s, o, 64);
+                if (j < j1) {
+                    const float sv = vis[u] ? s : -INFINITY;
+                    if (sub == 0) sc[r * ckp + j - j0] = sv;
+                    mx[r] = fmaxf(mx[r], sv);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r]) continue;
+        mx[r] = wave_max(mx[r]);
+        if (lane == 0) red[r * 4 * HD + wave] = mx[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r]) continue;
+        const float* rd = red + r * 4 * HD;
+        mx[r] = fmaxf(fmaxf(rd[0], rd[1]), fmaxf(rd[2], rd[3]));
+    }
+    __syncthreads();
+    float sum[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        sum[r] = 0.f;
+        if (!lv[r]) continue;
+        float sm = 0.f;
+        if (mx[r] != -INFINITY)
+            for (int j = t; j < j1 - j0; j += 256) { const float e = __expf(sc[r * ckp + j] - mx[r]); sc[r * ckp + j] = e; sm += e; }
+        sm = wave_sum(sm);
+        if (lane == 0) red[r * 4 * HD + wave] = sm;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r]) continue;
+        const float* rd = red + r * 4 * HD;
+        sum[r] = (rd[0] + rd[1]) + (rd[2] + rd[3]);
+    }
+    __syncthreads();
+    // o = sum_j p_j V[j]: every V chunk loaded once, one accumulator set per row
+    float acc[RT][8];
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[r][e] = 0.f;
+    for (int jb = jfirst; jb < j1; jb += UR * STEP) {
+        uint4 vraw[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int j = jb + u * STEP + grp;
+            vraw[u] = vpre[u];
+            if (jb != jfirst) {
+                vraw[u] = uint4{0u, 0u, 0u, 0u};
+                if (j < j1) vraw[u] = *reinterpret_cast<const uint4*>(vc + (long)j * a.kv_ss + h * HD + sub * 8);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (!lv[r] || mx[r] == -INFINITY) continue;
+#pragma unroll
+            for (int u = 0; u < UR; ++u) {
+                const int j = jb + u * STEP + grp;
+                if (j < j1) {
+                    const bf16_t* vv = reinterpret_cast<const bf16_t*>(&vraw[u]);
+                    const float pj = sc[r * ckp + j - j0];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[r][e] = fmaf(pj, (float)vv[e], acc[r][e]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r]) continue;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int o = CPR; o < 64; o <<= 1) acc[r][e] += __shfl_xor(acc[r][e], o, 64);
+        if (grp == 0)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[r * 4 * HD + wave * HD + sub * 8 + e] = acc[r][e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (!lv[r]) continue;
+        const float* rd = red + r * 4 * HD;
+        float* rec = a.part + (long)rowb[r] * a.part_rs + rec_off;
+        if (t == 0) { rec[0] = mx[r]; rec[1] = sum[r]; }
+        if (t < HD) rec[4 + t] = (rd[t] + rd[HD + t]) + (rd[2 * HD + t] + rd[3 * HD + t]);
+    }
 }
 
 // token embedding + learned position + LayerNorm of ONE decoder token per row at the position kept in device memory: i = ++pos[b]
@@ -1099,6 +1378,12 @@ struct Decoder {
     int ck_cross[BMAX] = {};
     int steps = 0, limit = 0;              // B == 1: positions enqueued since the reset and their bound (the single-row kernels do not check)
     size_t lds_attn = 0;
+    // pb_batch_decoder_share_cross: kv_cross is (n_groups, S, 2d) and row b reads slice kv_row[b] (0 groups: (B, S, 2d), row b its own)
+    int n_groups = 0, kv_row[BMAX] = {};
+    bool issued = false;                   // a step was issued or captured: the cross-cache layout is fixed
+    int group_rt = 0;                      // > 0: the grouped cross-attention kernel with this row tile; 0: the per-row kernel through kv_row
+    int n_tiles = 0, rows_by_group[BMAX] = {}, tile_first[BMAX] = {}, tile_n[BMAX] = {};
+    size_t lds_group = 0;                  // the grouped kernel's LDS: q, reduction, LN1 and score rows of a tile
 };
 
 template <int NC, int HD, bool ROWS>
@@ -1112,6 +1397,21 @@ static int dec_attn_launch(const DecAttnArgs<ROWS>& a, bool self, int H, int hd,
 #define PB_DA(NC_) do { if (hd == 64) dec_attn_go<NC_, 64>(a, self, H, nrec, B, lds, st); else dec_attn_go<NC_, 128>(a, self, H, nrec, B, lds, st); } while (0)
     if (nc == 1) PB_DA(1); else if (nc == 2) PB_DA(2); else if (nc == 3) PB_DA(3); else PB_DA(4);
 #undef PB_DA
+    PB_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int NC, int HD>
+static void dec_attn_group_go(const DecAttnGroupArgs& a, int rt, int H, int nrec, int ntile, size_t lds, hipStream_t st) {
+    if (rt == 2) hipLaunchKernelGGL((dec_attn_group_kernel<NC, HD, 2>), dim3(H, nrec, ntile), dim3(256), lds, st, a);
+    else if (rt == 4) hipLaunchKernelGGL((dec_attn_group_kernel<NC, HD, 4>), dim3(H, nrec, ntile), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((dec_attn_group_kernel<NC, HD, 8>), dim3(H, nrec, ntile), dim3(256), lds, st, a);
+}
+static int dec_attn_group_launch(const DecAttnGroupArgs& a, int rt, int H, int hd, int nrec, int ntile, size_t lds, hipStream_t st) {
+    const int nc = a.d / 256;
+#define PB_DG(NC_) do { if (hd == 64) dec_attn_group_go<NC_, 64>(a, rt, H, nrec, ntile, lds, st); else dec_attn_group_go<NC_, 128>(a, rt, H, nrec, ntile, lds, st); } while (0)
+    if (nc == 1) PB_DG(1); else if (nc == 2) PB_DG(2); else if (nc == 3) PB_DG(3); else PB_DG(4);
+#undef PB_DG
     PB_LAUNCH_CHECK();
     return 0;
 }
@@ -1141,8 +1441,9 @@ static int step_issue(Decoder* D, bool sample) {
     a.d = d; a.scale = scale; a.eps = 1e-5f; a.part = p->attn_part; a.st = D->st; a.kv_ss = 2 * d;
     if constexpr (ROWS) {
         a.kv_rs = (long)p->S * 2 * d; a.mask_rs = p->S; a.part_rs = part_rs;
-        for (int b = 0; b < B; ++b) { a.s_enc_[b] = D->bp.s_enc[b]; a.ck_[b] = D->ck_cross[b]; }
+        for (int b = 0; b < B; ++b) { a.s_enc_[b] = D->bp.s_enc[b]; a.ck_[b] = D->ck_cross[b]; a.kv_row_[b] = D->n_groups ? D->kv_row[b] : b; }
     }
+    D->issued = true;
     for (int l = 0; l < p->n_layers; ++l) {
         const pb_decode_layer& L = p->layers[l];
         // self-attention: LN2 of the layer below (or the embedding row), q|k|v of this token, keys 0 .. i
@@ -1160,7 +1461,18 @@ static int step_issue(Decoder* D, bool sample) {
         a.Wq = (const bf16_t*)L.wq_c; a.bq = L.bq_c; a.Wk = nullptr; a.bk = nullptr; a.Wv = nullptr; a.bv = nullptr;
         a.kc = (bf16_t*)const_cast<void*>(L.kv_cross); a.vc = a.kc + d; a.key_mask = p->enc_mask; a.nreg = D->ns_cross;
         if constexpr (!ROWS) { a.ck_fixed = D->ck_cross[0]; a.Sk_fixed = D->bp.s_enc[0]; }
-        if (dec_attn_launch(a, false, H, hd, D->ns_cross, B, D->lds_attn, st)) return -1;
+        bool grouped = false;
+        if constexpr (ROWS) {
+            if (D->group_rt > 0) {                        // rows of one cross K|V slice share a workgroup (same launch count)
+                DecAttnGroupArgs ga{};
+                static_cast<DecAttnArgs<true>&>(ga) = a;
+                for (int b = 0; b < B; ++b) ga.rows_[b] = D->rows_by_group[b];
+                for (int k = 0; k < D->n_tiles; ++k) { ga.tile_first[k] = D->tile_first[k]; ga.tile_n[k] = D->tile_n[k]; }
+                if (dec_attn_group_launch(ga, D->group_rt, H, hd, D->ns_cross, D->n_tiles, D->lds_group, st)) return -1;
+                grouped = true;
+            }
+        }
+        if (!grouped && dec_attn_launch(a, false, H, hd, D->ns_cross, B, D->lds_attn, st)) return -1;
         ++n;
         if (gemv_launch(L.wo_c, nullptr, L.bo_c, p->a, nullptr, d, d, d, PB_BF16, 0, 0, st, none, mg_cross, D->st, B)) return -1;
         ++n;
@@ -1285,6 +1597,52 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     if (D->logits_host) (void)hipHostFree(D->logits_host);
     if (D->stream) (void)hipStreamDestroy(D->stream);
     delete D;
+    return 0;
+}
+
+// Rows that share their prompt share its cross K|V (see the header). The map is validated whole before anything changes.
+extern "C" int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const int32_t* kv_row) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && kv_row, "pb_batch_decoder_share_cross: null argument");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_share_cross: a step was already issued; the cross-cache layout is fixed for this decoder");
+    const int B = D->B;
+    PB_REQUIRE(n_groups >= 1 && n_groups <= B, "pb_batch_decoder_share_cross: %d groups for %d rows", n_groups, B);
+    int count[BMAX] = {}, s_enc[BMAX] = {};
+    for (int b = 0; b < B; ++b) {
+        const int g = kv_row[b];
+        PB_REQUIRE(g >= 0 && g < n_groups, "pb_batch_decoder_share_cross: row %d names slice %d of %d", b, g, n_groups);
+        if (count[g]++ == 0) s_enc[g] = D->bp.s_enc[b];
+        PB_REQUIRE(D->bp.s_enc[b] == s_enc[g], "pb_batch_decoder_share_cross: rows of slice %d differ in s_enc (%d, %d): they are not one prompt",
+                   g, s_enc[g], D->bp.s_enc[b]);
+    }
+    for (int g = 0; g < n_groups; ++g) PB_REQUIRE(count[g] > 0, "pb_batch_decoder_share_cross: no row names slice %d", g);
+    D->n_groups = n_groups;
+    for (int b = 0; b < B; ++b) D->kv_row[b] = kv_row[b];
+    // The grouped kernel where rows really share a slice; PB_DECODE_CROSS_GROUPED=0 keeps the per-row kernel reading through kv_row (developer A/B
+    // and the fallback), PB_DECODE_GROUP_TILE = 2 / 4 / 8 rows per workgroup.
+    const char* eg = getenv("PB_DECODE_CROSS_GROUPED");
+    const char* et = getenv("PB_DECODE_GROUP_TILE");
+    int rt = et ? atoi(et) : 4;
+    rt = rt <= 2 ? 2 : (rt <= 4 ? 4 : 8);
+    D->group_rt = 0;
+    if (B > 1 && n_groups < B && !(eg && atoi(eg) == 0)) {
+        const int d = D->bp.plan.d, hd = d / D->bp.plan.H;
+        int ck_max = 0, nt = 0, at = 0;
+        for (int b = 0; b < B; ++b) ck_max = D->ck_cross[b] > ck_max ? D->ck_cross[b] : ck_max;
+        for (int g = 0; g < n_groups; ++g) {                 // rows in slice order, each slice cut into even tiles of <= rt rows
+            const int tiles = (count[g] + rt - 1) / rt;
+            int left = count[g], f = at;
+            for (int b = 0; b < B; ++b) if (kv_row[b] == g) D->rows_by_group[at++] = b;
+            for (int k = 0; k < tiles; ++k) {
+                const int n = (left + (tiles - k) - 1) / (tiles - k);
+                D->tile_first[nt] = f; D->tile_n[nt] = n; ++nt;
+                f += n; left -= n;
+            }
+        }
+        D->n_tiles = nt;
+        D->lds_group = (size_t)rt * (sizeof(float) * (size_t)(5 * hd + ((ck_max + 3) & ~3)) + 2 * (size_t)d);
+        if (D->lds_group <= 64 * 1024) D->group_rt = rt;   // else: the per-row kernel through kv_row
+    }
     return 0;
 }
 

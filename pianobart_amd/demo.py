@@ -23,11 +23,12 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16', prime=None):
+                 precision='bf16', prime=None, samples=1, seed=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
         self.prime = prime                  # None, N or 'half': continue the piece from its first rows (eval_generation's --prime rule)
+        self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
 def get_args(argv=None):
@@ -48,7 +49,24 @@ def get_args(argv=None):
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
     ap.add_argument('--prime', type=str, default=None, help='N or "half": keep the first k = min(N, L) (half: L // 2) rows of the piece and '
                     'continue from there (eval_generation --prime)')
+    ap.add_argument('--samples', type=int, default=1, help='continuations of the piece: n MIDI files, --output for the first, the others with '
+                    'the sample index in front of the extension (out.mid, out.1.mid, ..); n > 1 needs --seed')
+    ap.add_argument('--seed', type=int, default=None, help='with --samples: sample j draws from RandomState(seed + j)')
     return ap.parse_args(argv)
+
+
+def sample_paths(output, n):
+    """The n files of --samples n: the name as given, then the sample index in front of the extension."""
+    root, ext = os.path.splitext(output)
+    return [output] + ['%s.%d%s' % (root, j, ext) for j in range(1, n)]
+
+
+def check_samples_args(samples, seed):
+    """The --samples rules; raises PBError."""
+    if samples < 1:
+        raise PBError('--samples must be >= 1 (got %d)' % samples)
+    if samples > 1 and seed is None:
+        raise PBError('--samples %d needs --seed: sample j draws from its own RandomState(seed + j)' % samples)
 
 
 def demo(args=None):
@@ -59,6 +77,8 @@ def demo(args=None):
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
         raise PBError('generate is batch-1 sequential: give ONE device (the reference itself is single-device here, README.md:154)')
     from .eval_generation import parse_prime, prime_inputs, prime_lengths
+    samples, seed = getattr(args, 'samples', 1), getattr(args, 'seed', None)
+    check_samples_args(samples, seed)
     prime = parse_prime(getattr(args, 'prime', None))
     from .pretrain import _load_vocab
     print("Loading Dictionary")
@@ -78,16 +98,22 @@ def demo(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
-    octuple, prefix = octuple.long(), None
+    octuple, prefix, ks = octuple.long(), None, None
     if prime is not None:                    # the piece's first k rows primed, the encoder sees them only
         ks = prime_lengths(octuple.numpy(), prime, pianobart.bar_pad_word, pianobart.pad_word_np)
         octuple, prefix = prime_inputs(octuple, ks, pianobart.pad_word_np)
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
-        y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
-    if Octuple2Midi(y, args.output):
-        print(f"Saved to {args.output}")
+        if samples > 1:                      # n continuations from one encoder pass: sample j of the one piece under RandomState(seed + j)
+            from .engine import sample_seed
+            y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
+                                     decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples)
+        else:
+            y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
+    for j, path in enumerate(sample_paths(args.output, samples)):
+        if Octuple2Midi(y[j:j + 1], path):
+            print(f"Saved to {path}")
     print(octuple.shape, y.shape)
     return octuple, y
 

@@ -116,6 +116,37 @@ def check_prefix(prefix, prefix_len, B, S, pad):
     return k, rows
 
 
+def check_samples(samples, P, n_rngs):
+    """The argument rules of samples-per-prompt generation, on the host before any device work. samples: an int n >= 1 (n samples of every
+    prompt) or P ints >= 1 (n_p samples of prompt p); n_rngs: the generators the caller holds, one per output row. Returns the row-to-prompt
+    map of the R = sum(n_p) output rows in prompt-major order: [0] * n_0 + [1] * n_1 + ... Raises PBError."""
+    if isinstance(samples, (int, np.integer)) and not isinstance(samples, bool):
+        counts = [int(samples)] * P
+    else:
+        try:
+            counts = [v for v in (samples.tolist() if hasattr(samples, 'tolist') else list(samples))]
+        except TypeError:
+            raise PBError('samples_per_prompt must be an int or a sequence of ints (got %r)' % (samples,))
+        if len(counts) != P:
+            raise PBError('samples_per_prompt has %d entries for %d prompt(s)' % (len(counts), P))
+    for p, n in enumerate(counts):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise PBError('samples_per_prompt[%d] = %r is not an integer' % (p, n))
+        if n < 1:
+            raise PBError('samples_per_prompt[%d] = %d: every prompt needs at least one sample' % (p, n))
+    owner = [p for p, n in enumerate(counts) for _ in range(int(n))]
+    if n_rngs != len(owner):
+        raise PBError('generate_batch: %d generators for %d output rows (samples_per_prompt sums to %d over %d prompts)'
+                      % (n_rngs, len(owner), len(owner), P))
+    return owner
+
+
+def sample_seed(seed, j, i, N):
+    """The seed of sample j of prompt i among N prompts (eval_generation --samples, demo --samples): seed + j N + i. Sample 0 keeps the
+    seed + i of a run without samples, and no two (prompt, sample) pairs of a run share a generator."""
+    return int(seed) + int(j) * int(N) + int(i)
+
+
 class _Slot:
     __slots__ = ('off', 'shape', 'numel')
 
@@ -1470,14 +1501,15 @@ class Engine:
         ops.key_extent(em, km)
         return max(1, min(S, int(km.item())))
 
-    def _decode_plan(self, B, S, s_enc, em, dev):
+    def _decode_plan(self, B, S, s_enc, em, dev, G=None):
         """The pb_decode_batch of B prompts (pb_decode_step reads its plan at B = 1) and the buffers it points into: per decoder layer the
         (B, S, 2d) cross K|V cache (filled by the caller from each prompt's encoder pass) and self K|V cache, the (B, d) / (B, ffn)
-        scratch rows, (B, vocab) logits and the split records."""
+        scratch rows, (B, vocab) logits and the split records. G: the cross cache holds G <= B slices, one per distinct prompt
+        (pb_batch_decoder_share_cross maps the rows onto them)."""
         from ._lib import DecodeBatch
         d, X, ff, wf = self.d, self.xdt, self.fd, self.wf
         e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
-        bufs = dict(kvc=[e(B, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
+        bufs = dict(kvc=[e(B if G is None else G, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
                     rows={n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}, g=e(B, ff), stat=e(8, dt=torch.float32),
                     logits=e(B, ops.VOCAB, dt=torch.float32), tok16=torch.tensor(self.pb.sos_word_np, dtype=torch.int16, device=dev),
                     attn_part=e(B * self.H * 16 * (self.hd + 4), dt=torch.float32))      # PB_DECODE_MAX_SPLITS records per (row, head)
@@ -1546,7 +1578,7 @@ class Engine:
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
-    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None):
+    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -1556,7 +1588,12 @@ class Engine:
         the constants, up to BATCH_MAX prompts share one batched device-sampled decoder (pb_batch_decoder_*); every other case runs
         the per-prompt loop over `generate` (_generate_batch_loop).
         prefix (B, P, 8) with prefix_len (B lengths, None = P each): row b is primed with prefix[b, :prefix_len[b]] as in `generate`; rows with
-        length 0 are today's unprimed rows, so one batch may mix both (check_prefix holds the argument rules)."""
+        length 0 are today's unprimed rows, so one batch may mix both (check_prefix holds the argument rules).
+        samples (an int n or P ints, check_samples): enc_ids / emask / prefix / prefix_len describe P prompts and prompt p is sampled n_p
+        times: rngs holds R = sum(n_p) generators and the result R rows, prompt-major, every row under the contract above. What the samples
+        of a prompt have in common is computed and stored once (_generate_batch_samples)."""
+        if samples is not None:
+            return self._generate_batch_samples(enc_ids, emask, sample_row, rngs, max_new, sampler, prefix, prefix_len, samples)
         B = int(enc_ids.shape[0])
         ks, rows = check_prefix(prefix, prefix_len, B, int(enc_ids.shape[1]), self.pb.pad_word_np)
         if len(rngs) != B:
@@ -1572,6 +1609,34 @@ class Engine:
             outs.append(self._generate_batch_chunk(enc_ids[c0:c1], emask[c0:c1] if emask is not None else None, sample_row, rngs[c0:c1],
                                                    max_new, sampler, ks[c0:c1], rows[c0:c1] if rows is not None else None))
         return torch.cat(outs, 0)
+
+    def _generate_batch_samples(self, enc_ids, emask, sample_row, rngs, max_new, sampler, prefix, prefix_len, samples):
+        """generate_batch with n_p samples of prompt p. The R rows go through the fused decoder in chunks of BATCH_MAX; inside a chunk the
+        encoder pass, the cross K|V projections and the prefill run once per distinct prompt (a prompt whose samples straddle a chunk
+        boundary is encoded once per chunk). Shapes the fused decoder declines run the per-prompt loop over the repeated prompts."""
+        P = int(enc_ids.shape[0])
+        owner = check_samples(samples, P, len(rngs))
+        ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
+        self._await_updates(2)
+        R = len(owner)
+        if R == 0:
+            return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
+        if not self._batch_decoder_covers(sampler):
+            return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner)
+        outs = []
+        for c0 in range(0, R, self.BATCH_MAX):
+            own = owner[c0:c0 + self.BATCH_MAX]
+            p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
+            outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
+                                                   rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
+                                                   groups=[p - p0 for p in own]))
+        return torch.cat(outs, 0)
+
+    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner):
+        """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt."""
+        idx = torch.as_tensor(owner, dtype=torch.long)
+        return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
+                                         max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
@@ -1594,41 +1659,67 @@ class Engine:
         self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows):
-        """<= BATCH_MAX prompts through one fused decoder. Encoder pass and cross K/V projections run per prompt, exactly as `generate`
-        runs them, into that row's slice of the (B, S, 2d) caches; then the device-ahead / host-behind loop with per-row draws, per-row
-        verification and per-row rewinds (_decode_device_sampled)."""
-        B, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None):
+        """<= BATCH_MAX rows through one fused decoder. Encoder pass and cross K/V projections run per prompt, exactly as `generate`
+        runs them, into that prompt's slice of the cross caches; then the device-ahead / host-behind loop with per-row draws, per-row
+        verification and per-row rewinds (_decode_device_sampled).
+        groups None: one row per prompt, (B, S, 2d) cross caches. groups = [prompt of row b] (samples of a prompt, rows prompt-major):
+        enc_ids / emask / ks / rows describe the G distinct prompts; their encoder passes, projections and prefills run once each into
+        (G, S, 2d) cross caches that the rows read through pb_batch_decoder_share_cross, and a primed prompt's k prefix rows of every
+        layer's self cache are copied to its other samples' rows (a device copy, no arithmetic). The self caches, masks, positions,
+        limits, draws, verification and rewinds stay per row."""
+        G, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
+        shared = groups is not None
+        groups = list(groups) if shared else list(range(G))
+        B = len(groups)
+        first = [groups.index(g) for g in range(G)]                        # the row that receives prompt g's prefill
         self.bind(dev)
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
         em = emask.to(torch.float32).contiguous() if emask is not None else None
         enc16 = ops.ids_to_i16(enc_ids)
         self.note_ids(enc16); self.check_ids(collective=False)
         with torch.no_grad():
-            s_enc = [self._key_extent(em[b:b + 1] if em is not None else None, S) for b in range(B)]
-            bp, bufs = self._decode_plan(B, S, s_enc, em, dev)
+            t_setup = time.perf_counter()
+            s_enc_g = [self._key_extent(em[g:g + 1] if em is not None else None, S) for g in range(G)]
+            s_enc = [s_enc_g[g] for g in groups]
+            em_rows = em[torch.as_tensor(groups, device=dev)].contiguous() if shared and em is not None else em      # the decoder's masks stay per row
+            kb = [ks[g] for g in groups]
+            bp, bufs = self._decode_plan(B, S, s_enc, em_rows, dev, G=G if shared else None)
             dec = self._decoder_create(bp)
             if dec is None:                                                # not covered: the per-prompt loop
-                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups)
             res_cpu = pad_cpu.repeat(B, S, 1)
             timers = []
             try:
-                for b in range(B):                                         # the batch-1 encoder pass (and prefill) of each prompt, into its cache rows
-                    emb = em[b:b + 1] if em is not None else None
-                    _, enc_out = self.forward_hidden(enc16[b:b + 1], None, emb, None, False, 0)
+                if shared:
+                    kv_row = np.asarray(groups, dtype=np.int32)
+                    LIB.call('pb_batch_decoder_share_cross', dec, G, kv_row.ctypes.data)
+                for g in range(G):                                         # the batch-1 encoder pass (and prefill) of each prompt, into its cache slice
+                    emb = em[g:g + 1] if em is not None else None
+                    _, enc_out = self.forward_hidden(enc16[g:g + 1], None, emb, None, False, 0)
                     for l in range(self.ND):
-                        self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][b], S, 2 * self.d, self.d)
-                    if ks[b]:
-                        res_cpu[b, :ks[b]] = rows[b, :ks[b]]
-                        timers.append(self._prefill(enc16[b:b + 1], emb, rows[b], ks[b], [t[b] for t in bufs['kvs']]))
+                        self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][g], S, 2 * self.d, self.d)
+                    if ks[g]:
+                        b1 = first[g]
+                        timers.append(self._prefill(enc16[g:g + 1], emb, rows[g], ks[g], [t[b1] for t in bufs['kvs']]))
+                        for b in range(B):
+                            if groups[b] != g:
+                                continue
+                            res_cpu[b, :ks[g]] = rows[g, :ks[g]]
+                            if b != b1 and ks[g] < S:                      # the prefix rows of the prompt's other samples: copies of the prefilled ones
+                                for t in bufs['kvs']:
+                                    t[b, :ks[g]].copy_(t[b1, :ks[g]])
                 LIB.call('pb_batch_decoder_reset', dec, ops._stream(), _DECODE_GRAPH)
                 torch.cuda.current_stream().synchronize()
+                setup_ms = (time.perf_counter() - t_setup) * 1e3
                 fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
                 info = self._decode_device_sampled(dec, B, S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
-                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False, starts=list(ks))
+                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False, starts=kb)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
-            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B, prefix=list(ks), prefill_ms=sum(t() for t in timers))
+            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B, prefix=kb, prefill_ms=sum(t() for t in timers), groups=groups,
+                                    encoder_passes=G, prefill_passes=sum(1 for k in ks if 0 < k < S), setup_ms=setup_ms,
+                                    cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
             return res_cpu.to(dev)
 
     def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None):

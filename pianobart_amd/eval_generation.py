@@ -10,6 +10,10 @@ RNG rules:
     (PianoBartLM.forward(generate=True)); --batch_size > 1 is refused (the reference's model exits with ERROR for B != 1).
   * with --seed s: prompt i draws from its own RandomState(s + i) (PianoBartLM.generate_batch: up to 16 prompts per batched decode
     step), so the file is identical for every --batch_size.
+  * --samples n (default 1) asks for n continuations of every prompt. n = 1 writes the (N, max_seq_len, 8) file above, byte for byte.
+    n > 1 needs --seed and writes (N, n, max_seq_len, 8): sample j of prompt i draws from RandomState(seed + j N + i) (sample_seed), so
+    [:, 0] is the --samples 1 file. --batch_size then counts output rows; the samples of a prompt inside one batch share its encoder
+    pass and cross-attention K/V (PianoBartLM.generate_batch's samples_per_prompt), and the file does not depend on --batch_size.
 The prompts are sliced from the loaded array in order; --num_workers is accepted for the reference's command lines and not needed.
 """
 import argparse
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
+from .engine import sample_seed
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +51,8 @@ def get_args(argv=None):
     ap.add_argument('--seed', type=int, default=None, help='prompt i samples from RandomState(seed + i): the output is the same for every --batch_size')
     ap.add_argument('--prime', type=str, default=None, help='N or "half": continue each piece from its first k = min(N, L) (half: L // 2) rows, '
                     'L = rows whose bar id is not PAD (Ablation.py:134); the encoder sees rows < k only')
+    ap.add_argument('--samples', type=int, default=1, help='continuations per prompt; n > 1 needs --seed and writes (N, n, max_seq_len, 8), '
+                    'sample j of prompt i drawing from RandomState(seed + j * N + i)')
     return ap.parse_args(argv)
 
 
@@ -88,6 +95,12 @@ def check_args(args):
     parse_prime(getattr(args, 'prime', None))
     if args.batch_size < 1:
         raise PBError('--batch_size must be >= 1 (got %d)' % args.batch_size)
+    samples = getattr(args, 'samples', 1)
+    if samples < 1:
+        raise PBError('--samples must be >= 1 (got %d)' % samples)
+    if samples > 1 and args.seed is None:
+        raise PBError('--samples %d needs --seed: sample j of prompt i draws from its own RandomState(seed + j * N + i); the one global RNG '
+                      'stream of a run without --seed gives one continuation per prompt' % samples)
     if args.seed is None and args.batch_size > 1:
         raise PBError('--batch_size %d needs --seed: without it every prompt draws from the one global RNG stream in turn, which only the '
                       'batch-1 loop reproduces (the reference exits with ERROR for batches); with --seed s prompt i uses RandomState(s + i) '
@@ -117,7 +130,7 @@ def load_data(dataset_path, dataset_name):
 
 
 def eval_generation(args=None):
-    """Returns the (N, max_seq_len, 8) float32 array it saved to args.output."""
+    """Returns the float32 array it saved to args.output: (N, max_seq_len, 8), or (N, n, max_seq_len, 8) with --samples n > 1."""
     if args is None:
         args = get_args()
     check_args(args)
@@ -140,10 +153,26 @@ def eval_generation(args=None):
     model = model.to(device).eval()
     bar_pad = model.pianobart.bar_pad_word
     prime = parse_prime(getattr(args, 'prime', None))
-    output = np.zeros((N, args.max_seq_len, 8), dtype=np.float32)
+    samples = getattr(args, 'samples', 1)
+    output = np.zeros((N, args.max_seq_len, 8) if samples == 1 else (N, samples, args.max_seq_len, 8), dtype=np.float32)
     print("\nEval Start")
     with torch.no_grad():
-        for c0 in range(0, N, args.batch_size):
+        rows = [(i, j) for i in range(N) for j in range(samples)] if samples > 1 else []      # prompt-major output rows
+        for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
+            chunk = rows[r0:r0 + args.batch_size]
+            c0, c1 = chunk[0][0], chunk[-1][0] + 1
+            x = torch.as_tensor(np.asarray(data[c0:c1])).long()
+            prefix = ks = None
+            if prime is not None:
+                ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
+                x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
+            x = x.to(device)
+            y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
+                                     device_num=device_num, decoder_prefix=prefix, prefix_len=ks,
+                                     samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)]).float().cpu().numpy()
+            for r, (i, j) in enumerate(chunk):
+                output[i, j] = y[r]
+        for c0 in range(0, N if samples == 1 else 0, args.batch_size):
             c1 = min(N, c0 + args.batch_size)
             x = torch.as_tensor(np.asarray(data[c0:c1])).long()
             prefix = ks = None

@@ -363,24 +363,32 @@ class PianoBartLM(nn.Module):
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
-                       decoder_prefix=None, prefix_len=None):
+                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
         np.random stream is not touched. Placed like forward(generate=True): CPU for device_num == -1, else cuda:device_num.
         decoder_prefix (B, P, 8) + prefix_len (B lengths, None = P): prompt b is primed with its first prefix_len[b] rows, as
-        forward(generate=True, decoder_prefix=...) primes one prompt; length 0 = unprimed."""
+        forward(generate=True, decoder_prefix=...) primes one prompt; length 0 = unprimed.
+        samples_per_prompt (an int n >= 1, or one int >= 1 per prompt): several continuations of each prompt. input_ids_encoder, the mask,
+        decoder_prefix and prefix_len then describe P prompts, seeds / rngs hold R = sum(n_p) generators in prompt-major order (prompt 0's
+        samples first) and the result is (R, S, 8) in that order, every row under the contract above with its own generator. The samples
+        of a prompt share its encoder pass, cross-attention K/V and prefill (Engine.generate_batch's `samples`); None: one row per prompt."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
         if rngs is None:
             rngs = [np.random.RandomState(int(s)) for s in seeds]
         rngs = list(rngs)
-        if len(rngs) != B:
+        if samples_per_prompt is not None:
+            from .engine import check_samples
+            check_samples(samples_per_prompt, B, len(rngs))
+        elif len(rngs) != B:
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
-                                 sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len)
+                                 sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
+                                 samples=samples_per_prompt)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     # model.py:68-78 -- temperatures / nucleus thresholds per head

@@ -5,6 +5,12 @@ verification ms per step and an HBM-bytes estimate per step (decoder + LM-head w
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
     python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K]
+
+--samples n: n samples of ONE prompt instead. Three runs alternate in this process, --reps times: "grouped" (samples=n: one encoder pass,
+one (1, S, 2d) cross cache per layer, the grouped cross-attention kernel), "indirect" (the same with PB_DECODE_CROSS_GROUPED=0: the per-row
+kernel reading the shared slice) and "repeated" (the prompt repeated n times through generate_batch without samples: the yardstick). Per
+run: setup ms (encoder passes, cross K/V projections, prefill -- host time up to the decoder's start), ms per step, aggregate tokens/s over
+the decode loop and over the whole call, cross_cache_bytes. One JSON line; with --prime K the runs are primed with K rows.
 """
 import argparse
 import json
@@ -27,6 +33,10 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=256, help='generated positions per row')
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4, 8, 16])
     ap.add_argument('--prime', type=int, default=0, help='also time primed generation: K decoder rows given per prompt, --steps sampled after them')
+    ap.add_argument('--samples', type=int, default=0, help='time n samples of one prompt: grouped / indirect / repeated-prompt runs, alternating')
+    ap.add_argument('--reps', type=int, default=3, help='--samples: repetitions of the alternating runs')
+    ap.add_argument('--kinds', nargs='+', default=['grouped', 'indirect', 'repeated'], choices=['grouped', 'indirect', 'repeated'],
+                    help='--samples: the runs to alternate (one kind alone for a kernel trace)')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -58,6 +68,60 @@ def main(argv=None):
 
     def kv_bytes(rows):                                     # cross K/V over the visible rows + self K/V at the mean position
         return sum(L * (vis[b] + steps / 2) * 2 * d * 2 for b in range(rows))
+
+    if args.samples:
+        n = args.samples
+        K = min(args.prime, S - steps) if args.prime else 0
+        penc, pmask, piece = enc[:1], emask[:1], None
+        if K:                                               # primed as below: the encoder sees the K given rows only
+            piece = synth_octuple_batch(1, S + 1, seed=9, min_len=S + 1)[5][:, :K]
+            penc = enc[:1].clone()
+            penc[:, :K] = piece.to(dev)
+            penc[:, K:] = torch.tensor(model.pianobart.pad_word_np, device=dev)
+            pmask = (penc[:, :, 0] != 256).float()
+
+        def run(kind, max_new):
+            rngs = [np.random.RandomState(b) for b in range(n)]
+            os.environ['PB_DECODE_CROSS_GROUPED'] = '0' if kind == 'indirect' else '1'
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == 'repeated':
+                y = eng.generate_batch(penc.repeat(n, 1, 1), pmask.repeat(n, 1), model.sample_row, rngs, max_new=max_new, sampler=sampler,
+                                       prefix=piece.repeat(n, 1, 1) if K else None)
+            else:
+                y = eng.generate_batch(penc, pmask, model.sample_row, rngs, max_new=max_new, sampler=sampler, prefix=piece, samples=n)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            info = eng.last_decode
+            ntok = sum(info['tokens'])
+            return y.cpu(), dict(setup_ms=info['setup_ms'], prefill_ms=info['prefill_ms'], ms_per_step=info['loop_ms'] / max(1, info['steps']),
+                                 loop_tokens_per_s=ntok / (info['loop_ms'] * 1e-3), tokens_per_s=ntok / dt, wall_ms=dt * 1e3, tokens=ntok,
+                                 steps=info['steps'], rewinds=sum(info['rewinds']), cross_cache_bytes=info['cross_cache_bytes'],
+                                 encoder_passes=info['encoder_passes'], prefill_passes=info['prefill_passes'],
+                                 launches_per_step=info['launches_per_token'], graph=info['graph'], batch=info['batch'])
+        kinds = tuple(args.kinds)
+        for kind in kinds:
+            run(kind, 16)                                   # warm-up (capture, pinned logs, allocator)
+        reps = {k: [] for k in kinds}
+        same = True
+        for _ in range(args.reps):
+            ys = {}
+            for kind in kinds:
+                ys[kind], r = run(kind, steps)
+                reps[kind].append(r)
+            same = same and all(torch.equal(ys[k], ys[kinds[-1]]) for k in kinds)
+        summ = {}
+        for kind in kinds:
+            tps = [r['loop_tokens_per_s'] for r in reps[kind]]
+            summ[kind] = dict(loop_tokens_per_s_median=float(np.median(tps)), loop_tokens_per_s_min=min(tps), loop_tokens_per_s_max=max(tps),
+                              ms_per_step_median=float(np.median([r['ms_per_step'] for r in reps[kind]])),
+                              setup_ms_median=float(np.median([r['setup_ms'] for r in reps[kind]])),
+                              tokens_per_s_median=float(np.median([r['tokens_per_s'] for r in reps[kind]])),
+                              cross_cache_bytes=reps[kind][0]['cross_cache_bytes'])
+        print(json.dumps({"metric": "n samples of one prompt (%dL/%dd, S=%d, %d positions per row, %d prefix rows)" % (L, d, S, steps, K),
+                          "samples": n, "prefix_rows": K, "same_tokens_in_all_runs": bool(same), "summary": summ, "runs": reps,
+                          "group_tile": os.environ.get('PB_DECODE_GROUP_TILE', 'default')}), flush=True)
+        return
 
     # batch 1 through Engine.generate (the device-sampled batch-1 decoder), same process
     np.random.seed(0)
