@@ -106,7 +106,7 @@ def demo(args=None):
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
         if samples > 1:                      # n continuations from one encoder pass: sample j of the one piece under RandomState(seed + j)
-            from .engine import sample_seed
+            from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
                                      decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples)
         else:

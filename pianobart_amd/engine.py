@@ -1,4 +1,4 @@
-"""Execution engine of the PianoBART hot path on MI355X.
+"""Execution engine of the PianoBART hot path on MI355X (the training half; generation.py holds `generate` / `generate_batch`, which Engine inherits).
 
 Owns (a) one flat f32 parameter buffer + one flat f32 gradient buffer (+ Adam moments and a bf16
 weight shadow) whose slices are what the nn.Parameters of pianobart_amd.model alias, (b) the saved
@@ -11,9 +11,7 @@ Reference semantics followed (file:line into /root/reference; tf: = transformers
   heads:   model.py:119-126  -> one (d x 1280) GEMM
   loss:    pretrain.py:112-118,163-189 ; step: pretrain.py:192-196 (clip 3.0, HF AdamW)
 """
-import math
 import os
-import time
 
 import numpy as np
 import torch
@@ -21,23 +19,16 @@ import torch
 from . import ops, rowpack
 
 from ._lib import LIB, PB_BF16, PB_F32, PB_F32X3, PBError
+from .generation import LN_EPS, GenerationMixin, check_prefix, check_samples, sample_seed  # noqa: F401 (the helpers stay importable from here)
 
 _WGRAD_STREAM = int(os.environ.get('PB_WGRAD_STREAM', '7'))            # second HIP stream, bits: 1 = weight-gradient GEMMs, 2 = cross-attention K/V projections, 4 = backward GEMMs as ordinary grids (0: everything on one stream, for A/B)
 _WG_DXD_256 = int(os.environ.get('PB_WG_DXD_256', '1'))                         # the d x d weight gradients on the 256x256 ping-pong kernel (9 tiles x split-K 21) instead of 128x128 tiles (36 x 14); same-box A/B round 5: 58.01 / 58.01 -> 57.83 / 57.62 ms (profiles/r05_dxd_wgrad_ab.txt); 0 = the round-2 choice
 _WG_TARGET = 192 if _WGRAD_STREAM & 1 else 256            # split-K work items a weight-gradient GEMM aims for (256x256 tiles)
-_NO_DEFER = False                  # settled (round 2): True reduces every bias / LayerNorm gradient right behind its producer
-_DECODE_SPLIT = True               # settled (round 2): False = single-query attention with one workgroup per head
 _ROWDOT = int(os.environ.get('PB_ROWDOT', '1'))                                  # 1 = delta of the one-pass attention backward from the out-projection dgrad's epilogue (0: a separate pass)
 _X3_ONEHOT = int(os.environ.get('PB_X3_ONEHOT', '1'))                        # bf16x3: embedding-table gradient as two one-hot GEMMs over dz's (hi, lo) planes (0: the exact path's f32 atomics, for A/B)
 _DP_RESERVE_CUS = int(os.environ.get('PB_DP_RESERVE_CUS', '0'))                 # data parallel: 0 = backward GEMMs as ordinary grids (default: +0.45 ms at world 1, profiles/r06_dp_mode_ab.txt); n > 0 = persistent grids that leave n CUs to RCCL's kernels (+1.0 / +1.4 ms for 8 / 16)
 _SIDE_PRIORITY = int(os.environ.get('PB_SIDE_PRIORITY', '0'))                      # HIP priority of the second stream (1 = low, -1 = high; developer A/B)
 _X3_FLASH = int(os.environ.get('PB_X3_FLASH', '1'))                            # bf16x3: 1 = fused split-bf16 attention (pb_flash_*_x3), 0 = the unfused QK^T / softmax / PV chain of the exact-f32 path
-_DECODE_SPEC = int(os.environ.get('PB_DECODE_SPEC', '1'))                       # 1 = device-side sampling ahead of the host where the caller names the sampler (Engine._decode_device_sampled), 0 = one host round trip per token
-_DECODE_GRAPH = int(os.environ.get('PB_DECODE_GRAPH', '1'))                     # 1 = one hipGraph replay per token (6 launches per layer), 0 = the same launches issued directly, -1 = the round-2 per-launch loop (the persistent-kernel forms of round 4, measured slower, left the library in round 5: profiles/r04_decode_persistent.txt)
-_NO_FUSED_BIAS = False             # settled (round 2): True takes the bias gradients out of the GEMM / attention epilogues
-
-LN_EPS = 1e-5
-
 
 # copies of the backward scratch buffers that the second stream's weight-gradient GEMMs read (gB, du, dq, dkv, dqkv): with 2 the main
 # stream can write the next sublayer's cotangent while the weight gradient of the previous one is still reading its own (3: slower)
@@ -45,8 +36,6 @@ _RING = 2
 # events that order the two streams: HIP events without the system-scope fence (hipEventDisableSystemFence: 59.5 -> 59.1 ms/step
 # against plain hipEventDisableTiming events; hipEventReleaseToDevice: no gain)
 _EVENT_MODE = 1
-_SIDE_TAIL = 1   # settled (round 2). End of backward: decoder half of dP, the deferred reductions and one f32 GEMM on the second stream
-_DGRAD_NT = 1    # settled (round 2): backward dX = dY W from transposed weight copies (NT GEMM) instead of the NN form
 _FWD_GEMM_FLAGS = int(os.environ.get('PB_FWD_GEMM_FLAGS', '32768'))      # PB_GEMM_TAIL_SPLIT for the forward projections (0: off)
 # dead-row compaction of the fused pre-train step (Engine._pack_batch): PB_PACK_ROWS=0 keeps every step dense
 _PACK_ROWS = int(os.environ.get('PB_PACK_ROWS', '1'))
@@ -80,73 +69,6 @@ def _r4(n):
     return (n + 3) // 4 * 4
 
 
-def check_prefix(prefix, prefix_len, B, S, pad):
-    """The argument rules of primed generation, on the host before any device work. prefix: (B, P, 8) Octuple ids (tensor on any device, or
-    array) whose rows 0 .. k_b - 1 prime prompt b; prefix_len: B lengths (None: P for every row). Every id of a prefix row must be an ordinary
-    event, 0 <= id < pad[head] -- the range check of a decoder input (note_ids), without the special ids a decoder input may otherwise hold.
-    Returns (k, rows): k = [k_b], rows = int64 CPU (B, max k_b, 8), or None when no row is primed. Raises PBError."""
-    if prefix is None:
-        if prefix_len is not None and any(int(v) for v in (prefix_len.tolist() if hasattr(prefix_len, 'tolist') else prefix_len)):
-            raise PBError('prefix_len given without a prefix')
-        return [0] * B, None
-    p = torch.as_tensor(prefix)
-    if p.dim() != 3 or int(p.shape[0]) != B or int(p.shape[2]) != 8:
-        raise PBError('prefix of shape %s: expected (%d, P, 8) for %d prompt(s)' % (tuple(p.shape), B, B))
-    if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
-        raise PBError('prefix ids must be integers (got %s)' % p.dtype)
-    P = int(p.shape[1])
-    if prefix_len is None:
-        k = [P] * B
-    else:
-        k = [int(v) for v in (prefix_len.tolist() if hasattr(prefix_len, 'tolist') else prefix_len)]
-        if len(k) != B:
-            raise PBError('prefix_len has %d entries for %d prompt(s)' % (len(k), B))
-    for b, kb in enumerate(k):
-        if not 0 <= kb <= min(S, P):
-            raise PBError('prefix_len[%d] = %d outside 0 .. %d (window S = %d, prefix rows P = %d)' % (b, kb, min(S, P), S, P))
-    if max(k, default=0) == 0:
-        return k, None
-    rows = p[:, :max(k)].detach().to('cpu', torch.int64)
-    lim = torch.as_tensor(np.asarray(pad), dtype=torch.int64)
-    for b, kb in enumerate(k):
-        bad = ((rows[b, :kb] < 0) | (rows[b, :kb] >= lim)).nonzero()
-        if len(bad):
-            i, h = int(bad[0, 0]), int(bad[0, 1])
-            raise PBError('prefix of prompt %d, row %d, head %d: id %d is not an ordinary event (0 <= id < %d)' % (b, i, h, int(rows[b, i, h]), int(lim[h])))
-    return k, rows
-
-
-def check_samples(samples, P, n_rngs):
-    """The argument rules of samples-per-prompt generation, on the host before any device work. samples: an int n >= 1 (n samples of every
-    prompt) or P ints >= 1 (n_p samples of prompt p); n_rngs: the generators the caller holds, one per output row. Returns the row-to-prompt
-    map of the R = sum(n_p) output rows in prompt-major order: [0] * n_0 + [1] * n_1 + ... Raises PBError."""
-    if isinstance(samples, (int, np.integer)) and not isinstance(samples, bool):
-        counts = [int(samples)] * P
-    else:
-        try:
-            counts = [v for v in (samples.tolist() if hasattr(samples, 'tolist') else list(samples))]
-        except TypeError:
-            raise PBError('samples_per_prompt must be an int or a sequence of ints (got %r)' % (samples,))
-        if len(counts) != P:
-            raise PBError('samples_per_prompt has %d entries for %d prompt(s)' % (len(counts), P))
-    for p, n in enumerate(counts):
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-            raise PBError('samples_per_prompt[%d] = %r is not an integer' % (p, n))
-        if n < 1:
-            raise PBError('samples_per_prompt[%d] = %d: every prompt needs at least one sample' % (p, n))
-    owner = [p for p, n in enumerate(counts) for _ in range(int(n))]
-    if n_rngs != len(owner):
-        raise PBError('generate_batch: %d generators for %d output rows (samples_per_prompt sums to %d over %d prompts)'
-                      % (n_rngs, len(owner), len(owner), P))
-    return owner
-
-
-def sample_seed(seed, j, i, N):
-    """The seed of sample j of prompt i among N prompts (eval_generation --samples, demo --samples): seed + j N + i. Sample 0 keeps the
-    seed + i of a run without samples, and no two (prompt, sample) pairs of a run share a generator."""
-    return int(seed) + int(j) * int(N) + int(i)
-
-
 class _Slot:
     __slots__ = ('off', 'shape', 'numel')
 
@@ -170,7 +92,7 @@ def _new_stream(device):
     return torch.cuda.ExternalStream(st.value, device=device)
 
 
-class Engine:
+class Engine(GenerationMixin):
     def __init__(self, pianobart, mask_lm, precision='bf16'):
         if precision not in ('bf16', 'fp32', 'bf16x3'):
             raise PBError('precision must be "bf16", "fp32" or "bf16x3"')
@@ -340,7 +262,7 @@ class Engine:
         # kernel): same offsets in a second flat buffer, rewritten by one batched launch whenever the shadow changed
         self.wT, self._wT_table, self._wT_tiles = {}, None, 0
         self._shadow_gen, self._wT_gen, self._wT_done = 0, -1, None
-        if self.code == PB_BF16 and _DGRAD_NT:
+        if self.code == PB_BF16:
             self.PbfT = torch.empty_like(self.Pbf)
             rows, tiles = [], 0
             for name, s in self.slots.items():
@@ -536,7 +458,7 @@ class Engine:
         if self.use_flash:
             ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
             assert dout[1] == 0 and dout[2] == out[2]
-            fuse = dbias is not None and hd in (64, 96, 128) and not _NO_FUSED_BIAS
+            fuse = dbias is not None and hd in (64, 96, 128)
             wsb = None
             if fuse:
                 need = int(LIB.query('pb_flash_bias_ws_floats', B, H, Sq, Sk, hd))
@@ -855,11 +777,7 @@ class Engine:
         du = self._ring('du')
         du = du[:T, :ff] if du.shape[1] == ff else du.view(-1)[:T * ff].view(T, ff)
         # dU = (dG W2) * gelu'(U), and db1 = column sums of dU straight from the same epilogue registers
-        if _NO_FUSED_BIAS:
-            self._dgrad(gb, pf + 'w2', du, T, ff, d, False, gelu_grad_aux_in=L['u'], ldaux=ff)
-            ops.colsum(du, g[pf + 'b1'], self.partials, T, ff)
-        else:
-            self._dgrad(gb, pf + 'w2', du, T, ff, d, False, gelu_grad_aux_in=L['u'], ldaux=ff, colsum_out=g[pf + 'b1'], colsum_ws=self._cs_ws(T, ff))
+        self._dgrad(gb, pf + 'w2', du, T, ff, d, False, gelu_grad_aux_in=L['u'], ldaux=ff, colsum_out=g[pf + 'b1'], colsum_ws=self._cs_ws(T, ff))
         self._wgrad(du, y_in, pf + 'w1', ff, d, T)
         self._dgrad(du, pf + 'w1', gA, T, d, ff, True)
         return gA
@@ -928,15 +846,14 @@ class Engine:
         onehot_route = (self.code == PB_BF16 or (self.x3 and _X3_ONEHOT)) and Te % 64 == 0 and Td % 64 == 0      # dP = Onehot^T dz on the matrix cores, no atomics (bf16x3: dz as two bf16 planes, two GEMMs)
         dec_tab_done = None                                  # event: the decoder tokens' half of dP has been written
         base = ws.get('_base', ws)
-        if not _NO_DEFER:
-            # ~160 bias / LayerNorm-parameter reductions per pass: keep their partial rows and sum them in one launch at the end
-            if 'defer' not in base:
-                H, hd, ff = self.H, self.hd, max(self.fe, self.fd)
-                per_layer = 3 * self.partials.numel() + int(LIB.query('pb_gemm_colsum_ws_floats', T, ff)) + \
-                    2 * int(LIB.query('pb_flash_bias_ws_floats', B, H, S, S, hd if hd in (64, 96, 128) else 64)) + 64
-                base['defer'] = (torch.empty((self.NE + self.ND) * per_layer, dtype=torch.float32, device=self.device),
-                               torch.empty(64 * (8 * (self.NE + self.ND) + 8), dtype=torch.uint8, device=self.device))
-            ops.defer_begin(*base['defer'])
+        # ~160 bias / LayerNorm-parameter reductions per pass: keep their partial rows and sum them in one launch at the end
+        if 'defer' not in base:
+            H, hd, ff = self.H, self.hd, max(self.fe, self.fd)
+            per_layer = 3 * self.partials.numel() + int(LIB.query('pb_gemm_colsum_ws_floats', T, ff)) + \
+                2 * int(LIB.query('pb_flash_bias_ws_floats', B, H, S, S, hd if hd in (64, 96, 128) else 64)) + 64
+            base['defer'] = (torch.empty((self.NE + self.ND) * per_layer, dtype=torch.float32, device=self.device),
+                             torch.empty(64 * (8 * (self.NE + self.ND) + 8), dtype=torch.uint8, device=self.device))
+        ops.defer_begin(*base['defer'])
         if gy_dec is not None:
             cur = gy if gy_dec.data_ptr() == gy.data_ptr() else gy_dec
             for l in reversed(range(self.ND)):
@@ -1013,7 +930,7 @@ class Engine:
                 if onehot_route:
                     # the decoder tokens' half of dP = Onehot^T dz is ready now: on the second stream, beside the encoder's backward
                     ops.onehot_build(sv['dec16'], ws['onehot'][Te:Te + Td], padded=True)
-                    dec_tab_done = self._onehot_gemm(ws['onehot'][Te:Te + Td], ws['dz'][Te:Te + Td], Td, False, side=bool(_SIDE_TAIL))
+                    dec_tab_done = self._onehot_gemm(ws['onehot'][Te:Te + Td], ws['dz'][Te:Te + Td], Td, False, side=True)
             cur = genc
             if gy_enc_extra is not None:
                 cur = genc.add_(gy_enc_extra)
@@ -1039,7 +956,7 @@ class Engine:
             self._ready(pf + 'wqkv', pf + 'w2')
         # the layers have left their last bias / LayerNorm-parameter partial sums: the one launch that reduces them all runs on the second
         # stream, beside the embedding gradients
-        side_tail = _SIDE_TAIL and not _NO_DEFER and (_WGRAD_STREAM & 1) and self._side_stream() is not None and self.grad_hook is None
+        side_tail = (_WGRAD_STREAM & 1) and self._side_stream() is not None and self.grad_hook is None
         if side_tail:
             self._event().wait_on(self._side)
             with torch.cuda.stream(self._side):
@@ -1073,7 +990,7 @@ class Engine:
         if not side_tail:
             lin_w()
         self._ready('emb', 'lin.w')
-        if not _NO_DEFER and not side_tail:
+        if not side_tail:
             ops.defer_flush()
         self._join_side()
         if self.grad_hook is not None and self.Gcur is self.G32:
@@ -1389,542 +1306,6 @@ class Engine:
         """Call before reading parameters from outside the engine (checkpoints) when pipeline_updates is on."""
         self._await_updates(2)
 
-    # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None):
-        """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
-        any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
-        (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
-        and each step feeds ONE decoder token through the layers against a self-attention K/V cache. Position-i logits
-        only depend on decoder inputs <= i (causal), so the tokens are identical (tests/test_model_gpu.py).
-        max_new: stop after that many positions (None = the window). sampler = dict(T=[8 temperatures], P=[8 thresholds]): the caller
-        states that `sample_row` IS model.py:68-107 with these constants, drawing np.random.random_sample(8) per position; the decoder may
-        then sample on the device ahead of the host (`_decode_device_sampled`) -- `sample_row` still decides every token.
-        prefix (1, k, 8): primed generation -- the reference loop with decoder inputs 1 .. k and their mask set to the prefix, the loop
-        starting at position k and result[:, :k] = prefix. The forced positions draw nothing; max_new counts sampled positions
-        (the row stops at min(S, k + max_new)). The cache rows of the prefix come from one teacher-forced decoder pass (_prefill)."""
-        S = int(enc_ids.shape[1])
-        ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
-        k = ks[0]
-        pre = rows[0, :k] if k else None
-        self._await_updates(2)
-        if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre)
-        if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre)
-        import ctypes
-        pb = self.pb
-        self.bind(enc_ids.device)
-        dev = enc_ids.device
-        pad_cpu = torch.from_numpy(pb.pad_word_np)
-        em = emask.to(torch.float32).contiguous() if emask is not None else None
-        enc16 = ops.ids_to_i16(enc_ids)
-        self.note_ids(enc16); self.check_ids(collective=False)
-        with torch.no_grad():
-            s_enc = self._key_extent(em, S)
-            bp, bufs = self._decode_plan(1, S, [s_enc], em, dev)
-            _, enc_out = self.forward_hidden(enc16, None, em, None, False, 0)
-            for l in range(self.ND):
-                self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][0], S, 2 * self.d, self.d)
-            timer = self._prefill(enc16, em, pre, k, [t[0] for t in bufs['kvs']])
-            stream = ops._stream()
-            res_cpu = pad_cpu.repeat(1, S, 1)
-            if k:
-                res_cpu[0, :k] = pre
-            # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
-            # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
-            self.last_decode = None
-            dec = self._decoder_create(bp) if _DECODE_GRAPH >= 0 else None
-            if dec is not None:
-                try:
-                    LIB.call('pb_batch_decoder_reset', dec, stream, _DECODE_GRAPH)
-                    torch.cuda.current_stream().synchronize()           # the prompt's encoder pass: not part of the per-token time below
-                    if sampler is not None and _DECODE_SPEC:
-                        fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
-                        info = self._decode_device_sampled(dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
-                                                           res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k])
-                        info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0])
-                    else:
-                        info = self._decode_host_sampled(dec, S, sample_row, res_cpu, pad_cpu, max_new, k)
-                    self.last_decode = dict(info, s_enc=s_enc, prefix=k, prefill_ms=timer())
-                finally:
-                    LIB.call('pb_batch_decoder_destroy', dec)
-                return res_cpu.to(dev)
-            pref = ctypes.byref(bp.plan)
-            tok16 = bufs['tok16']
-            if k:
-                tok16.copy_(pre[k - 1].to(torch.int16))                     # the input of position k: the prefix's last row
-            tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
-            logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
-            for i in range(k, S):
-                LIB.call('pb_decode_step', pref, i, stream)
-                logit_pin.copy_(bufs['logits'][0])                          # D2H on the current stream, returns when the row has landed
-                tok = sample_row(logit_pin)
-                if (tok >= pad_cpu).any():
-                    break
-                res_cpu[0, i] = tok
-                tok_pin.copy_(tok)
-                tok16.copy_(tok_pin, non_blocking=True)                     # stream-ordered before the next step's kernels
-            return res_cpu.to(dev)
-
-    def _prefill(self, enc16, em, pre, k, kvs):
-        """Primed generation: rows 0 .. k-1 of the self-attention caches kvs[l] ((S, 2d) each, row j = K | V of decoder position j, the layout
-        pb_decode_step and the fused decoder's new-token workgroup write) get the K|V of the decoder inputs SOS, pre[0] .. pre[k-2]. ONE
-        teacher-forced decoder pass over them on the training kernels, against the encoder pass just run (reuse_encoder), then a row gather
-        (pb_gather_rows16: 16-byte copies, no arithmetic) out of each layer's q|k|v workspace: in d-wide blocks, cache blocks 2j, 2j + 1 <-
-        workspace blocks 3j + 1, 3j + 2. Per prompt, like the encoder pass, so that a row of generate_batch stays the batch-1 generate of its
-        prompt bit for bit. No-op unless 0 < k < S (k = S samples nothing). Returns a callable giving the pass's device milliseconds."""
-        if not 0 < k < int(enc16.shape[1]):
-            return lambda: 0.0
-        S, dev = int(enc16.shape[1]), enc16.device
-        dec = torch.from_numpy(self.pb.pad_word_np).repeat(1, S, 1)
-        dec[0, 0] = torch.from_numpy(self.pb.sos_word_np)
-        dec[0, 1:k] = pre[:k - 1]
-        dmask = torch.zeros(1, S, dtype=torch.float32)
-        dmask[0, :k] = 1
-        dec16, dmask = ops.ids_to_i16(dec.to(dev)), dmask.to(dev)
-        rows = torch.arange(k, dtype=torch.int32)
-        idx = torch.stack([3 * rows + 1, 3 * rows + 2], 1).reshape(-1).to(dev)
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=True)
-        esz = 2 if self.xdt == torch.bfloat16 else 4
-        for l in range(self.ND):
-            ops.gather_rows16(self._cur_ws['dec'][l]['qkv'], idx, kvs[l], 2 * k, self.d * esz)
-        t1.record()
-        return lambda: t0.elapsed_time(t1)
-
-    def _key_extent(self, em, S):
-        """Encoder positions a decoder query can see: keys behind the last visible one are masked for every query, so the decode stops there."""
-        if em is None:
-            return S
-        km = torch.empty(1, dtype=torch.int32, device=em.device)
-        ops.key_extent(em, km)
-        return max(1, min(S, int(km.item())))
-
-    def _decode_plan(self, B, S, s_enc, em, dev, G=None):
-        """The pb_decode_batch of B prompts (pb_decode_step reads its plan at B = 1) and the buffers it points into: per decoder layer the
-        (B, S, 2d) cross K|V cache (filled by the caller from each prompt's encoder pass) and self K|V cache, the (B, d) / (B, ffn)
-        scratch rows, (B, vocab) logits and the split records. G: the cross cache holds G <= B slices, one per distinct prompt
-        (pb_batch_decoder_share_cross maps the rows onto them)."""
-        from ._lib import DecodeBatch
-        d, X, ff, wf = self.d, self.xdt, self.fd, self.wf
-        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
-        bufs = dict(kvc=[e(B if G is None else G, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
-                    rows={n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}, g=e(B, ff), stat=e(8, dt=torch.float32),
-                    logits=e(B, ops.VOCAB, dt=torch.float32), tok16=torch.tensor(self.pb.sos_word_np, dtype=torch.int16, device=dev),
-                    attn_part=e(B * self.H * 16 * (self.hd + 4), dt=torch.float32))      # PB_DECODE_MAX_SPLITS records per (row, head)
-        bp = DecodeBatch()
-        plan = bp.plan
-        plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), self.ND, ops.VOCAB
-        for k in range(9):
-            plan.tab_off[k] = ops.TAB_OFF[k]
-        P = lambda t: t.data_ptr()
-        plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(bufs['tok16']), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
-        plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
-        for n, t in bufs['rows'].items():
-            setattr(plan, n, P(t))
-        plan.g, plan.stat, plan.logits, plan.head_w, plan.head_b = P(bufs['g']), P(bufs['stat']), P(bufs['logits']), P(self.w['head.w']), P(wf['head.b'])
-        # the split records are merged in the out-projection GEMV's prologue, which holds K = d in one chunk per thread (256 threads x
-        # 16 bytes): wider models keep the one-workgroup-per-head attention
-        epv = 8 if self.code == PB_BF16 else 4
-        plan.attn_part = P(bufs['attn_part']) if (_DECODE_SPLIT and d <= 256 * epv) else None
-        for l in range(self.ND):
-            pf, L = 'dec.%d.' % l, plan.layers[l]
-            L.wqkv, L.bqkv, L.wo, L.bo = P(self.w[pf + 'wqkv']), P(wf[pf + 'bqkv']), P(self.w[pf + 'wo']), P(wf[pf + 'bo'])
-            L.ln1_w, L.ln1_b = P(wf[pf + 'ln1.w']), P(wf[pf + 'ln1.b'])
-            L.wq_c, L.bq_c, L.wo_c, L.bo_c = P(self.w[pf + 'wq_c']), P(wf[pf + 'bq_c']), P(self.w[pf + 'wo_c']), P(wf[pf + 'bo_c'])
-            L.lnc_w, L.lnc_b = P(wf[pf + 'lnc.w']), P(wf[pf + 'lnc.b'])
-            L.w1, L.b1, L.w2, L.b2 = P(self.w[pf + 'w1']), P(wf[pf + 'b1']), P(self.w[pf + 'w2']), P(wf[pf + 'b2'])
-            L.ln2_w, L.ln2_b = P(wf[pf + 'ln2.w']), P(wf[pf + 'ln2.b'])
-            L.kv_self, L.kv_cross = P(bufs['kvs'][l]), P(bufs['kvc'][l])
-        bp.B = B
-        for b in range(B):
-            bp.s_enc[b] = s_enc[b]
-        return bp, bufs
-
-    @staticmethod
-    def _decoder_create(bp):
-        """The fused decoder of `bp`, or None where it does not cover the shape (pb_batch_decoder_create holds the one rule)."""
-        import ctypes
-        dec = ctypes.c_void_p()
-        rc = int(LIB.query('pb_batch_decoder_create', ctypes.byref(bp), ctypes.byref(dec))) if _DECODE_SPLIT else 1
-        if rc < 0:
-            raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
-        return dec if rc == 0 else None
-
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0):
-        """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
-        k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds."""
-        import ctypes
-        tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
-        if k:
-            last = np.asarray([k - 1], dtype=np.int32)
-            LIB.call('pb_batch_decoder_start', dec, last.ctypes.data, tok_np.ctypes.data, None)
-        logit_cpu = torch.empty(ops.VOCAB, dtype=torch.float32)
-        tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
-        n = 0
-        t_loop = time.perf_counter()
-        for i in range(k, S if max_new is None else min(S, k + max_new)):
-            LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
-            n += 1
-            tok = sample_row(logit_cpu)
-            if (tok >= pad_cpu).any():
-                break
-            res_cpu[0, i] = tok
-            tok_np[:] = tok.numpy()
-        return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
-                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3)
-
-    # ---- batched generation ----------------------------------------------------------------------------------------------------
-    BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
-
-    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None):
-        """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
-        prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
-        contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
-        (None = the global stream); it is called for different rows from a small thread pool, one generator per row. enc_ids (B, S, 8),
-        emask (B, S) or None; returns (B, S, 8) with PAD after each prompt's stop.
-        Where the fused decode kernels cover the shape (bf16, head_dim 64 / 128, d a multiple of 256 up to 1024) and `sampler` names
-        the constants, up to BATCH_MAX prompts share one batched device-sampled decoder (pb_batch_decoder_*); every other case runs
-        the per-prompt loop over `generate` (_generate_batch_loop).
-        prefix (B, P, 8) with prefix_len (B lengths, None = P each): row b is primed with prefix[b, :prefix_len[b]] as in `generate`; rows with
-        length 0 are today's unprimed rows, so one batch may mix both (check_prefix holds the argument rules).
-        samples (an int n or P ints, check_samples): enc_ids / emask / prefix / prefix_len describe P prompts and prompt p is sampled n_p
-        times: rngs holds R = sum(n_p) generators and the result R rows, prompt-major, every row under the contract above. What the samples
-        of a prompt have in common is computed and stored once (_generate_batch_samples)."""
-        if samples is not None:
-            return self._generate_batch_samples(enc_ids, emask, sample_row, rngs, max_new, sampler, prefix, prefix_len, samples)
-        B = int(enc_ids.shape[0])
-        ks, rows = check_prefix(prefix, prefix_len, B, int(enc_ids.shape[1]), self.pb.pad_word_np)
-        if len(rngs) != B:
-            raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))
-        self._await_updates(2)
-        if B == 0:
-            return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
-        if not self._batch_decoder_covers(sampler):
-            return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows)
-        outs = []
-        for c0 in range(0, B, self.BATCH_MAX):
-            c1 = min(B, c0 + self.BATCH_MAX)
-            outs.append(self._generate_batch_chunk(enc_ids[c0:c1], emask[c0:c1] if emask is not None else None, sample_row, rngs[c0:c1],
-                                                   max_new, sampler, ks[c0:c1], rows[c0:c1] if rows is not None else None))
-        return torch.cat(outs, 0)
-
-    def _generate_batch_samples(self, enc_ids, emask, sample_row, rngs, max_new, sampler, prefix, prefix_len, samples):
-        """generate_batch with n_p samples of prompt p. The R rows go through the fused decoder in chunks of BATCH_MAX; inside a chunk the
-        encoder pass, the cross K|V projections and the prefill run once per distinct prompt (a prompt whose samples straddle a chunk
-        boundary is encoded once per chunk). Shapes the fused decoder declines run the per-prompt loop over the repeated prompts."""
-        P = int(enc_ids.shape[0])
-        owner = check_samples(samples, P, len(rngs))
-        ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
-        self._await_updates(2)
-        R = len(owner)
-        if R == 0:
-            return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
-        if not self._batch_decoder_covers(sampler):
-            return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner)
-        outs = []
-        for c0 in range(0, R, self.BATCH_MAX):
-            own = owner[c0:c0 + self.BATCH_MAX]
-            p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
-            outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
-                                                   rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
-                                                   groups=[p - p0 for p in own]))
-        return torch.cat(outs, 0)
-
-    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner):
-        """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt."""
-        idx = torch.as_tensor(owner, dtype=torch.long)
-        return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
-                                         max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None)
-
-    def _batch_decoder_covers(self, sampler):
-        """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
-        return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0 and _DECODE_SPLIT
-
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None):
-        """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
-        caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed)."""
-        saved = np.random.get_state()
-        outs = []
-        try:
-            for b in range(int(enc_ids.shape[0])):
-                np.random.set_state(rngs[b].get_state())
-                pre = rows[b:b + 1, :ks[b]] if rows is not None and ks[b] else None
-                outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
-                                          max_new=max_new, sampler=sampler, prefix=pre))
-                rngs[b].set_state(np.random.get_state())
-        finally:
-            np.random.set_state(saved)
-        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
-        return torch.cat(outs, 0)
-
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None):
-        """<= BATCH_MAX rows through one fused decoder. Encoder pass and cross K/V projections run per prompt, exactly as `generate`
-        runs them, into that prompt's slice of the cross caches; then the device-ahead / host-behind loop with per-row draws, per-row
-        verification and per-row rewinds (_decode_device_sampled).
-        groups None: one row per prompt, (B, S, 2d) cross caches. groups = [prompt of row b] (samples of a prompt, rows prompt-major):
-        enc_ids / emask / ks / rows describe the G distinct prompts; their encoder passes, projections and prefills run once each into
-        (G, S, 2d) cross caches that the rows read through pb_batch_decoder_share_cross, and a primed prompt's k prefix rows of every
-        layer's self cache are copied to its other samples' rows (a device copy, no arithmetic). The self caches, masks, positions,
-        limits, draws, verification and rewinds stay per row."""
-        G, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
-        shared = groups is not None
-        groups = list(groups) if shared else list(range(G))
-        B = len(groups)
-        first = [groups.index(g) for g in range(G)]                        # the row that receives prompt g's prefill
-        self.bind(dev)
-        pad_cpu = torch.from_numpy(self.pb.pad_word_np)
-        em = emask.to(torch.float32).contiguous() if emask is not None else None
-        enc16 = ops.ids_to_i16(enc_ids)
-        self.note_ids(enc16); self.check_ids(collective=False)
-        with torch.no_grad():
-            t_setup = time.perf_counter()
-            s_enc_g = [self._key_extent(em[g:g + 1] if em is not None else None, S) for g in range(G)]
-            s_enc = [s_enc_g[g] for g in groups]
-            em_rows = em[torch.as_tensor(groups, device=dev)].contiguous() if shared and em is not None else em      # the decoder's masks stay per row
-            kb = [ks[g] for g in groups]
-            bp, bufs = self._decode_plan(B, S, s_enc, em_rows, dev, G=G if shared else None)
-            dec = self._decoder_create(bp)
-            if dec is None:                                                # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups)
-            res_cpu = pad_cpu.repeat(B, S, 1)
-            timers = []
-            try:
-                if shared:
-                    kv_row = np.asarray(groups, dtype=np.int32)
-                    LIB.call('pb_batch_decoder_share_cross', dec, G, kv_row.ctypes.data)
-                for g in range(G):                                         # the batch-1 encoder pass (and prefill) of each prompt, into its cache slice
-                    emb = em[g:g + 1] if em is not None else None
-                    _, enc_out = self.forward_hidden(enc16[g:g + 1], None, emb, None, False, 0)
-                    for l in range(self.ND):
-                        self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][g], S, 2 * self.d, self.d)
-                    if ks[g]:
-                        b1 = first[g]
-                        timers.append(self._prefill(enc16[g:g + 1], emb, rows[g], ks[g], [t[b1] for t in bufs['kvs']]))
-                        for b in range(B):
-                            if groups[b] != g:
-                                continue
-                            res_cpu[b, :ks[g]] = rows[g, :ks[g]]
-                            if b != b1 and ks[g] < S:                      # the prefix rows of the prompt's other samples: copies of the prefilled ones
-                                for t in bufs['kvs']:
-                                    t[b, :ks[g]].copy_(t[b1, :ks[g]])
-                LIB.call('pb_batch_decoder_reset', dec, ops._stream(), _DECODE_GRAPH)
-                torch.cuda.current_stream().synchronize()
-                setup_ms = (time.perf_counter() - t_setup) * 1e3
-                fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
-                info = self._decode_device_sampled(dec, B, S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
-                                                   res_cpu, pad_cpu, max_new, fault, inline_verify=False, starts=kb)
-            finally:
-                LIB.call('pb_batch_decoder_destroy', dec)
-            self.last_decode = dict(info, s_enc=s_enc, batched=True, batch=B, prefix=kb, prefill_ms=sum(t() for t in timers), groups=groups,
-                                    encoder_passes=G, prefill_passes=sum(1 for k in ks if 0 < k < S), setup_ms=setup_ms,
-                                    cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
-            return res_cpu.to(dev)
-
-    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None):
-        """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
-        logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
-        (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
-        itself (pb_batch_decoder_sampler_init: model.py:68-107 in pb_nucleus_rows' arithmetic order) and runs on, K steps per hipGraph
-        replay, two runs in flight. The host follows one run behind: for every row position it calls sample(b, logged row) -- the
-        reference code path, consuming that row's generator exactly as the per-token loop does, so its state ends where the reference's
-        does -- and compares with the ids the device chose. They differ only where the device's softmax rounding (1 ulp against torch's CPU
-        softmax) crosses a threshold or a tie; then that row alone is rewound to the position with the host's token (pb_batch_decoder_seek
-        drains, then moves that row only) and everything it decoded behind it is discarded. A row whose host token is special stops there.
-        The result is the host's, token for token. inline_verify: the rows are replayed in this thread (B = 1) instead of a small pool.
-        starts[b] = k_b (primed rows): row b's positions 0 .. k_b - 1 are its prefix (in res_cpu, their K|V in the cache), so it starts at
-        k_b with input res_cpu[b, k_b - 1], its draws start at position k_b and it stops before min(S, k_b + max_new)
-        (pb_batch_decoder_start: per-row positions, inputs and limits in one upload)."""
-        import contextlib
-        import ctypes
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
-        K, vocab = 8, ops.VOCAB
-        starts = list(starts) if starts is not None else [0] * B
-        lim = [S if max_new is None else max(0, min(S, k + int(max_new))) for k in starts]
-        limit = max(lim)
-        U = np.zeros((B, S * 8), dtype=np.float64)
-        for b in range(B):
-            ahead = np.random.RandomState()
-            ahead.set_state(states[b])
-            U[b, starts[b] * 8:] = ahead.random_sample((S - starts[b]) * 8)
-        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
-        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
-        pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
-        t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
-        LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
-                 U.ctypes.data, B * S * 8, limit, int(fault[0]), int(fault[1]))
-        lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
-        LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
-        log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
-        log_tok = np.ctypeslib.as_array((ctypes.c_int16 * (B * S * 8)).from_address(tp.value)).reshape(B, S, 8)
-        first = np.ascontiguousarray(np.tile(np.asarray(self.pb.sos_word_np, dtype=np.int16), (B, 1)))
-        for b in range(B):
-            if starts[b]:
-                first[b] = res_cpu[b, starts[b] - 1].numpy().astype(np.int16)
-        last_pos, lim32 = np.asarray([k - 1 for k in starts], dtype=np.int32), np.asarray(lim, dtype=np.int32)
-        LIB.call('pb_batch_decoder_start', dec, last_pos.ctypes.data, first.ctypes.data, lim32.ctypes.data)
-        nxt = list(starts)                         # next position the enqueued work decodes, per row
-        live = [lim[b] > starts[b] for b in range(B)]     # the host has not stopped the row
-        tokens, rewinds = [0] * B, [0] * B
-        runs = deque()
-        steps, host_s = 0, 0.0
-
-        def launch(tok=None):
-            nonlocal steps
-            cnt = min(K, max(lim[b] - nxt[b] for b in range(B) if live[b]))
-            tk = int(LIB.query('pb_batch_decoder_launch', dec, cnt, None if tok is None else tok.ctypes.data))
-            if tk < 0:
-                raise PBError('pb_batch_decoder_launch failed (%d): %s' % (tk, LIB.load().pb_last_error().decode()))
-            spans = []
-            for b in range(B):
-                s = nxt[b]
-                e = min(lim[b], s + cnt) if live[b] else s
-                spans.append([s, e])
-                nxt[b] = e
-            runs.append((tk, spans))
-            steps += cnt
-
-        def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
-            for i in range(s, e):
-                tok = sample(b, log_logits[b, i])
-                tokens[b] += 1
-                if (tok >= pad_cpu).any():
-                    return ('stop', i)
-                res_cpu[b, i] = tok
-                t16 = tok.numpy().astype(np.int16)
-                if not np.array_equal(t16, log_tok[b, i]):
-                    return ('seek', i, t16)
-            return None
-
-        pending = lambda: any(live[b] and nxt[b] < lim[b] for b in range(B))
-        t_loop = time.perf_counter()
-        with (contextlib.nullcontext() if inline_verify else ThreadPoolExecutor(max_workers=min(B, 8))) as pool:
-            while runs or pending():
-                while len(runs) < 2 and pending():
-                    launch()
-                tk, spans = runs.popleft()
-                LIB.call('pb_batch_decoder_wait', dec, tk)
-                t_h = time.perf_counter()
-                todo = [b for b in range(B) if live[b] and spans[b][1] > spans[b][0]]
-                outcome = dict(zip(todo, (pool.map if pool else map)(lambda b: verify(b, *spans[b]), todo)))
-                host_s += time.perf_counter() - t_h
-                for b in todo:
-                    r = outcome[b]
-                    if r is None:
-                        continue
-                    if r[0] == 'stop':
-                        live[b] = False
-                        LIB.call('pb_batch_decoder_seek', dec, b, r[1], None)
-                    else:                                                  # drain, move row b back; its spans in the queued runs are void
-                        i = r[1]
-                        rewinds[b] += 1
-                        LIB.call('pb_batch_decoder_seek', dec, b, i, r[2].ctypes.data)
-                        nxt[b] = i + 1
-                        for _, sp in runs:
-                            sp[b][0] = sp[b][1] = i + 1
-        return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
-                    tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
-                    device_sampler=True, tokens_per_graph_replay=K)
-
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None):
-        """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
-        kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
-        rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing."""
-        pb, d, H, X = self.pb, self.d, self.H, self.xdt
-        self.bind(enc_ids.device)
-        S, dev = enc_ids.shape[1], enc_ids.device
-        pad = torch.from_numpy(pb.pad_word_np).to(dev)
-        pad_cpu = torch.from_numpy(pb.pad_word_np)
-        result = pad.repeat(1, S, 1)
-        em = emask.to(torch.float32).contiguous() if emask is not None else None
-        enc16 = ops.ids_to_i16(enc_ids)
-        self.note_ids(enc16); self.check_ids(collective=False)
-        e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
-        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            _, enc_out = self.forward_hidden(enc16, None, em, None, False, 0)
-            wf, ff = self.wf, self.fd
-            kvc = [e(S, 2 * d) for _ in range(self.ND)]
-            for l in range(self.ND):
-                self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, kvc[l], S, 2 * d, d)
-            kvs = [e(S, 2 * d) for _ in range(self.ND)]
-            x, q, ctx, a, y1, qc, ctxc, yc, y2 = (e(1, d) for _ in range(9))
-            u, g = e(1, ff), e(1, ff)
-            mr = f(8)
-            logits = f(1, ops.VOCAB)
-            save = dict(lse=f(1, H, 1)) if self.use_flash else dict(P=e(1, H, 1, S))
-            cur = torch.tensor(pb.sos_word_np, device=dev).reshape(1, 1, 8)
-            for i in range(S):
-                tok16 = ops.ids_to_i16(cur)
-                ops.embed_ln_fwd(tok16.reshape(1, 8), self.ptab, wf['lin.b'], wf['dec.pos'][i:], wf['dec.lne.w'], wf['dec.lne.b'], x,
-                                 mr[0:1], mr[1:2], 1, LN_EPS, 0, 0, 0.0, padded=True)
-                h = x
-                for l in range(self.ND):
-                    pf = 'dec.%d.' % l
-                    wqkv, bqkv = self.w[pf + 'wqkv'], wf[pf + 'bqkv']
-                    ops.gemm(h, wqkv, q, M=1, N=d, K=d, dtype=self.gcode, bias=bqkv[:d])
-                    ops.gemm(h, wqkv, kvs[l], M=1, N=2 * d, K=d, dtype=self.gcode, bias=bqkv[d:], b_off=d * d, c_off=i * 2 * d)
-                    self._attn_fwd((q, 0, d), (kvs[l], 0, 2 * d), (kvs[l], d, 2 * d), (ctx, 0, d), None, False, 1, 1, i + 1, save)
-                    self._linear(ctx, pf + 'wo', pf + 'bo', a, 1, d, d)
-                    ops.add_ln_fwd(h, a, wf[pf + 'ln1.w'], wf[pf + 'ln1.b'], y1, mr[2:3], mr[3:4], LN_EPS, 0, 0, 0.0)
-                    self._linear(y1, pf + 'wq_c', pf + 'bq_c', qc, 1, d, d)
-                    self._attn_fwd((qc, 0, d), (kvc[l], 0, 2 * d), (kvc[l], d, 2 * d), (ctxc, 0, d), em, False, 1, 1, S, save)
-                    self._linear(ctxc, pf + 'wo_c', pf + 'bo_c', a, 1, d, d)
-                    ops.add_ln_fwd(y1, a, wf[pf + 'lnc.w'], wf[pf + 'lnc.b'], yc, mr[4:5], mr[5:6], LN_EPS, 0, 0, 0.0)
-                    self._linear(yc, pf + 'w1', pf + 'b1', g, 1, ff, d, gelu_aux_out=u)
-                    self._linear(g, pf + 'w2', pf + 'b2', a, 1, d, ff)
-                    out = y2 if h is not y2 else x
-                    ops.add_ln_fwd(yc, a, wf[pf + 'ln2.w'], wf[pf + 'ln2.b'], out, mr[6:7], mr[7:8], LN_EPS, 0, 0, 0.0)
-                    h = out
-                if i < k:                                                  # a forced position: its token is the prefix row, no draw
-                    result[:, i, :] = pre[i].to(dev)
-                    cur = pre[i].to(dev).reshape(1, 1, 8)
-                    continue
-                ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
-                tok = sample_row(logits[0].cpu())
-                if (tok >= pad_cpu).any():
-                    break
-                result[:, i, :] = tok.to(dev)
-                cur = tok.to(dev).reshape(1, 1, 8)
-        return result
-
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None):
-        """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
-        cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k."""
-        pb = self.pb
-        self.bind(enc_ids.device)
-        S = enc_ids.shape[1]
-        dev = enc_ids.device
-        pad = torch.from_numpy(pb.pad_word_np).to(dev)
-        dec = pad.repeat(1, S, 1)
-        result = pad.repeat(1, S, 1)
-        dmask = torch.zeros(1, S, dtype=torch.float32, device=dev)
-        dec[:, 0, :] = torch.tensor(pb.sos_word_np, device=dev)
-        dmask[:, 0] = 1
-        if k:
-            n = min(k, S - 1)                                              # k = S: the last prefix row is no decoder input
-            dec[0, 1:n + 1] = pre[:n].to(dev)
-            dmask[0, :n + 1] = 1
-            result[0, :k] = pre.to(dev)
-        pad_cpu = torch.from_numpy(pb.pad_word_np)
-        em = emask.to(torch.float32).contiguous() if emask is not None else None
-        enc16 = ops.ids_to_i16(enc_ids)
-        self.note_ids(enc16); self.check_ids(collective=False)
-        with torch.no_grad():
-            for i in range(k, S):
-                dec16 = ops.ids_to_i16(dec)
-                dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
-                logits = self.heads_forward(dec_h)
-                cur = sample_row(logits[i].float().cpu())
-                if i != S - 1:
-                    dec[:, i + 1, :] = cur.to(dev)
-                    dmask[:, i + 1] += 1
-                if (cur >= pad_cpu).any():
-                    break
-                result[:, i, :] = cur.to(dev)
-        return result
 
 
 class _LMFn(torch.autograd.Function):

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .engine import sample_seed
+from .generation import sample_seed
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -381,7 +381,7 @@ class PianoBartLM(nn.Module):
             rngs = [np.random.RandomState(int(s)) for s in seeds]
         rngs = list(rngs)
         if samples_per_prompt is not None:
-            from .engine import check_samples
+            from .generation import check_samples
             check_samples(samples_per_prompt, B, len(rngs))
         elif len(rngs) != B:
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), B))

@@ -795,7 +795,7 @@ def test_graph_decode_equals_the_per_launch_decode(monkeypatch, d, heads, S):
     per-launch loop (pb_decode_step): the same tokens fed, logits equal to bf16 rounding. head_dim 64 and 128; S = 200 takes the
     self-attention through several key splits (65+ keys) and the cross-attention through 4."""
     _need_gpu()
-    from pianobart_amd import engine as E
+    from pianobart_amd import generation as E
     m = _lm(S, d, 2, 512, heads, 31, 'bf16').eval()
     with torch.no_grad():
         for i, p0 in enumerate([256, 128, 129, 256, 128, 32, 254, 49]):
@@ -844,7 +844,7 @@ def test_device_sampled_decode_emits_the_host_loops_tokens(monkeypatch, d, heads
     distributions (random weights: ~230 candidates under the p = 0.9 heads) and peaked ones (LM head scaled up), with `max_new`, and with
     the device's choice corrupted at every 7th position (decode_fault_period: the rewind path must restore the host's sequence)."""
     _need_gpu()
-    from pianobart_amd import engine as E
+    from pianobart_amd import generation as E
     m = _lm(S, d, 2, 512, heads, 31, 'bf16').eval()
     with torch.no_grad():
         for i, p0 in enumerate([256, 128, 129, 256, 128, 32, 254, 49]):

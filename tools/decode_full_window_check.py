@@ -3,7 +3,7 @@ S = 1024, specials unsamplable so that nothing stops early; tokens and np.random
   gpurun -- 'python tools/decode_full_window_check.py'   (round 6: equal, 1 024 tokens, 0 rewinds; loop 138.3 ms per-token path, 72.0 ms device-sampled)"""
 import sys, os, numpy as np, torch
 sys.path.insert(0, os.getcwd())
-from pianobart_amd import engine as E
+from pianobart_amd import generation as E
 from pianobart_amd.model import BartConfig, PianoBart, PianoBartLM
 from tests.golden_util import load_vocab, randomize_params, synth_octuple_batch
 e2w, w2e = load_vocab()
