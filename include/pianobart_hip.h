@@ -271,6 +271,24 @@ int pb_mask_count(const float* loss_mask, float* counts, float* partials /* >= p
  * w_i = weight_i * n_tok_i with the denominator sum(n_tok), i.e. scale = sum_w / sum(n_tok)) */
 int pb_loss_coef(const float* counts, const float* w /*device 8*/, float* coef, float scale, void* stream);
 
+/* ---- K16: teacher-forced scoring (pb_score.hip; additions to ABI 9) ---------------------------------
+ * The forward-only quantity of Ablation.py:126-166 (a teacher-forced decoder pass evaluated against the piece), per token instead of
+ * K9's 24 batch-wide sums. logits (T,V) f32 and seg_off as for pb_ce_fwd_bwd; target (T,8) int16; mask (T) f32 of 0 / 1, one value per
+ * POSITION. Per position and head, each (T,8):
+ *   logp    f32   x[target] - logsumexp(head), maximum subtracted
+ *   entropy f32   -sum p log p of the head's softmax, as log(sum e) - sum e (x - max) / sum e with e = exp(x - max); p == 0 counts as 0
+ *   rank    int16 columns of the head that beat the target: a greater logit, or an equal one at a lower index -- rank == 0 iff the
+ *                 target is the first maximum, the argmax of pb_ce_fwd_bwd
+ * A position with mask == 0 gets logp = 0, entropy = 0, rank = -1 and neither its logits nor its target are read. entropy and rank may
+ * be NULL. Heads of 1 .. 320 classes (the register-resident row layout of K9); a target outside its head scores a logit of 0 as in K9.
+ * pb_seq_scores: out (B,4,8) f32 = per sequence and head {sum mask*logp, sum mask*entropy, sum mask*[rank == 0], sum mask} over the S
+ * positions of sequence b (rows b*S .. b*S + S - 1 of the (B*S,8) arrays); entropy / rank NULL leave their plane 0. One workgroup per
+ * sequence, fixed summation order, no atomics (bit-reproducible). */
+int pb_token_scores(const float* logits, const int16_t* target, const float* mask, const int32_t* seg_off /*host 9*/, float* logp,
+                    float* entropy, int16_t* rank, int32_t T, int32_t V, void* stream);
+int pb_seq_scores(const float* logp, const float* entropy, const int16_t* rank, const float* mask, float* out, int32_t B, int32_t S,
+                  void* stream);
+
 /* ---- K10/K11: global grad norm, clip, HF-AdamW, bf16 shadow refresh --------------------------------
  * Replaces clip_grad_norm_(.,3.0) (pretrain.py:195) and transformers.AdamW.step (pretrain.py:76,196;
  * 4.29.2 formula: eps added to sqrt(v) before bias correction, decoupled decay after the update). */

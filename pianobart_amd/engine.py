@@ -20,6 +20,7 @@ from . import ops, rowpack
 
 from ._lib import LIB, PB_BF16, PB_F32, PB_F32X3, PBError
 from .generation import LN_EPS, GenerationMixin, check_prefix, check_samples, sample_seed  # noqa: F401 (the helpers stay importable from here)
+from .scoring import ScoringMixin
 
 _WGRAD_STREAM = int(os.environ.get('PB_WGRAD_STREAM', '7'))            # second HIP stream, bits: 1 = weight-gradient GEMMs, 2 = cross-attention K/V projections, 4 = backward GEMMs as ordinary grids (0: everything on one stream, for A/B)
 _WG_DXD_256 = int(os.environ.get('PB_WG_DXD_256', '1'))                         # the d x d weight gradients on the 256x256 ping-pong kernel (9 tiles x split-K 21) instead of 128x128 tiles (36 x 14); same-box A/B round 5: 58.01 / 58.01 -> 57.83 / 57.62 ms (profiles/r05_dxd_wgrad_ab.txt); 0 = the round-2 choice
@@ -92,7 +93,7 @@ def _new_stream(device):
     return torch.cuda.ExternalStream(st.value, device=device)
 
 
-class Engine(GenerationMixin):
+class Engine(GenerationMixin, ScoringMixin):
     def __init__(self, pianobart, mask_lm, precision='bf16'):
         if precision not in ('bf16', 'fp32', 'bf16x3'):
             raise PBError('precision must be "bf16", "fp32" or "bf16x3"')

@@ -15,6 +15,17 @@ RNG rules:
     [:, 0] is the --samples 1 file. --batch_size then counts output rows; the samples of a prompt inside one batch share its encoder
     pass and cross-attention K/V (PianoBartLM.generate_batch's samples_per_prompt), and the file does not depend on --batch_size.
 The prompts are sliced from the loaded array in order; --num_workers is accepted for the reference's command lines and not needed.
+
+Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
+  * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
+    of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
+    The encoder input and mask are the ones the generation saw. Path: --score_output, default --output with .npy -> _score.npy.
+  * --pick best (needs --score): of each prompt's n samples only the one with the largest sum_heads(sum_logp) / count is written,
+    (N, max_seq_len, 8); rows without a scored position rank last, ties go to the lower sample index (scoring.pick_best). The score
+    file keeps all n samples.
+  * --score_dataset (needs --prime, no --samples): no generation -- the dataset rows themselves are the targets, the encoder sees the primed
+    split (prime_inputs), start = k_b, length = the rows before the first bar PAD. Writes the score file only and prints the per-head mean
+    log-probability and top-1 hit rate over the scored positions.
 """
 import argparse
 import os
@@ -24,6 +35,7 @@ import torch
 
 from ._lib import PBError
 from .generation import sample_seed
+from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,7 +65,22 @@ def get_args(argv=None):
                     'L = rows whose bar id is not PAD (Ablation.py:134); the encoder sees rows < k only')
     ap.add_argument('--samples', type=int, default=1, help='continuations per prompt; n > 1 needs --seed and writes (N, n, max_seq_len, 8), '
                     'sample j of prompt i drawing from RandomState(seed + j * N + i)')
+    ap.add_argument('--score', action='store_true', help='also write the teacher-forced scores of the generated rows: float32 (N, 9) or (N, n, 9) = the 8 '
+                    'per-head sums of log-probability and the number of scored positions')
+    ap.add_argument('--score_output', type=str, default=None, help='path of the score file (default: --output with .npy replaced by _score.npy)')
+    ap.add_argument('--pick', type=str, default=None, choices=['best'], help='best: write only the sample of each prompt with the largest mean '
+                    'log-probability per scored position, (N, max_seq_len, 8); needs --score')
+    ap.add_argument('--score_dataset', action='store_true', help='no generation: score the dataset rows themselves behind their prime (needs --prime); '
+                    'writes only the score file')
     return ap.parse_args(argv)
+
+
+def score_path(args):
+    """--score_output, or --output with .npy replaced by _score.npy."""
+    if getattr(args, 'score_output', None):
+        return args.score_output
+    out = args.output
+    return (out[:-4] if out.endswith('.npy') else out) + '_score.npy'
 
 
 def parse_prime(value):
@@ -105,6 +132,13 @@ def check_args(args):
         raise PBError('--batch_size %d needs --seed: without it every prompt draws from the one global RNG stream in turn, which only the '
                       'batch-1 loop reproduces (the reference exits with ERROR for batches); with --seed s prompt i uses RandomState(s + i) '
                       'and the output does not depend on --batch_size' % args.batch_size)
+    if getattr(args, 'pick', None) is not None and not getattr(args, 'score', False):
+        raise PBError('--pick %s needs --score: the pick is made from the scores of the samples' % args.pick)
+    if getattr(args, 'score_dataset', False):
+        if getattr(args, 'prime', None) is None:
+            raise PBError('--score_dataset needs --prime: the encoder sees the first k rows of a piece and the rows behind them are scored')
+        if samples > 1:
+            raise PBError('--score_dataset scores the dataset rows themselves: it takes no --samples (got %d)' % samples)
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
         raise PBError('eval_generation runs on ONE device: give one id to --cuda_devices')
     if args.cpu:
@@ -130,7 +164,8 @@ def load_data(dataset_path, dataset_name):
 
 
 def eval_generation(args=None):
-    """Returns the float32 array it saved to args.output: (N, max_seq_len, 8), or (N, n, max_seq_len, 8) with --samples n > 1."""
+    """Returns the float32 array it saved to args.output: (N, max_seq_len, 8), or (N, n, max_seq_len, 8) with --samples n > 1 and no --pick;
+    under --score_dataset the (N, 9) score array it saved instead."""
     if args is None:
         args = get_args()
     check_args(args)
@@ -155,7 +190,31 @@ def eval_generation(args=None):
     prime = parse_prime(getattr(args, 'prime', None))
     samples = getattr(args, 'samples', 1)
     output = np.zeros((N, args.max_seq_len, 8) if samples == 1 else (N, samples, args.max_seq_len, 8), dtype=np.float32)
+    do_score = getattr(args, 'score', False)
+    scores = np.zeros((N, 9) if samples == 1 else (N, samples, 9), dtype=np.float32)
+
+    def score_rows(x, y, start):
+        """(R, 9) scores of the rows y of one generate call: encoder input x and its mask as the generation saw them, one row of x per row of y."""
+        r = model.score(x, y.to(device), (x[:, :, 0] != bar_pad).float(), start=start, device_num=-1)
+        return torch.cat([r.sum_logp, r.count[:, None]], 1).numpy(), r.hits.double().sum(0).numpy()
+
     print("\nEval Start")
+    if getattr(args, 'score_dataset', False):
+        hits = np.zeros(8)
+        for c0 in range(0, N, args.batch_size):
+            c1 = min(N, c0 + args.batch_size)
+            piece = torch.as_tensor(np.asarray(data[c0:c1])).long()
+            ks = prime_lengths(piece.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
+            x, _ = prime_inputs(piece, ks, model.pianobart.pad_word_np)
+            scores[c0:c1], h = score_rows(x.to(device), piece, ks)
+            hits += h
+        np.save(score_path(args), scores)
+        print("Saved", scores.shape, "to", score_path(args))
+        count = max(float(scores[:, 8].astype(np.float64).sum()), 1.0)
+        logp, hit = scores[:, :8].astype(np.float64).sum(0) / count, hits / count
+        print('LogP: {:06f} | logp: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}'.format(np.average(logp), *logp))
+        print('Hit: {:06f} | hit: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}'.format(np.average(hit), *hit))
+        return scores
     with torch.no_grad():
         rows = [(i, j) for i in range(N) for j in range(samples)] if samples > 1 else []      # prompt-major output rows
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
@@ -169,9 +228,15 @@ def eval_generation(args=None):
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
                                      device_num=device_num, decoder_prefix=prefix, prefix_len=ks,
-                                     samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)]).float().cpu().numpy()
+                                     samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
+            if do_score:
+                own = [i - c0 for i, _ in chunk]
+                sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
+            y = y.float().cpu().numpy()
             for r, (i, j) in enumerate(chunk):
                 output[i, j] = y[r]
+                if do_score:
+                    scores[i, j] = sc[r]
         for c0 in range(0, N if samples == 1 else 0, args.batch_size):
             c1 = min(N, c0 + args.batch_size)
             x = torch.as_tensor(np.asarray(data[c0:c1])).long()
@@ -187,6 +252,13 @@ def eval_generation(args=None):
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
                                          decoder_prefix=prefix, prefix_len=ks)
             output[c0:c1] = y.float().cpu().numpy()
+            if do_score:
+                scores[c0:c1], _ = score_rows(x, y, ks)
+    if do_score:
+        np.save(score_path(args), scores)
+        print("Saved", scores.shape, "to", score_path(args))
+        if getattr(args, 'pick', None) == 'best' and samples > 1:
+            output = output[np.arange(N), pick_best(scores)]
     np.save(args.output, output)
     print("Saved", output.shape, "to", args.output)
     return output

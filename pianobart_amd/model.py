@@ -391,8 +391,29 @@ class PianoBartLM(nn.Module):
                                  samples=samples_per_prompt)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
+    def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):
+        """Teacher-forced scores of B pieces (scoring.py; the forward-only quantity of Ablation.py:126-166): what the model thinks of
+        target_ids (B, S, 8) as decoder output for the encoder input input_ids_encoder (B, S, 8). Position i of row b is scored iff
+        start_b <= i < length_b. Defaults: length_b = the leading rows of target_ids[b] whose bar id is not the bar PAD (for a
+        generate_batch result the row's emitted length), start_b = 0 (for a primed row pass its prefix length: forced positions are then
+        not scored). Special ids (the EOS row of a dataset piece) are legal targets; an id outside its table raises IndexError.
+        Returns a SimpleNamespace of tensors: logp, entropy (B, S, 8) f32 and rank (B, S, 8) int16 (0 / 0 / -1 where not scored),
+        sum_logp, sum_entropy, hits (B, 8) f32 (hits = scored positions whose target is the head's argmax) and count (B,) f32 =
+        scored positions. Placed like generate_batch: CPU for device_num == -1, else cuda:device_num. The argument rules
+        (scoring.check_score_args) raise PBError before any device work."""
+        from .scoring import check_score_args
+        start, length = check_score_args(input_ids_encoder, target_ids, start, length, self.pianobart.bartConfig.max_position_embeddings,
+                                         self.pianobart.bar_pad_word)
+        if input_ids_encoder.device.type != 'cuda':
+            raise PBError('pianobart_amd needs HIP device tensors (got %s); there is no CPU path' % input_ids_encoder.device)
+        eng = self._get_engine()
+        r = eng.score(ops.ids_to_i16(input_ids_encoder), ops.ids_to_i16(torch.as_tensor(target_ids).to(input_ids_encoder.device)), encoder_attention_mask,
+                      start, length)
+        dst = torch.device('cpu') if device_num == -1 else torch.device('cuda', device_num)
+        return SimpleNamespace(**{k: v.to(dst) for k, v in vars(r).items()})
+
     # model.py:68-78 -- temperatures / nucleus thresholds per head
-    SAMPLE_T = [1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
+    SAMPLE_T =[1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
     def sample_row(self, row_logits, rng=None):

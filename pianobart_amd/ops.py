@@ -188,6 +188,20 @@ def ce_fwd_bwd(logits, target16, loss_mask, sums, partials, coef, dlogits, argma
              _p(argmax_out), T, V, dtype_code(dlogits.dtype) if dlogits is not None else PB_F32, _stream())
 
 
+def token_scores(logits, target16, mask, logp, entropy=None, rank=None):
+    """pb_token_scores: logits (T, V) f32, target16 (T, 8) int16, mask (T,) f32 of 0 / 1 -> logp / entropy (T, 8) f32, rank (T, 8) int16
+    (entropy and rank may be None)."""
+    T, V = logits.shape
+    LIB.call('pb_token_scores', _p(logits), _p(target16), _p(mask), _SEG9, _p(logp), _p(entropy), _p(rank), T, V, _stream())
+
+
+def seq_scores(logp, entropy, rank, mask, out):
+    """pb_seq_scores: the (B * S, 8) outputs of token_scores and mask (B, S) -> out (B, 4, 8) f32 = per sequence and head
+    {sum mask * logp, sum mask * entropy, sum mask * [rank == 0], sum mask}."""
+    B, S = mask.shape
+    LIB.call('pb_seq_scores', _p(logp), _p(entropy), _p(rank), _p(mask), _p(out), B, S, _stream())
+
+
 def mask_count(loss_mask, counts, partials):
     LIB.call('pb_mask_count', _p(loss_mask), _p(counts), _p(partials), loss_mask.numel() // 8, _stream())
 
