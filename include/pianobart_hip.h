@@ -23,7 +23,7 @@ extern "C" {
                         bf16 matrix cores with f32 accumulation (~2^-16 relative per product): the parity-grade instantiation that is not bound by
                         the f32-input MFMA rate (precision="bf16x3"); every other op of that instantiation runs its PB_F32 form */
 
-#define PB_ABI_VERSION 9   /* 9: one fused decoder for every B (pb_batch_decoder_*, + pb_batch_decoder_step; pb_decoder_* removed); 8 (round 6): + pb_decoder_sampler_init / launch / wait / logs / seek (device-sampled decode), dtype PB_F32X3 in pb_gemm, pb_flash_*_x3, pb_gemm_reserve_cus; 7 (round 5): + PB_GEMM_ROWDOT / rowdot_out in pb_gemm_desc, delta_rows in pb_flash_bwd1*; 6 (round 5): + pb_flash_bwd1_supported; 5 (round 4): + pb_flash_bwd1*, bh_order in the packed attention calls; 4 (round 3): + pb_decoder_*, pb_nucleus_rows, pb_ids_check */
+#define PB_ABI_VERSION 10  /* 10: pb_attn_desc + pb_attn_fwd / pb_attn_bwd / pb_attn_desc_bytes (the ten pb_flash_fwd* / pb_flash_bwd* calls removed); 9: one fused decoder for every B (pb_batch_decoder_*, + pb_batch_decoder_step; pb_decoder_* removed); 8 (round 6): + pb_decoder_sampler_init / launch / wait / logs / seek (device-sampled decode), dtype PB_F32X3 in pb_gemm, pb_flash_*_x3, pb_gemm_reserve_cus; 7 (round 5): + PB_GEMM_ROWDOT / rowdot_out in pb_gemm_desc, delta_rows in pb_flash_bwd1*; 6 (round 5): + pb_flash_bwd1_supported; 5 (round 4): + pb_flash_bwd1*, bh_order in the packed attention calls; 4 (round 3): + pb_decoder_*, pb_nucleus_rows, pb_ids_check */
 int pb_abi_version(void);
 const char* pb_last_error(void);
 
@@ -74,7 +74,7 @@ typedef struct pb_gemm_desc {
     float* colsum_ws;                 /* workspace of pb_gemm_colsum_ws_floats(M, N) floats */
     float* rowdot_out; int64_t ld_rowdot; /* PB_GEMM_ROWDOT (ABI 7): rowdot_out[(n / 64) * ld_rowdot + m] = sum over columns 64 (n / 64) .. + 63 of
                                          bf16(C[m][.]) * aux_in[m][.], f32 -- with C = dO (the input gradient of the attention output
-                                         projection) and aux_in = O this is the delta = rowsum(dO * O) per head that pb_flash_bwd1* reads
+                                         projection) and aux_in = O this is the delta = rowsum(dO * O) per head that the one-pass pb_attn_bwd reads
                                          (delta_rows). NT layout, M and N multiples of 256, bf16, no other epilogue; refused otherwise */
 } pb_gemm_desc;
 int pb_gemm(const pb_gemm_desc* d, void* stream);
@@ -159,78 +159,68 @@ int pb_softmax_fwd(const float* scores, const float* key_mask, void* P, int32_t 
 int pb_softmax_bwd(const float* dP, const void* P, void* dS, int64_t rows, int32_t Sk, float scale,
                    int32_t dtype, void* stream);
 
-/* ---- K4 fused (bf16): flash attention forward / backward, head_dim 32/64/128 --------------------
+/* ---- K4 fused: flash attention forward / backward, one descriptor for every form (ABI 10) ------------
  * Replaces modeling_bart.py:115-140 (eager) / F.scaled_dot_product_attention and its autograd backward.
- * q,k,v,o,dout,dq,dk,dv: bf16, element (b,s,h,c) at ptr[b*sb + s*ss + h*hd + c]; lse, delta: (B,H,Sq) f32.
- * dout must have o's strides. Backward = delta + dKV + dQ kernels (no atomics, deterministic). */
-/* kmax (B) int32, optional: 1 + index of the last visible key of each batch row (pb_key_extent); key tiles at or beyond
- * it are skipped (they are masked for every query). NULL = no skipping. Used by the head_dim-64 kernels. */
-int pb_key_extent(const float* key_mask, int32_t* kmax, int32_t B, int32_t Sk, void* stream);
-int pb_flash_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* key_mask, const int32_t* kmax,
-                 int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss,
-                 int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss,
-                 float scale, int32_t causal, void* stream);
-int pb_flash_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                 const float* key_mask, const int32_t* kmax, void* dq, void* dk, void* dv, float* delta,
-                 int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss,
-                 int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss,
-                 int64_t dq_sb, int64_t dq_ss, int64_t dk_sb, int64_t dk_ss, int64_t dv_sb, int64_t dv_ss,
-                 float scale, int32_t causal,
-                 float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws /* optional (all or none; head_dim 64/96/128): dbias_x[c] +=
-                     column sums of dQ / dK / dV over (batch, position) = the bias gradients of the q / k / v projections, taken from the
-                     kernels' epilogue registers; dbias_ws: pb_flash_bias_ws_floats(B, H, Sq, Sk, hd) floats */,
-                 void* stream);
-int64_t pb_flash_bias_ws_floats(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd);
-
-/* ---- K4 on packed rows (dead-row compaction, head_dim 64 / 96 / 128) -----------------------------
- * The PAD tail the reference computes and then masks (PianoBart.py:60-75: attention_mask hides rows as keys only) is dropped: the
- * rows of the batch lie back to back. Batch b's query rows are rows q_off[b] .. q_off[b] + q_len[b] - 1 of q / o / dout / dq
- * (row stride *_ss, element (row, h, c) at ptr[row*ss + h*hd + c]), its key rows k_off[b] .. k_off[b] + k_len[b] - 1 of
- * k / v / dk / dv; the first k_vis[b] key rows of the batch are the visible ones (the rest receive no gradient and are seen
- * by no query). causal: key row j is visible to query row i of the same batch iff j <= i (row indices within the batch) and
- * j < k_vis[b]. Sq_max / Sk_max: maxima of q_len / k_len (grid and LDS sizing); lse and delta are (B, H, Sq_max) f32.
- * dbias_ws: pb_flash_bias_ws_floats(B, H, Sq_max, Sk_max, hd) floats. All five descriptors are device int32 (B).
+ * dtype PB_BF16: q,k,v,o,dout,dq,dk,dv bf16, head_dim 32 / 64 / 96 / 128, strides multiples of 8 elements (dq_ss: of 4 for the kernel pair).
+ *   head_dim 64 / 96 / 128 run the pipelined kernels (pb_flash64.hip), head_dim 32 or PB_ATTN_GENERIC the generic ones (pb_flash.hip).
+ *   Backward = dQ (+ delta) and dK/dV kernels, no atomics, deterministic.
+ * dtype PB_F32X3 (the "bf16x3" parity instantiation, round 6): f32 q / k / v / o / gradients, every product a split-bf16 triple on the bf16
+ *   matrix cores (see PB_F32X3), softmax in f32 -- instead of the unfused QK^T -> softmax -> PV chain of the exact-f32 path, whose
+ *   (B, H, S, S) f32 matrices dominate that path's HBM time. head_dim 32 / 64 / 128 (pb_flash_x3_supported), strides multiples of 4
+ *   elements, operands 16-byte aligned. No dbias_*, bh_order or one-pass backward; kmax is read only beside a key_mask.
+ * Element (b,s,h,c) of an operand at ptr[b*sb + s*ss + h*hd + c], strides in ELEMENTS; dout has o's strides; lse, delta: (B,H,Sq) f32
+ * (delta is scratch written by the backward). Masks: key_mask (B,Sk) float (!= 0 keeps) or NULL, PB_ATTN_CAUSAL: key j visible to
+ * query i iff j <= i; a query without a visible key gives a zero output row and lse = +inf.
+ * kmax (B) int32, optional: 1 + index of the last visible key of each batch row (pb_key_extent); key tiles at or beyond it are skipped
+ * (they are masked for every query). NULL = no skipping. Used by the pipelined and the split-bf16 kernels.
+ *
+ * Packed rows (dead-row compaction; bf16: head_dim 64 / 96 / 128): the PAD tail the reference computes and then masks (PianoBart.py:60-75:
+ * attention_mask hides rows as keys only) is dropped: the rows of the batch lie back to back. Batch b's query rows are rows q_off[b] ..
+ * q_off[b] + q_len[b] - 1 of q / o / dout / dq (row stride *_ss, element (row, h, c) at ptr[row*ss + h*hd + c]), its key rows k_off[b] ..
+ * k_off[b] + k_len[b] - 1 of k / v / dk / dv; the first k_vis[b] key rows of the batch are the visible ones (the rest receive no gradient
+ * and are seen by no query). Causal: key row j is visible to query row i of the same batch iff j <= i (row indices within the batch) and
+ * j < k_vis[b]. The five descriptors are device int32 (B), all set or all NULL; with them Sq / Sk are the maxima of q_len / k_len (grid
+ * and LDS sizing, row length of lse / delta), and key_mask, kmax and the batch strides are not read.
  * bh_order (device int32, B * H entries, or NULL): the order in which the grid takes the (batch, head) pairs (entry = b * H + h). Costs
  * spread 4x over a packed batch; a caller that lists the pairs longest first, dealt eight at a time (one per XCD), removes the tail
- * of a static grid. It changes the order of the work only: results are bit-identical with and without it. */
-int pb_flash_fwd_packed(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* q_off,
-                        const int32_t* q_len, const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis,
-                        int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss,
-                        int64_t v_ss, int64_t o_ss, float scale, int32_t causal, const int32_t* bh_order, void* stream);
-int pb_flash_bwd_packed(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                        void* dq, void* dk, void* dv, float* delta, const int32_t* q_off, const int32_t* q_len,
-                        const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H,
-                        int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss,
-                        int64_t dq_ss, int64_t dk_ss, int64_t dv_ss, float scale, int32_t causal,
-                        float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, const int32_t* bh_order, void* stream);
-
-/* ---- K4b: attention backward in ONE pass (pb_flash1.hip, head_dim 64) -------------------------------
- * Same math, arguments and results (to bf16 rounding) as pb_flash_bwd / pb_flash_bwd_packed, computed key-stationary: a workgroup
- * owns 256 keys of one (batch, head), keeps their dK / dV in accumulator registers and sweeps the query tiles once (5 matrix
- * products and one exp pass per (query, key) pair instead of 7 and 2). dQ is summed over the key blocks without atomics: block j
- * writes its partial into bf16 slab j of dq_ws (pb_flash_bwd1_ws_bytes(rows of the q side, H, hd, Sk_max) bytes; packed rows:
- * q_rows = rows of the q tensor), a second kernel adds a row's slabs in f32 in block order and rounds once. Deterministic.
- * delta_rows (ABI 7, may be NULL): delta = rowsum(dO * O) per head as [H][rows of the q side] (dense: row = b * Sq + s), e.g. written by the
- * PB_GEMM_ROWDOT epilogue of the GEMM that produced dO; NULL = the call computes it itself into `delta` (B, H, Sq) with one more launch.
- * Replaces the autograd backward of tf:modeling_bart.py:115-140 like K4. */
+ * of a static grid. It changes the order of the work only: results are bit-identical with and without it. Read with packed rows only.
+ *
+ * dbias_q / k / v, dbias_ws (optional, all or none; pipelined kernels only): dbias_x[c] += column sums of dQ / dK / dV over (batch, position)
+ * = the bias gradients of the q / k / v projections, taken from the kernels' epilogue registers; dbias_ws: pb_flash_bias_ws_floats(B, H,
+ * Sq, Sk, hd) floats.
+ *
+ * PB_ATTN_ONE_PASS (K4b, pb_flash1.hip, bf16 head_dim 64, where pb_flash_bwd1_supported): the same backward (to bf16 rounding) computed
+ * key-stationary: a workgroup owns 256 keys of one (batch, head), keeps their dK / dV in accumulator registers and sweeps the query tiles
+ * once (5 matrix products and one exp pass per (query, key) pair instead of 7 and 2). dQ is summed over the key blocks without atomics:
+ * block j writes its partial into bf16 slab j of dq_ws (required: pb_flash_bwd1_ws_bytes(rows of the q side, H, hd, Sk) bytes), a second
+ * kernel adds a row's slabs in f32 in block order and rounds once. Deterministic. q_rows: rows of the q tensor (packed rows; dense: B * Sq
+ * is used). delta_rows (may be NULL): delta = rowsum(dO * O) per head as [H][rows of the q side] (dense: row = b * Sq + s), e.g. written by
+ * the PB_GEMM_ROWDOT epilogue of the GEMM that produced dO; NULL = the call computes it itself into `delta` with one more launch.
+ *
+ * A descriptor starts zeroed: what a call does not use stays 0 / NULL. pb_attn_fwd reads q, k, v and writes o, lse; pb_attn_bwd reads
+ * q, k, v, o, dout, lse and writes dq, dk, dv, delta. Both refuse a descriptor that names a combination without kernels. */
+int pb_key_extent(const float* key_mask, int32_t* kmax, int32_t B, int32_t Sk, void* stream);
+#define PB_ATTN_CAUSAL 1
+#define PB_ATTN_GENERIC 2        /* bf16, dense: use the generic kernels whatever the head_dim (tests); not with head_dim 96 */
+#define PB_ATTN_ONE_PASS 4       /* pb_attn_bwd: the one-pass kernel; pb_attn_fwd refuses the bit where pb_attn_bwd would (dtype, head_dim, generic) and otherwise ignores it */
+typedef struct pb_attn_desc {
+    const void *q, *k, *v; void* o; const void* dout; void *dq, *dk, *dv; float *lse, *delta;
+    const float* key_mask; const int32_t* kmax;
+    const int32_t *q_off, *q_len, *k_off, *k_len, *k_vis, *bh_order;
+    float *dbias_q, *dbias_k, *dbias_v, *dbias_ws;
+    void* dq_ws; const float* delta_rows; int64_t q_rows;
+    int64_t q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss, dq_sb, dq_ss, dk_sb, dk_ss, dv_sb, dv_ss;
+    int32_t dtype, B, H, Sq, Sk, hd, flags; float scale;
+} pb_attn_desc;
+int pb_attn_fwd(const pb_attn_desc* d, void* stream);
+int pb_attn_bwd(const pb_attn_desc* d, void* stream);
+int64_t pb_attn_desc_bytes(void);
+int64_t pb_flash_bias_ws_floats(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd);
 int64_t pb_flash_bwd1_ws_bytes(int64_t rows, int32_t H, int32_t hd, int32_t Sk_max);
 /* 1 if the one-pass kernel takes the shape (head_dim 64, Sq_max <= 6144: its per-sequence -lse / -delta tables live in LDS; dQ slabs
- * <= 8 GiB), else 0: call pb_flash_bwd / pb_flash_bwd_packed. rows = rows of the q side (dense: B * Sq). */
+ * <= 8 GiB), else 0: call pb_attn_bwd without PB_ATTN_ONE_PASS. rows = rows of the q side (dense: B * Sq). */
 int32_t pb_flash_bwd1_supported(int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t rows, int32_t H);
-int pb_flash_bwd1(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                  const float* key_mask, const int32_t* kmax, void* dq, void* dk, void* dv, float* delta,
-                  int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss,
-                  int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss,
-                  int64_t dq_sb, int64_t dq_ss, int64_t dk_sb, int64_t dk_ss, int64_t dv_sb, int64_t dv_ss,
-                  float scale, int32_t causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws,
-                  void* dq_ws, const float* delta_rows, void* stream);
-int pb_flash_bwd1_packed(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                         void* dq, void* dk, void* dv, float* delta, const int32_t* q_off, const int32_t* q_len,
-                         const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H,
-                         int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss,
-                         int64_t dq_ss, int64_t dk_ss, int64_t dv_ss, float scale, int32_t causal,
-                         float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, void* dq_ws, int64_t q_rows,
-                         const int32_t* bh_order, const float* delta_rows, void* stream);
+int pb_flash_x3_supported(int32_t hd);
 
 /* ---- row maps for the packed step (pb_rowmap.hip) ------------------------------------------------
  * pb_rowmap_count: counts (B,8) int32 = {encoder rows visible as keys (emask != 0), decoder rows visible as keys (dmask != 0),
@@ -487,36 +477,10 @@ int pb_batch_decoder_launches(void* dec);
 int pb_batch_decoder_graph(void* dec);
 int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const int32_t* kv_row);
 
-/* ---- fused attention of the "bf16x3" parity instantiation (round 6, ABI 8): f32 q / k / v / o, every product a split-bf16 triple on the
- * bf16 matrix cores (see PB_F32X3), softmax in f32 -- instead of the unfused QK^T -> softmax -> PV chain of the exact-f32 path
- * (modeling_bart.py:115-140 through PianoBart.py:76), whose (B, H, S, S) f32 matrices dominate that path's HBM time. Same masks and
- * conventions as pb_flash_fwd / pb_flash_bwd (key padding row per batch, bit 0 of `causal`, zero output row + lse = +inf for a query
- * without a visible key); strides in ELEMENTS, multiples of 4; head_dim 32 / 64 / 128 (pb_flash_x3_supported). kmax (may be NULL): per batch
- * row 1 + the last visible key (pb_key_extent of the mask): key tiles behind it are skipped, results unchanged. delta: (B, H, Sq) f32 scratch,
- * written by the call. */
-int pb_flash_x3_supported(int32_t hd);
-int pb_flash_fwd_x3(const float* q, const float* k, const float* v, float* o, float* lse, const float* key_mask, const int32_t* kmax, int32_t B, int32_t H, int32_t Sq,
-                    int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb,
-                    int64_t o_ss, float scale, int32_t causal, void* stream);
-int pb_flash_bwd_x3(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse, const float* key_mask,
-                    const int32_t* kmax, float* dq, float* dk, float* dv, float* delta, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb,
-                    int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss, int64_t dq_sb,
-                    int64_t dq_ss, int64_t dk_sb, int64_t dk_ss, int64_t dv_sb, int64_t dv_ss, float scale, int32_t causal, void* stream);
-
-/* the same on packed rows (the layout of pb_flash_fwd_packed / pb_flash_bwd_packed: per-sequence q_off / q_len / k_off / k_len and the visible-key count k_vis
- * instead of a key mask; Sq_max / Sk_max = the longest sequence) */
-int pb_flash_fwd_x3_packed(const float* q, const float* k, const float* v, float* o, float* lse, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off,
-                           const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss,
-                           int64_t k_ss, int64_t v_ss, int64_t o_ss, float scale, int32_t causal, void* stream);
-int pb_flash_bwd_x3_packed(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse, float* dq, float* dk, float* dv,
-                           float* delta, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis,
-                           int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss,
-                           int64_t dq_ss, int64_t dk_ss, int64_t dv_ss, float scale, int32_t causal, void* stream);
-
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd
  * node under BartModel, modeling_bart.py:280-390) leave their kernels as per-workgroup partial rows. Between pb_defer_begin and
- * pb_defer_flush (same host thread) pb_add_ln_bwd, pb_gemm (colsum_out) and pb_flash_bwd (dbias_*) keep those rows in `arena`
+ * pb_defer_flush (same host thread) pb_add_ln_bwd, pb_gemm (colsum_out) and pb_attn_bwd (dbias_*) keep those rows in `arena`
  * instead of reducing them one small launch at a time, and pb_defer_flush sums all of them in ONE launch, in a fixed order
  * (bit-reproducible). arena: device floats, 16-byte aligned; table: device bytes, table_entries * pb_defer_desc_bytes(). When either
  * is full the calls fall back to the immediate reduction. Outputs are accumulated (+=) exactly as without deferral, so they must

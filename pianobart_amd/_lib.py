@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('PB_LIB_PATH') or os.path.join(HERE, 'libpianobart_hip
 PB_F32, PB_BF16, PB_F32X3 = 0, 1, 2
 GEMM_ACCUM, GEMM_C_F32, GEMM_GELU, GEMM_MUL_GELU_GRAD = 1, 2, 4, 8
 GEMM_ROWDOT = 131072
+ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS = 1, 2, 4
 
 
 class GemmDesc(ctypes.Structure):
@@ -55,12 +56,34 @@ _SCALARS = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint64_t': ct
             'uint32_t': ctypes.c_uint32, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int': ctypes.c_int}
 
 
-def parse_header(path=HEADER):
-    """Returns {name: (restype, [argtypes])} for every function the header declares."""
+def _header_source(path):
     src = open(path).read()
     src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
-    src = re.sub(r'//[^\n]*', ' ', src)
-    src = re.sub(r'typedef\s+struct.*?}\s*\w+\s*;', ' ', src, flags=re.S)
+    return re.sub(r'//[^\n]*', ' ', src)
+
+
+def parse_struct(name, path=HEADER):
+    """The ctypes _fields_ of the header's `typedef struct <name>`: pointers become c_void_p, scalars go through _SCALARS.
+    A declaration is all pointers or all scalars (`float *a, b;` is not understood: write two declarations), no arrays, no nested structs."""
+    body = re.search(r'typedef\s+struct\s+%s\s*{(.*?)}\s*%s\s*;' % (name, name), _header_source(path), flags=re.S).group(1)
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(';'))):
+        if '*' in decl:
+            fields += [(n, ctypes.c_void_p) for n in re.findall(r'\*\s*(\w+)', decl)]
+        else:
+            ctype, names = decl.replace('const', '').split(None, 1)
+            fields += [(n.strip(), _SCALARS[ctype]) for n in names.split(',')]
+    return fields
+
+
+class AttnDesc(ctypes.Structure):
+    """pb_attn_desc, laid out by the header itself."""
+    _fields_ = parse_struct('pb_attn_desc')
+
+
+def parse_header(path=HEADER):
+    """Returns {name: (restype, [argtypes])} for every function the header declares."""
+    src = re.sub(r'typedef\s+struct.*?}\s*\w+\s*;', ' ', _header_source(path), flags=re.S)
     decls = {}
     for m in re.finditer(r'(const\s+char\s*\*|int64_t|int)\s+(pb_\w+)\s*\(([^;{]*?)\)\s*;', src, flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
@@ -70,7 +93,7 @@ def parse_header(path=HEADER):
             for a in args.split(','):
                 a = a.strip()
                 if '*' in a:
-                    argtypes.append(ctypes.POINTER(GemmDesc) if 'pb_gemm_desc' in a else ctypes.c_void_p)
+                    argtypes.append(ctypes.POINTER(GemmDesc) if 'pb_gemm_desc' in a else ctypes.POINTER(AttnDesc) if 'pb_attn_desc' in a else ctypes.c_void_p)
                 else:
                     argtypes.append(_SCALARS[a.replace('const', '').split()[0]])
         decls[name] = (restype, argtypes)
@@ -97,8 +120,8 @@ class _Lib:
                 fn.restype = restype
                 fn.argtypes = argtypes
             ver = dll.pb_abi_version()
-            if ver != 9:
-                raise PBError('ABI version mismatch: library %d, binding 9' % ver)
+            if ver != 10:
+                raise PBError('ABI version mismatch: library %d, binding 10' % ver)
             self._dll = dll
         return self._dll
 

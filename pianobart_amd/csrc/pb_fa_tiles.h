@@ -22,7 +22,7 @@ struct Fa64Args {
     float scale; int causal;
     float* cs_q; float* cs_kv;        // bias-gradient partials (column sums of dQ | of dK, dV), or NULL
     const bf16_t* zeros;              // >= 16 bytes of zeros (source of the column chunks beyond head_dim in a partly filled image)
-    // packed rows ("varlen", pb_flash_*_packed): batch b's query rows are rows vl_q_off[b] .. + vl_q_len[b] - 1 of q / o / dout / dq (row
+    // packed rows ("varlen", the row descriptors of pb_attn_desc): batch b's query rows are rows vl_q_off[b] .. + vl_q_len[b] - 1 of q / o / dout / dq (row
     // stride *_ss; the batch strides are not used), its key rows vl_k_off[b] .. + vl_k_len[b] - 1 of k / v / dk / dv, of which the
     // first kmax[b] are visible; Sq / Sk are the maxima over the batch (grid, LDS, and the row length of lse / delta). NULL: dense.
     const int *vl_q_off, *vl_k_off, *vl_q_len, *vl_k_len;
@@ -31,6 +31,23 @@ struct Fa64Args {
     // longest first, eight at a time across the XCDs. Only the order of the work changes, never a result.
     const int* bh_order;
 };
+
+// The kernel arguments of a checked descriptor (pb_flash.hip: with packed rows its batch strides, key_mask and kmax are zero). Forward
+// writes d.o (`out`), backward reads it (`o`); cs_q / cs_kv are the backward's own. zeros == NULL: the zero page could not be made.
+inline Fa64Args fa64_args(const pb_attn_desc& d, bool bwd) {
+    Fa64Args a = {};
+    a.q = (const bf16_t*)d.q; a.k = (const bf16_t*)d.k; a.v = (const bf16_t*)d.v; a.dout = (const bf16_t*)d.dout;
+    if (bwd) a.o = (const bf16_t*)d.o; else a.out = (bf16_t*)d.o;
+    a.dq = (bf16_t*)d.dq; a.dk = (bf16_t*)d.dk; a.dv = (bf16_t*)d.dv; a.lse = d.lse; a.delta = d.delta;
+    a.key_mask = d.key_mask; a.kmax = d.q_off ? d.k_vis : d.kmax;
+    a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk;
+    a.q_sb = d.q_sb; a.q_ss = d.q_ss; a.k_sb = d.k_sb; a.k_ss = d.k_ss; a.v_sb = d.v_sb; a.v_ss = d.v_ss; a.o_sb = d.o_sb; a.o_ss = d.o_ss;
+    a.dq_sb = d.dq_sb; a.dq_ss = d.dq_ss; a.dk_sb = d.dk_sb; a.dk_ss = d.dk_ss; a.dv_sb = d.dv_sb; a.dv_ss = d.dv_ss;
+    a.scale = d.scale; a.causal = d.flags & PB_ATTN_CAUSAL;
+    a.zeros = (const bf16_t*)pb_zero_page();
+    a.vl_q_off = d.q_off; a.vl_k_off = d.k_off; a.vl_q_len = d.q_len; a.vl_k_len = d.k_len; a.bh_order = d.bh_order;
+    return a;
+}
 
 // Packed rows: give the kernel body the view of ONE batch -- its own Sq / Sk and base pointers rebased so that the dense address
 // arithmetic (ptr + b * batch_stride + row * row_stride) lands on the batch's first packed row.

@@ -402,23 +402,6 @@ __global__ __launch_bounds__(FA_THREADS) void fa_bwd_dq_kernel(const FaArgs p) {
     }
 }
 
-int check_common(const char* who, int hd, long a, long b2, long c2, long d2) {
-    PB_REQUIRE(hd == 32 || hd == 64 || hd == 96 || hd == 128, "%s: head_dim %d not supported by the flash kernels (32/64/96/128)", who, hd);
-    PB_REQUIRE(a % 8 == 0 && b2 % 8 == 0 && c2 % 8 == 0 && d2 % 8 == 0, "%s: strides must be multiples of 8 elements", who);
-    return 0;
-}
-
-}  // namespace
-
-int pb_flash64_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* key_mask, const int* kmax, int B, int H, int Sq, int Sk, int hd,
-                   long q_sb, long q_ss, long k_sb, long k_ss, long v_sb, long v_ss, long o_sb, long o_ss, float scale, int causal, hipStream_t stream,
-                   const int* const* vl = nullptr);
-int pb_flash64_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, const float* key_mask,
-                   const int* kmax, void* dq, void* dk, void* dv, int B, int H, int Sq, int Sk, int hd, long q_sb, long q_ss, long k_sb, long k_ss, long v_sb,
-                   long v_ss, long o_sb, long o_ss, long dq_sb, long dq_ss, long dk_sb, long dk_ss, long dv_sb, long dv_ss, float scale,
-                   int causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, hipStream_t stream, const int* const* vl = nullptr);
-
-namespace {
 __global__ void key_extent_kernel(const float* __restrict__ key_mask, int* __restrict__ kmax, int Sk) {
     const int b = blockIdx.x;
     int m = 0;
@@ -445,86 +428,92 @@ extern "C" int pb_key_extent(const float* key_mask, int32_t* kmax, int32_t B, in
         default: { constexpr int HD = 128; __VA_ARGS__; } break; \
     }
 
-extern "C" int pb_flash_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* key_mask, const int32_t* kmax, int32_t B,
-                            int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss,
-                            int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss, float scale, int32_t causal, void* stream_) {
-    if (check_common("pb_flash_fwd", hd, q_ss, k_ss, v_ss, o_ss)) return -2;
-    PB_REQUIRE(q_sb % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 && o_sb % 8 == 0, "pb_flash_fwd: batch strides must be multiples of 8");
-    if (B <= 0 || H <= 0 || Sq <= 0) return 0;
-    PB_REQUIRE(hd != 96 || !(causal & 2), "pb_flash_fwd: head_dim 96 exists in the pipelined kernel family only");
-    if ((hd == 64 || hd == 96 || hd == 128) && !(causal & 2))      // bit 1 of `causal` forces the generic kernel (tests)
-        return pb_flash64_fwd(q, k, v, o, lse, key_mask, kmax, B, H, Sq, Sk, hd, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss, scale, causal & 1, (hipStream_t)stream_);
+// the kernel arguments of a checked dense descriptor; forward writes d.o, backward reads it
+static FaArgs fa_args(const pb_attn_desc& d, bool bwd) {
     FaArgs a = {};
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse; a.key_mask = key_mask;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.scale = scale; a.causal = causal & 1;
-    dim3 grid((Sq + TQ - 1) / TQ, H, B);
-    FA_DISPATCH(hd, hipLaunchKernelGGL((fa_fwd_kernel<HD>), grid, dim3(FA_THREADS), 2 * 64 * HD * 2 + 256, (hipStream_t)stream_, a));
+    a.q = (const bf16_t*)d.q; a.k = (const bf16_t*)d.k; a.v = (const bf16_t*)d.v; a.dout = (const bf16_t*)d.dout;
+    if (bwd) a.o = (const bf16_t*)d.o; else a.out = (bf16_t*)d.o;
+    a.dq = (bf16_t*)d.dq; a.dk = (bf16_t*)d.dk; a.dv = (bf16_t*)d.dv; a.lse = d.lse; a.delta = d.delta; a.key_mask = d.key_mask;
+    a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk;
+    a.q_sb = d.q_sb; a.q_ss = d.q_ss; a.k_sb = d.k_sb; a.k_ss = d.k_ss; a.v_sb = d.v_sb; a.v_ss = d.v_ss; a.o_sb = d.o_sb; a.o_ss = d.o_ss;
+    a.dq_sb = d.dq_sb; a.dq_ss = d.dq_ss; a.dk_sb = d.dk_sb; a.dk_ss = d.dk_ss; a.dv_sb = d.dv_sb; a.dv_ss = d.dv_ss;
+    a.scale = d.scale; a.causal = d.flags & PB_ATTN_CAUSAL;
+    return a;
+}
+
+// Every precondition of pb_attn_fwd / pb_attn_bwd, before any HIP call. d is the call's own copy: with packed rows what is not read (batch
+// strides, key_mask, kmax) is zeroed here, and so is bh_order without them, so that the families see one form. The forward refuses a one-pass bit
+// that names no kernel, like the backward, and otherwise does not read it. < 0: refused; 1: an empty shape, nothing to do; 0: go on.
+static int attn_check(pb_attn_desc& d, const char* who, bool bwd) {
+    const bool x3 = d.dtype == PB_F32X3, generic = d.flags & PB_ATTN_GENERIC, hd64 = d.hd == 64 || d.hd == 96 || d.hd == 128;
+    PB_REQUIRE(x3 || d.dtype == PB_BF16, "%s: dtype %d (PB_BF16 or PB_F32X3)", who, d.dtype);
+    if (x3) PB_REQUIRE(d.hd == 32 || d.hd == 64 || d.hd == 128, "%s: head_dim %d (32 / 64 / 128 with PB_F32X3)", who, d.hd);
+    else PB_REQUIRE(d.hd == 32 || hd64, "%s: head_dim %d not supported by the flash kernels (32/64/96/128)", who, d.hd);
+    PB_REQUIRE(!(d.flags & PB_ATTN_ONE_PASS) || (!x3 && d.hd == 64 && !generic), "%s: the one-pass backward is bf16, head_dim 64, not generic (dtype %d, head_dim %d, flags %d)", who, d.dtype, d.hd, d.flags);
+    const bool one_pass = bwd && (d.flags & PB_ATTN_ONE_PASS);
+    const int32_t* const rows[5] = {d.q_off, d.q_len, d.k_off, d.k_len, d.k_vis};
+    static const char* const row_names[5] = {"q_off", "q_len", "k_off", "k_len", "k_vis"};
+    const bool packed = rows[0] || rows[1] || rows[2] || rows[3] || rows[4];
+    for (int i = 0; i < 5; ++i) PB_REQUIRE(!packed || rows[i], "%s: the five row descriptors are required (%s is NULL)", who, row_names[i]);
+    PB_REQUIRE(!packed || x3 || hd64, "%s: packed rows with head_dim %d (64 / 96 / 128 only)", who, d.hd);
+    PB_REQUIRE(!packed || !generic, "%s: the generic kernels (flags %d) do not take packed rows", who, d.flags);
+    if (packed) { d.q_sb = d.k_sb = d.v_sb = d.o_sb = d.dq_sb = d.dk_sb = d.dv_sb = 0; d.key_mask = nullptr; d.kmax = nullptr; }
+    else d.bh_order = nullptr;
+    // strides in elements: whole 16-byte pieces of a row; the kernel pair stores dQ in 8-byte pieces and dK / dV by element
+    const int64_t st[14] = {d.q_sb, d.q_ss, d.k_sb, d.k_ss, d.v_sb, d.v_ss, d.o_sb, d.o_ss, d.dq_sb, d.dq_ss, d.dk_sb, d.dk_ss, d.dv_sb, d.dv_ss};
+    static const char* const st_names[14] = {"q_sb", "q_ss", "k_sb", "k_ss", "v_sb", "v_ss", "o_sb", "o_ss", "dq_sb", "dq_ss", "dk_sb", "dk_ss", "dv_sb", "dv_ss"};
+    static const int m_pair[6] = {1, 4, 1, 1, 1, 1}, m_one_pass[6] = {8, 8, 1, 8, 1, 8};      // dq_sb, dq_ss, dk_sb, dk_ss, dv_sb, dv_ss
+    for (int i = 0; i < 14; ++i) {
+        const int m = x3 ? 4 : i < 8 ? 8 : (one_pass ? m_one_pass : m_pair)[i - 8];
+        PB_REQUIRE(st[i] % m == 0, "%s: stride %s = %lld must be a multiple of %d elements", who, st_names[i], (long long)st[i], m);
+    }
+    if (x3) PB_REQUIRE(((uintptr_t)d.q | (uintptr_t)d.k | (uintptr_t)d.v | (uintptr_t)d.o | (uintptr_t)d.dout | (uintptr_t)d.dq | (uintptr_t)d.dk | (uintptr_t)d.dv) % 16 == 0,
+                       "%s: PB_F32X3 operands must be 16-byte aligned", who);
+    if (d.B <= 0 || d.H <= 0 || d.Sq <= 0 || (one_pass && d.Sk <= 0)) return 1;
+    PB_REQUIRE(d.hd != 96 || !generic, "%s: head_dim 96 exists in the pipelined kernel family only", who);
+    PB_REQUIRE(!x3 || (!d.dbias_q && !d.dbias_k && !d.dbias_v && !d.dbias_ws && !d.bh_order), "%s: no dbias_* and no bh_order with PB_F32X3", who);
+    if (d.dbias_q) {
+        PB_REQUIRE(d.dbias_k && d.dbias_v && d.dbias_ws, "%s: dbias_q/k/v and dbias_ws go together", who);
+        PB_REQUIRE(hd64 && !generic, "%s: fused bias gradients (dbias_*) exist in the pipelined kernels (head_dim 64 / 96 / 128) only", who);
+    }
+    PB_REQUIRE(!one_pass || d.dq_ws, "%s: the dQ slab workspace dq_ws is required by the one-pass kernel (pb_flash_bwd1_ws_bytes)", who);
+    return 0;
+}
+
+extern "C" int64_t pb_attn_desc_bytes(void) { return (int64_t)sizeof(pb_attn_desc); }
+
+extern "C" int pb_attn_fwd(const pb_attn_desc* desc, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    pb_attn_desc d = *desc;
+    if (const int rc = attn_check(d, "pb_attn_fwd", false)) return rc < 0 ? rc : 0;
+    if (d.dtype == PB_F32X3) return pb_flash_x3_fwd(d, stream);
+    if (d.hd != 32 && !(d.flags & PB_ATTN_GENERIC)) return pb_flash64_fwd(d, stream);
+    const FaArgs a = fa_args(d, false);
+    dim3 grid((d.Sq + TQ - 1) / TQ, d.H, d.B);
+    FA_DISPATCH(d.hd, hipLaunchKernelGGL((fa_fwd_kernel<HD>), grid, dim3(FA_THREADS), 2 * 64 * HD * 2 + 256, stream, a));
     PB_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int pb_flash_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                            const float* key_mask, const int32_t* kmax, void* dq, void* dk, void* dv, float* delta, int32_t B, int32_t H, int32_t Sq,
-                            int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb,
-                            int64_t v_ss, int64_t o_sb, int64_t o_ss, int64_t dq_sb, int64_t dq_ss, int64_t dk_sb, int64_t dk_ss,
-                            int64_t dv_sb, int64_t dv_ss, float scale, int32_t causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws,
-                            void* stream_) {
+extern "C" int pb_attn_bwd(const pb_attn_desc* desc, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (check_common("pb_flash_bwd", hd, q_ss, k_ss, v_ss, o_ss)) return -2;
-    PB_REQUIRE(dq_ss % 4 == 0 && q_sb % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 && o_sb % 8 == 0, "pb_flash_bwd: bad strides");
-    if (B <= 0 || H <= 0 || Sq <= 0) return 0;
-    FaArgs a = {};
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dout = (const bf16_t*)dout;
-    a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = const_cast<float*>(lse); a.delta = delta; a.key_mask = key_mask;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
-    a.scale = scale; a.causal = causal & 1;
+    pb_attn_desc d = *desc;
+    if (const int rc = attn_check(d, "pb_attn_bwd", true)) return rc < 0 ? rc : 0;
+    if (d.dtype == PB_F32X3) return pb_flash_x3_bwd(d, stream);
+    if (d.flags & PB_ATTN_ONE_PASS) return pb_flash1_bwd(d, stream);
+    if (d.hd != 32 && !(d.flags & PB_ATTN_GENERIC)) return pb_flash64_bwd(d, stream);      // the pipelined family computes delta inside its dQ kernel
+    const FaArgs a = fa_args(d, true);
+    const int B = d.B, H = d.H, Sq = d.Sq, Sk = d.Sk;
     const long nrow = (long)B * H * Sq;
-    PB_REQUIRE(hd != 96 || !(causal & 2), "pb_flash_bwd: head_dim 96 exists in the pipelined kernel family only");
-    if ((hd == 64 || hd == 96 || hd == 128) && !(causal & 2))          // the pipelined family computes delta inside its dQ kernel
-        return pb_flash64_bwd(q, k, v, o, dout, lse, delta, key_mask, kmax, dq, dk, dv, B, H, Sq, Sk, hd, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss,
-                              dq_sb, dq_ss, dk_sb, dk_ss, dv_sb, dv_ss, scale, causal & 1, dbias_q, dbias_k, dbias_v, dbias_ws, stream);
-    FA_DISPATCH(hd, hipLaunchKernelGGL((fa_delta_kernel<HD>), dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, stream, a.o, a.dout, delta, B, H, Sq, o_sb, o_ss));
+    FA_DISPATCH(d.hd, hipLaunchKernelGGL((fa_delta_kernel<HD>), dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, stream, a.o, a.dout, d.delta, B, H, Sq, a.o_sb, a.o_ss));
     PB_LAUNCH_CHECK();
-    PB_REQUIRE(!dbias_q, "pb_flash_bwd: fused bias gradients exist in the pipelined kernels (head_dim 64 / 96 / 128) only");
     dim3 gk((Sk + TK - 1) / TK, H, B), gq((Sq + TQ - 1) / TQ, H, B);
-    if (hd == 128) {   // 4 x 16 KiB tiles exceed the default 64 KiB dynamic-LDS limit
+    if (d.hd == 128) {   // 4 x 16 KiB tiles exceed the default 64 KiB dynamic-LDS limit
         PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_bwd_dkv_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 512));
     }
-    FA_DISPATCH(hd, hipLaunchKernelGGL((fa_bwd_dkv_kernel<HD>), gk, dim3(FA_THREADS), 4 * 64 * HD * 2 + 512, stream, a));
+    FA_DISPATCH(d.hd, hipLaunchKernelGGL((fa_bwd_dkv_kernel<HD>), gk, dim3(FA_THREADS), 4 * 64 * HD * 2 + 512, stream, a));
     PB_LAUNCH_CHECK();
-    FA_DISPATCH(hd, hipLaunchKernelGGL((fa_bwd_dq_kernel<HD>), gq, dim3(FA_THREADS), 3 * 64 * HD * 2 + 256, stream, a));
+    FA_DISPATCH(d.hd, hipLaunchKernelGGL((fa_bwd_dq_kernel<HD>), gq, dim3(FA_THREADS), 3 * 64 * HD * 2 + 256, stream, a));
     PB_LAUNCH_CHECK();
     return 0;
-}
-
-// ---- packed rows ("varlen"): the batch rows of different lengths lie back to back; see include/pianobart_hip.h
-extern "C" int pb_flash_fwd_packed(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* q_off, const int32_t* q_len,
-                                   const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H, int32_t Sq_max,
-                                   int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss, float scale,
-                                   int32_t causal, const int32_t* bh_order, void* stream_) {
-    if (check_common("pb_flash_fwd_packed", hd, q_ss, k_ss, v_ss, o_ss)) return -2;
-    PB_REQUIRE(hd == 64 || hd == 96 || hd == 128, "pb_flash_fwd_packed: head_dim %d (64 / 96 / 128 only)", hd);
-    PB_REQUIRE(q_off && q_len && k_off && k_len && k_vis, "pb_flash_fwd_packed: the five row descriptors are required");
-    if (B <= 0 || H <= 0 || Sq_max <= 0) return 0;
-    const int* vl[5] = {q_off, q_len, k_off, k_len, bh_order};
-    return pb_flash64_fwd(q, k, v, o, lse, nullptr, k_vis, B, H, Sq_max, Sk_max, hd, 0, q_ss, 0, k_ss, 0, v_ss, 0, o_ss, scale, causal & 1,
-                          (hipStream_t)stream_, vl);
-}
-
-extern "C" int pb_flash_bwd_packed(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
-                                   void* dk, void* dv, float* delta, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off,
-                                   const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd,
-                                   int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss, int64_t dq_ss, int64_t dk_ss, int64_t dv_ss,
-                                   float scale, int32_t causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, const int32_t* bh_order,
-                                   void* stream_) {
-    if (check_common("pb_flash_bwd_packed", hd, q_ss, k_ss, v_ss, o_ss)) return -2;
-    PB_REQUIRE(hd == 64 || hd == 96 || hd == 128, "pb_flash_bwd_packed: head_dim %d (64 / 96 / 128 only)", hd);
-    PB_REQUIRE(q_off && q_len && k_off && k_len && k_vis, "pb_flash_bwd_packed: the five row descriptors are required");
-    PB_REQUIRE(dq_ss % 4 == 0, "pb_flash_bwd_packed: bad strides");
-    if (B <= 0 || H <= 0 || Sq_max <= 0) return 0;
-    const int* vl[5] = {q_off, q_len, k_off, k_len, bh_order};
-    return pb_flash64_bwd(q, k, v, o, dout, lse, delta, nullptr, k_vis, dq, dk, dv, B, H, Sq_max, Sk_max, hd, 0, q_ss, 0, k_ss, 0, v_ss, 0, o_ss,
-                          0, dq_ss, 0, dk_ss, 0, dv_ss, scale, causal & 1, dbias_q, dbias_k, dbias_v, dbias_ws, (hipStream_t)stream_, vl);
 }

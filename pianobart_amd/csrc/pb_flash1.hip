@@ -795,25 +795,13 @@ __global__ __launch_bounds__(1024) void fa1_reduce_kernel(const Fa1Args pin, int
 
 }  // namespace
 
-static const bf16_t* fa1_zero_page() {
-    static void* pages[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!pages[dev]) {
-        void* p = nullptr;
-        if (hipMalloc(&p, 256) != hipSuccess || hipMemset(p, 0, 256) != hipSuccess) return nullptr;
-        pages[dev] = p;
-    }
-    return (const bf16_t*)pages[dev];
-}
-
 // bytes of dQ slab workspace for `rows` query rows in all (packed: the row count of the q side; dense: B * Sq)
 extern "C" int64_t pb_flash_bwd1_ws_bytes(int64_t rows, int32_t H, int32_t hd, int32_t Sk_max) {
     if (hd != 64) return 0;
     return (int64_t)((Sk_max + KB1 - 1) / KB1) * rows * H * hd * 2;
 }
 
-// 1 when pb_flash_bwd1 / pb_flash_bwd1_packed can take the shape: head_dim 64, the per-sequence -lse / -delta tables of Sq_max queries fit the
+// 1 when the one-pass kernel can take the shape: head_dim 64, the per-sequence -lse / -delta tables of Sq_max queries fit the
 // 160 KiB of LDS beside the tile ring (Sq_max <= 6144) and the bf16 dQ slabs stay under 8 GiB; else 0: the caller keeps the dQ + dK/dV pair.
 extern "C" int32_t pb_flash_bwd1_supported(int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t rows, int32_t H) {
     if (hd != 64 || Sq_max <= 0 || Sk_max <= 0 || rows <= 0 || H <= 0 || H > 128) return 0;
@@ -821,85 +809,45 @@ extern "C" int32_t pb_flash_bwd1_supported(int32_t Sq_max, int32_t Sk_max, int32
     return pb_flash_bwd1_ws_bytes(rows, H, hd, Sk_max) <= ((int64_t)8 << 30) ? 1 : 0;
 }
 
-// One-pass backward, head_dim 64. vl = {q_off, q_len, k_off, k_len} (packed rows) or NULL (dense: batch strides). Same contract as
-// pb_flash64_bwd plus the slab workspace `ws` (pb_flash_bwd1_ws_bytes) and q_rows = rows of the q side (packed) / B * Sq (dense).
-int pb_flash1_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, const float* key_mask,
-                  const int* kmax, void* dq, void* dk, void* dv, int B, int H, int Sq, int Sk, long q_sb, long q_ss, long k_sb, long k_ss, long v_sb,
-                  long v_ss, long o_sb, long o_ss, long dq_sb, long dq_ss, long dk_sb, long dk_ss, long dv_sb, long dv_ss, float scale,
-                  int causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, void* ws, long q_rows, hipStream_t stream, const int* const* vl,
-                  const float* delta_rows) {
+// One-pass backward, head_dim 64 (pb_attn_bwd with PB_ATTN_ONE_PASS): the contract of pb_flash64_bwd plus the slab workspace d.dq_ws
+// (pb_flash_bwd1_ws_bytes) and d.q_rows = rows of the q side with packed rows (dense: B * Sq).
+int pb_flash1_bwd(const pb_attn_desc& d, hipStream_t stream) {
+    const int B = d.B, H = d.H, Sq = d.Sq, Sk = d.Sk;
+    const long q_rows = d.q_off ? d.q_rows : (long)B * Sq;
     Fa1Args A = {};
-    A.delta_rows = delta_rows; A.delta_ld = q_rows;
+    A.delta_rows = d.delta_rows; A.delta_ld = q_rows;
     Fa64Args& a = A.a;
-    if (vl) { a.vl_q_off = vl[0]; a.vl_q_len = vl[1]; a.vl_k_off = vl[2]; a.vl_k_len = vl[3]; a.bh_order = vl[4]; }
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dout = (const bf16_t*)dout;
-    a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = const_cast<float*>(lse); a.delta = delta; a.key_mask = key_mask; a.kmax = kmax;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
-    a.scale = scale; a.causal = causal;
-    a.zeros = fa1_zero_page();
-    PB_REQUIRE(a.zeros != nullptr, "pb_flash_bwd1: cannot allocate the zero page");
-    PB_REQUIRE(ws != nullptr, "pb_flash_bwd1: the dQ slab workspace is required (pb_flash_bwd1_ws_bytes)");
+    a = fa64_args(d, true);
+    PB_REQUIRE(a.zeros != nullptr, "pb_attn_bwd: cannot allocate the zero page");
     const int d_model = H * 64, nkb = (Sk + KB1 - 1) / KB1, nqb = (Sq + RCH - 1) / RCH;
-    A.slab = (bf16_t*)ws; A.slab_stride = q_rows * d_model; A.slab_sb = (long)Sq * d_model;
+    A.slab = (bf16_t*)d.dq_ws; A.slab_stride = q_rows * d_model; A.slab_sb = (long)Sq * d_model;
 #ifdef PB_FA1_STAMPS
     if (const char* e = getenv("PB_FA1_STAMP_PTR")) A.stamps = (unsigned*)strtoull(e, nullptr, 0);
 #endif
-    if (dbias_q) {
-        PB_REQUIRE(dbias_k && dbias_v && dbias_ws, "pb_flash_bwd1: dbias_q/k/v and dbias_ws go together");
+    if (d.dbias_q) {
         // partial rows: 2 per (batch, 256-key block) + 1 per (batch, 64-query chunk) <= what pb_flash_bias_ws_floats provides
         const size_t n_kv = (size_t)B * nkb * 2 * d_model;
-        if (float* slice = pb_defer_alloc(n_kv + (size_t)B * nqb * d_model)) dbias_ws = slice;
-        a.cs_kv = dbias_ws; a.cs_q = dbias_ws + n_kv;
+        float* ws = pb_defer_alloc(n_kv + (size_t)B * nqb * d_model);
+        if (!ws) ws = d.dbias_ws;
+        a.cs_kv = ws; a.cs_q = ws + n_kv;
     }
     const size_t lds = (size_t)OFF_TAB + (size_t)((Sq + 63) / 64) * 64 * 8;
-    PB_REQUIRE(lds <= 160 * 1024, "pb_flash_bwd1: Sq=%d needs %zu bytes of LDS", Sq, lds);
+    PB_REQUIRE(lds <= 160 * 1024, "pb_attn_bwd: one-pass kernel, Sq=%d needs %zu bytes of LDS", Sq, lds);
     // every launch, like the other kernels: the attribute is per device, and a process may drive several
     PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fa1_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int rpb = 64;
-    if (!delta_rows) {                                                     // the caller's GEMM epilogue has not made the row sums: one pass over dO and O
+    if (!d.delta_rows) {                                                   // the caller's GEMM epilogue has not made the row sums: one pass over dO and O
         hipLaunchKernelGGL(fa1_delta_kernel, dim3((Sq + rpb - 1) / rpb, B), dim3(256), 0, stream, a, rpb);
         PB_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(fa1_bwd_kernel, dim3(nkb * H * B), dim3(FT), lds, stream, A);
     PB_LAUNCH_CHECK();
     const int G = H * 8;
-    PB_REQUIRE(G <= 1024, "pb_flash_bwd1: more than 128 heads");
+    PB_REQUIRE(G <= 1024, "pb_attn_bwd: one-pass kernel, more than 128 heads");
     const int nrl = std::min(8, 1024 / G);
-    hipLaunchKernelGGL(fa1_reduce_kernel, dim3(nqb, B), dim3(G * nrl), dbias_q ? (size_t)nrl * d_model * 4 : 0, stream, A, nrl);
+    hipLaunchKernelGGL(fa1_reduce_kernel, dim3(nqb, B), dim3(G * nrl), d.dbias_q ? (size_t)nrl * d_model * 4 : 0, stream, A, nrl);
     PB_LAUNCH_CHECK();
-    if (!dbias_q) return 0;
-    if (pb_finalize_rows(a.cs_kv, B * nkb, d_model, dbias_k, stream, 2, dbias_v)) return -1;
-    return pb_finalize_rows(a.cs_q, B * nqb, d_model, dbias_q, stream);
-}
-
-extern "C" int pb_flash_bwd1(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                             const float* key_mask, const int32_t* kmax, void* dq, void* dk, void* dv, float* delta, int32_t B, int32_t H, int32_t Sq,
-                             int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb,
-                             int64_t v_ss, int64_t o_sb, int64_t o_ss, int64_t dq_sb, int64_t dq_ss, int64_t dk_sb, int64_t dk_ss,
-                             int64_t dv_sb, int64_t dv_ss, float scale, int32_t causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws,
-                             void* dq_ws, const float* delta_rows, void* stream_) {
-    PB_REQUIRE(hd == 64, "pb_flash_bwd1: head_dim %d (64 only)", hd);
-    PB_REQUIRE(q_ss % 8 == 0 && k_ss % 8 == 0 && v_ss % 8 == 0 && o_ss % 8 == 0 && dq_ss % 8 == 0 && dk_ss % 8 == 0 && dv_ss % 8 == 0 &&
-               q_sb % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 && o_sb % 8 == 0 && dq_sb % 8 == 0, "pb_flash_bwd1: strides must be multiples of 8 elements");
-    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return 0;
-    return pb_flash1_bwd(q, k, v, o, dout, lse, delta, key_mask, kmax, dq, dk, dv, B, H, Sq, Sk, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss,
-                         dq_sb, dq_ss, dk_sb, dk_ss, dv_sb, dv_ss, scale, causal & 1, dbias_q, dbias_k, dbias_v, dbias_ws, dq_ws, (long)B * Sq,
-                         (hipStream_t)stream_, nullptr, delta_rows);
-}
-
-extern "C" int pb_flash_bwd1_packed(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
-                                    void* dk, void* dv, float* delta, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off,
-                                    const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd,
-                                    int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss, int64_t dq_ss, int64_t dk_ss, int64_t dv_ss,
-                                    float scale, int32_t causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws,
-                                    void* dq_ws, int64_t q_rows, const int32_t* bh_order, const float* delta_rows, void* stream_) {
-    PB_REQUIRE(hd == 64, "pb_flash_bwd1_packed: head_dim %d (64 only)", hd);
-    PB_REQUIRE(q_ss % 8 == 0 && k_ss % 8 == 0 && v_ss % 8 == 0 && o_ss % 8 == 0 && dq_ss % 8 == 0 && dk_ss % 8 == 0 && dv_ss % 8 == 0,
-               "pb_flash_bwd1_packed: strides must be multiples of 8 elements");
-    PB_REQUIRE(q_off && q_len && k_off && k_len && k_vis, "pb_flash_bwd1_packed: the five row descriptors are required");
-    if (B <= 0 || H <= 0 || Sq_max <= 0 || Sk_max <= 0) return 0;
-    const int* vl[5] = {q_off, q_len, k_off, k_len, bh_order};
-    return pb_flash1_bwd(q, k, v, o, dout, lse, delta, nullptr, k_vis, dq, dk, dv, B, H, Sq_max, Sk_max, 0, q_ss, 0, k_ss, 0, v_ss, 0, o_ss,
-                         0, dq_ss, 0, dk_ss, 0, dv_ss, scale, causal & 1, dbias_q, dbias_k, dbias_v, dbias_ws, dq_ws, q_rows, (hipStream_t)stream_, vl, delta_rows);
+    if (!d.dbias_q) return 0;
+    if (pb_finalize_rows(a.cs_kv, B * nkb, d_model, d.dbias_k, stream, 2, d.dbias_v)) return -1;
+    return pb_finalize_rows(a.cs_q, B * nqb, d_model, d.dbias_q, stream);
 }

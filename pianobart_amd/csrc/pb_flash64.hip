@@ -752,8 +752,7 @@ __global__ __launch_bounds__(FT) void fa64_bwd_dq_kernel(const Fa64Args pin) {
 
 }  // namespace
 
-// 256 bytes of device zeros per device, allocated on first use (never freed: lives as long as the process' HIP context)
-static const bf16_t* fa_zero_page() {
+const void* pb_zero_page() {
     static void* pages[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
@@ -762,32 +761,25 @@ static const bf16_t* fa_zero_page() {
         if (hipMalloc(&p, 256) != hipSuccess || hipMemset(p, 0, 256) != hipSuccess) return nullptr;
         pages[dev] = p;
     }
-    return (const bf16_t*)pages[dev];
+    return pages[dev];
 }
 
-// entry points used by pb_flash.hip's dispatch (same argument meaning as pb_flash_fwd / pb_flash_bwd; hd = 64, 96 or 128)
+// the pipelined family of pb_attn_fwd / pb_attn_bwd (hd = 64, 96 or 128)
 template <int HD>
 static int fa64_fwd_launch(const Fa64Args& a, hipStream_t stream) {
     using C = FaCfg<(HD + 63) / 64>;
     const size_t lds = (size_t)C::NS * C::STB + (size_t)((a.Sk + 63) / 64) * (64 * 4 + 4);
-    PB_REQUIRE(lds <= 160 * 1024, "pb_flash_fwd: Sk=%d needs %zu bytes of LDS", a.Sk, lds);
+    PB_REQUIRE(lds <= 160 * 1024, "pb_attn_fwd: Sk=%d needs %zu bytes of LDS", a.Sk, lds);
     if (lds > 65536) hipFuncSetAttribute(reinterpret_cast<const void*>(fa64_fwd_kernel<HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(fa64_fwd_kernel<HD>, dim3(((a.Sq + 127) / 128) * a.H * a.B), dim3(FT), lds, stream, a);
     PB_LAUNCH_CHECK();
     return 0;
 }
 
-int pb_flash64_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* key_mask, const int* kmax, int B, int H, int Sq, int Sk, int hd,
-                   long q_sb, long q_ss, long k_sb, long k_ss, long v_sb, long v_ss, long o_sb, long o_ss, float scale, int causal, hipStream_t stream,
-                   const int* const* vl) {
-    Fa64Args a = {};
-    if (vl) { a.vl_q_off = vl[0]; a.vl_q_len = vl[1]; a.vl_k_off = vl[2]; a.vl_k_len = vl[3]; a.bh_order = vl[4]; }
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse; a.key_mask = key_mask; a.kmax = kmax;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.scale = scale; a.causal = causal;
-    a.zeros = fa_zero_page();
-    PB_REQUIRE(a.zeros != nullptr, "pb_flash_fwd: cannot allocate the zero page");
-    return hd == 128 ? fa64_fwd_launch<128>(a, stream) : hd == 96 ? fa64_fwd_launch<96>(a, stream) : fa64_fwd_launch<64>(a, stream);
+int pb_flash64_fwd(const pb_attn_desc& d, hipStream_t stream) {
+    const Fa64Args a = fa64_args(d, false);
+    PB_REQUIRE(a.zeros != nullptr, "pb_attn_fwd: cannot allocate the zero page");
+    return d.hd == 128 ? fa64_fwd_launch<128>(a, stream) : d.hd == 96 ? fa64_fwd_launch<96>(a, stream) : fa64_fwd_launch<64>(a, stream);
 }
 
 template <int HD>
@@ -795,7 +787,7 @@ static int fa64_bwd_launch(const Fa64Args& a, hipStream_t stream) {
     using C = FaCfg<(HD + 63) / 64>;
     const size_t lds_dkv = (size_t)C::NS * C::STB + (size_t)((a.Sq + 63) / 64) * 64 * 8;
     const size_t lds_dq = (size_t)C::NS * C::STB + (size_t)((a.Sk + 63) / 64) * (64 * 4 + 4);
-    PB_REQUIRE(lds_dkv <= 160 * 1024 && lds_dq <= 160 * 1024, "pb_flash_bwd: Sq=%d Sk=%d need %zu / %zu bytes of LDS", a.Sq, a.Sk, lds_dkv, lds_dq);
+    PB_REQUIRE(lds_dkv <= 160 * 1024 && lds_dq <= 160 * 1024, "pb_attn_bwd: Sq=%d Sk=%d need %zu / %zu bytes of LDS", a.Sq, a.Sk, lds_dkv, lds_dq);
     if (lds_dkv > 65536) hipFuncSetAttribute(reinterpret_cast<const void*>(fa64_bwd_dkv_kernel<HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dkv);
     if (lds_dq > 65536) hipFuncSetAttribute(reinterpret_cast<const void*>(fa64_bwd_dq_kernel<HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dq);
     constexpr int BK_ = 64 * C::KT;
@@ -806,33 +798,23 @@ static int fa64_bwd_launch(const Fa64Args& a, hipStream_t stream) {
     return 0;
 }
 
-int pb_flash64_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, const float* key_mask,
-                   const int* kmax, void* dq, void* dk, void* dv, int B, int H, int Sq, int Sk, int hd, long q_sb, long q_ss, long k_sb, long k_ss, long v_sb,
-                   long v_ss, long o_sb, long o_ss, long dq_sb, long dq_ss, long dk_sb, long dk_ss, long dv_sb, long dv_ss, float scale,
-                   int causal, float* dbias_q, float* dbias_k, float* dbias_v, float* dbias_ws, hipStream_t stream, const int* const* vl) {
-    Fa64Args a = {};
-    if (vl) { a.vl_q_off = vl[0]; a.vl_q_len = vl[1]; a.vl_k_off = vl[2]; a.vl_k_len = vl[3]; a.bh_order = vl[4]; }
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dout = (const bf16_t*)dout;
-    a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = const_cast<float*>(lse); a.delta = delta; a.key_mask = key_mask; a.kmax = kmax;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
-    a.scale = scale; a.causal = causal;
-    a.zeros = fa_zero_page();
-    PB_REQUIRE(a.zeros != nullptr, "pb_flash_bwd: cannot allocate the zero page");
-    const int kt_ = hd == 64 ? 2 : 1, nkb = (Sk + 64 * kt_ - 1) / (64 * kt_), nqb = (Sq + 127) / 128, d_model = H * hd;
-    if (dbias_q) {
-        PB_REQUIRE(dbias_k && dbias_v && dbias_ws, "pb_flash_bwd: dbias_q/k/v and dbias_ws go together");
-        const size_t n_kv = (size_t)B * nkb * 2 * d_model;
-        if (float* slice = pb_defer_alloc(n_kv + (size_t)B * nqb * d_model)) dbias_ws = slice;     // deferred reduction: the partial rows must outlive this call
-        a.cs_kv = dbias_ws; a.cs_q = dbias_ws + n_kv;
+int pb_flash64_bwd(const pb_attn_desc& d, hipStream_t stream) {
+    Fa64Args a = fa64_args(d, true);
+    PB_REQUIRE(a.zeros != nullptr, "pb_attn_bwd: cannot allocate the zero page");
+    const int kt_ = d.hd == 64 ? 2 : 1, nkb = (d.Sk + 64 * kt_ - 1) / (64 * kt_), nqb = (d.Sq + 127) / 128, d_model = d.H * d.hd;
+    if (d.dbias_q) {
+        const size_t n_kv = (size_t)d.B * nkb * 2 * d_model;
+        float* ws = pb_defer_alloc(n_kv + (size_t)d.B * nqb * d_model);      // deferred reduction: the partial rows must outlive this call
+        if (!ws) ws = d.dbias_ws;
+        a.cs_kv = ws; a.cs_q = ws + n_kv;
     }
-    const int rc = hd == 128 ? fa64_bwd_launch<128>(a, stream) : hd == 96 ? fa64_bwd_launch<96>(a, stream) : fa64_bwd_launch<64>(a, stream);
-    if (rc || !dbias_q) return rc;
-    if (pb_finalize_rows(a.cs_kv, B * nkb, d_model, dbias_k, stream, 2, dbias_v)) return -1;
-    return pb_finalize_rows(a.cs_q, B * nqb, d_model, dbias_q, stream);
+    const int rc = d.hd == 128 ? fa64_bwd_launch<128>(a, stream) : d.hd == 96 ? fa64_bwd_launch<96>(a, stream) : fa64_bwd_launch<64>(a, stream);
+    if (rc || !d.dbias_q) return rc;
+    if (pb_finalize_rows(a.cs_kv, d.B * nkb, d_model, d.dbias_k, stream, 2, d.dbias_v)) return -1;
+    return pb_finalize_rows(a.cs_q, d.B * nqb, d_model, d.dbias_q, stream);
 }
 
-// floats of workspace for the fused bias gradients of pb_flash_bwd (head_dim 64 / 96 / 128)
+// floats of workspace for the fused bias gradients of pb_attn_bwd (head_dim 64 / 96 / 128)
 extern "C" int64_t pb_flash_bias_ws_floats(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd) {
     const int kt_ = hd == 64 ? 2 : 1, nkb = (Sk + 64 * kt_ - 1) / (64 * kt_), nqb = (Sq + 63) / 64;      // 64-row query chunks: the one-pass backward's partial rows (pb_flash1.hip)
     return (int64_t)B * H * hd * (2 * nkb + nqb);

@@ -709,12 +709,6 @@ __global__ __launch_bounds__(FX_THREADS) void fx_bwd_dq2_kernel(const FxArgs p) 
         }
 }
 
-int xcheck(const char* who, int hd, const long* st, int n) {
-    PB_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (32 / 64 / 128)", who, hd);
-    for (int i = 0; i < n; ++i) PB_REQUIRE(st[i] % 4 == 0, "%s: strides must be multiples of 4 elements (16-byte f32 rows)", who);
-    return 0;
-}
-
 #define FX_DISPATCH(HDV, ...)                                   \
     switch (HDV) {                                              \
         case 32: { constexpr int HD = 32; __VA_ARGS__; } break; \
@@ -733,49 +727,41 @@ template <class F> int opt_in_lds(F fn, size_t bytes) {
 
 extern "C" int pb_flash_x3_supported(int32_t hd) { return (hd == 32 || hd == 64 || hd == 128) ? 1 : 0; }
 
-static int fx_fwd_impl(const float* q, const float* k, const float* v, float* o, float* lse, const float* key_mask, const int32_t* kmax, int32_t B, int32_t H, int32_t Sq,
-                       int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb,
-                       int64_t o_ss, float scale, int32_t causal, void* stream_, const int* const* vl) {
-    const long st[8] = {q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss};
-    if (xcheck("pb_flash_fwd_x3", hd, st, 8)) return -2;
-    PB_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, "pb_flash_fwd_x3: operands must be 16-byte aligned");
-    if (B <= 0 || H <= 0 || Sq <= 0) return 0;
+// the kernel arguments of a checked descriptor (pb_flash.hip: with packed rows its batch strides, key_mask and kmax are zero); forward writes d.o, backward reads it
+static FxArgs fx_args(const pb_attn_desc& d, bool bwd) {
     FxArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse; a.key_mask = key_mask; a.kmax = key_mask ? kmax : nullptr;
-    if (vl) { a.vq_off = vl[0]; a.vq_len = vl[1]; a.vk_off = vl[2]; a.vk_len = vl[3]; a.vk_vis = vl[4]; }
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.scale = scale; a.causal = causal & 1;
-    const int nt = fx_nt(hd, B, H, Sq);
-    dim3 grid((Sq + XQ * nt - 1) / (XQ * nt), H, B);
+    a.q = (const float*)d.q; a.k = (const float*)d.k; a.v = (const float*)d.v; a.dout = (const float*)d.dout;
+    if (bwd) a.o = (const float*)d.o; else a.out = (float*)d.o;
+    a.dq = (float*)d.dq; a.dk = (float*)d.dk; a.dv = (float*)d.dv; a.lse = d.lse; a.delta = d.delta;
+    a.key_mask = d.key_mask; a.kmax = d.key_mask ? d.kmax : nullptr;
+    a.vq_off = d.q_off; a.vq_len = d.q_len; a.vk_off = d.k_off; a.vk_len = d.k_len; a.vk_vis = d.k_vis;
+    a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk;
+    a.q_sb = d.q_sb; a.q_ss = d.q_ss; a.k_sb = d.k_sb; a.k_ss = d.k_ss; a.v_sb = d.v_sb; a.v_ss = d.v_ss; a.o_sb = d.o_sb; a.o_ss = d.o_ss;
+    a.dq_sb = d.dq_sb; a.dq_ss = d.dq_ss; a.dk_sb = d.dk_sb; a.dk_ss = d.dk_ss; a.dv_sb = d.dv_sb; a.dv_ss = d.dv_ss;
+    a.scale = d.scale; a.causal = d.flags & PB_ATTN_CAUSAL;
+    return a;
+}
+
+int pb_flash_x3_fwd(const pb_attn_desc& d, hipStream_t stream) {
+    const FxArgs a = fx_args(d, false);
+    const int hd = d.hd, nt = fx_nt(hd, d.B, d.H, d.Sq);
+    dim3 grid((d.Sq + XQ * nt - 1) / (XQ * nt), d.H, d.B);
     const size_t lds = 4 * 64 * (size_t)hd * 2 + 256;
     if (nt == 2) {
-        if (hd == 32) { if (opt_in_lds(&fx_fwd2_kernel<32, 2>, lds)) return -1; hipLaunchKernelGGL((fx_fwd2_kernel<32, 2>), grid, dim3(FX_THREADS), lds, (hipStream_t)stream_, a); }
-        else { if (opt_in_lds(&fx_fwd2_kernel<64, 2>, lds)) return -1; hipLaunchKernelGGL((fx_fwd2_kernel<64, 2>), grid, dim3(FX_THREADS), lds, (hipStream_t)stream_, a); }
+        if (hd == 32) { if (opt_in_lds(&fx_fwd2_kernel<32, 2>, lds)) return -1; hipLaunchKernelGGL((fx_fwd2_kernel<32, 2>), grid, dim3(FX_THREADS), lds, stream, a); }
+        else { if (opt_in_lds(&fx_fwd2_kernel<64, 2>, lds)) return -1; hipLaunchKernelGGL((fx_fwd2_kernel<64, 2>), grid, dim3(FX_THREADS), lds, stream, a); }
     } else {
-        FX_DISPATCH(hd, if (opt_in_lds(&fx_fwd_kernel<HD>, lds)) return -1; hipLaunchKernelGGL((fx_fwd_kernel<HD>), grid, dim3(FX_THREADS), lds, (hipStream_t)stream_, a));
+        FX_DISPATCH(hd, if (opt_in_lds(&fx_fwd_kernel<HD>, lds)) return -1; hipLaunchKernelGGL((fx_fwd_kernel<HD>), grid, dim3(FX_THREADS), lds, stream, a));
     }
     PB_LAUNCH_CHECK();
     return 0;
 }
 
-static int fx_bwd_impl(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse, const float* key_mask,
-                       const int32_t* kmax, float* dq, float* dk, float* dv, float* delta, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb,
-                       int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss, int64_t dq_sb,
-                       int64_t dq_ss, int64_t dk_sb, int64_t dk_ss, int64_t dv_sb, int64_t dv_ss, float scale, int32_t causal, void* stream_, const int* const* vl) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const long st[14] = {q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss, dq_sb, dq_ss, dk_sb, dk_ss, dv_sb, dv_ss};
-    if (xcheck("pb_flash_bwd_x3", hd, st, 14)) return -2;
-    PB_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0,
-               "pb_flash_bwd_x3: operands must be 16-byte aligned");
-    if (B <= 0 || H <= 0 || Sq <= 0) return 0;
-    FxArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.dq = dq; a.dk = dk; a.dv = dv; a.lse = const_cast<float*>(lse); a.delta = delta; a.key_mask = key_mask; a.kmax = key_mask ? kmax : nullptr;
-    if (vl) { a.vq_off = vl[0]; a.vq_len = vl[1]; a.vk_off = vl[2]; a.vk_len = vl[3]; a.vk_vis = vl[4]; }
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss;
-    a.o_sb = o_sb; a.o_ss = o_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
-    a.scale = scale; a.causal = causal & 1;
+int pb_flash_x3_bwd(const pb_attn_desc& d, hipStream_t stream) {
+    const FxArgs a = fx_args(d, true);
+    const int hd = d.hd, B = d.B, H = d.H, Sq = d.Sq, Sk = d.Sk;
     const long nrow = (long)B * H * Sq;
-    FX_DISPATCH(hd, hipLaunchKernelGGL((fx_delta_kernel<HD>), dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, stream, o, dout, delta, B, H, Sq, (long)o_sb, (long)o_ss, vl ? vl[0] : nullptr, vl ? vl[1] : nullptr));
+    FX_DISPATCH(hd, hipLaunchKernelGGL((fx_delta_kernel<HD>), dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, stream, a.o, a.dout, d.delta, B, H, Sq, a.o_sb, a.o_ss, a.vq_off, a.vq_len));
     PB_LAUNCH_CHECK();
     const int nt = fx_nt(hd, B, H, Sq);
     dim3 gk((Sk + XK - 1) / XK, H, B), gq((Sq + XQ * nt - 1) / (XQ * nt), H, B);
@@ -790,35 +776,4 @@ static int fx_bwd_impl(const float* q, const float* k, const float* v, const flo
     }
     PB_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int pb_flash_fwd_x3(const float* q, const float* k, const float* v, float* o, float* lse, const float* key_mask, const int32_t* kmax, int32_t B, int32_t H, int32_t Sq,
-                               int32_t Sk, int32_t hd, int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb,
-                               int64_t o_ss, float scale, int32_t causal, void* stream_) {
-    return fx_fwd_impl(q, k, v, o, lse, key_mask, kmax, B, H, Sq, Sk, hd, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss, scale, causal, stream_, nullptr);
-}
-extern "C" int pb_flash_bwd_x3(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse, const float* key_mask,
-                               const int32_t* kmax, float* dq, float* dk, float* dv, float* delta, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t hd, int64_t q_sb,
-                               int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss, int64_t o_sb, int64_t o_ss, int64_t dq_sb,
-                               int64_t dq_ss, int64_t dk_sb, int64_t dk_ss, int64_t dv_sb, int64_t dv_ss, float scale, int32_t causal, void* stream_) {
-    return fx_bwd_impl(q, k, v, o, dout, lse, key_mask, kmax, dq, dk, dv, delta, B, H, Sq, Sk, hd, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, o_sb, o_ss, dq_sb, dq_ss, dk_sb, dk_ss,
-                       dv_sb, dv_ss, scale, causal, stream_, nullptr);
-}
-// packed rows (see pb_flash_fwd_packed): the rows of the batch's sequences lie back to back in (rows, H hd) tensors; q_off / q_len / k_off / k_len / k_vis are
-// device int32 (B) arrays, Sq_max / Sk_max the longest sequence (grid, lse / delta row length)
-extern "C" int pb_flash_fwd_x3_packed(const float* q, const float* k, const float* v, float* o, float* lse, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off,
-                                      const int32_t* k_len, const int32_t* k_vis, int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss,
-                                      int64_t k_ss, int64_t v_ss, int64_t o_ss, float scale, int32_t causal, void* stream_) {
-    PB_REQUIRE(q_off && q_len && k_off && k_len && k_vis, "pb_flash_fwd_x3_packed: the five row descriptors are required");
-    const int* vl[5] = {q_off, q_len, k_off, k_len, k_vis};
-    return fx_fwd_impl(q, k, v, o, lse, nullptr, nullptr, B, H, Sq_max, Sk_max, hd, 0, q_ss, 0, k_ss, 0, v_ss, 0, o_ss, scale, causal, stream_, vl);
-}
-extern "C" int pb_flash_bwd_x3_packed(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse, float* dq, float* dk, float* dv,
-                                      float* delta, const int32_t* q_off, const int32_t* q_len, const int32_t* k_off, const int32_t* k_len, const int32_t* k_vis,
-                                      int32_t B, int32_t H, int32_t Sq_max, int32_t Sk_max, int32_t hd, int64_t q_ss, int64_t k_ss, int64_t v_ss, int64_t o_ss,
-                                      int64_t dq_ss, int64_t dk_ss, int64_t dv_ss, float scale, int32_t causal, void* stream_) {
-    PB_REQUIRE(q_off && q_len && k_off && k_len && k_vis, "pb_flash_bwd_x3_packed: the five row descriptors are required");
-    const int* vl[5] = {q_off, q_len, k_off, k_len, k_vis};
-    return fx_bwd_impl(q, k, v, o, dout, lse, nullptr, nullptr, dq, dk, dv, delta, B, H, Sq_max, Sk_max, hd, 0, q_ss, 0, k_ss, 0, v_ss, 0, o_ss, 0, dq_ss, 0, dk_ss, 0, dv_ss,
-                       scale, causal, stream_, vl);
 }

@@ -29,7 +29,7 @@ _ROWDOT = int(os.environ.get('PB_ROWDOT', '1'))                                 
 _X3_ONEHOT = int(os.environ.get('PB_X3_ONEHOT', '1'))                        # bf16x3: embedding-table gradient as two one-hot GEMMs over dz's (hi, lo) planes (0: the exact path's f32 atomics, for A/B)
 _DP_RESERVE_CUS = int(os.environ.get('PB_DP_RESERVE_CUS', '0'))                 # data parallel: 0 = backward GEMMs as ordinary grids (default: +0.45 ms at world 1, profiles/r06_dp_mode_ab.txt); n > 0 = persistent grids that leave n CUs to RCCL's kernels (+1.0 / +1.4 ms for 8 / 16)
 _SIDE_PRIORITY = int(os.environ.get('PB_SIDE_PRIORITY', '0'))                      # HIP priority of the second stream (1 = low, -1 = high; developer A/B)
-_X3_FLASH = int(os.environ.get('PB_X3_FLASH', '1'))                            # bf16x3: 1 = fused split-bf16 attention (pb_flash_*_x3), 0 = the unfused QK^T / softmax / PV chain of the exact-f32 path
+_X3_FLASH = int(os.environ.get('PB_X3_FLASH', '1'))                            # bf16x3: 1 = fused split-bf16 attention (pb_attn_* with PB_F32X3), 0 = the unfused QK^T / softmax / PV chain of the exact-f32 path
 
 # copies of the backward scratch buffers that the second stream's weight-gradient GEMMs read (gB, du, dq, dkv, dqkv): with 2 the main
 # stream can write the next sublayer's cotangent while the weight gradient of the previous one is still reading its own (3: slower)
@@ -405,25 +405,22 @@ class Engine(GenerationMixin, ScoringMixin):
         # forward GEMMs run alone on their stream (nothing fills a partly filled last round of the persistent grid): allow the tail split
         ops.gemm(x, self.w[wname], out, M=M, N=N, K=K, dtype=self.gcode, bias=self.wf[bname] if bname else None, dbg=_FWD_GEMM_FLAGS, **kw)
 
+    def _fused_form(self, rows, key_mask, B, Sq, Sk):
+        """What tells one fused attention call's ops.flash_* wrappers apart: the suffix of their names (bf16 or bf16x3, dense or packed rows), the
+        form of a strided operand, and the mask, shape and keyword arguments in the wrappers' positional order."""
+        sfx = '_x3' if self.x3 else ''
+        if rows is not None:
+            return sfx + '_packed', (lambda a, n: a), (), (rows, B, self.H, self.hd), {}
+        ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
+        return sfx, ex, (key_mask,), (B, self.H, Sq, Sk, self.hd), {'kmax': self._kmax.get(id(key_mask)) if key_mask is not None else None}
+
     def _attn_fwd(self, q, k, v, out, key_mask, causal, B, Sq, Sk, save, rows=None):
         """q,k,v,out: (tensor, elem offset, row stride). Unfused form: QK^T -> masked softmax -> PV. rows: packed-row descriptors."""
         H, hd = self.H, self.hd
         ws = self._cur_ws
-        if rows is not None and self.x3:
-            ops.flash_fwd_x3_packed(q, k, v, out, save['lse'], rows, B, H, hd, hd ** -0.5, causal)
-            return
-        if rows is not None:
-            ops.flash_fwd_packed(q, k, v, out, save['lse'], rows, B, H, hd, hd ** -0.5, causal)
-            return
-        if self.use_flash and self.x3:
-            ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
-            ops.flash_fwd_x3(ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), save['lse'], key_mask, B, H, Sq, Sk, hd, hd ** -0.5, causal,
-                             kmax=self._kmax.get(id(key_mask)) if key_mask is not None else None)
-            return
-        if self.use_flash:
-            ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
-            ops.flash_fwd(ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), save['lse'], key_mask, B, H, Sq, Sk, hd, hd ** -0.5, causal,
-                          kmax=self._kmax.get(id(key_mask)) if key_mask is not None else None)
+        if rows is not None or self.use_flash:
+            sfx, ex, mask, shape, kw = self._fused_form(rows, key_mask, B, Sq, Sk)
+            getattr(ops, 'flash_fwd' + sfx)(ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), save['lse'], *mask, *shape, hd ** -0.5, causal, **kw)
             return
         scores, P = ws['scores'], save['P']
         (qt, qo, ql), (kt, ko, kl), (vt, vo, vl), (ot, oo, ol) = q, k, v, out
@@ -446,40 +443,26 @@ class Engine(GenerationMixin, ScoringMixin):
         delta_rows: rowsum(dO * O) per head, [H][rows], already made by the GEMM that produced dout (PB_GEMM_ROWDOT); one-pass kernel only."""
         H, hd = self.H, self.hd
         ws = self._cur_ws
-        if self.use_flash and self.x3 and rows is not None:
-            assert dout[1] == 0 and dout[2] == out[2]
-            ops.flash_bwd_x3_packed(q, k, v, out, dout[0], save['lse'], dq, dk, dv, ws['delta'], rows, B, H, hd, hd ** -0.5, causal)
-            return False
-        if self.use_flash and self.x3:
-            ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
-            assert dout[1] == 0 and dout[2] == out[2]
-            ops.flash_bwd_x3(ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), dout[0], save['lse'], key_mask, ex(dq, Sq), ex(dk, Sk), ex(dv, Sk),
-                             ws['delta'], B, H, Sq, Sk, hd, hd ** -0.5, causal, kmax=self._kmax.get(id(key_mask)) if key_mask is not None else None)
-            return False
         if self.use_flash:
-            ex = lambda a, n: (a[0], a[1], a[2], n * a[2])
             assert dout[1] == 0 and dout[2] == out[2]
-            fuse = dbias is not None and hd in (64, 96, 128)
-            wsb = None
+            sfx, ex, mask, shape, kw = self._fused_form(rows, key_mask, B, Sq, Sk)
+            fuse = not self.x3 and dbias is not None and hd in (64, 96, 128)
             if fuse:
                 need = int(LIB.query('pb_flash_bias_ws_floats', B, H, Sq, Sk, hd))
                 if getattr(self, '_fbws', None) is None or self._fbws.numel() < need:
                     self._fbws = torch.empty(need, dtype=torch.float32, device=self.device)
-                wsb = self._fbws
-            one_pass = self._one_pass_bwd(causal, rows, B, Sq, Sk, q[0].shape[0] if rows is not None else B * Sq)
+            q_rows = q[0].shape[0] if rows is not None else B * Sq
+            one_pass = self._one_pass_bwd(causal, rows, B, Sq, Sk, q_rows)
             assert one_pass or delta_rows is None
-            if rows is not None:
-                if one_pass:
-                    ops.flash_bwd1_packed(q, k, v, out, dout[0], save['lse'], dq, dk, dv, ws['delta'], rows, B, H, hd, hd ** -0.5, causal, q[0].shape[0],
-                                          dbias=dbias if fuse else None, dbias_ws=wsb, delta_rows=delta_rows)
-                else:
-                    ops.flash_bwd_packed(q, k, v, out, dout[0], save['lse'], dq, dk, dv, ws['delta'], rows, B, H, hd, hd ** -0.5, causal,
-                                         dbias=dbias if fuse else None, dbias_ws=wsb)
-                return fuse
-            (ops.flash_bwd1 if one_pass else ops.flash_bwd)(
-                ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), dout[0], save['lse'], key_mask, ex(dq, Sq), ex(dk, Sk), ex(dv, Sk),
-                ws['delta'], B, H, Sq, Sk, hd, hd ** -0.5, causal, kmax=self._kmax.get(id(key_mask)) if key_mask is not None else None,
-                dbias=dbias if fuse else None, dbias_ws=wsb, **({'delta_rows': delta_rows} if one_pass else {}))
+            # what the backward wrappers take beyond the forward's: bias gradients (bf16), and for the one-pass kernel delta_rows and, packed, q_rows
+            tail = ()
+            if not self.x3:
+                kw.update(dbias=dbias if fuse else None, dbias_ws=self._fbws if fuse else None)
+            if one_pass:
+                sfx, tail = '1' + sfx, (q_rows,) if rows is not None else ()
+                kw['delta_rows'] = delta_rows
+            getattr(ops, 'flash_bwd' + sfx)(ex(q, Sq), ex(k, Sk), ex(v, Sk), ex(out, Sq), dout[0], save['lse'], *mask, ex(dq, Sq), ex(dk, Sk), ex(dv, Sk),
+                                            ws['delta'], *shape, hd ** -0.5, causal, *tail, **kw)
             return fuse
         dP, dS, P = ws['scores'], ws['dS'], save['P']
         (qt, qo, ql), (kt, ko, kl), (vt, vo, vl) = q, k, v

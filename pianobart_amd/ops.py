@@ -6,8 +6,8 @@ import os
 
 import torch
 
-from ._lib import (LIB, PB_BF16, PB_F32, PB_F32X3, GemmDesc, PBError, GEMM_ACCUM, GEMM_C_F32, GEMM_GELU,
-                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT)
+from ._lib import (LIB, PB_BF16, PB_F32, PB_F32X3, AttnDesc, GemmDesc, PBError, GEMM_ACCUM, GEMM_C_F32, GEMM_GELU,
+                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS)
 
 SEG_SIZES = [262, 134, 135, 262, 134, 38, 260, 55]          # PianoBart.classes order
 SEG_OFF = [0]
@@ -45,6 +45,12 @@ def _p(t):
     if not t.is_cuda:
         raise PBError('pianobart_amd ops need HIP device tensors (got %s); there is no CPU path' % t.device)
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _adr(t):
+    """_p(t) as a plain address for a descriptor field (None stays None): a tensor that is not on the device is refused alike."""
+    p = _p(t)
+    return None if p is None else p.value
 
 
 # developer aid for same-box A/B runs (tools/ab_step.sh): extra flag bits for every GEMM, e.g. PB_GEMM_FLAGS=4096 = ordinary grids
@@ -247,84 +253,14 @@ def shift_right(ids16, sos_row16, out, B, S):
     LIB.call('pb_shift_right', _p(ids16), _p(sos_row16), _p(out), B, S, _stream())
 
 
-def flash_fwd(q, k, v, o, lse, key_mask, B, H, Sq, Sk, hd, scale, causal, force_generic=False, kmax=None):
-    """q,k,v,o: (tensor, element offset, row stride, batch stride) bf16."""
-    (qt, qo, qs, qb), (kt, ko, ks, kb), (vt, vo, vs, vb), (ot, oo, os_, ob) = q, k, v, o
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    LIB.call('pb_flash_fwd', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(lse), _p(key_mask), _p(kmax), B, H, Sq, Sk, hd,
-             qb, qs, kb, ks, vb, vs, ob, os_, scale, int(causal) | (2 if force_generic else 0), _stream())
-
-
-def flash_bwd(q, k, v, o, dout, lse, key_mask, dq, dk, dv, delta, B, H, Sq, Sk, hd, scale, causal, force_generic=False, kmax=None, dbias=None, dbias_ws=None):
-    """dbias = (gq, gk, gv): f32 vectors of H*hd that receive += the column sums of dq / dk / dv (bias gradients), with dbias_ws."""
-    (qt, qo, qs, qb), (kt, ko, ks, kb), (vt, vo, vs, vb), (ot, oo, os_, ob) = q, k, v, o
-    (dqt, dqo, dqs, dqb), (dkt, dko, dks, dkb), (dvt, dvo, dvs, dvb) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    LIB.call('pb_flash_bwd', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), _p(key_mask), _p(kmax), pp(dqt, dqo),
-             pp(dkt, dko), pp(dvt, dvo), _p(delta), B, H, Sq, Sk, hd, qb, qs, kb, ks, vb, vs, ob, os_, dqb, dqs, dkb, dks, dvb, dvs,
-             scale, int(causal) | (2 if force_generic else 0), _p(dbias[0]) if dbias else None, _p(dbias[1]) if dbias else None,
-             _p(dbias[2]) if dbias else None, _p(dbias_ws) if dbias else None, _stream())
-
-
-def flash_fwd_x3(q, k, v, o, lse, key_mask, B, H, Sq, Sk, hd, scale, causal, kmax=None):
-    """Fused attention of the bf16x3 instantiation. q,k,v,o: (tensor, element offset, row stride, batch stride) f32."""
-    (qt, qo, qs, qb), (kt, ko, ks, kb), (vt, vo, vs, vb), (ot, oo, os_, ob) = q, k, v, o
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
-    LIB.call('pb_flash_fwd_x3', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(lse), _p(key_mask), _p(kmax), B, H, Sq, Sk, hd,
-             qb, qs, kb, ks, vb, vs, ob, os_, scale, int(causal), _stream())
-
-
-def flash_bwd_x3(q, k, v, o, dout, lse, key_mask, dq, dk, dv, delta, B, H, Sq, Sk, hd, scale, causal, kmax=None):
-    (qt, qo, qs, qb), (kt, ko, ks, kb), (vt, vo, vs, vb), (ot, oo, os_, ob) = q, k, v, o
-    (dqt, dqo, dqs, dqb), (dkt, dko, dks, dkb), (dvt, dvo, dvs, dvb) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
-    LIB.call('pb_flash_bwd_x3', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), _p(key_mask), _p(kmax), pp(dqt, dqo), pp(dkt, dko),
-             pp(dvt, dvo), _p(delta), B, H, Sq, Sk, hd, qb, qs, kb, ks, vb, vs, ob, os_, dqb, dqs, dkb, dks, dvb, dvs, scale, int(causal), _stream())
-
-
-def flash_fwd_x3_packed(q, k, v, o, lse, rows, B, H, hd, scale, causal):
-    """q,k,v,o: (tensor, element offset, row stride) f32 over packed rows (bf16x3 instantiation)."""
-    (qt, qo, qs), (kt, ko, ks), (vt, vo, vs), (ot, oo, os_) = q, k, v, o
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
-    LIB.call('pb_flash_fwd_x3_packed', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(lse), _p(rows.q_off), _p(rows.q_len), _p(rows.k_off),
-             _p(rows.k_len), _p(rows.k_vis), B, H, rows.Sq_max, rows.Sk_max, hd, qs, ks, vs, os_, scale, int(causal), _stream())
-
-
-def flash_bwd_x3_packed(q, k, v, o, dout, lse, dq, dk, dv, delta, rows, B, H, hd, scale, causal):
-    (qt, qo, qs), (kt, ko, ks), (vt, vo, vs), (ot, oo, os_) = q, k, v, o
-    (dqt, dqo, dqs), (dkt, dko, dks), (dvt, dvo, dvs) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off)
-    LIB.call('pb_flash_bwd_x3_packed', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), pp(dqt, dqo), pp(dkt, dko), pp(dvt, dvo),
-             _p(delta), _p(rows.q_off), _p(rows.q_len), _p(rows.k_off), _p(rows.k_len), _p(rows.k_vis), B, H, rows.Sq_max, rows.Sk_max, hd,
-             qs, ks, vs, os_, dqs, dks, dvs, scale, int(causal), _stream())
-
-
 class PackedRows:
-    """Row descriptors of one packed attention call (include/pianobart_hip.h, pb_flash_*_packed): device int32 (B) tensors plus
+    """Row descriptors of one packed attention call (include/pianobart_hip.h, pb_attn_desc): device int32 (B) tensors plus
     the two maxima."""
 
     def __init__(self, q_off, q_len, k_off, k_len, k_vis, Sq_max, Sk_max, kind='', order=None):
         self.q_off, self.q_len, self.k_off, self.k_len, self.k_vis, self.Sq_max, self.Sk_max = q_off, q_len, k_off, k_len, k_vis, Sq_max, Sk_max
         self.kind = kind                    # a label for profiles ('enc', 'dec', 'cross')
         self.order = order                  # device int32 (B * H): dispatch order of the (batch, head) pairs, longest first (or None)
-
-
-def flash_fwd_packed(q, k, v, o, lse, rows, B, H, hd, scale, causal):
-    """q,k,v,o: (tensor, element offset, row stride) bf16 over packed rows."""
-    (qt, qo, qs), (kt, ko, ks), (vt, vo, vs), (ot, oo, os_) = q, k, v, o
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    LIB.call('pb_flash_fwd_packed', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(lse), _p(rows.q_off), _p(rows.q_len), _p(rows.k_off),
-             _p(rows.k_len), _p(rows.k_vis), B, H, rows.Sq_max, rows.Sk_max, hd, qs, ks, vs, os_, scale, int(causal), _p(rows.order), _stream())
-
-
-def flash_bwd_packed(q, k, v, o, dout, lse, dq, dk, dv, delta, rows, B, H, hd, scale, causal, dbias=None, dbias_ws=None):
-    (qt, qo, qs), (kt, ko, ks), (vt, vo, vs), (ot, oo, os_) = q, k, v, o
-    (dqt, dqo, dqs), (dkt, dko, dks), (dvt, dvo, dvs) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    LIB.call('pb_flash_bwd_packed', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), pp(dqt, dqo), pp(dkt, dko), pp(dvt, dvo),
-             _p(delta), _p(rows.q_off), _p(rows.q_len), _p(rows.k_off), _p(rows.k_len), _p(rows.k_vis), B, H, rows.Sq_max, rows.Sk_max, hd,
-             qs, ks, vs, os_, dqs, dks, dvs, scale, int(causal), _p(dbias[0]) if dbias else None, _p(dbias[1]) if dbias else None,
-             _p(dbias[2]) if dbias else None, _p(dbias_ws) if dbias else None, _p(rows.order), _stream())
 
 
 _fa1_ws = {}
@@ -338,28 +274,82 @@ def _flash1_ws(nbytes, device):
     return ws
 
 
+def _attn(entry, dtype, q, k, v, o, lse, B, H, hd, scale, causal, *, Sq=0, Sk=0, key_mask=None, kmax=None, rows=None, generic=False,
+          dout=None, grads=None, delta=None, dbias=None, dbias_ws=None, one_pass=False, q_rows=None, delta_rows=None):
+    """One pb_attn_desc, one call (entry = 'pb_attn_fwd' / 'pb_attn_bwd'). q, k, v, o and grads = (dq, dk, dv) are (tensor, element
+    offset, row stride[, batch stride]); dout is a tensor with o's strides. rows (a PackedRows) replaces Sq / Sk / key_mask / kmax
+    (its dispatch order is for the bf16 kernels only). one_pass: the one-pass backward with its slab workspace (q_rows: rows of the q side)."""
+    d = AttnDesc()
+    esz = 2 if dtype == PB_BF16 else 4
+    for name, (t, off, ss, *sb) in zip(('q', 'k', 'v', 'o', 'dq', 'dk', 'dv'), (q, k, v, o) + tuple(grads or ())):
+        setattr(d, name, _adr(t) + esz * off)
+        setattr(d, name + '_ss', ss)
+        setattr(d, name + '_sb', sb[0] if sb else 0)
+    d.dout, d.lse, d.delta, d.key_mask, d.kmax, d.delta_rows = _adr(dout), _adr(lse), _adr(delta), _adr(key_mask), _adr(kmax), _adr(delta_rows)
+    if rows is not None:
+        Sq, Sk = rows.Sq_max, rows.Sk_max
+        d.q_off, d.q_len, d.k_off, d.k_len, d.k_vis = _adr(rows.q_off), _adr(rows.q_len), _adr(rows.k_off), _adr(rows.k_len), _adr(rows.k_vis)
+        d.bh_order = _adr(rows.order) if dtype == PB_BF16 else None
+    if dbias:
+        d.dbias_q, d.dbias_k, d.dbias_v, d.dbias_ws = _adr(dbias[0]), _adr(dbias[1]), _adr(dbias[2]), _adr(dbias_ws)
+    if one_pass:
+        d.q_rows = q_rows if q_rows is not None else B * Sq
+        d.dq_ws = _adr(_flash1_ws(int(LIB.query('pb_flash_bwd1_ws_bytes', d.q_rows, H, hd, Sk)), q[0].device))
+    d.dtype, d.B, d.H, d.Sq, d.Sk, d.hd, d.scale = dtype, B, H, Sq, Sk, hd, scale
+    d.flags = (ATTN_CAUSAL if causal else 0) | (ATTN_GENERIC if generic else 0) | (ATTN_ONE_PASS if one_pass else 0)
+    LIB.call(entry, ctypes.byref(d), _stream())
+
+
+def flash_fwd(q, k, v, o, lse, key_mask, B, H, Sq, Sk, hd, scale, causal, force_generic=False, kmax=None):
+    """q,k,v,o: (tensor, element offset, row stride, batch stride) bf16."""
+    _attn('pb_attn_fwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, Sq=Sq, Sk=Sk, key_mask=key_mask, kmax=kmax, generic=force_generic)
+
+
+def flash_bwd(q, k, v, o, dout, lse, key_mask, dq, dk, dv, delta, B, H, Sq, Sk, hd, scale, causal, force_generic=False, kmax=None, dbias=None, dbias_ws=None):
+    """dbias = (gq, gk, gv): f32 vectors of H*hd that receive += the column sums of dq / dk / dv (bias gradients), with dbias_ws."""
+    _attn('pb_attn_bwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, Sq=Sq, Sk=Sk, key_mask=key_mask, kmax=kmax, generic=force_generic,
+          dout=dout, grads=(dq, dk, dv), delta=delta, dbias=dbias, dbias_ws=dbias_ws)
+
+
 def flash_bwd1(q, k, v, o, dout, lse, key_mask, dq, dk, dv, delta, B, H, Sq, Sk, hd, scale, causal, kmax=None, dbias=None, dbias_ws=None, delta_rows=None):
-    """pb_flash_bwd1: flash_bwd's arguments and results, one pass over the (key block, query tile) pairs (head_dim 64)."""
-    (qt, qo, qs, qb), (kt, ko, ks, kb), (vt, vo, vs, vb), (ot, oo, os_, ob) = q, k, v, o
-    (dqt, dqo, dqs, dqb), (dkt, dko, dks, dkb), (dvt, dvo, dvs, dvb) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    ws = _flash1_ws(int(LIB.query('pb_flash_bwd1_ws_bytes', B * Sq, H, hd, Sk)), qt.device)
-    LIB.call('pb_flash_bwd1', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), _p(key_mask), _p(kmax), pp(dqt, dqo),
-             pp(dkt, dko), pp(dvt, dvo), _p(delta), B, H, Sq, Sk, hd, qb, qs, kb, ks, vb, vs, ob, os_, dqb, dqs, dkb, dks, dvb, dvs,
-             scale, int(causal), _p(dbias[0]) if dbias else None, _p(dbias[1]) if dbias else None,
-             _p(dbias[2]) if dbias else None, _p(dbias_ws) if dbias else None, _p(ws), _p(delta_rows), _stream())
+    """flash_bwd's arguments and results, one pass over the (key block, query tile) pairs (head_dim 64)."""
+    _attn('pb_attn_bwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, Sq=Sq, Sk=Sk, key_mask=key_mask, kmax=kmax, dout=dout, grads=(dq, dk, dv),
+          delta=delta, dbias=dbias, dbias_ws=dbias_ws, one_pass=True, delta_rows=delta_rows)
+
+
+def flash_fwd_packed(q, k, v, o, lse, rows, B, H, hd, scale, causal):
+    """q,k,v,o: (tensor, element offset, row stride) bf16 over packed rows."""
+    _attn('pb_attn_fwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, rows=rows)
+
+
+def flash_bwd_packed(q, k, v, o, dout, lse, dq, dk, dv, delta, rows, B, H, hd, scale, causal, dbias=None, dbias_ws=None):
+    _attn('pb_attn_bwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, rows=rows, dout=dout, grads=(dq, dk, dv), delta=delta,
+          dbias=dbias, dbias_ws=dbias_ws)
 
 
 def flash_bwd1_packed(q, k, v, o, dout, lse, dq, dk, dv, delta, rows, B, H, hd, scale, causal, q_rows, dbias=None, dbias_ws=None, delta_rows=None):
-    """pb_flash_bwd1_packed: flash_bwd_packed's arguments and results in one pass; q_rows = rows of the q-side tensors."""
-    (qt, qo, qs), (kt, ko, ks), (vt, vo, vs), (ot, oo, os_) = q, k, v, o
-    (dqt, dqo, dqs), (dkt, dko, dks), (dvt, dvo, dvs) = dq, dk, dv
-    pp = lambda t, off: ctypes.c_void_p(t.data_ptr() + 2 * off)
-    ws = _flash1_ws(int(LIB.query('pb_flash_bwd1_ws_bytes', q_rows, H, hd, rows.Sk_max)), qt.device)
-    LIB.call('pb_flash_bwd1_packed', pp(qt, qo), pp(kt, ko), pp(vt, vo), pp(ot, oo), _p(dout), _p(lse), pp(dqt, dqo), pp(dkt, dko), pp(dvt, dvo),
-             _p(delta), _p(rows.q_off), _p(rows.q_len), _p(rows.k_off), _p(rows.k_len), _p(rows.k_vis), B, H, rows.Sq_max, rows.Sk_max, hd,
-             qs, ks, vs, os_, dqs, dks, dvs, scale, int(causal), _p(dbias[0]) if dbias else None, _p(dbias[1]) if dbias else None,
-             _p(dbias[2]) if dbias else None, _p(dbias_ws) if dbias else None, _p(ws), q_rows, _p(rows.order), _p(delta_rows), _stream())
+    """flash_bwd_packed's arguments and results in one pass; q_rows = rows of the q-side tensors."""
+    _attn('pb_attn_bwd', PB_BF16, q, k, v, o, lse, B, H, hd, scale, causal, rows=rows, dout=dout, grads=(dq, dk, dv), delta=delta,
+          dbias=dbias, dbias_ws=dbias_ws, one_pass=True, q_rows=q_rows, delta_rows=delta_rows)
+
+
+def flash_fwd_x3(q, k, v, o, lse, key_mask, B, H, Sq, Sk, hd, scale, causal, kmax=None):
+    """Fused attention of the bf16x3 instantiation. q,k,v,o: (tensor, element offset, row stride, batch stride) f32."""
+    _attn('pb_attn_fwd', PB_F32X3, q, k, v, o, lse, B, H, hd, scale, causal, Sq=Sq, Sk=Sk, key_mask=key_mask, kmax=kmax)
+
+
+def flash_bwd_x3(q, k, v, o, dout, lse, key_mask, dq, dk, dv, delta, B, H, Sq, Sk, hd, scale, causal, kmax=None):
+    _attn('pb_attn_bwd', PB_F32X3, q, k, v, o, lse, B, H, hd, scale, causal, Sq=Sq, Sk=Sk, key_mask=key_mask, kmax=kmax,
+          dout=dout, grads=(dq, dk, dv), delta=delta)
+
+
+def flash_fwd_x3_packed(q, k, v, o, lse, rows, B, H, hd, scale, causal):
+    """q,k,v,o: (tensor, element offset, row stride) f32 over packed rows (bf16x3 instantiation)."""
+    _attn('pb_attn_fwd', PB_F32X3, q, k, v, o, lse, B, H, hd, scale, causal, rows=rows)
+
+
+def flash_bwd_x3_packed(q, k, v, o, dout, lse, dq, dk, dv, delta, rows, B, H, hd, scale, causal):
+    _attn('pb_attn_bwd', PB_F32X3, q, k, v, o, lse, B, H, hd, scale, causal, rows=rows, dout=dout, grads=(dq, dk, dv), delta=delta)
 
 
 def rowmap_count(emask, dmask, loss_mask, counts):

@@ -79,6 +79,6 @@ def test_batched_decoder_abi_is_declared_and_exported():
     assert len(decls['pb_batch_decoder_sampler_init'][1]) == 11
     # pb_decode_batch = the plan, B, padding, s_enc[16]
     assert ctypes.sizeof(_lib.DecodeBatch) == ctypes.sizeof(_lib.DecodePlan) + 4 + 4 + 16 * 4
-    assert _lib.LIB.query('pb_abi_version') == 9
+    assert _lib.LIB.query('pb_abi_version') == 10
     dll = ctypes.CDLL(_lib.LIB_PATH)
     assert all(hasattr(dll, n) for n in names)

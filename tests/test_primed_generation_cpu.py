@@ -114,5 +114,5 @@ def test_demo_takes_the_prime_flag():
 def test_batch_decoder_start_is_declared_and_exported():
     decls = _lib.parse_header()
     assert decls['pb_batch_decoder_start'][1] == [ctypes.c_void_p] * 4
-    assert _lib.LIB.query('pb_abi_version') == 9
+    assert _lib.LIB.query('pb_abi_version') == 10
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 'pb_batch_decoder_start')

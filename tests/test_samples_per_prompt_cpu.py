@@ -98,7 +98,7 @@ def test_demo_samples_flag_rules_and_file_names():
         D.check_samples_args(2, None)
 
 
-def test_share_cross_is_declared_exported_and_the_abi_stays_9():
+def test_share_cross_is_declared_and_exported():
     decls = _lib.parse_header()
     assert 'pb_batch_decoder_share_cross' in decls
     restype, argtypes = decls['pb_batch_decoder_share_cross']
@@ -108,7 +108,7 @@ def test_share_cross_is_declared_exported_and_the_abi_stays_9():
         build(verbose=False)
     dll = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(dll, 'pb_batch_decoder_share_cross')
-    assert _lib.LIB.query('pb_abi_version') == 9
+    assert _lib.LIB.query('pb_abi_version') == 10
     # a null decoder or map is refused through pb_last_error, without touching a device
     assert _lib.LIB.query('pb_batch_decoder_share_cross', None, 1, None) < 0
     assert b'share_cross' in _lib.LIB.load().pb_last_error()

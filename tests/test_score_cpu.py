@@ -141,7 +141,7 @@ def test_header_declares_and_library_exports_the_score_symbols():
         build(verbose=False)
     dll = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(dll, 'pb_token_scores') and hasattr(dll, 'pb_seq_scores')
-    assert _lib.LIB.query('pb_abi_version') == 9
+    assert _lib.LIB.query('pb_abi_version') == 10
 
 
 def test_score_ops_refuse_cpu_tensors():
