@@ -455,7 +455,19 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   workgroup per (head, key split, tile of <= 4 rows of a slice) loads the K / V chunks, W_q rows and b_q
  *                                   once for the tile; each row's arithmetic, hence its logits, is bit for bit the per-row kernel's, and the
  *                                   launches per step do not change. PB_DECODE_CROSS_GROUPED=0 keeps the per-row kernel reading through
- *                                   kv_row, PB_DECODE_GROUP_TILE=2|4|8 sets the tile (developer A/B switches). */
+ *                                   kv_row, PB_DECODE_GROUP_TILE=2|4|8 sets the tile (developer A/B switches).
+ * Forced tokens (an addition to ABI 10): part of a piece is given, per position and head, and the rest is sampled.
+ *   pb_batch_decoder_force          after pb_batch_decoder_sampler_init, before the first pb_batch_decoder_start / launch of the run:
+ *                                   forced = (B, S, 8) host int16 in model column order, -1 = the head is free, v >= 0 = head h of
+ *                                   position i of row b is v (any id of the head's table, specials included). The table is copied to
+ *                                   device memory the decoder owns. The sampler kernel then reads its position's 8 entries with its draws:
+ *                                   a given head's id replaces the sampled one (in front of the done test, so a given special id stops
+ *                                   the row and a given ordinary id keeps it going), a free head's id is what the unforced kernel picks
+ *                                   for the same logits and draw, and a position with all 8 heads given writes its ids without sampling
+ *                                   (and without logging its logits row). Launches per step and the single-stream graph do not change;
+ *                                   a decoder without the call runs the unforced kernel. A value that is neither -1 nor inside its
+ *                                   head's table (n8 of sampler_init), a call before sampler_init, or a call after a step was issued or
+ *                                   captured is refused (< 0, pb_last_error) and changes nothing. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -476,6 +488,7 @@ int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const int16_t* ne
 int pb_batch_decoder_launches(void* dec);
 int pb_batch_decoder_graph(void* dec);
 int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const int32_t* kv_row);
+int pb_batch_decoder_force(void* dec, const int16_t* forced);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

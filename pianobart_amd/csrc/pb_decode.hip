@@ -1208,6 +1208,10 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // One workgroup of 512 threads: wave h = head h for the softmax and the scans; the rank counting of the heads with p < 1 uses one
 // thread per (head, class). fault_period > 0 (tests only) corrupts head 0's id of row fault_row (the single row: row 0) at every
 // fault_period-th position. Row form: a special id (>= pad[h] for any head) marks the row done.
+// FORCED (pb_batch_decoder_force): a (B, S, 8) table of given ids, -1 = free. The given heads of a position overwrite the sampled ones
+// in the last stage, in front of the fault injection and the done test, so the arithmetic of a free head is the unforced kernel's; a
+// position with all 8 heads given writes its ids and returns (no logits log: the host does not read that row). The FORCED = false
+// instantiations are the kernels and kernarg layouts of a decoder without a table.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1228,6 +1232,11 @@ template <> struct SampleArgs<true> : SampleCommon {
     int off[8], n[8], pad[8];             // pad: the first special id of each head
     float temp[8], p[8];
 };
+template <bool ROWS> struct ForcedSampleArgs : SampleArgs<ROWS> {
+    const int16_t* force;                 // (B, S, 8) given ids of every position, -1 = free, device
+};
+template <bool ROWS, bool FORCED> struct SampleKernArgs { using type = SampleArgs<ROWS>; };
+template <bool ROWS> struct SampleKernArgs<ROWS, true> { using type = ForcedSampleArgs<ROWS>; };
 constexpr int SMP_W = 272;                // >= the largest head (262), multiple of 16
 // inclusive prefix sums over a wave (lane order), by shuffles
 __device__ __forceinline__ float wave_scan_f(float v, int lane) {
@@ -1235,8 +1244,8 @@ __device__ __forceinline__ float wave_scan_f(float v, int lane) {
     for (int o = 1; o < 64; o <<= 1) { const float u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
     return v;
 }
-template <bool ROWS>
-__global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs<ROWS> a) {
+template <bool ROWS, bool FORCED>
+__global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKernArgs<ROWS, FORCED>::type a) {
     __shared__ __attribute__((aligned(16))) float pn[8][SMP_W];     // normalised probabilities, class order
     __shared__ float sp[8][SMP_W + 64];   // ... in descending order (heads with p < 1), zero tail
     __shared__ int si[8][SMP_W];          // class of each sorted entry
@@ -1250,6 +1259,21 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs<ROWS> 
     const int n = a.n[h], off = a.off[h];
     const float T = a.temp[h];
     const double u_draw = a.u[((size_t)b * a.S + pos) * 8 + h];  // requested now: a load that depends on pos would otherwise sit at the end of the chain
+    [[maybe_unused]] int f = -1;                                 // the given id of head t & 7 at this position
+    if constexpr (FORCED) {
+        const int16_t* fr = a.force + ((size_t)b * a.S + pos) * 8;
+        const uint4 all = *reinterpret_cast<const uint4*>(fr);   // the 8 entries of the position: 16 bytes, 16-byte aligned
+        f = fr[t & 7];
+        if ((((all.x | all.y) | (all.z | all.w)) & 0x80008000u) == 0) {     // all 8 heads given (block-uniform): nothing to sample
+            if constexpr (ROWS) __syncthreads();                 // every thread has read done[b] before it may change
+            if (t < 8) {
+                a.tok_dev[b * 8 + t] = (int16_t)f;
+                a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)f;
+                if constexpr (ROWS) { if (f >= a.pad[t]) a.st->done[b] = 1; }
+            }
+            return;
+        }
+    }
     // softmax(logit / T) of head h (torch.softmax(logit / t, dim=-1), model.py:103-104), then probs /= (sum(probs) + 1e-5) (model.py:85).
     // The sums here are wave reductions, not numpy's left-to-right ones: a common divisor that differs in its last bit moves every
     // probability alike, so the order and (but for a 1e-7 neighbourhood of a threshold) the choice stay -- the host checks every position.
@@ -1345,6 +1369,7 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const SampleArgs<ROWS> 
     __syncthreads();
     if (t < 8) {
         int id = htok[t];
+        if constexpr (FORCED) { if (f >= 0) id = f; }
         if (a.fault_period > 0 && (!ROWS || b == a.fault_row) && t == 0 && (pos % a.fault_period) == a.fault_period - 1) id = (id + 1) % a.n[0];
         a.tok_dev[b * 8 + t] = (int16_t)id;
         a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)id;
@@ -1369,6 +1394,7 @@ struct Decoder {
     int16_t* log_tok = nullptr;            // pinned (B, S, 8)
     SampleArgs<true> sa{};                 // the sampler constants (the single-row kernel takes its subset)
     bool sampler = false;
+    int16_t* force_dev = nullptr;          // pb_batch_decoder_force: (B, S, 8) given ids, -1 = free; the steps then end with the FORCED sampler
     hipGraph_t graph[N_GRAPHS] = {};
     hipGraphExec_t exec[N_GRAPHS] = {};
     hipEvent_t ev = nullptr;
@@ -1487,13 +1513,27 @@ static int step_issue(Decoder* D, bool sample) {
     ++n;
     if (sample) {
         if constexpr (ROWS) {
-            hipLaunchKernelGGL(dec_sample_kernel<true>, dim3(B), dim3(512), 0, st, D->sa);
+            if (D->force_dev) {
+                ForcedSampleArgs<true> sf{};
+                static_cast<SampleArgs<true>&>(sf) = D->sa;
+                sf.force = D->force_dev;
+                hipLaunchKernelGGL((dec_sample_kernel<true, true>), dim3(B), dim3(512), 0, st, sf);
+            } else {
+                hipLaunchKernelGGL((dec_sample_kernel<true, false>), dim3(B), dim3(512), 0, st, D->sa);
+            }
         } else {
             SampleArgs<false> s1{};
             static_cast<SampleCommon&>(s1) = D->sa;
             s1.vocab = D->sa.vocab; s1.fault_period = D->sa.fault_period;
             for (int k = 0; k < 8; ++k) { s1.off[k] = D->sa.off[k]; s1.n[k] = D->sa.n[k]; s1.temp[k] = D->sa.temp[k]; s1.p[k] = D->sa.p[k]; }
-            hipLaunchKernelGGL(dec_sample_kernel<false>, dim3(1), dim3(512), 0, st, s1);
+            if (D->force_dev) {
+                ForcedSampleArgs<false> sf{};
+                static_cast<SampleArgs<false>&>(sf) = s1;
+                sf.force = D->force_dev;
+                hipLaunchKernelGGL((dec_sample_kernel<false, true>), dim3(1), dim3(512), 0, st, sf);
+            } else {
+                hipLaunchKernelGGL((dec_sample_kernel<false, false>), dim3(1), dim3(512), 0, st, s1);
+            }
         }
         PB_LAUNCH_CHECK(); ++n;
     }
@@ -1588,6 +1628,7 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     drop_graphs(D);
     for (int i = 0; i < SPEC_EVENTS; ++i) if (D->evs[i]) (void)hipEventDestroy(D->evs[i]);
     if (D->u_dev) (void)hipFree(D->u_dev);
+    if (D->force_dev) (void)hipFree(D->force_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
     if (D->ev) (void)hipEventDestroy(D->ev);
@@ -1714,6 +1755,35 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
     drop_graphs(D);                                                     // captured with the previous constants
     D->sampler = true;
+    return 0;
+}
+
+// Forced tokens (see the header): the (B, S, 8) table of given ids goes up once, into memory the decoder owns. Every value is checked on
+// the host against the n8 / S of sampler_init before anything changes; the graphs are captured afterwards, with the FORCED sampler node.
+extern "C" int pb_batch_decoder_force(void* dec, const int16_t* forced) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && forced, "pb_batch_decoder_force: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_force: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_force: a step was already issued; the sampler kernel is fixed for this decoder");
+    const size_t n = (size_t)D->B * (size_t)D->bp.plan.S * 8;
+    for (size_t k = 0; k < n; ++k) {
+        const int v = forced[k], h = (int)(k & 7);
+        PB_REQUIRE(v == -1 || (v >= 0 && v < D->sa.n[h]), "pb_batch_decoder_force: row %d, position %d, head %d: id %d is neither -1 nor inside the "
+                   "head's table (%d ids)", (int)(k / 8 / (size_t)D->bp.plan.S), (int)(k / 8 % (size_t)D->bp.plan.S), h, v, D->sa.n[h]);
+    }
+    int16_t* tab = nullptr;
+    if (hipMalloc(&tab, sizeof(int16_t) * n) != hipSuccess) {
+        pb_set_error("pb_batch_decoder_force: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    if (hipMemcpyAsync(tab, forced, sizeof(int16_t) * n, hipMemcpyHostToDevice, D->stream) != hipSuccess ||
+        hipStreamSynchronize(D->stream) != hipSuccess) {         // `forced` may be pageable: the copy is done when we return
+        pb_set_error("pb_batch_decoder_force: upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(tab);
+        return -1;
+    }
+    if (D->force_dev) (void)hipFree(D->force_dev);
+    D->force_dev = tab;
     return 0;
 }
 

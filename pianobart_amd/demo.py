@@ -23,11 +23,12 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16', prime=None, samples=1, seed=None):
+                 precision='bf16', prime=None, samples=1, seed=None, keep=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
         self.prime = prime                  # None, N or 'half': continue the piece from its first rows (eval_generation's --prime rule)
+        self.keep = keep                    # None or 'ATTR[,ATTR...]': attributes of the piece's own rows behind the prime that are kept (needs prime)
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -49,6 +50,8 @@ def get_args(argv=None):
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
     ap.add_argument('--prime', type=str, default=None, help='N or "half": keep the first k = min(N, L) (half: L // 2) rows of the piece and '
                     'continue from there (eval_generation --prime)')
+    ap.add_argument('--keep', type=str, default=None, help='ATTR[,ATTR...] of bar, position, instrument, pitch, duration, velocity, timesig, tempo (needs '
+                    '--prime): these attributes of the input piece behind the prime are kept and the model writes the others')
     ap.add_argument('--samples', type=int, default=1, help='continuations of the piece: n MIDI files, --output for the first, the others with '
                     'the sample index in front of the extension (out.mid, out.1.mid, ..); n > 1 needs --seed')
     ap.add_argument('--seed', type=int, default=None, help='with --samples: sample j draws from RandomState(seed + j)')
@@ -69,9 +72,21 @@ def check_samples_args(samples, seed):
         raise PBError('--samples %d needs --seed: sample j draws from its own RandomState(seed + j)' % samples)
 
 
+def check_keep_args(keep, prime):
+    """The --keep rules; raises PBError. Returns the kept head indices, or None."""
+    if keep is None:
+        return None
+    from .generation import parse_keep
+    heads = parse_keep(keep)
+    if prime is None:
+        raise PBError('--keep needs --prime: the kept attributes come from the piece\'s own rows behind the prime')
+    return heads
+
+
 def demo(args=None):
     if not args:
         args = get_args()
+    keep = check_keep_args(getattr(args, 'keep', None), getattr(args, 'prime', None))
     if args.cpu or not torch.cuda.is_available():
         raise PBError('pianobart_amd has no CPU execution path: demo() needs an MI355X')
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
@@ -98,9 +113,12 @@ def demo(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
-    octuple, prefix, ks = octuple.long(), None, None
+    octuple, prefix, ks, forced = octuple.long(), None, None, None
     if prime is not None:                    # the piece's first k rows primed, the encoder sees them only
         ks = prime_lengths(octuple.numpy(), prime, pianobart.bar_pad_word, pianobart.pad_word_np)
+        if keep is not None:                 # the kept attributes of the piece's rows behind the prime are given, the others sampled
+            from .generation import keep_mask
+            forced = keep_mask(octuple, keep, ks, pianobart.bar_pad_word)
         octuple, prefix = prime_inputs(octuple, ks, pianobart.pad_word_np)
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
@@ -108,9 +126,11 @@ def demo(args=None):
         if samples > 1:                      # n continuations from one encoder pass: sample j of the one piece under RandomState(seed + j)
             from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
-                                     decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples)
+                                     decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples,
+                                     decoder_forced=forced)
         else:
-            y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
+            y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
+                      decoder_forced=forced)
     for j, path in enumerate(sample_paths(args.output, samples)):
         if Octuple2Midi(y[j:j + 1], path):
             print(f"Saved to {path}")

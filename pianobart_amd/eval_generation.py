@@ -16,6 +16,11 @@ RNG rules:
     pass and cross-attention K/V (PianoBartLM.generate_batch's samples_per_prompt), and the file does not depend on --batch_size.
 The prompts are sliced from the loaded array in order; --num_workers is accepted for the reference's command lines and not needed.
 
+Kept attributes (--keep ATTR[,ATTR...], needs --prime): the named attributes (bar, position, instrument, pitch, duration, velocity, timesig,
+tempo) of the dataset piece's own rows behind the prime, up to and including its EOS row, are given to the generation and the model samples
+the other attributes (generation.keep_mask with start = k_b -> PianoBartLM.generate_batch's decoder_forced). The generation file has the
+shape and dtype it has without the flag, and without the flag it is byte-identical. --score still scores all 8 heads of a position.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -34,7 +39,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import sample_seed
+from .generation import keep_mask, parse_keep, sample_seed
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -65,8 +70,10 @@ def get_args(argv=None):
                     'L = rows whose bar id is not PAD (Ablation.py:134); the encoder sees rows < k only')
     ap.add_argument('--samples', type=int, default=1, help='continuations per prompt; n > 1 needs --seed and writes (N, n, max_seq_len, 8), '
                     'sample j of prompt i drawing from RandomState(seed + j * N + i)')
+    ap.add_argument('--keep', type=str, default=None, help='ATTR[,ATTR...] of bar, position, instrument, pitch, duration, velocity, timesig, tempo (needs '
+                    '--prime): these attributes of the piece\'s own rows behind the prime are kept and the model samples the others')
     ap.add_argument('--score', action='store_true', help='also write the teacher-forced scores of the generated rows: float32 (N, 9) or (N, n, 9) = the 8 '
-                    'per-head sums of log-probability and the number of scored positions')
+                    'per-head sums of log-probability and the number of scored positions (all 8 heads of a position, kept by --keep or sampled)')
     ap.add_argument('--score_output', type=str, default=None, help='path of the score file (default: --output with .npy replaced by _score.npy)')
     ap.add_argument('--pick', type=str, default=None, choices=['best'], help='best: write only the sample of each prompt with the largest mean '
                     'log-probability per scored position, (N, max_seq_len, 8); needs --score')
@@ -122,6 +129,12 @@ def check_args(args):
     parse_prime(getattr(args, 'prime', None))
     if args.batch_size < 1:
         raise PBError('--batch_size must be >= 1 (got %d)' % args.batch_size)
+    if getattr(args, 'keep', None) is not None:
+        parse_keep(args.keep)
+        if getattr(args, 'prime', None) is None:
+            raise PBError('--keep needs --prime: the kept attributes come from the piece\'s own rows behind the prime')
+        if getattr(args, 'score_dataset', False):
+            raise PBError('--score_dataset generates nothing: it takes no --keep')
     samples = getattr(args, 'samples', 1)
     if samples < 1:
         raise PBError('--samples must be >= 1 (got %d)' % samples)
@@ -189,6 +202,7 @@ def eval_generation(args=None):
     bar_pad = model.pianobart.bar_pad_word
     prime = parse_prime(getattr(args, 'prime', None))
     samples = getattr(args, 'samples', 1)
+    keep = parse_keep(args.keep) if getattr(args, 'keep', None) is not None else None
     output = np.zeros((N, args.max_seq_len, 8) if samples == 1 else (N, samples, args.max_seq_len, 8), dtype=np.float32)
     do_score = getattr(args, 'score', False)
     scores = np.zeros((N, 9) if samples == 1 else (N, samples, 9), dtype=np.float32)
@@ -221,13 +235,14 @@ def eval_generation(args=None):
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
             x = torch.as_tensor(np.asarray(data[c0:c1])).long()
-            prefix = ks = None
+            prefix = ks = forced = None
             if prime is not None:
                 ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
+                forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None
                 x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
-                                     device_num=device_num, decoder_prefix=prefix, prefix_len=ks,
+                                     device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced,
                                      samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
             if do_score:
                 own = [i - c0 for i, _ in chunk]
@@ -240,17 +255,19 @@ def eval_generation(args=None):
         for c0 in range(0, N if samples == 1 else 0, args.batch_size):
             c1 = min(N, c0 + args.batch_size)
             x = torch.as_tensor(np.asarray(data[c0:c1])).long()
-            prefix = ks = None
+            prefix = ks = forced = None
             if prime is not None:                     # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
                 ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
+                forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None     # from the piece's rows, before prime_inputs pads them
                 x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
-                y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix)
+                y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
+                          decoder_forced=forced)
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
-                                         decoder_prefix=prefix, prefix_len=ks)
+                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced)
             output[c0:c1] = y.float().cpu().numpy()
             if do_score:
                 scores[c0:c1], _ = score_rows(x, y, ks)

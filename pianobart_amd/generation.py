@@ -84,6 +84,112 @@ def check_samples(samples, P, n_rngs):
     return owner
 
 
+KEEP_NAMES = ('bar', 'position', 'instrument', 'pitch', 'duration', 'velocity', 'timesig', 'tempo')       # the 8 heads, model column order
+
+
+def check_forced(forced, P, S, sizes, ks, owner=None):
+    """The argument rules of forced tokens, on the host before any device work. forced: (P, S, 8) integers in model column order (tensor on
+    any device, or array): -1 = the head is free, v >= 0 = head h of position i of prompt p is v. sizes: the 8 table sizes (a given id may be
+    any id of its head's table, specials included); ks: the prefix lengths of check_prefix -- positions below k_p belong to the prefix and
+    must be all -1. owner (row -> prompt, check_samples): the table is expanded to one row per output row. Returns an int16 array
+    (P, S, 8), or (R, S, 8) with owner; None for forced=None or a table that is -1 everywhere (no forcing: the caller runs what it ran
+    before). Raises PBError for a bad shape, dtype or a conflict with a prefix, IndexError for an id outside its table."""
+    if forced is None:
+        return None
+    f = forced.detach().cpu().numpy() if isinstance(forced, torch.Tensor) else np.asarray(forced)
+    if f.ndim != 3 or f.shape != (P, S, 8):
+        raise PBError('forced of shape %s: expected (%d, %d, 8) for %d prompt(s) and a window of %d' % (tuple(f.shape), P, S, P, S))
+    if f.dtype == np.bool_ or not np.issubdtype(f.dtype, np.integer):
+        raise PBError('forced ids must be integers (got %s)' % f.dtype)
+    if not (f != -1).any():
+        return None
+    bad = np.argwhere((f < -1) | (f >= np.asarray(sizes, dtype=np.int64)))
+    if len(bad):
+        b, i, h = (int(v) for v in bad[0])
+        raise IndexError('index out of range in self: forced id %d of prompt %d, position %d, head %d is neither -1 nor inside its table (sizes %s)'
+                         % (int(f[b, i, h]), b, i, h, list(sizes)))
+    for b, kb in enumerate(ks):
+        if (f[b, :kb] != -1).any():
+            raise PBError('forced: prompt %d gives a head at position %d, inside its prefix of %d rows (the prefix already gives those positions)'
+                          % (b, int(np.argwhere((f[b, :kb] != -1).any(1))[0, 0]), kb))
+    f = f.astype(np.int16)
+    return np.ascontiguousarray(f if owner is None else f[np.asarray(owner, dtype=np.int64)])
+
+
+def forced_token(frow, sample):
+    """The token of ONE position under the forced-token contract, for every decode path: the reference's `current_output = self.sample(x, i)`
+    (model.py:46) followed by the overwrite of the given heads. frow: the position's 8 entries (-1 = free) or None; sample(): the path's own
+    sampling of the position, 8 ids. A position with a free head samples (one random_sample(8): the draws of its given heads are consumed and
+    unused); a position whose 8 heads are given does not call sample() at all, so it draws nothing."""
+    if frow is None:
+        return sample()
+    given = frow >= 0
+    if given.all():
+        return torch.from_numpy(frow.astype(np.int64))
+    tok = sample()
+    if given.any():
+        tok = tok.clone()
+        tok[torch.from_numpy(given)] = torch.from_numpy(frow[given].astype(np.int64))
+    return tok
+
+
+def forced_draws(rng, frow, start, S):
+    """The (S, 8) uniform draws of one row made ahead of its decode: one block of 8 from `rng` for every position >= start that has a free
+    head, in position order -- the stream forced_token's sample() calls consume. Positions below start and positions whose 8 heads are
+    given keep 0. frow: the row's (S, 8) forced table or None (every position free)."""
+    U = np.zeros((S, 8), dtype=np.float64)
+    free = np.ones(S, dtype=bool) if frow is None else (np.asarray(frow) < 0).any(1)
+    free[:start] = False
+    U[free] = rng.random_sample(int(free.sum()) * 8).reshape(-1, 8)
+    return U
+
+
+def parse_keep(keep):
+    """The head indices of a list of attribute names (KEEP_NAMES, case-insensitive) and / or indices 0 .. 7, or of one comma-separated
+    string of them (the --keep flag), sorted, each once. Raises PBError for an unknown name or an empty list."""
+    if isinstance(keep, str):
+        keep = [v for v in (w.strip() for w in keep.split(',')) if v]
+    heads = set()
+    for v in keep:
+        if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+            h = int(v)
+        elif isinstance(v, str) and v.lower() in KEEP_NAMES:
+            h = KEEP_NAMES.index(v.lower())
+        elif isinstance(v, str) and v.isdigit():
+            h = int(v)
+        else:
+            h = -1
+        if not 0 <= h < 8:
+            raise PBError('keep: %r is no Octuple attribute (%s, or a head index 0 .. 7)' % (v, ', '.join(KEEP_NAMES)))
+        heads.add(h)
+    if not heads:
+        raise PBError('keep: no attribute named (%s)' % ', '.join(KEEP_NAMES))
+    return sorted(heads)
+
+
+def keep_mask(piece, keep, start=None, bar_pad=256):
+    """The `forced` table that keeps some attributes of a piece and leaves the rest to the model. piece (B, S, 8) Octuple ids; keep: attribute
+    names / head indices (parse_keep); start: B positions (None = 0). For row b the kept heads of positions start_b .. e_b are copied, e_b =
+    the piece's first row whose bar id is special (>= bar_pad: the EOS row, so the generated row ends where the piece ends; the last row if
+    there is none). Every other head and position, the PAD tail included, is -1. Returns int16 (B, S, 8)."""
+    heads = parse_keep(keep)
+    x = piece.detach().cpu().numpy() if isinstance(piece, torch.Tensor) else np.asarray(piece)
+    if x.ndim != 3 or x.shape[2] != 8:
+        raise PBError('keep_mask: piece of shape %s, expected (B, S, 8)' % (tuple(x.shape),))
+    B, S = x.shape[:2]
+    start = [0] * B if start is None else [int(v) for v in (start.tolist() if hasattr(start, 'tolist') else start)]
+    if len(start) != B:
+        raise PBError('keep_mask: %d start positions for %d pieces' % (len(start), B))
+    forced = np.full((B, S, 8), -1, dtype=np.int16)
+    for b in range(B):
+        special = np.flatnonzero(x[b, :, 0] >= bar_pad)
+        e = int(special[0]) if len(special) else S - 1
+        s = max(0, start[b])
+        if s <= e:
+            forced[b, s:e + 1, heads] = x[b, s:e + 1][:, heads].T
+    return forced
+
+
 def sample_seed(seed, j, i, N):
     """The seed of sample j of prompt i among N prompts (eval_generation --samples, demo --samples): seed + j N + i. Sample 0 keeps the
     seed + i of a run without samples, and no two (prompt, sample) pairs of a run share a generator."""
@@ -92,7 +198,7 @@ def sample_seed(seed, j, i, N):
 
 class GenerationMixin:
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -103,16 +209,23 @@ class GenerationMixin:
         then sample on the device ahead of the host (`_decode_device_sampled`) -- `sample_row` still decides every token.
         prefix (1, k, 8): primed generation -- the reference loop with decoder inputs 1 .. k and their mask set to the prefix, the loop
         starting at position k and result[:, :k] = prefix. The forced positions draw nothing; max_new counts sampled positions
-        (the row stops at min(S, k + max_new)). The cache rows of the prefix come from one teacher-forced decoder pass (_prefill)."""
+        (the row stops at min(S, k + max_new)). The cache rows of the prefix come from one teacher-forced decoder pass (_prefill).
+        forced (1, S, 8), -1 = free (check_forced): forced tokens -- the reference loop with the given heads of `current_output` overwritten
+        by forced[0, i] right after `self.sample(x, i)` (forced_token). The stop rule sees the token after forcing; a position with a free
+        head draws its 8 uniforms as ever, a position with all 8 heads given draws nothing; positions below k must be free; max_new counts
+        positions from k on, given or sampled. Leading given positions are stepped through, not prefilled. None, or -1 everywhere: exactly
+        the launches and bytes of a call without the argument."""
         S = int(enc_ids.shape[1])
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
+        forced = check_forced(forced, 1, S, ops.SEG_SIZES, ks)
+        fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -122,10 +235,10 @@ class GenerationMixin:
                 if sampler is not None and _DECODE_SPEC:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                     info = self._decode_device_sampled(run.dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
-                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k])
+                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced)
                     info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k)
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr)
                 self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()))
             else:
                 import ctypes
@@ -138,7 +251,7 @@ class GenerationMixin:
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
-                    tok = sample_row(logit_pin)
+                    tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_pin))
                     if (tok >= pad_cpu).any():
                         break
                     res_cpu[0, i] = tok
@@ -304,9 +417,10 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
-        k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds."""
+        k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
+        fr (S, 8): the row's forced table (forced_token)."""
         import ctypes
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
         if k:
@@ -319,7 +433,7 @@ class GenerationMixin:
         for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
-            tok = sample_row(logit_cpu)
+            tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_cpu))
             if (tok >= pad_cpu).any():
                 break
             res_cpu[0, i] = tok
@@ -330,7 +444,7 @@ class GenerationMixin:
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
-    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None):
+    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -346,10 +460,14 @@ class GenerationMixin:
         through the fused decoder in chunks of BATCH_MAX; inside a chunk the encoder pass, the cross K|V projections and the prefill run
         once per distinct prompt (a prompt whose samples straddle a chunk boundary is encoded once per chunk). Shapes the fused decoder
         declines run the per-prompt loop over the repeated prompts. samples=None is one row per prompt with a cache slice of its own; an
-        explicit samples=1 gives the same rows through the shared-cache form."""
+        explicit samples=1 gives the same rows through the shared-cache form.
+        forced (B, S, 8), -1 = free (check_forced): forced tokens, row b under `generate`'s contract with forced[b]; rows that are -1
+        everywhere are today's rows, so one batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder
+        reads the table on the device (pb_batch_decoder_force) and the host's verification applies it to its own tokens."""
         P = int(enc_ids.shape[0])
         owner = check_samples(samples, P, len(rngs)) if samples is not None else list(range(P))        # row -> prompt
         ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
+        forced = check_forced(forced, P, int(enc_ids.shape[1]), ops.SEG_SIZES, ks)
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -358,30 +476,33 @@ class GenerationMixin:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows)
-            return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner)
+                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced)
+            return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced)
         outs = []
         for c0 in range(0, R, self.BATCH_MAX):
             own = owner[c0:c0 + self.BATCH_MAX]
             p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
             outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
-                                                   groups=[p - p0 for p in own] if samples is not None else None))
+                                                   groups=[p - p0 for p in own] if samples is not None else None,
+                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None))
         return torch.cat(outs, 0)
 
-    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner):
+    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None):
         """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
-                                         max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None)
+                                         max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
+                                         forced[idx.numpy()] if forced is not None else None)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None):
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
-        caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed)."""
+        caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
+        checked table per row (check_forced) or None."""
         saved = np.random.get_state()
         outs = []
         try:
@@ -389,28 +510,29 @@ class GenerationMixin:
                 np.random.set_state(rngs[b].get_state())
                 pre = rows[b:b + 1, :ks[b]] if rows is not None and ks[b] else None
                 outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
-                                          max_new=max_new, sampler=sampler, prefix=pre))
+                                          max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None))
                 rngs[b].set_state(np.random.get_state())
         finally:
             np.random.set_state(saved)
         self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None):
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
         loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled)."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
             info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
-                                               run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts)
+                                               run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
+                                               forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None):
+    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -423,7 +545,11 @@ class GenerationMixin:
         The result is the host's, token for token. inline_verify: the rows are replayed in this thread (B = 1) instead of a small pool.
         starts[b] = k_b (primed rows): row b's positions 0 .. k_b - 1 are its prefix (in res_cpu, their K|V in the cache), so it starts at
         k_b with input res_cpu[b, k_b - 1], its draws start at position k_b and it stops before min(S, k_b + max_new)
-        (pb_batch_decoder_start: per-row positions, inputs and limits in one upload)."""
+        (pb_batch_decoder_start: per-row positions, inputs and limits in one upload).
+        forced (B, S, 8) int16, -1 = free (check_forced), or None: the table goes to the device sampler (pb_batch_decoder_force, between
+        sampler_init and start), the draws made ahead follow it (forced_draws: a fully given position draws nothing) and the host applies
+        it to its own tokens (forced_token: sample() is called only at positions with a free head, the stop test sees the token after
+        forcing), so a given head cannot disagree and the result stays the host's."""
         import contextlib
         import ctypes
         from collections import deque
@@ -436,13 +562,15 @@ class GenerationMixin:
         for b in range(B):
             ahead = np.random.RandomState()
             ahead.set_state(states[b])
-            U[b, starts[b] * 8:] = ahead.random_sample((S - starts[b]) * 8)
+            U[b] = forced_draws(ahead, forced[b] if forced is not None else None, starts[b], S).reshape(-1)
         n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
         off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
         pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
         t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
         LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
                  U.ctypes.data, B * S * 8, limit, int(fault[0]), int(fault[1]))
+        if forced is not None:
+            LIB.call('pb_batch_decoder_force', dec, forced.ctypes.data)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
@@ -476,7 +604,7 @@ class GenerationMixin:
 
         def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(s, e):
-                tok = sample(b, log_logits[b, i])
+                tok = forced_token(forced[b, i] if forced is not None else None, lambda: sample(b, log_logits[b, i]))
                 tokens[b] += 1
                 if (tok >= pad_cpu).any():
                     return ('stop', i)
@@ -516,10 +644,11 @@ class GenerationMixin:
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
                     device_sampler=True, tokens_per_graph_replay=K)
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
-        rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing."""
+        rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
+        fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
@@ -567,17 +696,20 @@ class GenerationMixin:
                     result[:, i, :] = pre[i].to(dev)
                     cur = pre[i].to(dev).reshape(1, 1, 8)
                     continue
-                ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
-                tok = sample_row(logits[0].cpu())
+                frow = fr[i] if fr is not None else None
+                if frow is None or (frow < 0).any():
+                    ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
+                tok = forced_token(frow, lambda: sample_row(logits[0].cpu()))
                 if (tok >= pad_cpu).any():
                     break
                 result[:, i, :] = tok.to(dev)
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
-        cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k."""
+        cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
+        fr (S, 8): the row's forced table (forced_token)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -599,7 +731,7 @@ class GenerationMixin:
                 dec16 = ops.ids_to_i16(dec)
                 dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
                 logits = self.heads_forward(dec_h)
-                cur = sample_row(logits[i].float().cpu())
+                cur = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logits[i].float().cpu()))
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)
                     dmask[:, i + 1] += 1

@@ -344,13 +344,22 @@ class PianoBartLM(nn.Module):
         return self._engine
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
-                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None):
+                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
-        position k on (Engine.generate's `prefix`)."""
+        position k on (Engine.generate's `prefix`).
+        decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
+        "head h of position i is v" (generation.keep_mask builds the table from a piece). The result is the reference loop
+        (model.py:42-65) with the given heads of `current_output` overwritten right after `self.sample(x, i)`: the stop rule sees the token
+        after forcing (a given special id ends the piece there, a given ordinary id keeps it going where the sample would have been
+        special); a position with a free head draws its 8 uniforms as ever (the draws of its given heads are consumed and unused), a
+        position whose 8 heads are given draws nothing; a given id may be any id of its head's table (IndexError otherwise); positions
+        inside decoder_prefix must be -1 (PBError). None, or -1 everywhere, is the call without the argument."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
                 raise PBError('decoder_prefix primes generation: it needs generate=True')
+            if decoder_forced is not None:
+                raise PBError('decoder_forced gives tokens of a generated piece: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             return [logits[..., ops.SEG_OFF[i]:ops.SEG_OFF[i + 1]] for i in range(8)]
@@ -358,12 +367,12 @@ class PianoBartLM(nn.Module):
             print("ERROR")
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
-                           prefix=decoder_prefix)
+                           prefix=decoder_prefix, forced=decoder_forced)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
-                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None):
+                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -373,7 +382,11 @@ class PianoBartLM(nn.Module):
         samples_per_prompt (an int n >= 1, or one int >= 1 per prompt): several continuations of each prompt. input_ids_encoder, the mask,
         decoder_prefix and prefix_len then describe P prompts, seeds / rngs hold R = sum(n_p) generators in prompt-major order (prompt 0's
         samples first) and the result is (R, S, 8) in that order, every row under the contract above with its own generator. The samples
-        of a prompt share its encoder pass, cross-attention K/V and prefill (Engine.generate_batch's `samples`); None: one row per prompt."""
+        of a prompt share its encoder pass, cross-attention K/V and prefill (Engine.generate_batch's `samples`); None: one row per prompt.
+        decoder_forced (B, S, 8), -1 = free: forced tokens, prompt b under forward(generate=True, decoder_forced=...)'s contract with its
+        own table (rows that are -1 everywhere are unforced rows; positions below prefix_len[b] must be -1; max_new counts positions from
+        prefix_len[b] on, given or sampled). With samples_per_prompt it describes the P prompts, like decoder_prefix. The given heads are
+        applied inside the fused decoder's device sampler, so a forced batch keeps the batched decode's launches per step."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -388,7 +401,7 @@ class PianoBartLM(nn.Module):
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
-                                 samples=samples_per_prompt)
+                                 samples=samples_per_prompt, forced=decoder_forced)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):

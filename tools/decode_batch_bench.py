@@ -4,7 +4,10 @@ positions). Prints ONE JSON line: per B in --batches, aggregate tokens/s, ms per
 verification ms per step and an HBM-bytes estimate per step (decoder + LM-head weights once, plus each row's cross K/V over its visible
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
-    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K]
+    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]]
+
+--keep pitch,velocity: forced tokens -- the named attributes of synthetic pieces are given at every position (generation.keep_mask) and the
+model samples the others, at the largest B of --batches: ms per step and rewinds per row, beside the unforced run of the same process.
 
 --samples n: n samples of ONE prompt instead. Three runs alternate in this process, --reps times: "grouped" (samples=n: one encoder pass,
 one (1, S, 2d) cross cache per layer, the grouped cross-attention kernel), "indirect" (the same with PB_DECODE_CROSS_GROUPED=0: the per-row
@@ -33,6 +36,7 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=256, help='generated positions per row')
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4, 8, 16])
     ap.add_argument('--prime', type=int, default=0, help='also time primed generation: K decoder rows given per prompt, --steps sampled after them')
+    ap.add_argument('--keep', type=str, default=None, help='also time forced generation at the largest batch: these attributes of synthetic pieces given, the others sampled')
     ap.add_argument('--samples', type=int, default=0, help='time n samples of one prompt: grouped / indirect / repeated-prompt runs, alternating')
     ap.add_argument('--reps', type=int, default=3, help='--samples: repetitions of the alternating runs')
     ap.add_argument('--kinds', nargs='+', default=['grouped', 'indirect', 'repeated'], choices=['grouped', 'indirect', 'repeated'],
@@ -181,6 +185,25 @@ def main(argv=None):
             if str(B) in res:
                 primed[str(B)]['unprimed_loop_tokens_per_s'] = res[str(B)]['tokens'] / (res[str(B)]['loop_ms'] * 1e-3)
         out['primed'] = dict(prefix_rows=K, by_batch=primed)
+    if args.keep:
+        # forced tokens: the kept attributes of each row's synthetic piece (ordinary events only) are given at every position, the other
+        # heads are sampled; same launches per step, and a given head cannot disagree with the host
+        from pianobart_amd.generation import keep_mask
+        B = Bmax
+        forced = keep_mask(synth_octuple_batch(B, S + 1, seed=11, min_len=S + 1)[5][:, :S], args.keep)
+        by = {}
+        for tag, tab in (('unforced', None), ('forced', forced)):
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=16, sampler=sampler, forced=tab)     # warm-up (capture)
+            torch.cuda.synchronize()
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=steps, sampler=sampler, forced=tab)
+            torch.cuda.synchronize()
+            info = eng.last_decode
+            by[tag] = dict(ms_per_step=info['loop_ms'] / max(1, info['steps']), rewinds_per_row=sum(info['rewinds']) / B, steps=info['steps'],
+                           tokens=sum(info['tokens']), launches_per_step=info['launches_per_token'], graph=info['graph'],
+                           host_ms_per_step=info['host_ms'] / max(1, info['steps']))
+        out['forced'] = dict(keep=args.keep, batch=B, **by)
     print(json.dumps(out), flush=True)
 
 
