@@ -305,6 +305,14 @@ int pb_transpose_batch_bf16(const void* src, void* dst, const int32_t* table, in
  * data-parallel exchange (pianobart_amd/parallel.py; replaces the logits gather + gradient reduce of nn.DataParallel, pretrain.py:63-65) */
 int pb_sum_rows_bf16(const void* src, void* dst, int32_t rows, int64_t n, void* stream);
 
+/* ---- K17: gradient accumulation over micro-batches (pb_accum.hip; an addition to ABI 10) -----------
+ * dst[i] = src[i] (add = 0) or dst[i] += src[i] (add = 1) for 0 <= i < n, both f32. The reference takes one optimizer step per loader
+ * batch (pretrain.py:192-196); this is the `+=` of torch's .grad between backward calls for the flat gradient buffer. Called on whole
+ * flat buffers and on slot ranges of them: the pointers need 4-byte alignment only (a misaligned head and tail are done with scalar
+ * accesses, the body with 16-byte ones; pointers that are offset differently from a 16-byte boundary take scalar accesses throughout).
+ * Nothing outside [0, n) is read or written; no atomics (bit-reproducible); n <= 0 is a no-op that returns 0. */
+int pb_accum_f32(float* dst, const float* src, int64_t n, int32_t add, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

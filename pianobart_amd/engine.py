@@ -142,6 +142,9 @@ class Engine(GenerationMixin, ScoringMixin):
         self._side, self._side_last, self._readers = None, None, {}
         self._kmax = {}
         self.grad_hook = None          # callable(lo, hi): flat gradient range is final (data-parallel bucketing)
+        # gradient accumulation (loss_and_grads(micro=(i, K))): the f32 sum of the micro-batches before the last one (allocated by the first
+        # K > 1 step), the (i, K) of the backward in flight, and the (i, K) the next call must continue
+        self.G_acc, self._micro, self._micro_prev = None, None, None
 
     # ------------------------------------------------------------------ flat parameter layout
     def _layout(self):
@@ -248,6 +251,7 @@ class Engine(GenerationMixin, ScoringMixin):
         self.P32 = P32
         self.G32 = torch.zeros(self.n_total, dtype=torch.float32, device=device)
         self.G32_alt = None
+        self.G_acc, self._micro_prev = None, None
         self.Pbf = torch.empty(self.n_total, dtype=torch.bfloat16, device=device) if self.code == PB_BF16 else None
         self.params = [p for p, _, _ in pm]
         self.param_slots = [(s, r) for _, s, r in pm]
@@ -768,14 +772,29 @@ class Engine(GenerationMixin, ScoringMixin):
 
     def _ready(self, first, last=None):
         if self.grad_hook is not None and self.Gcur is self.G32:
+            if self._micro is not None and self._micro[0] < self._micro[1] - 1:
+                return                                      # gradient accumulation: only the last micro-batch's ranges are final
             a, b = self.slots[first], self.slots[last or first]
+            lo, hi = a.off, b.off + b.numel
             if self._side_last is None:
-                return self.grad_hook(a.off, b.off + b.numel)
+                self._add_accumulated(lo, hi)
+                return self.grad_hook(lo, hi)
             # the range was produced by both streams: let the second stream catch up with this one and issue the exchange from it
             # (the collective's own stream orders itself after the stream that is current at the call), so this one never waits
             self._event().wait_on(self._side)
             with torch.cuda.stream(self._side):
-                self.grad_hook(a.off, b.off + b.numel)
+                if self._add_accumulated(lo, hi):
+                    self._side_last = self._event()        # _join_side: the next write of G_acc and the norm of G32 come after this add
+                self.grad_hook(lo, hi)
+
+    def _add_accumulated(self, lo, hi):
+        """Last micro-batch of an accumulated step: G32[lo:hi] += G_acc[lo:hi] on the current stream, in front of the range's grad_hook. The
+        stream has every producer of G32[lo:hi] behind it (that is what makes the range final), G_acc was last written on the main stream
+        before this backward began, and the previous step's pipelined optimizer pass, which reads G32, was awaited by this step's forward."""
+        if self._micro is None:
+            return False
+        ops.accum_f32(self.G32[lo:hi], self.G_acc[lo:hi], add=True)
+        return True
 
     def _attn_block_bwd(self, L, pf, names, gy, x_in, q, k, v, dq, dk, dv, ctx, a, attn_save, mean, rstd, lnw, lnb_g, lnw_g, gout, seed, site, p, B, Sq, Sk, key_mask, causal, dbias=None,
                         T=None, rows=None, row_ids=None):
@@ -977,7 +996,8 @@ class Engine(GenerationMixin, ScoringMixin):
         if not side_tail:
             ops.defer_flush()
         self._join_side()
-        if self.grad_hook is not None and self.Gcur is self.G32:
+        if self.grad_hook is not None and self.Gcur is self.G32 and not (self._micro is not None and self._micro[0] < self._micro[1] - 1):
+            self._add_accumulated(self.n_matrix, self.n_total)
             self.grad_hook(self.n_matrix, self.n_total)          # vectors / position tables (accumulated region)
 
     def _onehot_gemm(self, onehot, dz, K, accum, side):
@@ -1175,15 +1195,21 @@ class Engine(GenerationMixin, ScoringMixin):
 
     # ------------------------------------------------------------------ fused pre-train step (bench / Pretrainer)
     def loss_and_grads(self, enc16, dec16, tgt16, loss_mask, emask, dmask, train=True, count_hook=None, head_w=None, w_scale=1.0,
-                       argmax_out=None, ids_checked=False):
+                       argmax_out=None, ids_checked=False, micro=None):
         """Forward + fused CE/argmax/acc + full backward. Returns the (24,) device tensor of sums
         {sum ce*m, sum m, sum correct*m} x 8 heads. `count_hook(counts)` may all-reduce the 8 mask counts (DP).
         ids_checked: the caller vouches that every id lies inside its embedding table (ids generated on the device, or a host batch it
         has validated); otherwise the ids are range-checked here (PianoBart.py:15-16: nn.Embedding raises IndexError; an offending id is
         replaced by 0 so that no gather leaves its table) and IndexError is raised at the first point where the host knows the verdict
-        without draining the stream: inside this call when the packing plan waits for its row counts, else on the next engine call."""
+        without draining the stream: inside this call when the packing plan waits for its row counts, else on the next engine call.
+        micro = (i, K): this batch is micro-batch i of an optimizer step over K of them (DESIGN.md 5 "Gradient accumulation"). Every micro-batch
+        runs the same forward and backward into G32; the first K - 1 are summed into G_acc, the last one adds G_acc to G32 (range by range in front
+        of grad_hook, which the earlier ones do not call), so that optimizer_step sees one summed gradient. The 8 heads are normalised by their mask
+        counts and meet in the backbone, so the K gradients cannot be rescaled afterwards: the caller passes the counts of the WHOLE step to
+        every micro-batch through count_hook (mask_counts). None and (0, 1) are the step without accumulation."""
         B, S = enc16.shape[:2]
         T = B * S
+        micro = self._check_micro(micro, train)
         self._raise_if_bad_ids()
         if not ids_checked:
             enc16 = self.note_ids(enc16, owned=False)
@@ -1215,10 +1241,61 @@ class Engine(GenerationMixin, ScoringMixin):
         dlogits = ws['dlogits'][:logits.shape[0]] if train else None
         ops.ce_fwd_bwd(logits, tgt, lm, sums, self.partials, coef, dlogits, argmax_out)
         if train:
-            self.zero_accumulated_grads()
-            gy = self.heads_backward(dlogits, dec_h)
-            self.backward(gy)
+            self._micro = micro
+            try:
+                self.zero_accumulated_grads()
+                gy = self.heads_backward(dlogits, dec_h)
+                self.backward(gy)
+            finally:
+                self._micro = None
+            if micro is not None:
+                i, K = micro
+                if i < K - 1:
+                    if self.G_acc is None:
+                        self.G_acc = torch.empty_like(self.G32)
+                    # backward has joined the second stream: every writer of G32 is behind this stream, and so is the last reader of G_acc
+                    ops.accum_f32(self.G_acc, self.G32, add=i > 0)
+                    self._micro_prev = micro
+                else:
+                    if self.grad_hook is None:                 # with a hook the ranges were added one by one (_ready)
+                        ops.accum_f32(self.G32, self.G_acc, add=True)
+                    self._micro_prev = None
         return sums
+
+    def _check_micro(self, micro, train):
+        """(i, K) of an accumulated step, or None for the step without accumulation (micro=None or (0, 1))."""
+        if micro is not None:
+            try:
+                i, K = micro
+                ok = int(i) == i and int(K) == K and 0 <= i < K
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise PBError('micro must be None or (i, K) with integers 0 <= i < K (got %r)' % (micro,))
+            i, K = int(i), int(K)
+            if K > 1:
+                if not train:
+                    raise PBError('micro=(%d, %d): gradient accumulation belongs to training steps (train=False computes no gradient)' % (i, K))
+                if i > 0 and self._micro_prev != (i - 1, K):
+                    raise PBError('micro=(%d, %d) must follow micro=(%d, %d) of the same step (the last accumulated micro-batch was %s)'
+                                  % (i, K, i - 1, K, self._micro_prev))
+                self._micro_prev = None                     # an interrupted step is not continued by accident
+                return i, K
+        self._micro_prev = None
+        return None
+
+    def mask_counts(self, loss_mask):
+        """The 8 per-head loss-mask counts of one batch ((B, S, 8) f32 mask, unpacked) as an (8,) f32 device tensor, without a host read: what a
+        trainer sums over the micro-batches of an accumulated step (ops.accum_f32; under data parallelism one reducer.reduce_counts of the
+        total) and hands to every micro-batch as count_hook=lambda c: c.copy_(total). Partial sums live in a buffer of their own, so the call
+        may run on another stream than the step."""
+        if self.device is None:
+            self.bind(loss_mask.device)
+        if getattr(self, '_count_partials', None) is None or self._count_partials.device != loss_mask.device:
+            self._count_partials = torch.empty(int(LIB.query('pb_ce_partials_floats')), dtype=torch.float32, device=loss_mask.device)
+        out = torch.empty(8, dtype=torch.float32, device=loss_mask.device)
+        ops.mask_count(loss_mask.to(torch.float32).reshape(-1, 8).contiguous(), out, self._count_partials)
+        return out
 
     def _pack_batch(self, enc16, dec16, tgt16, loss_mask, emask, dmask):
         return rowpack.pack_batch(self, enc16, dec16, tgt16, loss_mask, emask, dmask)

@@ -21,6 +21,7 @@ import torch
 from . import ops
 from ._lib import PBError
 from .model import PianoBartLM, checkpoint_state_dict
+from .pretrain import _positive_int, group_batches, run_micro_batches
 
 HEAD_WEIGHT = [1.0, 1.0, 0.3, 1.5, 1.0, 1.0, 0.3, 0.3]          # finetune_generation.py:241-248 (index = head i)
 
@@ -47,6 +48,8 @@ def get_args_generation(argv=None):
     parser.add_argument("--cuda_devices", type=int, nargs='+', default=[0], help="HIP device ids (one per process)")
     parser.add_argument("--eval", action="store_true")
     parser.add_argument('--precision', choices=['bf16', 'fp32', 'bf16x3'], default='bf16', help='backbone arithmetic (not in the reference)')
+    parser.add_argument('--accum_steps', type=_positive_int, default=1,
+                        help='gradient accumulation: one optimizer step over this many consecutive training batches (not in the reference)')
     return parser.parse_args(argv)
 
 
@@ -79,6 +82,7 @@ class GenerationTrainer:
         self.train_data, self.valid_data, self.test_data = train_dataloader, valid_dataloader, test_dataloader
         self.testset_shape = testset_shape
         self.lr = lr
+        self.accum_steps = 1                                                 # --accum_steps: training batches per optimizer step
         self.world = int(os.environ.get('WORLD_SIZE', 1))
         self.reducer = None
         if self.world > 1:                                                   # one process per GPU, same exchange as the pre-train step
@@ -113,16 +117,33 @@ class GenerationTrainer:
         if mode == 0 and hasattr(sampler, 'set_epoch'):                      # rank-sharded training set (make_finetune_loaders)
             self._epoch = getattr(self, '_epoch', -1) + 1
             sampler.set_epoch(self._epoch)
-        for x, y in training_data:
-            x, y = x.to(self.device).long(), y.to(self.device).long()
-            B, S = x.shape[:2]
-            x16, y16 = ops.ids_to_i16(x), ops.ids_to_i16(y)
-            attn_enc = (x16[:, :, 0] != pad).float()
-            attn_dec = attn_enc                                        # y_shift = x
-            loss_mask = attn_dec[:, :, None].expand(B, S, 8).contiguous()
+        K = int(self.accum_steps) if mode == 0 else 1                        # validation and test ignore --accum_steps
+        if K < 1:
+            raise PBError('accum_steps must be >= 1 (got %r)' % (self.accum_steps,))
+        steps = 0
+        for group in group_batches(training_data, K):
+            # the batches of one optimizer step; with more than one, every micro-batch is normalised by the loss-mask counts of the whole
+            # step (Engine.loss_and_grads(micro=...)), summed here before the first backward
+            micro, total = [], None
+            for x, y in group:
+                x, y = x.to(self.device).long(), y.to(self.device).long()
+                B, S = x.shape[:2]
+                x16, y16 = ops.ids_to_i16(x), ops.ids_to_i16(y)
+                attn_enc = (x16[:, :, 0] != pad).float()
+                loss_mask = attn_enc[:, :, None].expand(B, S, 8).contiguous()   # y_shift = x: the decoder mask is the encoder's
+                micro.append((x16, y16, attn_enc, loss_mask))
+                if len(group) > 1:
+                    c = eng.mask_counts(loss_mask)
+                    if total is None:
+                        total = c
+                    else:
+                        ops.accum_f32(total, c, add=True)
+            n_micro = len(micro)
+            B, S = micro[-1][0].shape[:2]
             am = torch.empty(B * S, 8, dtype=torch.int16, device=self.device) if mode == 2 else None
-            sums = eng.loss_and_grads(x16, x16, y16, loss_mask, attn_enc, attn_dec, train=(mode == 0), head_w=self._hw, w_scale=self._scale,
-                                      argmax_out=am, count_hook=self.reducer.reduce_counts if self.reducer else None)
+            step_sums = torch.empty(24, dtype=torch.float32, device=self.device) if n_micro > 1 else None
+            sums = run_micro_batches(eng, self.reducer, [(x16, x16, y16, lm, am_enc, am_enc) for x16, y16, am_enc, lm in micro], total, step_sums,
+                                     train=(mode == 0), head_w=self._hw, w_scale=self._scale, argmax_out=am)
             if mode == 0:
                 if self.reducer:
                     self.reducer.all_reduce_grads()
@@ -141,7 +162,8 @@ class GenerationTrainer:
             sys.stdout.write('FAD(BAR) Similarity: n/a , FAD Similarity n/a \n')            # `shapesimilarity` is not installed: not measured
             total_acc += accs
             total_loss += loss
-        n = max(1, len(training_data))
+            steps += 1
+        n = max(1, len(training_data)) if K == 1 else max(1, steps)          # accumulation: the averages are over optimizer steps
         out = (round(total_loss / n, 4), [round(float(a) / n, 4) for a in total_acc], None, None)           # FAD(BAR), FAD: not measured
         return out + (all_output,) if mode == 2 else out
 
@@ -198,6 +220,7 @@ def finetune_generation(argv=None):
             pianobart.load_state_dict(sd)
     print("\nCreating Finetune Trainer")
     trainer = GenerationTrainer(pianobart, loaders[0], loaders[1], loaders[2], args.lr, y_test.shape, args.cpu, args.cuda_devices, model)
+    trainer.accum_steps = args.accum_steps
     print("\nTraining Start")
     save_dir = os.path.join('result/finetune/generation_' + args.name)
     os.makedirs(save_dir, exist_ok=True)

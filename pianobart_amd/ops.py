@@ -241,6 +241,13 @@ def sum_rows_bf16(src, dst, rows):
     LIB.call('pb_sum_rows_bf16', _p(src), _p(dst), rows, dst.numel(), _stream())
 
 
+def accum_f32(dst, src, add=True):
+    """pb_accum_f32 over two contiguous f32 tensors of one size (views into flat buffers included): dst += src, or dst = src with add=False."""
+    if dst.dtype != torch.float32 or src.dtype != torch.float32 or dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+        raise PBError('accum_f32 needs two contiguous f32 tensors of the same size')
+    LIB.call('pb_accum_f32', _p(dst), _p(src), dst.numel(), int(bool(add)), _stream())
+
+
 def transpose_batch_bf16(src, dst, table, n_tiles):
     LIB.call('pb_transpose_batch_bf16', _p(src), _p(dst), _p(table), table.shape[0], n_tiles, _stream())
 

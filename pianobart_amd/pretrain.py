@@ -35,6 +35,13 @@ from .data import BalancedDistributedSampler, MidiDataset, OctupleShards, sequen
 from .model import BartConfig, PianoBart, PianoBartLM
 
 
+def _positive_int(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError('must be an integer >= 1 (got %s)' % text)
+    return n
+
+
 def get_args_pretrain(argv=None):
     """pretrain.py:18-48, flag for flag."""
     parser = argparse.ArgumentParser(description='')
@@ -58,6 +65,8 @@ def get_args_pretrain(argv=None):
     parser.add_argument('--precision', type=str, default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
     parser.add_argument('--data_root', type=str, default='Data/output_pretrain')
     parser.add_argument('--quiet', action='store_true', help='do not print the two per-step Loss/Acc lines')
+    parser.add_argument('--accum_steps', type=_positive_int, default=1,
+                        help='gradient accumulation: one optimizer step over this many consecutive loader batches (global loss normalisation)')
     parser.add_argument('--resume', type=str, default='', help='continue from a checkpoint THIS driver wrote: weights, LM heads, AdamW moments and step, epoch, best_acc')
     return parser.parse_args(argv)
 
@@ -148,8 +157,46 @@ def make_loaders(X_train, X_val, batch_size, num_workers, seed=None, balance=Tru
     return tuple(loaders)
 
 
+def group_batches(batches, k):
+    """Lists of at most k consecutive items of `batches`, in order: the micro-batches of one optimizer step under --accum_steps k. Every
+    group holds k items except the last one of an epoch, which holds what is left (it steps with those, normalised by their own counts)."""
+    if k < 1:
+        raise ValueError('group size must be >= 1')
+    group = []
+    for b in batches:
+        group.append(b)
+        if len(group) == k:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def run_micro_batches(eng, reducer, micro, total, step_sums, before=None, **kw):
+    """The Engine.loss_and_grads calls of ONE optimizer step over the batches `micro` (argument tuples enc16, dec16, tgt16, loss_mask, emask,
+    dmask); returns the step's (24,) sums. One batch: the call without accumulation, the reducer's count exchange inside it. Several:
+    `total` holds the summed Engine.mask_counts of all of them; it is all-reduced ONCE, every micro-batch receives it through count_hook
+    (the heads are normalised by the counts of the whole step), micro-batch i runs as micro=(i, len(micro)), and the 24 sums, which the
+    engine overwrites in every call, are added up in `step_sums`, a (24,) buffer of the caller's. before(i) runs in front of call i."""
+    n = len(micro)
+    if n == 1:
+        count_hook = reducer.reduce_counts if reducer else None
+    else:
+        if reducer:
+            reducer.reduce_counts(total)                                # once per optimizer step: the global M_i of all ranks and micro-batches
+        count_hook = lambda c: c.copy_(total)
+    for i, tensors in enumerate(micro):
+        if before is not None:
+            before(i)
+        sums = eng.loss_and_grads(*tensors, count_hook=count_hook, micro=(i, n) if n > 1 else None, **kw)
+        if n > 1:
+            ops.accum_f32(step_sums, sums, add=i > 0)
+    return sums if n == 1 else step_sums
+
+
 class Pretrainer:
-    """pretrain.py:51-546. Same constructor arguments and public methods."""
+    """pretrain.py:51-546. Same constructor arguments and public methods (+ accum_steps, absent from the reference: an optimizer step over
+    that many consecutive loader batches, --accum_steps)."""
 
     def __init__(self, pianobart: PianoBart, train_dataloader, valid_dataloader, lr, batch, max_seq_len, mask_percent, cpu,
                  cuda_devices=None):
@@ -179,6 +226,7 @@ class Pretrainer:
         self.max_seq_len = max_seq_len
         self.mask_percent = mask_percent
         self.quiet = False
+        self.accum_steps = 1                                    # --accum_steps: loader batches per optimizer step (training only)
         self.world = int(os.environ.get('WORLD_SIZE', 1))
         self.reducer = None
         self.rank = int(os.environ.get('RANK', 0))
@@ -319,16 +367,37 @@ class Pretrainer:
             self._sum_pins = [torch.empty(24, dtype=torch.float32).pin_memory() for _ in range(3)]
         prep = self._prep_stream
 
-        def stage(batch):
+        K = int(self.accum_steps) if train else 1               # validation ignores --accum_steps
+        if K < 1:
+            raise PBError('accum_steps must be >= 1 (got %r)' % (self.accum_steps,))
+
+        def stage(group):
+            """The batches of one optimizer step, prepared on the side stream; with more than one, the sum of their loss-mask counts too (the
+            heads are normalised by the counts of the WHOLE step, which every micro-batch must know before its backward)."""
             prep.wait_stream(main)                                      # everything the previous batches were given (their buffers may be recycled)
             with torch.cuda.stream(prep):
-                tensors = self.prepare_batch(batch)
-                eng.prefetch_pack(tensors[3], tensors[4], tensors[5], stream=prep)
+                micro = [self.prepare_batch(batch) for batch in group]
+                total = None
+                if len(micro) > 1:
+                    total = eng.mask_counts(micro[0][3])
+                    for tensors in micro[1:]:
+                        ops.accum_f32(total, eng.mask_counts(tensors[3]), add=True)
                 ev = torch.cuda.Event()
                 ev.record(prep)
-            for t in tensors:
-                t.record_stream(main)
-            return tensors, ev
+            for tensors in micro:
+                for t in tensors:
+                    t.record_stream(main)
+            if total is not None:
+                total.record_stream(main)
+            return micro, total, ev
+
+        def announce(tensors):
+            """Engine.prefetch_pack for the micro-batch that runs NEXT, on the stream that made its masks. The engine keeps two requests (the
+            batch about to run and the one after it) and drops older ones on the way to a match, so requests are made in the order the
+            batches run, one micro-batch ahead. A micro-batch that was not announced takes pack_batch's synchronous path: correct, merely
+            slower (the step's stream is drained for its row counts)."""
+            with torch.cuda.stream(prep):
+                eng.prefetch_pack(tensors[3], tensors[4], tensors[5], stream=prep)
 
         def enqueue_read(sums, k):
             """24 floats device -> pinned host behind an event on the launch stream; nothing waits here."""
@@ -339,26 +408,39 @@ class Pretrainer:
             return pin, ev
 
         eng._pack_prefetch.clear()                                      # requests of an epoch that ended early (an exception between stage and step)
-        it = iter(training_data)
+        it = group_batches(training_data, K)
         first = next(it, None)
         staged = stage(first) if first is not None else None
-        pending, k = None, 0
+        if staged is not None:
+            announce(staged[0][0])
+        pending, k, steps = None, 0, 0
         while staged is not None:
-            (enc16, dec16, tgt16, loss_mask, emask, dmask), ready = staged
+            micro, total, ready = staged
             main.wait_event(ready)
             nxt = next(it, None)
             staged = stage(nxt) if nxt is not None else None            # on the side stream, beside the step below
-            sums = eng.loss_and_grads(enc16, dec16, tgt16, loss_mask, emask, dmask, train=train, ids_checked=True,      # prepare_batch validated the host batch
-                                      count_hook=self.reducer.reduce_counts if self.reducer else None)
+            n_micro = len(micro)
+            if n_micro > 1 and getattr(self, '_step_sums', None) is None:
+                self._step_sums = torch.empty(24, dtype=torch.float32, device=self.device)
+
+            def before(i, micro=micro, nxt_group=staged):
+                after = micro[i + 1] if i + 1 < len(micro) else (nxt_group[0][0] if nxt_group is not None else None)
+                if after is not None:
+                    announce(after)
+
+            sums = run_micro_batches(eng, self.reducer, micro, total, getattr(self, '_step_sums', None), before=before,
+                                     train=train, ids_checked=True)      # prepare_batch validated the host batch
             if train:
                 if self.reducer:
                     self.reducer.all_reduce_grads()
                 eng.optimizer_step(lr=self.lr)
             if self.reducer:
-                sums = sums.clone()                                     # the engine reuses its scalar buffer in the next step
+                if n_micro == 1:
+                    sums = sums.clone()                                 # the engine reuses its scalar buffer in the next step
                 self.reducer.reduce_sums(sums)
             cur = enqueue_read(sums, k)
             k += 1
+            steps += 1
             if pending is not None:
                 pending[1].synchronize()
                 report(pending[0])
@@ -366,6 +448,8 @@ class Pretrainer:
         if pending is not None:
             pending[1].synchronize()
             report(pending[0])
+        if K > 1:                                                       # the epoch averages are over optimizer steps
+            return round(total_losses / max(1, steps), 3), [round(float(x) / max(1, steps), 3) for x in total_acc]
         n = max(1, len(training_data))
         return round(total_losses / n, 3), [round(float(x) / n, 3) for x in total_acc]
 
@@ -420,6 +504,7 @@ def pretrain(argv=None):
     trainer = Pretrainer(pianobart, train_loader, valid_loader, args.lr, args.batch_size, args.max_seq_len, args.mask_percent,
                          args.cpu, args.cuda_devices)
     trainer.quiet = args.quiet
+    trainer.accum_steps = args.accum_steps
     print("\nTraining Start")
     run = _RunLog(args.name, rank == 0)
     print("   save model at {}".format(run.filename))
