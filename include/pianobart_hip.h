@@ -475,7 +475,44 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   (and without logging its logits row). Launches per step and the single-stream graph do not change;
  *                                   a decoder without the call runs the unforced kernel. A value that is neither -1 nor inside its
  *                                   head's table (n8 of sampler_init), a call before sampler_init, or a call after a step was issued or
- *                                   captured is refused (< 0, pb_last_error) and changes nothing. */
+ *                                   captured is refused (< 0, pb_last_error) and changes nothing.
+ * Refill (an addition to ABI 10): one decoder serves more prompts than it has rows. A row is a SLOT: when its prompt stops, the host hands
+ * the slot to the next waiting prompt while the other rows decode on. The cross K|V of a prompt lives in a SLICE of kv_cross, prepared
+ * ahead of the hand-over on the caller's stream.
+ *   pb_batch_decoder_dynamic        after pb_batch_decoder_create, before the first step is issued or captured: layers[l].kv_cross is
+ *                                   read as (n_slices, S, 2d), B <= n_slices <= 2 PB_DECODE_BATCH_MAX. Each row's visible key count, keys
+ *                                   per split and slice index then live in device memory beside its position, done flag and limit
+ *                                   (initially s_enc[b] of the plan and slice b; reset restores that), and the cross-attention launch is a
+ *                                   third argument form of the per-row kernel that reads them there -- same arithmetic, lane-to-key mapping
+ *                                   and reduction order, so a row's logits are bit for bit those of a decoder without the call. Its LDS is
+ *                                   sized for the largest keys-per-split any s_enc <= S gives. The launches per step and the single-stream
+ *                                   graph do not change; a decoder without the call captures exactly the kernels and arguments it captured
+ *                                   before. Refused (< 0, pb_last_error, nothing changed): after a step was issued or captured, on a B = 1
+ *                                   decoder, after pb_batch_decoder_share_cross (which in turn is refused on a dynamic decoder: the grouped
+ *                                   kernel is not used), n_slices out of range, a second call.
+ *   pb_batch_decoder_admit          puts a prompt into slot `row` of a dynamic decoder, after pb_batch_decoder_sampler_init. The row must
+ *                                   have been ended by the host (pb_batch_decoder_seek with tok8 = NULL); a live row is refused. The call
+ *                                   orders itself behind the work enqueued on `caller_stream` so far (an event, as reset does): the prompt's
+ *                                   encoder pass, its wkv_c projections into cross slice `slice`, and its prefill into the row's kv_self rows
+ *                                   0 .. last_pos. Then, in decoder-stream order, it replaces the row's key count s_enc, keys per split (the
+ *                                   rule of pb_batch_decoder_create), slice, last decoded position last_pos (-1 = none), next input
+ *                                   next_tok8 (8 host ids), limit and done = 0, and copies in u_row ((S, 8) f64 draws), forced_row ((S, 8)
+ *                                   int16, -1 = free; NULL = every head free) and mask_row ((S) f32 into row `row` of enc_mask; NULL exactly
+ *                                   when the plan has no mask). The host arrays are free when the call returns. It does not drain: no
+ *                                   synchronize and no host wait; steps already enqueued for the previous occupant finish first, and the
+ *                                   other rows' positions, inputs, logs, draws and flags are untouched. The logs stay indexed by row, so
+ *                                   the caller reads the previous occupant's log rows before it admits. If any prompt of a run has given
+ *                                   heads, the caller installs a force table up front (pb_batch_decoder_force; all -1 will do) so that the
+ *                                   graphs end in the forced sampler for the whole run: a forced_row on a decoder without a table is
+ *                                   refused. Checked on the host before anything changes (< 0, pb_last_error): row, slice (also: no live row
+ *                                   reads it), 0 < s_enc <= S, -1 <= last_pos < limit <= S, the input ids and the forced ids against n8 of
+ *                                   sampler_init, the mask rule, and more than 2 PB_DECODE_BATCH_MAX admissions in flight. Launches per
+ *                                   step do not change.
+ *   pb_batch_decoder_fence          `caller_stream` waits (an event, no host wait) for everything enqueued on the decoder's stream so
+ *                                   far. The caller serialises its use of a cross slice and of a row's kv_self rows with it: after the
+ *                                   slice's last reader was ended (seek with NULL), fence, then enqueue the next prompt's projections into
+ *                                   the slice. pb_event_* / pb_stream_wait_event do not suffice here, because the decoder's stream is not
+ *                                   the caller's to record on. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -497,6 +534,10 @@ int pb_batch_decoder_launches(void* dec);
 int pb_batch_decoder_graph(void* dec);
 int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const int32_t* kv_row);
 int pb_batch_decoder_force(void* dec, const int16_t* forced);
+int pb_batch_decoder_dynamic(void* dec, int32_t n_slices);
+int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int32_t s_enc, int32_t last_pos, const int16_t* next_tok8, int32_t limit,
+                           const double* u_row, const int16_t* forced_row, const float* mask_row, void* caller_stream);
+int pb_batch_decoder_fence(void* dec, void* caller_stream);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

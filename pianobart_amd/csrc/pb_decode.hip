@@ -50,6 +50,11 @@ struct BState {
     int pos[BMAX];                         // last decoded position of each row (-1 at reset)
     int done[BMAX];                        // row form: 0 = live; 1 = special id sampled / stopped by the host; 2 = position limit reached
     int limit[BMAX];                       // row form: the row stops before this position (a primed row: its prefix + max_new)
+    // cross-attention geometry of each row, read by the dynamic decoder's cross-attention launch only (pb_batch_decoder_dynamic; the other
+    // forms carry it in their kernarg block): set at create, reset, start and by pb_batch_decoder_admit
+    int s_enc[BMAX];                       // visible encoder keys
+    int ck[BMAX];                          // keys per split
+    int kv_row[BMAX];                      // the slice of the cross K|V cache the row attends to
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -654,6 +659,19 @@ template <> struct DecAttnArgs<true> : DecAttnCommon {           // x_in, res, a
     __device__ int ck(int b) const { return ck_[b]; }
     __device__ int kv_row(int b) const { return kv_row_[b]; }
 };
+// The dynamic form (pb_batch_decoder_dynamic): a row's cross-attention geometry lives in BState, so a slot can change its prompt between two
+// replays of a captured graph (pb_batch_decoder_admit). The kernel loads done[b] and pos[b] from the same struct anyway.
+struct DecAttnDynArgs : DecAttnCommon {
+    long kv_rs;
+    const float* key_mask; long mask_rs;
+    BState* st;
+    int d, nreg;
+    float scale, eps;
+    float* part; long part_rs;
+    __device__ int s_enc(int b) const { return st->s_enc[b]; }
+    __device__ int ck(int b) const { return st->ck[b]; }
+    __device__ int kv_row(int b) const { return st->kv_row[b]; }
+};
 // The grouped cross-attention form (dec_attn_group_kernel): the rows ordered by their cross K|V slice and cut into tiles of <= RT rows of
 // one slice; tile t = rows_[tile_first[t] .. + tile_n[t]).
 struct DecAttnGroupArgs : DecAttnArgs<true> {
@@ -663,8 +681,10 @@ struct DecAttnGroupArgs : DecAttnArgs<true> {
 // Threads: 256; the self-attention form launches 768 so that the new token's workgroup projects q, k and v side by side (wave
 // groups 0 / 1 / 2, every weight load of a group in flight at once: ONE memory round trip instead of six dependent ones -- these
 // kernels are pure latency); in the other workgroups of that launch waves 4 .. 11 leave at once.
-template <int NC, int HD, bool SELF, bool ROWS>
-__global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const DecAttnArgs<ROWS> a) {
+// A = the argument form: DecAttnArgs<ROWS>, or DecAttnDynArgs for the cross-attention of a dynamic decoder (same body, the three geometry
+// accessors read device memory).
+template <int NC, int HD, bool SELF, bool ROWS, typename A = DecAttnArgs<ROWS>>
+__global__ __launch_bounds__(SELF ? 768 : 256) void dec_attn_kernel(const A a) {
     constexpr int CPR = HD / 8, KPW = 64 / CPR, STEP = 4 * KPW, UR = 4, RPW = HD / 4, NP = RPW / 2;
     constexpr int PBATCH = (NC <= 3 && !SELF) || NC <= 2 ? (NP < 8 ? NP : 8) : 4;       // passes of weight rows in flight per lane (registers)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1377,7 +1397,29 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     }
 }
 
+// ---------------------------------------------------------------- the rows' cross-attention geometry and the hand-over of a slot
+// Both take their values by kernarg, so nothing on the host has to outlive the call and the stores land in stream order.
+struct GeomArgs { int s_enc[BMAX], ck[BMAX], kv_row[BMAX]; };
+__global__ __launch_bounds__(64) void dec_geom_kernel(BState* __restrict__ st, const GeomArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) { st->s_enc[t] = g.s_enc[t]; st->ck[t] = g.ck[t]; st->kv_row[t] = g.kv_row[t]; }
+}
+struct AdmitArgs {
+    BState* st; int16_t* tok_dev;
+    int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
+    int16_t tok[8];
+};
+__global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
+    const int t = threadIdx.x, b = a.row;
+    if (t < 8) a.tok_dev[b * 8 + t] = a.tok[t];
+    if (t == 0) {
+        a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
+        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0;
+    }
+}
+
 constexpr int SPEC_K = 8;                  // steps per graph replay of the device-sampled decode
+constexpr int N_STAGE = 2 * BMAX;          // pinned staging entries of pb_batch_decoder_admit
 constexpr int SPEC_EVENTS = 8;
 enum { G_STEP, G_ONE, G_RUN, N_GRAPHS };   // captured graphs: one host-sampled step; 1 and SPEC_K device-sampled steps
 
@@ -1410,6 +1452,16 @@ struct Decoder {
     int group_rt = 0;                      // > 0: the grouped cross-attention kernel with this row tile; 0: the per-row kernel through kv_row
     int n_tiles = 0, rows_by_group[BMAX] = {}, tile_first[BMAX] = {}, tile_n[BMAX] = {};
     size_t lds_group = 0;                  // the grouped kernel's LDS: q, reduction, LN1 and score rows of a tile
+    // pb_batch_decoder_dynamic: kv_cross is (dynamic, S, 2d) and each row's geometry is read from BState; 0 = not dynamic
+    int dynamic = 0;
+    GeomArgs geo{};                        // host mirror of the rows' geometry in BState
+    bool live[BMAX] = {};                  // the host has started the row and not ended it (pb_batch_decoder_admit refuses a live row)
+    hipEvent_t ev_fence = nullptr;
+    char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
+    size_t stage_bytes = 0;
+    hipEvent_t stage_ev[N_STAGE] = {};     // recorded behind the copies out of an entry
+    bool stage_used[N_STAGE] = {};
+    int next_stage = 0;
 };
 
 template <int NC, int HD, bool ROWS>
@@ -1423,6 +1475,19 @@ static int dec_attn_launch(const DecAttnArgs<ROWS>& a, bool self, int H, int hd,
 #define PB_DA(NC_) do { if (hd == 64) dec_attn_go<NC_, 64>(a, self, H, nrec, B, lds, st); else dec_attn_go<NC_, 128>(a, self, H, nrec, B, lds, st); } while (0)
     if (nc == 1) PB_DA(1); else if (nc == 2) PB_DA(2); else if (nc == 3) PB_DA(3); else PB_DA(4);
 #undef PB_DA
+    PB_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int NC, int HD>
+static void dec_attn_dyn_go(const DecAttnDynArgs& a, int H, int nrec, int B, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((dec_attn_kernel<NC, HD, false, true, DecAttnDynArgs>), dim3(H, nrec, B), dim3(256), lds, st, a);
+}
+static int dec_attn_dyn_launch(const DecAttnDynArgs& a, int H, int hd, int nrec, int B, size_t lds, hipStream_t st) {
+    const int nc = a.d / 256;
+#define PB_DD(NC_) do { if (hd == 64) dec_attn_dyn_go<NC_, 64>(a, H, nrec, B, lds, st); else dec_attn_dyn_go<NC_, 128>(a, H, nrec, B, lds, st); } while (0)
+    if (nc == 1) PB_DD(1); else if (nc == 2) PB_DD(2); else if (nc == 3) PB_DD(3); else PB_DD(4);
+#undef PB_DD
     PB_LAUNCH_CHECK();
     return 0;
 }
@@ -1489,7 +1554,14 @@ static int step_issue(Decoder* D, bool sample) {
         if constexpr (!ROWS) { a.ck_fixed = D->ck_cross[0]; a.Sk_fixed = D->bp.s_enc[0]; }
         bool grouped = false;
         if constexpr (ROWS) {
-            if (D->group_rt > 0) {                        // rows of one cross K|V slice share a workgroup (same launch count)
+            if (D->dynamic) {                             // the geometry comes from BState: a slot may change its prompt between replays
+                DecAttnDynArgs da{};
+                static_cast<DecAttnCommon&>(da) = a;
+                da.kv_rs = a.kv_rs; da.key_mask = a.key_mask; da.mask_rs = a.mask_rs; da.st = a.st; da.d = a.d; da.nreg = a.nreg;
+                da.scale = a.scale; da.eps = a.eps; da.part = a.part; da.part_rs = a.part_rs;
+                if (dec_attn_dyn_launch(da, H, hd, D->ns_cross, B, D->lds_attn, st)) return -1;
+                grouped = true;
+            } else if (D->group_rt > 0) {                 // rows of one cross K|V slice share a workgroup (same launch count)
                 DecAttnGroupArgs ga{};
                 static_cast<DecAttnArgs<true>&>(ga) = a;
                 for (int b = 0; b < B; ++b) ga.rows_[b] = D->rows_by_group[b];
@@ -1568,6 +1640,24 @@ static bool capture(Decoder* D, int g, int ntok) {
     return true;
 }
 
+// keys per cross-attention split of a row with s_enc visible keys: <= ns_cross splits of >= 64 keys
+static int cross_chunk(const Decoder* D, int s_enc) {
+    const int ck = (s_enc + D->ns_cross - 1) / D->ns_cross;
+    return ck < 64 ? 64 : (ck + 15) & ~15;
+}
+
+// the rows' geometry as the plan has it (row b: s_enc[b], its own slice b), into the host mirror and, in stream order, into BState
+static int geom_reset(Decoder* D) {
+    for (int b = 0; b < BMAX; ++b) {
+        const int se = b < D->B ? D->bp.s_enc[b] : 1;
+        D->geo.s_enc[b] = se; D->geo.ck[b] = cross_chunk(D, se); D->geo.kv_row[b] = b < D->B ? b : 0;
+        if (b < D->B) D->ck_cross[b] = D->geo.ck[b];
+    }
+    hipLaunchKernelGGL(dec_geom_kernel, dim3(1), dim3(64), 0, D->stream, D->st, D->geo);
+    PB_LAUNCH_CHECK();
+    return 0;
+}
+
 static void drop_graphs(Decoder* D) {
     for (int g = 0; g < N_GRAPHS; ++g) {
         if (D->exec[g]) (void)hipGraphExecDestroy(D->exec[g]);
@@ -1594,6 +1684,7 @@ extern "C" int pb_batch_decoder_create(const pb_decode_batch* bp, void** out) {
     D->bp = *bp;
     D->B = bp->B;
     if (hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&D->ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&D->ev_fence, hipEventDisableTiming) != hipSuccess ||
         hipMalloc(&D->st, sizeof(BState)) != hipSuccess || hipMalloc(&D->tok_dev, 16 * BMAX) != hipSuccess ||
         hipHostMalloc(&D->tok_host, 16 * BMAX, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&D->logits_host, sizeof(float) * (size_t)plan->vocab, hipHostMallocDefault) != hipSuccess) {
@@ -1609,14 +1700,14 @@ extern "C" int pb_batch_decoder_create(const pb_decode_batch* bp, void** out) {
     D->ns_cross = env_splits("PB_DECODE_SPLITS_CROSS", PB_DECODE_MAX_SPLITS);
     int ck_max = 0;
     for (int b = 0; b < D->B; ++b) {
-        int ck = (bp->s_enc[b] + D->ns_cross - 1) / D->ns_cross;
-        ck = ck < 64 ? 64 : (ck + 15) & ~15;
+        const int ck = cross_chunk(D, bp->s_enc[b]);
         D->ck_cross[b] = ck;
         ck_max = ck > ck_max ? ck : ck_max;
     }
     int ck_self = (plan->S + D->ns_self - 2) / (D->ns_self - 1);
     ck_self = ck_self < 64 ? 64 : (ck_self + 15) & ~15;
     D->lds_attn = sizeof(float) * (size_t)(5 * hd + (ck_max > ck_self ? ck_max : ck_self) + 16);
+    if (geom_reset(D)) { pb_batch_decoder_destroy(D); return -1; }     // BState's geometry fields are never read uninitialised
     *out = D;
     return 0;
 }
@@ -1631,6 +1722,9 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     if (D->force_dev) (void)hipFree(D->force_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
+    for (int i = 0; i < N_STAGE; ++i) if (D->stage_ev[i]) (void)hipEventDestroy(D->stage_ev[i]);
+    if (D->stage) (void)hipHostFree(D->stage);
+    if (D->ev_fence) (void)hipEventDestroy(D->ev_fence);
     if (D->ev) (void)hipEventDestroy(D->ev);
     if (D->st) (void)hipFree(D->st);
     if (D->tok_dev) (void)hipFree(D->tok_dev);
@@ -1646,6 +1740,7 @@ extern "C" int pb_batch_decoder_share_cross(void* dec, int32_t n_groups, const i
     Decoder* D = (Decoder*)dec;
     PB_REQUIRE(D && kv_row, "pb_batch_decoder_share_cross: null argument");
     PB_REQUIRE(!D->issued, "pb_batch_decoder_share_cross: a step was already issued; the cross-cache layout is fixed for this decoder");
+    PB_REQUIRE(!D->dynamic, "pb_batch_decoder_share_cross: the decoder is dynamic (pb_batch_decoder_dynamic): its rows change slices one by one");
     const int B = D->B;
     PB_REQUIRE(n_groups >= 1 && n_groups <= B, "pb_batch_decoder_share_cross: %d groups for %d rows", n_groups, B);
     int count[BMAX] = {}, s_enc[BMAX] = {};
@@ -1696,6 +1791,8 @@ extern "C" int pb_batch_decoder_reset(void* dec, void* caller_stream, int32_t us
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
     PB_CHECK_HIP(hipMemsetAsync(D->st->pos, 0xff, sizeof(int) * BMAX, D->stream));
     PB_CHECK_HIP(hipMemsetAsync(D->st->done, 0, sizeof(int) * BMAX, D->stream));
+    if (D->dynamic && geom_reset(D)) return -1;                        // every slot back to the plan's prompt and its own slice
+    for (int b = 0; b < BMAX; ++b) D->live[b] = b < D->B;
     D->steps = 0;
     D->use_graph = use_graph;
     return 0;
@@ -1831,6 +1928,7 @@ extern "C" int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const 
     PB_REQUIRE(D && row >= 0 && row < D->B, "pb_batch_decoder_seek: row %d", row);
     if (!tok8) {
         PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->done[row], 1, 1, D->stream));
+        D->live[row] = false;
         return 0;
     }
     PB_REQUIRE(pos >= -1 && pos < D->bp.plan.S, "pb_batch_decoder_seek: position %d", pos);
@@ -1841,6 +1939,7 @@ extern "C" int pb_batch_decoder_seek(void* dec, int32_t row, int32_t pos, const 
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->done[row], 0, 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));
     D->steps = pos + 1;
+    D->live[row] = true;
     return 0;
 }
 
@@ -1853,7 +1952,10 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
     PB_REQUIRE(D && last_pos && next_tok, "pb_batch_decoder_start: null argument");
     const int S = D->bp.plan.S, B = D->B, dflt = D->sampler ? D->limit : S;
     BState h{};
-    for (int b = 0; b < BMAX; ++b) { h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt; }
+    for (int b = 0; b < BMAX; ++b) {
+        h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt;
+        h.s_enc[b] = D->geo.s_enc[b]; h.ck[b] = D->geo.ck[b]; h.kv_row[b] = D->geo.kv_row[b];
+    }
     for (int b = 0; b < B; ++b) {
         PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
         PB_REQUIRE(!limit || (limit[b] >= 0 && limit[b] <= S), "pb_batch_decoder_start: row %d limit %d outside 0..%d", b, limit[b], S);
@@ -1867,6 +1969,115 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `h` lives on this stack
     D->steps = h.pos[0] + 1;
     D->limit = h.limit[0];
+    for (int b = 0; b < BMAX; ++b) D->live[b] = b < B;
+    return 0;
+}
+
+// Refill (see the header): from here on the rows' cross-attention geometry is read from BState, so pb_batch_decoder_admit can hand a
+// slot to another prompt between two replays of the captured graphs. The LDS of the cross-attention launch is sized for the largest
+// keys-per-split any s_enc <= S gives.
+extern "C" int pb_batch_decoder_dynamic(void* dec, int32_t n_slices) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D, "pb_batch_decoder_dynamic: null decoder");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_dynamic: a step was already issued; the cross-attention kernel is fixed for this decoder");
+    PB_REQUIRE(D->B > 1, "pb_batch_decoder_dynamic: a B = 1 decoder runs the single-row kernels");
+    PB_REQUIRE(!D->n_groups, "pb_batch_decoder_dynamic: the decoder shares cross slices (pb_batch_decoder_share_cross)");
+    PB_REQUIRE(!D->dynamic, "pb_batch_decoder_dynamic: the decoder is already dynamic");
+    PB_REQUIRE(n_slices >= D->B && n_slices <= 2 * BMAX, "pb_batch_decoder_dynamic: %d slices for %d rows (B .. %d)", n_slices, D->B, 2 * BMAX);
+    const int S = D->bp.plan.S, hd = D->bp.plan.d / D->bp.plan.H;
+    const size_t bytes = ((size_t)S * (8 * sizeof(double) + 8 * sizeof(int16_t) + sizeof(float)) + 63) & ~(size_t)63;
+    char* stage = nullptr;
+    if (hipHostMalloc(&stage, bytes * N_STAGE, hipHostMallocDefault) != hipSuccess) {
+        pb_set_error("pb_batch_decoder_dynamic: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    for (int i = 0; i < N_STAGE; ++i)
+        if (hipEventCreateWithFlags(&D->stage_ev[i], hipEventDisableTiming) != hipSuccess) {
+            pb_set_error("pb_batch_decoder_dynamic: event creation failed: %s", hipGetErrorString(hipGetLastError()));
+            for (int k = 0; k <= i; ++k) if (D->stage_ev[k]) { (void)hipEventDestroy(D->stage_ev[k]); D->stage_ev[k] = nullptr; }
+            (void)hipHostFree(stage);
+            return -1;
+        }
+    D->stage = stage; D->stage_bytes = bytes;
+    int ck_self = (S + D->ns_self - 2) / (D->ns_self - 1);
+    ck_self = ck_self < 64 ? 64 : (ck_self + 15) & ~15;
+    const int ck_max = cross_chunk(D, S);                              // ck grows with s_enc
+    D->lds_attn = sizeof(float) * (size_t)(5 * hd + (ck_max > ck_self ? ck_max : ck_self) + 16);
+    D->dynamic = n_slices;
+    return 0;
+}
+
+// The hand-over of a slot. Everything is checked on the host first; then, in decoder-stream order behind an event on the caller's stream:
+// the row's draws, forced entries and mask (out of a pinned staging entry: the caller's arrays are free when we return) and one small
+// kernel that replaces the row's state. No synchronize and no host wait: the other rows run on.
+extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int32_t s_enc, int32_t last_pos, const int16_t* next_tok8, int32_t limit,
+                                      const double* u_row, const int16_t* forced_row, const float* mask_row, void* caller_stream) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler && D->u_dev, "pb_batch_decoder_admit: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(next_tok8 && u_row, "pb_batch_decoder_admit: null argument");
+    const int S = D->bp.plan.S;
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit: row %d of %d", row, D->B);
+    PB_REQUIRE(!D->live[row], "pb_batch_decoder_admit: row %d is live; end it first (pb_batch_decoder_seek with tok8 = NULL)", row);
+    PB_REQUIRE(slice >= 0 && slice < D->dynamic, "pb_batch_decoder_admit: slice %d of %d", slice, D->dynamic);
+    for (int b = 0; b < D->B; ++b)
+        PB_REQUIRE(!(D->live[b] && D->geo.kv_row[b] == slice), "pb_batch_decoder_admit: slice %d is being read by the live row %d", slice, b);
+    PB_REQUIRE(s_enc > 0 && s_enc <= S, "pb_batch_decoder_admit: s_enc %d outside 1..%d", s_enc, S);
+    PB_REQUIRE(last_pos >= -1 && last_pos < limit && limit <= S, "pb_batch_decoder_admit: position %d, limit %d (-1 <= position < limit <= %d)", last_pos, limit, S);
+    PB_REQUIRE(!forced_row || D->force_dev, "pb_batch_decoder_admit: a forced row needs the decoder's force table (pb_batch_decoder_force before the first step; "
+               "an all -1 table will do)");
+    PB_REQUIRE((mask_row != nullptr) == (D->bp.plan.enc_mask != nullptr), "pb_batch_decoder_admit: the plan has %s encoder mask", D->bp.plan.enc_mask ? "an" : "no");
+    for (int h = 0; h < 8; ++h)
+        PB_REQUIRE(next_tok8[h] >= 0 && next_tok8[h] < D->sa.n[h], "pb_batch_decoder_admit: input id %d of head %d is outside its table (%d ids)",
+                   next_tok8[h], h, D->sa.n[h]);
+    if (forced_row)
+        for (size_t k = 0; k < (size_t)S * 8; ++k) {
+            const int v = forced_row[k], h = (int)(k & 7);
+            PB_REQUIRE(v == -1 || (v >= 0 && v < D->sa.n[h]), "pb_batch_decoder_admit: position %d, head %d: id %d is neither -1 nor inside the head's table "
+                       "(%d ids)", (int)(k / 8), h, v, D->sa.n[h]);
+        }
+    const int e = D->next_stage;
+    if (D->stage_used[e] && hipEventQuery(D->stage_ev[e]) != hipSuccess) {
+        (void)hipGetLastError();
+        pb_set_error("pb_batch_decoder_admit: %d admissions are still in flight; wait for a launch ticket first", N_STAGE);
+        return -1;
+    }
+    char* sg = D->stage + (size_t)e * D->stage_bytes;
+    double* su = (double*)sg;
+    int16_t* sf = (int16_t*)(su + (size_t)S * 8);
+    float* sm = (float*)(sf + (size_t)S * 8);
+    for (size_t k = 0; k < (size_t)S * 8; ++k) su[k] = u_row[k];
+    if (forced_row) for (size_t k = 0; k < (size_t)S * 8; ++k) sf[k] = forced_row[k];
+    if (mask_row) for (int k = 0; k < S; ++k) sm[k] = mask_row[k];
+    AdmitArgs a{};
+    a.st = D->st; a.tok_dev = D->tok_dev; a.row = row; a.s_enc = s_enc; a.ck = cross_chunk(D, s_enc); a.slice = slice; a.pos = last_pos; a.limit = limit;
+    for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
+    PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
+    PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
+    D->stage_used[e] = true;
+    D->next_stage = (e + 1) % N_STAGE;
+    PB_CHECK_HIP(hipMemcpyAsync(D->u_dev + (size_t)row * S * 8, su, sizeof(double) * (size_t)S * 8, hipMemcpyHostToDevice, D->stream));
+    if (D->force_dev) {
+        int16_t* fr = D->force_dev + (size_t)row * S * 8;
+        if (forced_row) PB_CHECK_HIP(hipMemcpyAsync(fr, sf, sizeof(int16_t) * (size_t)S * 8, hipMemcpyHostToDevice, D->stream));
+        else PB_CHECK_HIP(hipMemsetAsync(fr, 0xff, sizeof(int16_t) * (size_t)S * 8, D->stream));       // -1 everywhere: all free
+    }
+    if (mask_row)
+        PB_CHECK_HIP(hipMemcpyAsync(const_cast<float*>(D->bp.plan.enc_mask) + (size_t)row * S, sm, sizeof(float) * (size_t)S, hipMemcpyHostToDevice, D->stream));
+    hipLaunchKernelGGL(dec_admit_kernel, dim3(1), dim3(64), 0, D->stream, a);
+    PB_LAUNCH_CHECK();
+    PB_CHECK_HIP(hipEventRecord(D->stage_ev[e], D->stream));
+    D->geo.s_enc[row] = s_enc; D->geo.ck[row] = a.ck; D->geo.kv_row[row] = slice; D->ck_cross[row] = a.ck;
+    D->live[row] = true;
+    return 0;
+}
+
+// `caller_stream` waits for everything enqueued on the decoder's stream so far (an event; the host does not wait).
+extern "C" int pb_batch_decoder_fence(void* dec, void* caller_stream) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D, "pb_batch_decoder_fence: null decoder");
+    PB_CHECK_HIP(hipEventRecord(D->ev_fence, D->stream));
+    PB_CHECK_HIP(hipStreamWaitEvent((hipStream_t)caller_stream, D->ev_fence, 0));
     return 0;
 }
 

@@ -14,6 +14,9 @@ RNG rules:
     n > 1 needs --seed and writes (N, n, max_seq_len, 8): sample j of prompt i draws from RandomState(seed + j N + i) (sample_seed), so
     [:, 0] is the --samples 1 file. --batch_size then counts output rows; the samples of a prompt inside one batch share its encoder
     pass and cross-attention K/V (PianoBartLM.generate_batch's samples_per_prompt), and the file does not depend on --batch_size.
+  * --refill [N] (needs --seed, not with --samples > 1): all prompts go to ONE generate_batch call with refill = N (no N: 16 slots): one
+    decoder whose rows are handed to the next prompt as they stop. --batch_size then only sets the score batches. The generation file
+    is byte-identical to the run without the flag.
 The prompts are sliced from the loaded array in order; --num_workers is accepted for the reference's command lines and not needed.
 
 Kept attributes (--keep ATTR[,ATTR...], needs --prime): the named attributes (bar, position, instrument, pitch, duration, velocity, timesig,
@@ -39,7 +42,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import keep_mask, parse_keep, sample_seed
+from .generation import check_refill, keep_mask, parse_keep, sample_seed
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -72,6 +75,8 @@ def get_args(argv=None):
                     'sample j of prompt i drawing from RandomState(seed + j * N + i)')
     ap.add_argument('--keep', type=str, default=None, help='ATTR[,ATTR...] of bar, position, instrument, pitch, duration, velocity, timesig, tempo (needs '
                     '--prime): these attributes of the piece\'s own rows behind the prime are kept and the model samples the others')
+    ap.add_argument('--refill', type=int, nargs='?', const=0, default=None, metavar='N', help='one batched decoder of N slots (no N: 16) for the whole '
+                    'test set, a finished row\'s slot going to the next prompt; needs --seed, not with --samples > 1; same output file')
     ap.add_argument('--score', action='store_true', help='also write the teacher-forced scores of the generated rows: float32 (N, 9) or (N, n, 9) = the 8 '
                     'per-head sums of log-probability and the number of scored positions (all 8 heads of a position, kept by --keep or sampled)')
     ap.add_argument('--score_output', type=str, default=None, help='path of the score file (default: --output with .npy replaced by _score.npy)')
@@ -141,6 +146,14 @@ def check_args(args):
     if samples > 1 and args.seed is None:
         raise PBError('--samples %d needs --seed: sample j of prompt i draws from its own RandomState(seed + j * N + i); the one global RNG '
                       'stream of a run without --seed gives one continuation per prompt' % samples)
+    if getattr(args, 'refill', None) is not None:
+        check_refill(args.refill or True)
+        if args.seed is None:
+            raise PBError('--refill needs --seed: the prompts of a refilled decoder run side by side, each from its own RandomState(seed + i)')
+        if samples > 1:
+            raise PBError('--refill does not combine with --samples %d: the samples of a prompt share one cache slice' % samples)
+        if getattr(args, 'score_dataset', False):
+            raise PBError('--score_dataset generates nothing: it takes no --refill')
     if args.seed is None and args.batch_size > 1:
         raise PBError('--batch_size %d needs --seed: without it every prompt draws from the one global RNG stream in turn, which only the '
                       'batch-1 loop reproduces (the reference exits with ERROR for batches); with --seed s prompt i uses RandomState(s + i) '
@@ -252,8 +265,10 @@ def eval_generation(args=None):
                 output[i, j] = y[r]
                 if do_score:
                     scores[i, j] = sc[r]
-        for c0 in range(0, N if samples == 1 else 0, args.batch_size):
-            c1 = min(N, c0 + args.batch_size)
+        refill = getattr(args, 'refill', None)
+        gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
+        for c0 in range(0, N if samples == 1 else 0, gen_rows):
+            c1 = min(N, c0 + gen_rows)
             x = torch.as_tensor(np.asarray(data[c0:c1])).long()
             prefix = ks = forced = None
             if prime is not None:                     # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
@@ -267,10 +282,12 @@ def eval_generation(args=None):
                           decoder_forced=forced)
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
-                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced)
+                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced,
+                                         refill=(refill or True) if refill is not None else False)
             output[c0:c1] = y.float().cpu().numpy()
-            if do_score:
-                scores[c0:c1], _ = score_rows(x, y, ks)
+            for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):
+                s1 = min(c1 - c0, s0 + args.batch_size)
+                scores[c0 + s0:c0 + s1], _ = score_rows(x[s0:s1], y[s0:s1], ks[s0:s1] if ks is not None else None)
     if do_score:
         np.save(score_path(args), scores)
         print("Saved", scores.shape, "to", score_path(args))

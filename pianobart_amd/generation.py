@@ -84,6 +84,25 @@ def check_samples(samples, P, n_rngs):
     return owner
 
 
+def check_refill(refill, samples=None, batch_max=16):
+    """The argument rules of refilled batched generation, on the host before any device work. refill: False / None (off), True (batch_max
+    slots) or an int n, 2 <= n <= batch_max (n slots). It does not combine with samples-per-prompt generation: the samples of a prompt
+    share a cache slice, which would have to change owners. Returns the slot count, 0 for off. Raises PBError."""
+    if refill is None or refill is False:
+        return 0
+    if refill is True:
+        n = int(batch_max)
+    elif isinstance(refill, (int, np.integer)):
+        n = int(refill)
+        if not 2 <= n <= batch_max:
+            raise PBError('refill = %d: the slot count must be 2 .. %d (True = %d)' % (n, batch_max, batch_max))
+    else:
+        raise PBError('refill must be False, True or an int 2 .. %d (got %r)' % (batch_max, refill))
+    if samples is not None:
+        raise PBError('refill does not combine with samples: the samples of a prompt share one cache slice')
+    return n
+
+
 KEEP_NAMES = ('bar', 'position', 'instrument', 'pitch', 'duration', 'velocity', 'timesig', 'tempo')       # the 8 heads, model column order
 
 
@@ -331,24 +350,30 @@ class GenerationMixin:
             if dec is not None:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
-    def _prefill(self, enc16, em, pre, k, kvs):
-        """Primed generation: rows 0 .. k-1 of the self-attention caches kvs[l] ((S, 2d) each, row j = K | V of decoder position j, the layout
-        pb_decode_step and the fused decoder's new-token workgroup write) get the K|V of the decoder inputs SOS, pre[0] .. pre[k-2]. ONE
-        teacher-forced decoder pass over them on the training kernels, against the encoder pass just run (reuse_encoder), then a row gather
-        (pb_gather_rows16: 16-byte copies, no arithmetic) out of each layer's q|k|v workspace: in d-wide blocks, cache blocks 2j, 2j + 1 <-
-        workspace blocks 3j + 1, 3j + 2. Per prompt, like the encoder pass, so that a row of generate_batch stays the batch-1 generate of its
-        prompt bit for bit. No-op unless 0 < k < S (k = S samples nothing). Returns a callable giving the pass's device milliseconds."""
-        if not 0 < k < int(enc16.shape[1]):
-            return lambda: 0.0
-        S, dev = int(enc16.shape[1]), enc16.device
+    def _prefill_inputs(self, pre, k, S, dev):
+        """The device inputs of _prefill for a prefix of k rows (0 < k < S): the decoder ids SOS, pre[0] .. pre[k-2], their mask, and the
+        gather index of the k cache rows. Host-to-device copies only, so a caller may make them ahead of the pass."""
         dec = torch.from_numpy(self.pb.pad_word_np).repeat(1, S, 1)
         dec[0, 0] = torch.from_numpy(self.pb.sos_word_np)
         dec[0, 1:k] = pre[:k - 1]
         dmask = torch.zeros(1, S, dtype=torch.float32)
         dmask[0, :k] = 1
-        dec16, dmask = ops.ids_to_i16(dec.to(dev)), dmask.to(dev)
         rows = torch.arange(k, dtype=torch.int32)
         idx = torch.stack([3 * rows + 1, 3 * rows + 2], 1).reshape(-1).to(dev)
+        return ops.ids_to_i16(dec.to(dev)), dmask.to(dev), idx
+
+    def _prefill(self, enc16, em, pre, k, kvs, inputs=None):
+        """Primed generation: rows 0 .. k-1 of the self-attention caches kvs[l] ((S, 2d) each, row j = K | V of decoder position j, the layout
+        pb_decode_step and the fused decoder's new-token workgroup write) get the K|V of the decoder inputs SOS, pre[0] .. pre[k-2]. ONE
+        teacher-forced decoder pass over them on the training kernels, against the encoder pass just run (reuse_encoder), then a row gather
+        (pb_gather_rows16: 16-byte copies, no arithmetic) out of each layer's q|k|v workspace: in d-wide blocks, cache blocks 2j, 2j + 1 <-
+        workspace blocks 3j + 1, 3j + 2. Per prompt, like the encoder pass, so that a row of generate_batch stays the batch-1 generate of its
+        prompt bit for bit. No-op unless 0 < k < S (k = S samples nothing). inputs: what _prefill_inputs returned for (pre, k), made ahead.
+        Returns a callable giving the pass's device milliseconds."""
+        if not 0 < k < int(enc16.shape[1]):
+            return lambda: 0.0
+        S, dev = int(enc16.shape[1]), enc16.device
+        dec16, dmask, idx = inputs if inputs is not None else self._prefill_inputs(pre, k, S, dev)
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=True)
@@ -444,7 +469,8 @@ class GenerationMixin:
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
-    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None):
+    def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
+                       refill=False):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -463,8 +489,14 @@ class GenerationMixin:
         explicit samples=1 gives the same rows through the shared-cache form.
         forced (B, S, 8), -1 = free (check_forced): forced tokens, row b under `generate`'s contract with forced[b]; rows that are -1
         everywhere are today's rows, so one batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder
-        reads the table on the device (pb_batch_decoder_force) and the host's verification applies it to its own tokens."""
+        reads the table on the device (pb_batch_decoder_force) and the host's verification applies it to its own tokens.
+        refill (False, True = BATCH_MAX slots, or an int 2 .. BATCH_MAX; check_refill): ONE decoder of that many rows ("slots") for the
+        whole call instead of one per chunk of BATCH_MAX: when a row stops, its slot goes to the next waiting prompt while the other rows
+        decode on (_generate_batch_refill), so a short row does not wait for the longest row of its chunk and the set-up is paid once.
+        Every row stays under the contract above; the result and the final generator states are those of refill=False. With no more rows
+        than slots, or where the fused decoder does not cover the shape, the call runs as with refill=False. Not with `samples`."""
         P = int(enc_ids.shape[0])
+        slots = check_refill(refill, samples, self.BATCH_MAX)
         owner = check_samples(samples, P, len(rngs)) if samples is not None else list(range(P))        # row -> prompt
         ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
         forced = check_forced(forced, P, int(enc_ids.shape[1]), ops.SEG_SIZES, ks)
@@ -478,6 +510,10 @@ class GenerationMixin:
             if samples is None:
                 return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced)
             return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced)
+        if slots and R > slots:
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots)
+            if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
+                return out
         outs = []
         for c0 in range(0, R, self.BATCH_MAX):
             own = owner[c0:c0 + self.BATCH_MAX]
@@ -531,6 +567,227 @@ class GenerationMixin:
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
+
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n):
+        """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
+        waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
+        in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
+        passes, projections and prefills run AHEAD on the caller's stream while the decoder is busy; a hand-over is then a slice index plus
+        the row's draws, forced entries and mask (and, for a primed row, a device copy of its prefilled cache rows into the slot).
+        The set-up is _decoder_run's, once; the loop is _decode_device_sampled's with slots for rows: the first n rows start as a chunk
+        starts (sampler_init, force, start), the device samples ahead, the host verifies one run behind from the pinned logs (indexed by
+        SLOT: an occupant's log rows are read before the next one is admitted) and rewinds a row alone. Each row's draws are made at its
+        admission from a copy of rngs[r] (forced_draws). Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        pb_batch_decoder_create declines the shape."""
+        R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
+        pad_cpu = torch.from_numpy(self.pb.pad_word_np)
+        with torch.no_grad():
+            em, enc16 = self._prompt_inputs(enc_ids, emask)
+            t_setup = time.perf_counter()
+            s_enc = [self._key_extent(em[r:r + 1] if em is not None else None, S) for r in range(R)]
+            NS = n + min(n, R - n)                                         # slices: one per slot plus the prompts prepared ahead
+            em_slots = em[:n].clone() if em is not None else None          # the decoder's mask rows belong to the slots
+            bp, bufs = self._decode_plan(n, S, s_enc[:n], em_slots, dev, G=NS)
+            dec = self._decoder_create(bp)
+            if dec is None:
+                return None
+            try:
+                return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
+                                        pad_cpu).to(dev)
+            finally:
+                LIB.call('pb_batch_decoder_destroy', dec)
+
+    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu):
+        """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
+        import ctypes
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        from .refill import RefillSchedule
+        R, S, dev = int(enc16.shape[0]), int(enc16.shape[1]), enc16.device
+        K, vocab = 8, ops.VOCAB
+        LIB.call('pb_batch_decoder_dynamic', dec, NS)
+        sched = RefillSchedule(R, n, NS)
+        res_cpu = pad_cpu.repeat(R, S, 1)
+        lim = [S if max_new is None else max(0, min(S, k + int(max_new))) for k in ks]
+        primed = [0 < ks[r] < S for r in range(R)]
+        # everything a later prepare needs from the host goes up now: behind a fence the caller's stream waits for the decoder, and a
+        # pageable copy enqueued there would make the host wait with it
+        pre_in = {r: self._prefill_inputs(rows[r], ks[r], S, dev) for r in range(R) if primed[r]}
+        stage = [torch.zeros(NS, S, 2 * self.d, dtype=self.xdt, device=dev) for _ in range(self.ND)] if any(primed[n:]) else None
+        em_host = np.ascontiguousarray(em.cpu().numpy(), dtype=np.float32) if em is not None else None
+        timers, counts = [], dict(encoder_passes=0, admissions=0)
+        stream = ops._stream
+        used = set()                               # slices that have had a reader
+
+        def prepare(r, c, kvs_rows, ahead=False):
+            """Row r's batch-1 encoder pass, cross K|V projections into slice c and prefill into kvs_rows, as a lone `generate` runs them.
+            ahead: the decoder is running -- the projected embedding table it reads was built by the first rows' passes from the same
+            weights and is not rebuilt under it."""
+            emb = em[r:r + 1] if em is not None else None
+            if ahead:
+                self._tables_ready = True
+            _, enc_out = self.forward_hidden(enc16[r:r + 1], None, emb, None, False, 0)
+            for l in range(self.ND):
+                self._linear(enc_out, 'dec.%d.wkv_c' % l, 'dec.%d.bkv_c' % l, bufs['kvc'][l][c], S, 2 * self.d, self.d)
+            if ks[r]:
+                if ahead and primed[r]:
+                    self._tables_ready = True
+                timers.append(self._prefill(enc16[r:r + 1], emb, rows[r], ks[r], kvs_rows, inputs=pre_in.get(r)))
+                res_cpu[r, :ks[r]] = rows[r, :ks[r]]
+            used.add(c)
+            counts['encoder_passes'] += 1
+
+        for b in range(n):                                                 # the first n rows: slot b, slice b, as a chunk sets them up
+            r, c = sched.prepare()
+            prepare(r, c, [t[b] for t in bufs['kvs']])
+            assert sched.admit() == (b, b, b)
+        LIB.call('pb_batch_decoder_reset', dec, stream(), _DECODE_GRAPH)
+        torch.cuda.current_stream().synchronize()
+        setup_ms = (time.perf_counter() - t_setup) * 1e3
+
+        def draws(r):
+            ahead = np.random.RandomState()
+            ahead.set_state(rngs[r].get_state())
+            return forced_draws(ahead, forced[r] if forced is not None else None, ks[r], S).reshape(-1)
+
+        def first_tok(r):
+            return np.ascontiguousarray((res_cpu[r, ks[r] - 1].numpy() if ks[r] else np.asarray(self.pb.sos_word_np)).astype(np.int16))
+
+        fault = getattr(self, 'decode_fault_row', None) or (-1, 0)         # tests: the device's choice of one SLOT corrupted
+        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
+        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
+        pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
+        t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
+        U = np.ascontiguousarray(np.stack([draws(r) for r in range(n)]))
+        LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
+                 U.ctypes.data, n * S * 8, max(lim), int(fault[0]), int(fault[1]))
+        if forced is not None:                                             # the graphs end in the forced sampler for the whole run
+            LIB.call('pb_batch_decoder_force', dec, np.ascontiguousarray(forced[:n]).ctypes.data)
+        lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
+        LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
+        log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (n * S * vocab)).from_address(lp.value)).reshape(n, S, vocab))
+        log_tok = np.ctypeslib.as_array((ctypes.c_int16 * (n * S * 8)).from_address(tp.value)).reshape(n, S, 8)
+        first = np.ascontiguousarray(np.stack([first_tok(r) for r in range(n)]))
+        last_pos, lim32 = np.asarray([ks[r] - 1 for r in range(n)], dtype=np.int32), np.asarray(lim[:n], dtype=np.int32)
+        LIB.call('pb_batch_decoder_start', dec, last_pos.ctypes.data, first.ctypes.data, lim32.ctypes.data)
+        slot_row = list(range(n))                  # the row in each slot (None: empty)
+        nxt = [ks[r] for r in range(n)]            # next position the enqueued work decodes, per slot
+        tokens, rewinds = [0] * R, [0] * R
+        row_slot = list(range(n)) + [-1] * (R - n)                         # the slot each row sat in (-1: it had nothing to decode)
+        runs = deque()
+        stat = dict(steps=0, row_steps=0, host_s=0.0)
+
+        def top_up():
+            """Prepare waiting rows ahead into free slices. A slice is reused only behind its last reader's last enqueued step."""
+            while True:
+                got = sched.prepare()
+                if got is None:
+                    return
+                r, c = got
+                if c in used:
+                    LIB.call('pb_batch_decoder_fence', dec, stream())
+                prepare(r, c, [t[c] for t in stage] if stage is not None else None, ahead=True)
+
+        def hand_over(s):
+            """The free slot s goes to the next row (prepared ahead where a slice was free in time). Rows with nothing to decode pass through."""
+            while True:
+                got = sched.admit()
+                if got is None:
+                    top_up()
+                    got = sched.admit()
+                    if got is None:                                        # no row waits: the slot stays empty
+                        slot_row[s] = None
+                        return
+                r, s2, c = got
+                assert s2 == s
+                if lim[r] <= ks[r]:
+                    sched.finish(s)
+                    continue
+                if primed[r]:                                              # its prefilled cache rows, behind the previous occupant's last step
+                    LIB.call('pb_batch_decoder_fence', dec, stream())
+                    for l in range(self.ND):
+                        bufs['kvs'][l][s, :ks[r]].copy_(stage[l][c, :ks[r]])
+                u, tok = draws(r), first_tok(r)
+                fr = np.ascontiguousarray(forced[r]) if forced is not None and (forced[r] != -1).any() else None
+                LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
+                         fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
+                counts['admissions'] += 1
+                slot_row[s], nxt[s], row_slot[r] = r, ks[r], s
+                return
+
+        def finish(s, i):
+            LIB.call('pb_batch_decoder_seek', dec, s, i, None)
+            sched.finish(s)
+            hand_over(s)
+
+        def launch():
+            livs = [s for s in range(n) if slot_row[s] is not None]
+            cnt = min(K, max(lim[slot_row[s]] - nxt[s] for s in livs))
+            tk = int(LIB.query('pb_batch_decoder_launch', dec, cnt, None))
+            if tk < 0:
+                raise PBError('pb_batch_decoder_launch failed (%d): %s' % (tk, LIB.load().pb_last_error().decode()))
+            spans = [None] * n
+            for s in livs:
+                e = min(lim[slot_row[s]], nxt[s] + cnt)
+                spans[s] = [slot_row[s], nxt[s], e]
+                stat['row_steps'] += e - nxt[s]
+                nxt[s] = e
+            runs.append((tk, spans))
+            stat['steps'] += cnt
+
+        def verify(s, r, a, e):                    # positions a .. e-1 of row r in slot s, in order: None, ('stop', i) or ('seek', i, ids)
+            for i in range(a, e):
+                tok = forced_token(forced[r, i] if forced is not None else None, lambda: sample_row(log_logits[s, i], rngs[r]))
+                tokens[r] += 1
+                if (tok >= pad_cpu).any():
+                    return ('stop', i)
+                res_cpu[r, i] = tok
+                t16 = tok.numpy().astype(np.int16)
+                if not np.array_equal(t16, log_tok[s, i]):
+                    return ('seek', i, t16)
+            return None
+
+        pending = lambda: any(slot_row[s] is not None and nxt[s] < lim[slot_row[s]] for s in range(n))
+        t_loop = time.perf_counter()
+        for s in range(n):                                                 # rows with nothing to decode leave before the first step
+            if lim[s] <= ks[s]:
+                finish(s, 0)
+        with ThreadPoolExecutor(max_workers=min(n, 8)) as pool:
+            while runs or pending():
+                while len(runs) < 2 and pending():
+                    launch()
+                top_up()                                                   # the next prompts' passes run while the decoder is busy
+                tk, spans = runs.popleft()
+                LIB.call('pb_batch_decoder_wait', dec, tk)
+                t_h = time.perf_counter()
+                todo = [s for s in range(n) if spans[s] is not None and spans[s][0] == slot_row[s] and spans[s][2] > spans[s][1]]
+                outcome = dict(zip(todo, pool.map(lambda s: verify(s, *spans[s]), todo)))
+                stat['host_s'] += time.perf_counter() - t_h
+                for s in todo:
+                    out, (r, _, e) = outcome[s], spans[s]
+                    if out is None:
+                        if e >= lim[r]:                                    # the row's last position is verified
+                            finish(s, e - 1)
+                    elif out[0] == 'stop':
+                        finish(s, out[1])
+                    else:                                                  # drain, move slot s back; its spans in the queued runs are void
+                        i = out[1]
+                        rewinds[r] += 1
+                        LIB.call('pb_batch_decoder_seek', dec, s, i, out[2].ctypes.data)
+                        nxt[s] = i + 1
+                        for _, sp in runs:
+                            if sp[s] is not None and sp[s][0] == r:
+                                sp[s][1] = sp[s][2] = i + 1
+                        if i + 1 >= lim[r]:                                # rewound at its last position: nothing left to decode
+                            finish(s, i)
+        assert sched.done(), (sched.finished, R)
+        self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
+                                tokens=tokens, rewinds=rewinds, steps=stat['steps'], row_steps=stat['row_steps'], loop_ms=(time.perf_counter() - t_loop) * 1e3,
+                                host_ms=stat['host_s'] * 1e3, device_sampler=True, tokens_per_graph_replay=K, refill=n, slices=NS,
+                                admissions=counts['admissions'], row_slot=row_slot, encoder_passes=counts['encoder_passes'], s_enc=s_enc, batched=True, batch=n,
+                                prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms,
+                                cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
+        return res_cpu
 
     def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its

@@ -372,7 +372,7 @@ class PianoBartLM(nn.Module):
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
-                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None):
+                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -386,13 +386,17 @@ class PianoBartLM(nn.Module):
         decoder_forced (B, S, 8), -1 = free: forced tokens, prompt b under forward(generate=True, decoder_forced=...)'s contract with its
         own table (rows that are -1 everywhere are unforced rows; positions below prefix_len[b] must be -1; max_new counts positions from
         prefix_len[b] on, given or sampled). With samples_per_prompt it describes the P prompts, like decoder_prefix. The given heads are
-        applied inside the fused decoder's device sampler, so a forced batch keeps the batched decode's launches per step."""
+        applied inside the fused decoder's device sampler, so a forced batch keeps the batched decode's launches per step.
+        refill (False, True or a slot count 2 .. 16): one decoder for the whole call whose rows are handed to the next waiting prompt as
+        they stop (Engine.generate_batch's `refill`); the result is that of refill=False. Not with samples_per_prompt."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
         if rngs is None:
             rngs = [np.random.RandomState(int(s)) for s in seeds]
         rngs = list(rngs)
+        from .generation import check_refill
+        check_refill(refill, samples_per_prompt)
         if samples_per_prompt is not None:
             from .generation import check_samples
             check_samples(samples_per_prompt, B, len(rngs))
@@ -401,7 +405,7 @@ class PianoBartLM(nn.Module):
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
-                                 samples=samples_per_prompt, forced=decoder_forced)
+                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):

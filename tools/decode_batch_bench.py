@@ -14,6 +14,12 @@ one (1, S, 2d) cross cache per layer, the grouped cross-attention kernel), "indi
 kernel reading the shared slice) and "repeated" (the prompt repeated n times through generate_batch without samples: the yardstick). Per
 run: setup ms (encoder passes, cross K/V projections, prefill -- host time up to the decoder's start), ms per step, aggregate tokens/s over
 the decode loop and over the whole call, cross_cache_bytes. One JSON line; with --prime K the runs are primed with K rows.
+
+--refill [N]: refilled against chunked generation of --prompts (64) prompts whose lengths are fixed by a seeded table of given EOS rows,
+uniform in --len_min .. --len_max (16 .. 256) positions, every other head free. "refill" (generate_batch(refill=N or True): one decoder, a
+finished row's slot going to the next prompt) and "chunked" (refill=False: chunks of 16, each lasting until its longest row) alternate in
+this process, --reps times. Per run: tokens/s of the whole call with the set-up included, steps, occupancy (row_steps / (steps * slots)),
+setup_ms (summed over the chunks) and rewinds. One JSON line per run and a summary line, printed and appended to profiles/refill_b16.jsonl.
 """
 import argparse
 import json
@@ -41,6 +47,11 @@ def main(argv=None):
     ap.add_argument('--reps', type=int, default=3, help='--samples: repetitions of the alternating runs')
     ap.add_argument('--kinds', nargs='+', default=['grouped', 'indirect', 'repeated'], choices=['grouped', 'indirect', 'repeated'],
                     help='--samples: the runs to alternate (one kind alone for a kernel trace)')
+    ap.add_argument('--refill', type=int, nargs='?', const=0, default=None, metavar='N', help='time refilled against chunked generation (N slots; no N: 16)')
+    ap.add_argument('--prompts', type=int, default=64, help='--refill: prompts of the call')
+    ap.add_argument('--len_min', type=int, default=16, help='--refill: shortest row')
+    ap.add_argument('--len_max', type=int, default=256, help='--refill: longest row')
+    ap.add_argument('--log', type=str, default=os.path.join(ROOT, 'profiles', 'refill_b16.jsonl'), help='--refill: the file the lines are appended to')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -60,7 +71,7 @@ def main(argv=None):
     eng = model._get_engine()
     eng.bind(dev)
     sampler = dict(T=model.SAMPLE_T, P=model.SAMPLE_P)
-    Bmax = max(args.batches)
+    Bmax = max(args.batches) if args.refill is None else args.prompts
     enc = synth_octuple_batch(Bmax, S, seed=7, min_len=S // 2)[5].to(dev)     # S/2 .. S visible rows, as bench.py's decode prompt
     emask = (enc[:, :, 0] != 256).float()
     steps = min(args.steps, S)
@@ -72,6 +83,61 @@ def main(argv=None):
 
     def kv_bytes(rows):                                     # cross K/V over the visible rows + self K/V at the mean position
         return sum(L * (vis[b] + steps / 2) * 2 * d * 2 for b in range(rows))
+
+    if args.refill is not None:
+        R, slots = args.prompts, args.refill or eng.BATCH_MAX
+        eos = [p0 + 3 for p0 in (256, 128, 129, 256, 128, 32, 254, 49)]
+        lens = np.random.RandomState(17).randint(args.len_min, min(args.len_max, S - 1) + 1, size=R)
+        forced = np.full((R, S, 8), -1, dtype=np.int64)
+        for r in range(R):
+            forced[r, lens[r]] = eos                        # specials are unsamplable: row r decodes lens[r] positions and its EOS row
+        chunks = []
+        chunk_fn = eng._generate_batch_chunk
+
+        def counted(*a, **k):                               # last_decode holds the last chunk only: keep every chunk's
+            y = chunk_fn(*a, **k)
+            chunks.append(dict(eng.last_decode))
+            return y
+        eng._generate_batch_chunk = counted
+
+        def run(kind, rows):
+            rngs = [np.random.RandomState(b) for b in range(rows)]
+            del chunks[:]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            y = eng.generate_batch(enc[:rows], emask[:rows], model.sample_row, rngs, sampler=sampler, forced=forced[:rows],
+                                   refill=(args.refill or True) if kind == 'refill' else False)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            infos = [dict(eng.last_decode)] if kind == 'refill' else list(chunks)
+            ntok = sum(sum(i['tokens']) for i in infos)
+            nsteps = sum(i['steps'] for i in infos)
+            row_steps = sum(i.get('row_steps', sum(i['tokens'])) for i in infos)      # chunked: verified positions (equal without rewinds)
+            width = sum(i['steps'] * i['batch'] for i in infos)
+            return y.cpu(), dict(kind=kind, prompts=rows, slots=slots if kind == 'refill' else eng.BATCH_MAX, tokens=ntok, wall_ms=dt * 1e3,
+                                 tokens_per_s=ntok / dt, steps=nsteps, occupancy=row_steps / max(1, width), setup_ms=sum(i['setup_ms'] for i in infos),
+                                 loop_ms=sum(i['loop_ms'] for i in infos), rewinds=sum(sum(i['rewinds']) for i in infos),
+                                 encoder_passes=sum(i['encoder_passes'] for i in infos), decoders=len(infos),
+                                 admissions=infos[0].get('admissions', 0), launches_per_step=infos[0]['launches_per_token'], graph=infos[0]['graph'])
+        for kind in ('refill', 'chunked'):
+            run(kind, min(R, 2 * slots))                    # warm-up (capture, pinned logs, allocator)
+        lines, same = [], True
+        for _ in range(args.reps):
+            ya, ra = run('refill', R)
+            yb, rb = run('chunked', R)
+            same = same and bool(torch.equal(ya, yb))
+            lines += [ra, rb]
+        med = lambda kind, key: float(np.median([r[key] for r in lines if r['kind'] == kind]))
+        summ = {kind: {key: med(kind, key) for key in ('tokens_per_s', 'steps', 'occupancy', 'setup_ms', 'wall_ms', 'rewinds')} for kind in ('refill', 'chunked')}
+        lines.append(dict(kind='summary', metric='refill vs chunked generate_batch (%dL/%dd, S=%d, %d prompts, rows of %d .. %d positions)'
+                          % (L, d, S, R, args.len_min, args.len_max), same_tokens_in_all_runs=same, medians=summ,
+                          speedup_tokens_per_s=summ['refill']['tokens_per_s'] / summ['chunked']['tokens_per_s']))
+        eng._generate_batch_chunk = chunk_fn
+        with open(args.log, 'a') as fh:
+            for ln in lines:
+                print(json.dumps(ln), flush=True)
+                fh.write(json.dumps(ln) + '\n')
+        return
 
     if args.samples:
         n = args.samples
