@@ -512,7 +512,27 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   far. The caller serialises its use of a cross slice and of a row's kv_self rows with it: after the
  *                                   slice's last reader was ended (seek with NULL), fence, then enqueue the next prompt's projections into
  *                                   the slice. pb_event_* / pb_stream_wait_event do not suffice here, because the decoder's stream is not
- *                                   the caller's to record on. */
+ *                                   the caller's to record on.
+ * Stop at a bar (an addition to ABI 10): a row also ends at the first token whose bar id (head 0) reaches a given bar.
+ *   pb_batch_decoder_stop           after pb_batch_decoder_sampler_init, before the first pb_batch_decoder_start / launch of the run:
+ *                                   stop_bar = (B) host ints, 0 <= stop_bar[b] <= pad8[0] of sampler_init; pad8[0] = no stop (what
+ *                                   sampler_init sets for every row). The values are stored beside the rows' positions, limits and done
+ *                                   flags, in decoder-stream order (a small kernel that takes them by kernarg: the caller's array is free
+ *                                   when the call returns), and pb_batch_decoder_start keeps them. The row-form sampler kernel then tests
+ *                                   head 0 of the token it wrote -- after forcing, as the special-id test does -- against stop_bar[b] in
+ *                                   place of pad8[0]; since stop_bar[b] <= pad8[0] the one comparison covers both rules. Heads 1 .. 7 are
+ *                                   tested against pad8 as before. What a free head samples does not change, and the done flag stays a
+ *                                   prediction the host confirms or rewinds. Same kernel, same kernarg layout, same launches per step: one
+ *                                   more 4-byte load next to done[b] and pos[b]. A B = 1 decoder accepts the call and does nothing on the
+ *                                   device (the single-row kernels have no done flag: the host ends the run). A value outside
+ *                                   0 .. pad8[0], a call before sampler_init, or a call after a step was issued or captured is refused
+ *                                   (< 0, pb_last_error) and changes nothing.
+ *   pb_batch_decoder_admit_stop     refill: stages the stop bar (0 .. pad8[0]) that the next pb_batch_decoder_admit of `row` stores, in
+ *                                   the same small kernel as the row's position, limit and done = 0. An admit without a staged value
+ *                                   stores pad8[0]: a slot never inherits its previous occupant's stop. pb_batch_decoder_seek does not
+ *                                   touch the value (a rewound row keeps its occupant's). Host state only, no device work. Refused (< 0,
+ *                                   pb_last_error, nothing changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1,
+ *                                   a value outside 0 .. pad8[0]. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -538,6 +558,8 @@ int pb_batch_decoder_dynamic(void* dec, int32_t n_slices);
 int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int32_t s_enc, int32_t last_pos, const int16_t* next_tok8, int32_t limit,
                            const double* u_row, const int16_t* forced_row, const float* mask_row, void* caller_stream);
 int pb_batch_decoder_fence(void* dec, void* caller_stream);
+int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar);
+int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_bar);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

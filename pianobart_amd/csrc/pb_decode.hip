@@ -55,6 +55,9 @@ struct BState {
     int s_enc[BMAX];                       // visible encoder keys
     int ck[BMAX];                          // keys per split
     int kv_row[BMAX];                      // the slice of the cross K|V cache the row attends to
+    // row form, the device sampler only: the row is done when head 0 (the bar) of its token is >= stop[b]. pad[0] = no stop beyond the special
+    // ids; a lower value is the bar the row stops at (pb_batch_decoder_stop, pb_batch_decoder_admit_stop). Set by sampler_init, start and admit
+    int stop[BMAX];
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -1232,6 +1235,10 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // in the last stage, in front of the fault injection and the done test, so the arithmetic of a free head is the unforced kernel's; a
 // position with all 8 heads given writes its ids and returns (no logits log: the host does not read that row). The FORCED = false
 // instantiations are the kernels and kernarg layouts of a decoder without a table.
+// Stop at a bar (pb_batch_decoder_stop), row form: head 0's done test compares against stop[b] of BState in place of pad[0]; stop[b] <=
+// pad[0], so the one comparison covers the special ids and the bar. It is no template parameter and no kernarg form of its own: one 4-byte
+// load, from the struct done[b] and pos[b] are read from and issued with them, in 1 of the step's launches does not justify doubling the
+// instantiations. The ROWS = false kernels have no done flag and are untouched: the host ends a B = 1 run, as it does for EOS.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1274,6 +1281,8 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     if (ROWS && a.st->done[b]) return;                           // block-uniform
     const int t = threadIdx.x, lane = t & 63, h = t >> 6;
     const int pos = a.st->pos[b];
+    [[maybe_unused]] int stop0 = 0;                              // head 0's first id that ends the row: requested with done[b] and pos[b]
+    if constexpr (ROWS) stop0 = a.st->stop[b];
     const float* logits = a.logits + (size_t)b * a.vocab;
     float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
     const int n = a.n[h], off = a.off[h];
@@ -1289,7 +1298,7 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
             if (t < 8) {
                 a.tok_dev[b * 8 + t] = (int16_t)f;
                 a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)f;
-                if constexpr (ROWS) { if (f >= a.pad[t]) a.st->done[b] = 1; }
+                if constexpr (ROWS) { if (f >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }
             }
             return;
         }
@@ -1393,7 +1402,7 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         if (a.fault_period > 0 && (!ROWS || b == a.fault_row) && t == 0 && (pos % a.fault_period) == a.fault_period - 1) id = (id + 1) % a.n[0];
         a.tok_dev[b * 8 + t] = (int16_t)id;
         a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)id;
-        if constexpr (ROWS) { if (id >= a.pad[t]) a.st->done[b] = 1; }    // the device stops the row here; the host confirms or rewinds it
+        if constexpr (ROWS) { if (id >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }    // the device stops the row here; the host confirms or rewinds it
     }
 }
 
@@ -1404,9 +1413,15 @@ __global__ __launch_bounds__(64) void dec_geom_kernel(BState* __restrict__ st, c
     const int t = threadIdx.x;
     if (t < BMAX) { st->s_enc[t] = g.s_enc[t]; st->ck[t] = g.ck[t]; st->kv_row[t] = g.kv_row[t]; }
 }
+struct StopArgs { int stop[BMAX]; };
+__global__ __launch_bounds__(64) void dec_stop_kernel(BState* __restrict__ st, const StopArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) st->stop[t] = g.stop[t];
+}
 struct AdmitArgs {
     BState* st; int16_t* tok_dev;
     int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
+    int stop;                                // the new occupant's stop bar (pad[0]: none)
     int16_t tok[8];
 };
 __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
@@ -1414,7 +1429,7 @@ __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
     if (t < 8) a.tok_dev[b * 8 + t] = a.tok[t];
     if (t == 0) {
         a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
-        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0;
+        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop;
     }
 }
 
@@ -1456,6 +1471,8 @@ struct Decoder {
     int dynamic = 0;
     GeomArgs geo{};                        // host mirror of the rows' geometry in BState
     bool live[BMAX] = {};                  // the host has started the row and not ended it (pb_batch_decoder_admit refuses a live row)
+    StopArgs stop{};                       // host mirror of the rows' stop bars in BState (pb_batch_decoder_start uploads the whole struct)
+    int admit_stop[BMAX] = {};             // pb_batch_decoder_admit_stop: the value the row's next admit stores (-1: none staged -> pad[0])
     hipEvent_t ev_fence = nullptr;
     char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
     size_t stage_bytes = 0;
@@ -1845,8 +1862,10 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     }
     PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->limit, limit, BMAX, D->stream));    // every row; pb_batch_decoder_start may set them one by one
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->stop, pad8[0], BMAX, D->stream));   // no row stops at a bar until pb_batch_decoder_stop says so
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
     D->limit = limit;
+    for (int b = 0; b < BMAX; ++b) { D->stop.stop[b] = pad8[0]; D->admit_stop[b] = -1; }
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
     D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
@@ -1881,6 +1900,25 @@ extern "C" int pb_batch_decoder_force(void* dec, const int16_t* forced) {
     }
     if (D->force_dev) (void)hipFree(D->force_dev);
     D->force_dev = tab;
+    return 0;
+}
+
+// Stop at a bar (see the header): one bar id per row, checked whole on the host before anything changes, then stored in decoder-stream
+// order by a small kernel that takes the values by kernarg (as dec_geom_kernel does), so nothing of the caller's has to outlive the call.
+extern "C" int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && stop_bar, "pb_batch_decoder_stop: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_stop: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_stop: a step was already issued; the rows' stop bars are set before the run's first step");
+    for (int b = 0; b < D->B; ++b)
+        PB_REQUIRE(stop_bar[b] >= 0 && stop_bar[b] <= D->sa.pad[0], "pb_batch_decoder_stop: row %d: bar %d outside 0..%d (%d = no stop)", b, stop_bar[b],
+                   D->sa.pad[0], D->sa.pad[0]);
+    if (D->B == 1) return 0;                                           // the single-row kernels have no done flag: the host ends the run
+    StopArgs g = D->stop;
+    for (int b = 0; b < D->B; ++b) g.stop[b] = stop_bar[b];
+    hipLaunchKernelGGL(dec_stop_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
+    PB_LAUNCH_CHECK();
+    D->stop = g;
     return 0;
 }
 
@@ -1955,6 +1993,7 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
     for (int b = 0; b < BMAX; ++b) {
         h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt;
         h.s_enc[b] = D->geo.s_enc[b]; h.ck[b] = D->geo.ck[b]; h.kv_row[b] = D->geo.kv_row[b];
+        h.stop[b] = D->stop.stop[b];                                  // as sampler_init / pb_batch_decoder_stop left it (unread without a sampler)
     }
     for (int b = 0; b < B; ++b) {
         PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
@@ -2051,6 +2090,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     if (mask_row) for (int k = 0; k < S; ++k) sm[k] = mask_row[k];
     AdmitArgs a{};
     a.st = D->st; a.tok_dev = D->tok_dev; a.row = row; a.s_enc = s_enc; a.ck = cross_chunk(D, s_enc); a.slice = slice; a.pos = last_pos; a.limit = limit;
+    a.stop = D->admit_stop[row] >= 0 ? D->admit_stop[row] : D->sa.pad[0];    // never the previous occupant's
     for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
@@ -2068,7 +2108,20 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     PB_LAUNCH_CHECK();
     PB_CHECK_HIP(hipEventRecord(D->stage_ev[e], D->stream));
     D->geo.s_enc[row] = s_enc; D->geo.ck[row] = a.ck; D->geo.kv_row[row] = slice; D->ck_cross[row] = a.ck;
+    D->stop.stop[row] = a.stop; D->admit_stop[row] = -1;
     D->live[row] = true;
+    return 0;
+}
+
+// The stop bar of the prompt the next pb_batch_decoder_admit puts into `row` (see the header). Host state only: the store is the admit's.
+extern "C" int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_bar) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit_stop: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_admit_stop: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit_stop: row %d of %d", row, D->B);
+    PB_REQUIRE(stop_bar >= 0 && stop_bar <= D->sa.pad[0], "pb_batch_decoder_admit_stop: row %d: bar %d outside 0..%d (%d = no stop)", row, stop_bar,
+               D->sa.pad[0], D->sa.pad[0]);
+    D->admit_stop[row] = stop_bar;
     return 0;
 }
 

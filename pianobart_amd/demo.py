@@ -8,6 +8,7 @@ encoder + decoder pass per position: same tokens), `Octuple2Midi` (demo.py:72-10
 import argparse
 import os
 
+import numpy as np
 import torch
 
 from ._lib import PBError
@@ -23,12 +24,14 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16', prime=None, samples=1, seed=None, keep=None):
+                 precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows'):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
         self.prime = prime                  # None, N or 'half': continue the piece from its first rows (eval_generation's --prime rule)
         self.keep = keep                    # None or 'ATTR[,ATTR...]': attributes of the piece's own rows behind the prime that are kept (needs prime)
+        self.bars = bars                    # None or N: finish the bar the prime ends in, write N whole new bars, stop (eval_generation --bars)
+        self.infill, self.infill_mode = infill, infill_mode     # None or 'LO:HI': rewrite bars LO .. HI-1 of the piece (eval_generation --infill; needs a seed)
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -55,6 +58,11 @@ def get_args(argv=None):
     ap.add_argument('--samples', type=int, default=1, help='continuations of the piece: n MIDI files, --output for the first, the others with '
                     'the sample index in front of the extension (out.mid, out.1.mid, ..); n > 1 needs --seed')
     ap.add_argument('--seed', type=int, default=None, help='with --samples: sample j draws from RandomState(seed + j)')
+    ap.add_argument('--bars', type=int, default=None, metavar='N', help='finish the bar the prime ends in, write N whole new bars, then stop')
+    ap.add_argument('--infill', type=str, default=None, metavar='LO:HI', help='rewrite bars LO .. HI-1 of the piece and leave the rest alone (needs --seed; '
+                    'not with --prime, --keep or --bars)')
+    ap.add_argument('--infill_mode', type=str, default='rows', choices=['rows', 'span'], help='the encoder sees a MASK row per row of the region (rows) '
+                    'or one MASK row for the whole region (span)')
     return ap.parse_args(argv)
 
 
@@ -83,10 +91,27 @@ def check_keep_args(keep, prime):
     return heads
 
 
+def check_bar_args(bars, infill, prime, keep, seed):
+    """The --bars and --infill rules (eval_generation's); raises PBError. Returns (lo, hi) or None."""
+    from .eval_generation import parse_infill
+    if bars is not None and bars < 0:
+        raise PBError('--bars must be >= 0 (got %d)' % bars)
+    region = parse_infill(infill)
+    if region is not None:
+        if seed is None:
+            raise PBError('--infill needs --seed: the piece is generated from its own RandomState(seed)')
+        for flag, v in (('prime', prime), ('keep', keep), ('bars', bars)):
+            if v is not None:
+                raise PBError('--infill does not combine with --%s: it sets the prime, the kept attributes and the stop bar itself' % flag)
+    return region
+
+
 def demo(args=None):
     if not args:
         args = get_args()
     keep = check_keep_args(getattr(args, 'keep', None), getattr(args, 'prime', None))
+    bars = getattr(args, 'bars', None)
+    region = check_bar_args(bars, getattr(args, 'infill', None), getattr(args, 'prime', None), getattr(args, 'keep', None), getattr(args, 'seed', None))
     if args.cpu or not torch.cuda.is_available():
         raise PBError('pianobart_amd has no CPU execution path: demo() needs an MI355X')
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
@@ -113,24 +138,38 @@ def demo(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
-    octuple, prefix, ks, forced = octuple.long(), None, None, None
-    if prime is not None:                    # the piece's first k rows primed, the encoder sees them only
+    octuple, prefix, ks, forced, stops, plan = octuple.long(), None, None, None, None, None
+    if region is not None:                   # the rows in front of the region prime the decoder, the encoder sees the region as MASK
+        from .generation import infill_plan
+        plan = infill_plan(octuple[0], region[0], region[1], pianobart.mask_word_np, pianobart.pad_word_np, getattr(args, 'infill_mode', 'rows'))
+        ks, stops = [plan['k']], [plan['stop']]
+        prefix = torch.as_tensor(plan['prefix']).long()[None]
+        octuple = torch.as_tensor(plan['enc']).long()[None]
+    elif prime is not None:                    # the piece's first k rows primed, the encoder sees them only
         ks = prime_lengths(octuple.numpy(), prime, pianobart.bar_pad_word, pianobart.pad_word_np)
         if keep is not None:                 # the kept attributes of the piece's rows behind the prime are given, the others sampled
             from .generation import keep_mask
             forced = keep_mask(octuple, keep, ks, pianobart.bar_pad_word)
         octuple, prefix = prime_inputs(octuple, ks, pianobart.pad_word_np)
+    if bars is not None:                     # the row finishes the bar its prime ends in and writes `bars` whole new bars
+        from .generation import stop_after_bars
+        stops = [stop_after_bars(prefix[0, :ks[0]] if ks is not None else None, bars, pianobart.bar_pad_word)]
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
-        if samples > 1:                      # n continuations from one encoder pass: sample j of the one piece under RandomState(seed + j)
+        if samples > 1 or region is not None:        # n continuations from one encoder pass: sample j of the one piece under RandomState(seed + j)
             from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
                                      decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples,
-                                     decoder_forced=forced)
+                                     decoder_forced=forced, decoder_stop=stops)
         else:
             y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                      decoder_forced=forced)
+                      decoder_forced=forced, decoder_stop=stops)
+    if plan is not None:                     # the rows behind the region go back behind the new ones
+        from .generation import infill_splice
+        spliced = [infill_splice(row, plan['suffix'], args.max_seq_len, pianobart.bar_pad_word) for row in y.cpu()]
+        y = torch.as_tensor(np.stack([r for r, _ in spliced])).to(y.dtype)
+        print("Truncated pieces:", sum(int(c) for _, c in spliced))
     for j, path in enumerate(sample_paths(args.output, samples)):
         if Octuple2Midi(y[j:j + 1], path):
             print(f"Saved to {path}")

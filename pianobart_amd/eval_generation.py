@@ -24,6 +24,18 @@ tempo) of the dataset piece's own rows behind the prime, up to and including its
 the other attributes (generation.keep_mask with start = k_b -> PianoBartLM.generate_batch's decoder_forced). The generation file has the
 shape and dtype it has without the flag, and without the flag it is byte-identical. --score still scores all 8 heads of a position.
 
+Bar-bounded generation (--bars N): every row also stops at a bar -- generation.stop_after_bars of its prime (q = the bar of the prime's last
+row, -1 without --prime; the stop bar is min(q + 1 + N, 256)), so the row finishes the bar it is in and writes N whole new bars
+(PianoBartLM.generate_batch's decoder_stop). Works with and without --prime and with --keep, --samples, --refill, --score and --pick.
+
+Infilling (--infill LO:HI [--infill_mode rows|span], needs --seed): bars LO .. HI-1 of every piece are rewritten and the rest is left alone.
+Per piece generation.infill_plan gives the prime (the rows with bar < LO), the stop bar HI, the encoder input (rows: every row of the region
+replaced by the MASK row, TokenMask's convention; span: the region replaced by one MASK row, TokenInfilling's) and the suffix (the rows with
+bar >= HI and the EOS row); the generated row is spliced with the suffix (generation.infill_splice) and the output file holds the spliced
+pieces, cut at max_seq_len (the number of truncated pieces is printed). The flag sets the prime, the kept attributes and the stop itself, so
+it excludes --prime, --keep, --bars and --score_dataset; it combines with --samples, --refill, --score and --pick. --score scores the
+generated row before the splice, with start = the prime length, as a primed row is scored.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -42,7 +54,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import check_refill, keep_mask, parse_keep, sample_seed
+from .generation import check_refill, infill_plan, infill_splice, keep_mask, parse_keep, sample_seed, stop_after_bars
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -84,6 +96,12 @@ def get_args(argv=None):
                     'log-probability per scored position, (N, max_seq_len, 8); needs --score')
     ap.add_argument('--score_dataset', action='store_true', help='no generation: score the dataset rows themselves behind their prime (needs --prime); '
                     'writes only the score file')
+    ap.add_argument('--bars', type=int, default=None, metavar='N', help='every row finishes the bar its prime ends in and writes N whole new bars, then '
+                    'stops (with and without --prime)')
+    ap.add_argument('--infill', type=str, default=None, metavar='LO:HI', help='rewrite bars LO .. HI-1 of every piece and leave the rest alone: the rows '
+                    'in front prime the decoder, the region is a MASK for the encoder, the rows behind are spliced back; needs --seed')
+    ap.add_argument('--infill_mode', type=str, default='rows', choices=['rows', 'span'], help='the encoder sees a MASK row per row of the region (rows) '
+                    'or one MASK row for the whole region (span)')
     return ap.parse_args(argv)
 
 
@@ -106,6 +124,20 @@ def parse_prime(value):
     if n < 0:
         raise PBError('--prime takes a number of rows >= 0 or "half" (got %r)' % value)
     return n
+
+
+def parse_infill(value, bar_pad=256):
+    """--infill -> None or (lo, hi) with 0 <= lo < hi <= bar_pad; PBError otherwise."""
+    if value is None:
+        return None
+    parts = str(value).split(':')
+    try:
+        lo, hi = (int(v) for v in parts) if len(parts) == 2 else (-1, -1)
+    except ValueError:
+        lo, hi = -1, -1
+    if not 0 <= lo < hi <= bar_pad:
+        raise PBError('--infill takes LO:HI, two bar ids with 0 <= LO < HI <= %d (got %r)' % (bar_pad, value))
+    return lo, hi
 
 
 def prime_lengths(x, prime, bar_pad, pad_word):
@@ -134,6 +166,21 @@ def check_args(args):
     parse_prime(getattr(args, 'prime', None))
     if args.batch_size < 1:
         raise PBError('--batch_size must be >= 1 (got %d)' % args.batch_size)
+    if getattr(args, 'bars', None) is not None and args.bars < 0:
+        raise PBError('--bars must be >= 0 (got %d)' % args.bars)
+    if getattr(args, 'bars', None) is not None and getattr(args, 'score_dataset', False):
+        raise PBError('--score_dataset generates nothing: it takes no --bars')
+    if getattr(args, 'infill', None) is not None:
+        parse_infill(args.infill)
+        if args.seed is None:
+            raise PBError('--infill needs --seed: the pieces are generated side by side, each from its own RandomState(seed + i)')
+        for flag in ('prime', 'keep', 'bars'):
+            if getattr(args, flag, None) is not None:
+                raise PBError('--infill does not combine with --%s: it sets the prime, the kept attributes and the stop bar itself' % flag)
+        if getattr(args, 'score_dataset', False):
+            raise PBError('--score_dataset generates nothing: it takes no --infill')
+    elif getattr(args, 'infill_mode', 'rows') != 'rows':
+        raise PBError('--infill_mode %s needs --infill' % args.infill_mode)
     if getattr(args, 'keep', None) is not None:
         parse_keep(args.keep)
         if getattr(args, 'prime', None) is None:
@@ -216,6 +263,35 @@ def eval_generation(args=None):
     prime = parse_prime(getattr(args, 'prime', None))
     samples = getattr(args, 'samples', 1)
     keep = parse_keep(args.keep) if getattr(args, 'keep', None) is not None else None
+    bars, infill, truncated = getattr(args, 'bars', None), parse_infill(getattr(args, 'infill', None), bar_pad), 0
+    pad_word = model.pianobart.pad_word_np
+
+    def inputs(x):
+        """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars
+        and (--infill) the plans."""
+        prefix = ks = forced = stops = plans = None
+        if infill is not None:
+            plans = [infill_plan(p, infill[0], infill[1], model.pianobart.mask_word_np, pad_word, getattr(args, 'infill_mode', 'rows')) for p in x.numpy()]
+            ks, stops = [pl['k'] for pl in plans], [pl['stop'] for pl in plans]
+            prefix = torch.as_tensor(np.asarray(pad_word)).long().repeat(len(plans), max(ks, default=0), 1)
+            for b, pl in enumerate(plans):
+                prefix[b, :ks[b]] = torch.as_tensor(pl['prefix'])
+            x = torch.as_tensor(np.stack([pl['enc'] for pl in plans])).long() if plans else x
+        elif prime is not None:                       # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
+            ks = prime_lengths(x.numpy(), prime, bar_pad, pad_word)
+            forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None     # from the piece's rows, before prime_inputs pads them
+            x, prefix = prime_inputs(x, ks, pad_word)
+        if bars is not None:
+            stops = [stop_after_bars(prefix[b, :ks[b]] if ks is not None else None, bars, bar_pad) for b in range(len(x))]
+        return x, prefix, ks, forced, stops, plans
+
+    def splice(y, plans, own):
+        """--infill: row r of y (numpy) spliced with the suffix of its piece own[r]; counts the truncated ones."""
+        nonlocal truncated
+        for r, p in enumerate(own):
+            y[r], cut = infill_splice(y[r], plans[p]['suffix'], args.max_seq_len, bar_pad)
+            truncated += int(cut)
+        return y
     output = np.zeros((N, args.max_seq_len, 8) if samples == 1 else (N, samples, args.max_seq_len, 8), dtype=np.float32)
     do_score = getattr(args, 'score', False)
     scores = np.zeros((N, 9) if samples == 1 else (N, samples, 9), dtype=np.float32)
@@ -247,20 +323,17 @@ def eval_generation(args=None):
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
-            x = torch.as_tensor(np.asarray(data[c0:c1])).long()
-            prefix = ks = forced = None
-            if prime is not None:
-                ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
-                forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None
-                x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
+            x, prefix, ks, forced, stops, plans = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
-                                     device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced,
+                                     device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
                                      samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
+            own = [i - c0 for i, _ in chunk]
             if do_score:
-                own = [i - c0 for i, _ in chunk]
                 sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
             y = y.float().cpu().numpy()
+            if plans is not None:
+                y = splice(y, plans, own)
             for r, (i, j) in enumerate(chunk):
                 output[i, j] = y[r]
                 if do_score:
@@ -269,22 +342,17 @@ def eval_generation(args=None):
         gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
         for c0 in range(0, N if samples == 1 else 0, gen_rows):
             c1 = min(N, c0 + gen_rows)
-            x = torch.as_tensor(np.asarray(data[c0:c1])).long()
-            prefix = ks = forced = None
-            if prime is not None:                     # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
-                ks = prime_lengths(x.numpy(), prime, bar_pad, model.pianobart.pad_word_np)
-                forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None     # from the piece's rows, before prime_inputs pads them
-                x, prefix = prime_inputs(x, ks, model.pianobart.pad_word_np)
+            x, prefix, ks, forced, stops, plans = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
                 y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                          decoder_forced=forced)
+                          decoder_forced=forced, decoder_stop=stops)
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
-                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced,
+                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
                                          refill=(refill or True) if refill is not None else False)
-            output[c0:c1] = y.float().cpu().numpy()
+            output[c0:c1] = y.float().cpu().numpy() if plans is None else splice(y.float().cpu().numpy(), plans, list(range(c1 - c0)))
             for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):
                 s1 = min(c1 - c0, s0 + args.batch_size)
                 scores[c0 + s0:c0 + s1], _ = score_rows(x[s0:s1], y[s0:s1], ks[s0:s1] if ks is not None else None)
@@ -293,6 +361,8 @@ def eval_generation(args=None):
         print("Saved", scores.shape, "to", score_path(args))
         if getattr(args, 'pick', None) == 'best' and samples > 1:
             output = output[np.arange(N), pick_best(scores)]
+    if infill is not None:
+        print("Truncated pieces:", truncated)
     np.save(args.output, output)
     print("Saved", output.shape, "to", args.output)
     return output

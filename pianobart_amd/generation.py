@@ -103,6 +103,106 @@ def check_refill(refill, samples=None, batch_max=16):
     return n
 
 
+def check_stop(stop, P, pad0, owner=None):
+    """The argument rules of bar-bounded generation, on the host before any device work. stop: P bar ids (list, array or tensor on any
+    device), one per prompt: row p also ends at its first token, from its prefix length on, whose bar id (head 0) is >= stop[p];
+    0 <= stop[p] <= pad0, pad0 (the bar head's first special id) = no stop. owner (row -> prompt, check_samples): the list is expanded to
+    one entry per output row. Returns a list of ints, P or R long; None for stop=None or a list that is pad0 everywhere (no stop: the
+    caller runs what it ran before). Raises PBError for a wrong length, a non-integer or a value outside 0 .. pad0."""
+    if stop is None:
+        return None
+    try:
+        vals = stop.tolist() if hasattr(stop, 'tolist') else list(stop)
+    except TypeError:
+        raise PBError('stop must be a sequence of %d bar ids, one per prompt (got %r)' % (P, stop))
+    if not isinstance(vals, list) or len(vals) != P:
+        raise PBError('stop has %d entries for %d prompt(s)' % (len(vals) if isinstance(vals, list) else 1, P))
+    for p, v in enumerate(vals):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise PBError('stop[%d] = %r is not an integer' % (p, v))
+        if not 0 <= v <= pad0:
+            raise PBError('stop[%d] = %d outside 0 .. %d (a bar id; %d = no stop)' % (p, v, pad0, pad0))
+    if all(int(v) == pad0 for v in vals):
+        return None
+    vals = [int(v) for v in vals]
+    return vals if owner is None else [vals[p] for p in owner]
+
+
+def stop_vector(pad_cpu, s):
+    """The 8 thresholds of ONE row's stop test, for every decode path: the reference's `(current_output >= pad).any()` (model.py:47)
+    becomes `(current_output >= stop_vector(pad, s)).any()` -- pad with its head 0 lowered to the row's stop bar s, so the one comparison
+    covers the special ids and the bar. s None (or pad[0]): pad itself."""
+    if s is None or int(s) == int(pad_cpu[0]):
+        return pad_cpu
+    v = pad_cpu.clone()
+    v[0] = int(s)
+    return v
+
+
+def end_reason(tok, pad_cpu):
+    """Why a token that tripped a row's stop test ended the row: 'special' (a special id in any head) or 'bar' (its bar reached the stop)."""
+    return 'special' if bool((tok >= pad_cpu).any()) else 'bar'
+
+
+def stop_after_bars(prefix_rows, n, pad0):
+    """The stop bar of "write n more bars": with q the bar of the prime's last row (-1 for an unprimed row: prefix_rows None or empty),
+    min(q + 1 + n, pad0) -- the row finishes the bar it is in and writes n whole new bars. prefix_rows (k, 8) Octuple ids; n >= 0."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise PBError('bars: the number of new bars must be an integer >= 0 (got %r)' % (n,))
+    rows = None if prefix_rows is None else (prefix_rows.detach().cpu().numpy() if isinstance(prefix_rows, torch.Tensor) else np.asarray(prefix_rows))
+    q = int(rows[-1, 0]) if rows is not None and len(rows) else -1
+    return min(q + 1 + int(n), int(pad0))
+
+
+def infill_plan(piece, lo, hi, mask_word, pad_word, mode='rows'):
+    """The plan of "rewrite bars lo .. hi-1 of this piece and leave the rest alone", host only. piece (S, 8) Octuple ids: ordinary rows with
+    non-decreasing bar ids (ValueError otherwise: the piece has no region), then usually an EOS row, then PAD; 0 <= lo < hi <= pad_word[0].
+    Returns a dict: k = the leading rows with bar < lo; prefix = those rows (the decoder prime); stop = hi (the row's stop bar); suffix = the
+    rows with bar >= hi up to and including the piece's first row with a special bar id unless that row is PAD (the EOS row travels with
+    the suffix); enc = the (S, 8) encoder input. mode 'rows' (TokenMask's convention): every row of the region is replaced by mask_word,
+    the length is preserved. mode 'span' (TokenInfilling's): the region is replaced by ONE mask_word row, the rest moves up and pad_word
+    fills the tail (cut at S). An empty region is legal: 'rows' masks nothing, 'span' inserts the one row."""
+    x = piece.detach().cpu().numpy() if isinstance(piece, torch.Tensor) else np.asarray(piece)
+    if x.ndim != 2 or x.shape[1] != 8:
+        raise PBError('infill_plan: piece of shape %s, expected (S, 8)' % (tuple(x.shape),))
+    x = x.astype(np.int64)
+    mask_word, pad_word = np.asarray(mask_word, dtype=np.int64).reshape(8), np.asarray(pad_word, dtype=np.int64).reshape(8)
+    S, pad0 = x.shape[0], int(pad_word[0])
+    if isinstance(lo, bool) or isinstance(hi, bool) or not isinstance(lo, (int, np.integer)) or not isinstance(hi, (int, np.integer)) or not 0 <= lo < hi <= pad0:
+        raise PBError('infill_plan: bars %r:%r: expected integers 0 <= lo < hi <= %d' % (lo, hi, pad0))
+    if mode not in ('rows', 'span'):
+        raise PBError('infill_plan: mode %r is neither "rows" nor "span"' % (mode,))
+    special = np.flatnonzero(x[:, 0] >= pad0)
+    e = int(special[0]) if len(special) else S                             # the ordinary rows are x[:e]
+    bars = x[:e, 0]
+    if (np.diff(bars) < 0).any():
+        i = int(np.flatnonzero(np.diff(bars) < 0)[0]) + 1
+        raise ValueError('infill_plan: the bar ids of the piece decrease at row %d (%d after %d): it has no region of bars %d .. %d'
+                         % (i, int(bars[i]), int(bars[i - 1]), lo, hi - 1))
+    k, m = int((bars < lo).sum()), int((bars < hi).sum())                  # the region is x[k:m]
+    tail = e + 1 if e < S and int(x[e, 0]) != pad0 else e
+    if mode == 'rows':
+        enc = x.copy()
+        enc[k:m] = mask_word
+    else:
+        enc = np.concatenate([x[:k], mask_word[None], x[m:], np.tile(pad_word, (max(0, m - k - 1), 1))])[:S]
+    return dict(k=k, prefix=x[:k].copy(), stop=int(hi), suffix=x[m:tail].copy(), enc=enc)
+
+
+def infill_splice(out_row, suffix, S, bar_pad):
+    """The piece after infilling: the emitted rows of out_row (a generated (S, 8) row: the prime, the new region, PAD behind its stop --
+    the rows in front of its first bar PAD), followed by suffix (infill_plan), with PAD behind. Returns (row (S, 8), truncated): a piece
+    longer than S is cut at S and truncated is True."""
+    y = out_row.detach().cpu().numpy() if isinstance(out_row, torch.Tensor) else np.asarray(out_row)
+    pad_rows = np.flatnonzero(y[:, 0] == bar_pad)
+    n = int(pad_rows[0]) if len(pad_rows) else y.shape[0]
+    row = np.concatenate([y[:n], np.asarray(suffix, dtype=y.dtype).reshape(-1, 8)])
+    truncated = len(row) > S
+    if len(row) < S:
+        row = np.concatenate([row, np.tile(y[n], (S - len(row), 1))])      # len(row) < S <= len(y) + len(suffix): y[n] is a PAD row
+    return row[:S], truncated
+
+
 KEEP_NAMES = ('bar', 'position', 'instrument', 'pitch', 'duration', 'velocity', 'timesig', 'tempo')       # the 8 heads, model column order
 
 
@@ -217,7 +317,7 @@ def sample_seed(seed, j, i, N):
 
 class GenerationMixin:
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -233,18 +333,27 @@ class GenerationMixin:
         by forced[0, i] right after `self.sample(x, i)` (forced_token). The stop rule sees the token after forcing; a position with a free
         head draws its 8 uniforms as ever, a position with all 8 heads given draws nothing; positions below k must be free; max_new counts
         positions from k on, given or sampled. Leading given positions are stepped through, not prefilled. None, or -1 everywhere: exactly
-        the launches and bytes of a call without the argument."""
+        the launches and bytes of a call without the argument.
+        stop (an int, or a sequence of one; check_stop): stop at a bar -- the reference loop with the stop test `(current_output >=
+        pad).any()` replaced by `(current_output >= pad).any() or current_output[0] >= stop` (stop_vector). The test sees the token after
+        forcing; the token that trips it is not written (result[0, i:] stays PAD) and its draws are consumed; positions below k are not
+        tested; max_new and the window still apply. pad[0] (256), or None: no stop, the call without the argument. A call that
+        passes `stop` (256 included) finds last_decode['ended']: what ended the row, 'special', 'bar' or 'limit'; a call without the
+        argument leaves the record it always left."""
         S = int(enc_ids.shape[1])
+        with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
         forced = check_forced(forced, 1, S, ops.SEG_SIZES, ks)
+        stop = check_stop([stop] if isinstance(stop, (int, np.integer)) and not isinstance(stop, bool) else stop, 1, int(self.pb.pad_word_np[0]))
+        sb = stop[0] if stop is not None else None
         fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -254,11 +363,13 @@ class GenerationMixin:
                 if sampler is not None and _DECODE_SPEC:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                     info = self._decode_device_sampled(run.dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
-                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced)
-                    info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0])
+                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop)
+                    info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0], ended=info['ended'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr)
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb)
                 self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()))
+                if not with_ended:
+                    del self.last_decode['ended']
             else:
                 import ctypes
                 pref, stream = ctypes.byref(run.bp.plan), ops._stream()
@@ -267,11 +378,12 @@ class GenerationMixin:
                     tok16.copy_(pre[k - 1].to(torch.int16))                     # the input of position k: the prefix's last row
                 tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
                 logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
+                sv = stop_vector(pad_cpu, sb)
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
                     tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_pin))
-                    if (tok >= pad_cpu).any():
+                    if (tok >= sv).any():
                         break
                     res_cpu[0, i] = tok
                     tok_pin.copy_(tok)
@@ -442,11 +554,12 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
         k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
-        fr (S, 8): the row's forced table (forced_token)."""
+        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector)."""
         import ctypes
+        sv, ended = stop_vector(pad_cpu, stop), 'limit'
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
         if k:
             last = np.asarray([k - 1], dtype=np.int32)
@@ -459,18 +572,19 @@ class GenerationMixin:
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
             tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_cpu))
-            if (tok >= pad_cpu).any():
+            if (tok >= sv).any():
+                ended = end_reason(tok, pad_cpu)
                 break
             res_cpu[0, i] = tok
             tok_np[:] = tok.numpy()
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
-                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3)
+                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, ended=ended)
 
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
     def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
-                       refill=False):
+                       refill=False, stop=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -494,12 +608,24 @@ class GenerationMixin:
         whole call instead of one per chunk of BATCH_MAX: when a row stops, its slot goes to the next waiting prompt while the other rows
         decode on (_generate_batch_refill), so a short row does not wait for the longest row of its chunk and the set-up is paid once.
         Every row stays under the contract above; the result and the final generator states are those of refill=False. With no more rows
-        than slots, or where the fused decoder does not cover the shape, the call runs as with refill=False. Not with `samples`."""
+        than slots, or where the fused decoder does not cover the shape, the call runs as with refill=False. Not with `samples`.
+        stop (B bar ids, check_stop): stop at a bar, row b under `generate`'s contract with stop[b]; pad[0] (256) = no stop, so one batch
+        may mix both. With samples it describes the P prompts, like the prefix. The fused decoder's device sampler makes the same test
+        (pb_batch_decoder_stop; a refilled slot gets its row's value with the hand-over, pb_batch_decoder_admit_stop), so a stopped row
+        frees its place at once; the host's verification decides, as for every token. None, or pad[0] everywhere: the call without the
+        argument. A call that passes `stop` finds last_decode['ended'][b]: 'special', 'bar' or 'limit', for every row of the call; a call
+        without the argument leaves the record it always left."""
+        def done(out, with_ended=stop is not None):      # every path below records `ended`; a call without `stop` keeps the record it had
+            if not with_ended and self.last_decode is not None:
+                self.last_decode.pop('ended', None)
+            return out
         P = int(enc_ids.shape[0])
         slots = check_refill(refill, samples, self.BATCH_MAX)
         owner = check_samples(samples, P, len(rngs)) if samples is not None else list(range(P))        # row -> prompt
         ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
         forced = check_forced(forced, P, int(enc_ids.shape[1]), ops.SEG_SIZES, ks)
+        pad0 = int(self.pb.pad_word_np[0])
+        stop = check_stop(stop, P, pad0, owner if samples is not None else None)         # one entry per output row
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -508,67 +634,75 @@ class GenerationMixin:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced)
-            return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced)
+                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop))
+            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop))
         if slots and R > slots:
-            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots)
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop)
             if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
-                return out
-        outs = []
+                return done(out)
+        outs, ended = [], []
         for c0 in range(0, R, self.BATCH_MAX):
             own = owner[c0:c0 + self.BATCH_MAX]
+            st = stop[c0:c0 + len(own)] if stop is not None else None
+            st = st if st is not None and any(v != pad0 for v in st) else None     # a chunk without a real stop is today's chunk
             p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
             outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
                                                    groups=[p - p0 for p in own] if samples is not None else None,
-                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None))
-        return torch.cat(outs, 0)
+                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st))
+            ended += (self.last_decode or {}).get('ended') or [None] * len(own)
+        if len(outs) > 1 and self.last_decode is not None:                # last_decode describes the last chunk; `ended` covers every row
+            self.last_decode['ended'] = ended
+        return done(torch.cat(outs, 0))
 
-    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None):
-        """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt."""
+    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None):
+        """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt. stop: one
+        entry per ROW (check_stop expands it), or None."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
                                          max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
-                                         forced[idx.numpy()] if forced is not None else None)
+                                         forced[idx.numpy()] if forced is not None else None, stop)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None):
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
         caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
-        checked table per row (check_forced) or None."""
+        checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None."""
         saved = np.random.get_state()
-        outs = []
+        outs, ended, pad0 = [], [], int(self.pb.pad_word_np[0])
         try:
             for b in range(int(enc_ids.shape[0])):
                 np.random.set_state(rngs[b].get_state())
                 pre = rows[b:b + 1, :ks[b]] if rows is not None and ks[b] else None
                 outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
-                                          max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None))
+                                          max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None,
+                                          stop=stop[b] if stop is not None else pad0))        # 256: no stop, and the row's `ended`
+                ended.append((self.last_decode or {}).get('ended'))
                 rngs[b].set_state(np.random.get_state())
         finally:
             np.random.set_state(saved)
-        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]))
+        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended)
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None):
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
-        loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled)."""
+        loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
             info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
                                                run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
-                                               forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None)
+                                               forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n):
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None):
         """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
         waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
         in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
@@ -577,7 +711,9 @@ class GenerationMixin:
         The set-up is _decoder_run's, once; the loop is _decode_device_sampled's with slots for rows: the first n rows start as a chunk
         starts (sampler_init, force, start), the device samples ahead, the host verifies one run behind from the pinned logs (indexed by
         SLOT: an occupant's log rows are read before the next one is admitted) and rewinds a row alone. Each row's draws are made at its
-        admission from a copy of rngs[r] (forced_draws). Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        admission from a copy of rngs[r] (forced_draws). stop (R stop bars or None): the first n rows' values go up as a chunk's do
+        (pb_batch_decoder_stop), a later row's is staged in front of its admission (pb_batch_decoder_admit_stop); a row without a stop
+        stages nothing and its slot gets pad[0], never the previous occupant's value. Returns the (R, S, 8) result, or None -- before any encoder work -- where
         pb_batch_decoder_create declines the shape."""
         R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
@@ -593,11 +729,11 @@ class GenerationMixin:
                 return None
             try:
                 return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
-                                        pad_cpu).to(dev)
+                                        pad_cpu, stop).to(dev)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
-    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu):
+    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None):
         """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
         import ctypes
         from collections import deque
@@ -663,6 +799,11 @@ class GenerationMixin:
                  U.ctypes.data, n * S * 8, max(lim), int(fault[0]), int(fault[1]))
         if forced is not None:                                             # the graphs end in the forced sampler for the whole run
             LIB.call('pb_batch_decoder_force', dec, np.ascontiguousarray(forced[:n]).ctypes.data)
+        pad0 = int(pad_cpu[0])
+        svs = [stop_vector(pad_cpu, stop[r] if stop is not None else None) for r in range(R)]
+        ended = ['limit'] * R
+        if stop is not None and any(v != pad0 for v in stop[:n]):
+            LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop[:n], dtype=np.int32).ctypes.data)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (n * S * vocab)).from_address(lp.value)).reshape(n, S, vocab))
@@ -709,6 +850,8 @@ class GenerationMixin:
                         bufs['kvs'][l][s, :ks[r]].copy_(stage[l][c, :ks[r]])
                 u, tok = draws(r), first_tok(r)
                 fr = np.ascontiguousarray(forced[r]) if forced is not None and (forced[r] != -1).any() else None
+                if stop is not None and stop[r] != pad0:                   # stored by the admit's kernel, with the row's position and done = 0
+                    LIB.call('pb_batch_decoder_admit_stop', dec, s, stop[r])
                 LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
                          fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
                 counts['admissions'] += 1
@@ -739,7 +882,8 @@ class GenerationMixin:
             for i in range(a, e):
                 tok = forced_token(forced[r, i] if forced is not None else None, lambda: sample_row(log_logits[s, i], rngs[r]))
                 tokens[r] += 1
-                if (tok >= pad_cpu).any():
+                if (tok >= svs[r]).any():
+                    ended[r] = end_reason(tok, pad_cpu)
                     return ('stop', i)
                 res_cpu[r, i] = tok
                 t16 = tok.numpy().astype(np.int16)
@@ -785,11 +929,11 @@ class GenerationMixin:
                                 tokens=tokens, rewinds=rewinds, steps=stat['steps'], row_steps=stat['row_steps'], loop_ms=(time.perf_counter() - t_loop) * 1e3,
                                 host_ms=stat['host_s'] * 1e3, device_sampler=True, tokens_per_graph_replay=K, refill=n, slices=NS,
                                 admissions=counts['admissions'], row_slot=row_slot, encoder_passes=counts['encoder_passes'], s_enc=s_enc, batched=True, batch=n,
-                                prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms,
+                                prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms, ended=ended,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
         return res_cpu
 
-    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None):
+    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -806,7 +950,11 @@ class GenerationMixin:
         forced (B, S, 8) int16, -1 = free (check_forced), or None: the table goes to the device sampler (pb_batch_decoder_force, between
         sampler_init and start), the draws made ahead follow it (forced_draws: a fully given position draws nothing) and the host applies
         it to its own tokens (forced_token: sample() is called only at positions with a free head, the stop test sees the token after
-        forcing), so a given head cannot disagree and the result stays the host's."""
+        forcing), so a given head cannot disagree and the result stays the host's.
+        stop (B stop bars, check_stop) or None: the values go to the device sampler behind sampler_init and force (pb_batch_decoder_stop: its
+        done test of head 0 then compares against the row's bar) and the host's stop test uses the row's stop_vector. The device's done
+        flag stays a prediction: where it stopped a row the host does not stop, or the other way round, the tokens differ and the rewind
+        below handles it. Returns `ended` per row: 'special', 'bar' or 'limit', as the host decided."""
         import contextlib
         import ctypes
         from collections import deque
@@ -828,6 +976,10 @@ class GenerationMixin:
                  U.ctypes.data, B * S * 8, limit, int(fault[0]), int(fault[1]))
         if forced is not None:
             LIB.call('pb_batch_decoder_force', dec, forced.ctypes.data)
+        svs = [stop_vector(pad_cpu, stop[b] if stop is not None else None) for b in range(B)]
+        ended = ['limit'] * B
+        if stop is not None:
+            LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop, dtype=np.int32).ctypes.data)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
@@ -863,7 +1015,8 @@ class GenerationMixin:
             for i in range(s, e):
                 tok = forced_token(forced[b, i] if forced is not None else None, lambda: sample(b, log_logits[b, i]))
                 tokens[b] += 1
-                if (tok >= pad_cpu).any():
+                if (tok >= svs[b]).any():
+                    ended[b] = end_reason(tok, pad_cpu)
                     return ('stop', i)
                 res_cpu[b, i] = tok
                 t16 = tok.numpy().astype(np.int16)
@@ -899,17 +1052,19 @@ class GenerationMixin:
                             sp[b][0] = sp[b][1] = i + 1
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
-                    device_sampler=True, tokens_per_graph_replay=K)
+                    device_sampler=True, tokens_per_graph_replay=K, ended=ended)
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
         rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
-        fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads."""
+        fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads.
+        stop: the row's stop bar or None (stop_vector)."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
         pad_cpu = torch.from_numpy(pb.pad_word_np)
+        sv = stop_vector(pad_cpu, stop)
         result = pad.repeat(1, S, 1)
         em, enc16 = self._prompt_inputs(enc_ids, emask)
         e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
@@ -957,16 +1112,16 @@ class GenerationMixin:
                 if frow is None or (frow < 0).any():
                     ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
                 tok = forced_token(frow, lambda: sample_row(logits[0].cpu()))
-                if (tok >= pad_cpu).any():
+                if (tok >= sv).any():
                     break
                 result[:, i, :] = tok.to(dev)
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
         cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
-        fr (S, 8): the row's forced table (forced_token)."""
+        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -982,6 +1137,7 @@ class GenerationMixin:
             dmask[0, :n + 1] = 1
             result[0, :k] = pre.to(dev)
         pad_cpu = torch.from_numpy(pb.pad_word_np)
+        sv = stop_vector(pad_cpu, stop)
         em, enc16 = self._prompt_inputs(enc_ids, emask)
         with torch.no_grad():
             for i in range(k, S):
@@ -992,7 +1148,7 @@ class GenerationMixin:
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)
                     dmask[:, i + 1] += 1
-                if (cur >= pad_cpu).any():
+                if (cur >= sv).any():
                     break
                 result[:, i, :] = cur.to(dev)
         return result

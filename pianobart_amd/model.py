@@ -344,7 +344,7 @@ class PianoBartLM(nn.Module):
         return self._engine
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
-                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None):
+                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
         position k on (Engine.generate's `prefix`).
         decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
@@ -353,13 +353,19 @@ class PianoBartLM(nn.Module):
         after forcing (a given special id ends the piece there, a given ordinary id keeps it going where the sample would have been
         special); a position with a free head draws its 8 uniforms as ever (the draws of its given heads are consumed and unused), a
         position whose 8 heads are given draws nothing; a given id may be any id of its head's table (IndexError otherwise); positions
-        inside decoder_prefix must be -1 (PBError). None, or -1 everywhere, is the call without the argument."""
+        inside decoder_prefix must be -1 (PBError). None, or -1 everywhere, is the call without the argument.
+        decoder_stop (a bar id 0 .. 256, or a sequence of one; generate=True only): stop at a bar -- the reference loop with its stop test
+        `(current_output >= pad).any()` replaced by `(current_output >= pad).any() or current_output[0] >= decoder_stop`. The test sees the
+        token after forcing; the token that trips it is not written and its draws are consumed; positions inside decoder_prefix are not
+        tested (generation.stop_after_bars turns "n more bars" into the bar id). 256 (the bar head's PAD id), or None: no stop."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
                 raise PBError('decoder_prefix primes generation: it needs generate=True')
             if decoder_forced is not None:
                 raise PBError('decoder_forced gives tokens of a generated piece: it needs generate=True')
+            if decoder_stop is not None:
+                raise PBError('decoder_stop ends a generated piece at a bar: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             return [logits[..., ops.SEG_OFF[i]:ops.SEG_OFF[i + 1]] for i in range(8)]
@@ -367,12 +373,13 @@ class PianoBartLM(nn.Module):
             print("ERROR")
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
-                           prefix=decoder_prefix, forced=decoder_forced)
+                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
-                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False):
+                       decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False,
+                       decoder_stop=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -388,7 +395,10 @@ class PianoBartLM(nn.Module):
         prefix_len[b] on, given or sampled). With samples_per_prompt it describes the P prompts, like decoder_prefix. The given heads are
         applied inside the fused decoder's device sampler, so a forced batch keeps the batched decode's launches per step.
         refill (False, True or a slot count 2 .. 16): one decoder for the whole call whose rows are handed to the next waiting prompt as
-        they stop (Engine.generate_batch's `refill`); the result is that of refill=False. Not with samples_per_prompt."""
+        they stop (Engine.generate_batch's `refill`); the result is that of refill=False. Not with samples_per_prompt.
+        decoder_stop (B bar ids 0 .. 256): prompt b under forward(generate=True, decoder_stop=...)'s contract with its own bar; 256 = no
+        stop, so one batch may mix both. With samples_per_prompt it describes the P prompts. The fused decoder's device sampler makes the
+        test too, so a stopped row leaves the batch (or frees its slot under refill) at once."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -405,7 +415,7 @@ class PianoBartLM(nn.Module):
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
-                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill)
+                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):

@@ -4,7 +4,7 @@ positions). Prints ONE JSON line: per B in --batches, aggregate tokens/s, ms per
 verification ms per step and an HBM-bytes estimate per step (decoder + LM-head weights once, plus each row's cross K/V over its visible
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
-    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]]
+    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]] [--bars N]
 
 --keep pitch,velocity: forced tokens -- the named attributes of synthetic pieces are given at every position (generation.keep_mask) and the
 model samples the others, at the largest B of --batches: ms per step and rewinds per row, beside the unforced run of the same process.
@@ -20,6 +20,13 @@ uniform in --len_min .. --len_max (16 .. 256) positions, every other head free. 
 finished row's slot going to the next prompt) and "chunked" (refill=False: chunks of 16, each lasting until its longest row) alternate in
 this process, --reps times. Per run: tokens/s of the whole call with the set-up included, steps, occupancy (row_steps / (steps * slots)),
 setup_ms (summed over the chunks) and rewinds. One JSON line per run and a summary line, printed and appended to profiles/refill_b16.jsonl.
+
+--bars N: what the stop at a bar buys. --prompts (64) synthetic pieces, each primed with its first S/4 .. S/2 rows, the bar attribute of the
+rows behind the prime given (generation.keep_mask: a piece's own bars, a new one every ~17 rows) and the other heads sampled; row r stops at
+generation.stop_after_bars(prime, N). Four runs alternate in this process, --reps times: "refill" and "chunked" with the stop, and
+"nostop_refill" / "nostop_chunked" -- the same prompts decoded to the window's end without it and cut afterwards, which is what a caller had
+to do before and the yardstick here. Per run: tokens/s of KEPT tokens over the whole call (kept = the positions of the stopped rows, the
+same in all four runs), steps and occupancy. One JSON line per run and a summary line, printed and appended to profiles/bar_stop_b16.jsonl.
 """
 import argparse
 import json
@@ -52,6 +59,9 @@ def main(argv=None):
     ap.add_argument('--len_min', type=int, default=16, help='--refill: shortest row')
     ap.add_argument('--len_max', type=int, default=256, help='--refill: longest row')
     ap.add_argument('--log', type=str, default=os.path.join(ROOT, 'profiles', 'refill_b16.jsonl'), help='--refill: the file the lines are appended to')
+    ap.add_argument('--bars', type=int, default=None, metavar='N', help='time bar-bounded generation (N new bars per primed row), refilled and chunked, '
+                    'against the same prompts decoded without the stop and cut afterwards')
+    ap.add_argument('--bars_log', type=str, default=os.path.join(ROOT, 'profiles', 'bar_stop_b16.jsonl'), help='--bars: the file the lines are appended to')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -71,7 +81,7 @@ def main(argv=None):
     eng = model._get_engine()
     eng.bind(dev)
     sampler = dict(T=model.SAMPLE_T, P=model.SAMPLE_P)
-    Bmax = max(args.batches) if args.refill is None else args.prompts
+    Bmax = max(args.batches) if args.refill is None and args.bars is None else args.prompts
     enc = synth_octuple_batch(Bmax, S, seed=7, min_len=S // 2)[5].to(dev)     # S/2 .. S visible rows, as bench.py's decode prompt
     emask = (enc[:, :, 0] != 256).float()
     steps = min(args.steps, S)
@@ -83,6 +93,80 @@ def main(argv=None):
 
     def kv_bytes(rows):                                     # cross K/V over the visible rows + self K/V at the mean position
         return sum(L * (vis[b] + steps / 2) * 2 * d * 2 for b in range(rows))
+
+    if args.bars is not None:
+        from pianobart_amd.generation import keep_mask, stop_after_bars
+        R, slots = args.prompts, args.refill or eng.BATCH_MAX
+        piece = synth_octuple_batch(R, S + 1, seed=9, min_len=S + 1)[5][:, :S]       # ordinary rows all the way, bars non-decreasing
+        ks = [int(v) for v in np.random.RandomState(17).randint(S // 4, S // 2 + 1, size=R)]
+        forced = keep_mask(piece, 'bar', ks)                 # the bar of every position behind the prime is the piece's own
+        stops = [stop_after_bars(piece[r, :ks[r]], args.bars, 256) for r in range(R)]
+        penc = piece.clone().to(dev)
+        for r in range(R):                                   # the encoder sees the prime only (Ablation.py:132-139)
+            penc[r, ks[r]:] = torch.tensor(model.pianobart.pad_word_np, device=dev)
+        pmask = (penc[:, :, 0] != 256).float()
+        chunks = []
+        chunk_fn = eng._generate_batch_chunk
+
+        def counted(*a, **k):                               # last_decode holds the last chunk only: keep every chunk's
+            y = chunk_fn(*a, **k)
+            chunks.append(dict(eng.last_decode))
+            return y
+        eng._generate_batch_chunk = counted
+
+        def cut(y):                                         # what a caller did before: decode on, then drop everything from the stop bar on
+            y = y.clone()
+            for r in range(len(y)):
+                hit = (y[r, ks[r]:, 0] >= stops[r]).nonzero()
+                if len(hit):
+                    y[r, ks[r] + int(hit[0, 0]):] = torch.tensor(model.pianobart.pad_word_np)
+            return y
+
+        def run(kind, rows):
+            rngs = [np.random.RandomState(b) for b in range(rows)]
+            del chunks[:]
+            refill = (args.refill or True) if kind.endswith('refill') else False
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            y = eng.generate_batch(penc[:rows], pmask[:rows], model.sample_row, rngs, sampler=sampler, prefix=piece[:rows], prefix_len=ks[:rows],
+                                   forced=forced[:rows], refill=refill, stop=None if kind.startswith('nostop') else stops[:rows]).cpu()
+            if kind.startswith('nostop'):
+                y = cut(y)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            infos = list(chunks) if chunks else [dict(eng.last_decode)]
+            kept = int(sum(int((y[r, ks[r]:, 0] != 256).sum()) for r in range(rows)))
+            nsteps = sum(i['steps'] for i in infos)
+            row_steps = sum(i.get('row_steps', sum(i['tokens'])) for i in infos)
+            width = sum(i['steps'] * i['batch'] for i in infos)
+            return y, dict(kind=kind, prompts=rows, bars=args.bars, slots=slots if refill else eng.BATCH_MAX, kept_tokens=kept, wall_ms=dt * 1e3,
+                           kept_tokens_per_s=kept / dt, decoded_tokens=sum(sum(i['tokens']) for i in infos), steps=nsteps,
+                           occupancy=row_steps / max(1, width), setup_ms=sum(i['setup_ms'] for i in infos), loop_ms=sum(i['loop_ms'] for i in infos),
+                           rewinds=sum(sum(i['rewinds']) for i in infos), decoders=len(infos), admissions=infos[0].get('admissions', 0),
+                           launches_per_step=infos[0]['launches_per_token'], graph=infos[0]['graph'])
+        kinds = ('refill', 'chunked', 'nostop_refill', 'nostop_chunked')
+        for kind in kinds[:2]:
+            run(kind, min(R, 2 * slots))                    # warm-up (capture, pinned logs, allocator)
+        lines, same = [], True
+        for _ in range(args.reps):
+            ys = {}
+            for kind in kinds:
+                ys[kind], r = run(kind, R)
+                lines.append(r)
+            same = same and all(bool(torch.equal(ys[k], ys['refill'])) for k in kinds)
+        med = lambda kind, key: float(np.median([r[key] for r in lines if r['kind'] == kind]))
+        summ = {kind: {key: med(kind, key) for key in ('kept_tokens_per_s', 'kept_tokens', 'decoded_tokens', 'steps', 'occupancy', 'wall_ms', 'rewinds')}
+                for kind in kinds}
+        lines.append(dict(kind='summary', metric='stop at a bar vs decode-and-cut (%dL/%dd, S=%d, %d prompts primed with S/4 .. S/2 rows, %d new bars)'
+                          % (L, d, S, R, args.bars), same_tokens_in_all_runs=same, medians=summ,
+                          speedup_refill=summ['refill']['kept_tokens_per_s'] / summ['nostop_refill']['kept_tokens_per_s'],
+                          speedup_chunked=summ['chunked']['kept_tokens_per_s'] / summ['nostop_chunked']['kept_tokens_per_s']))
+        eng._generate_batch_chunk = chunk_fn
+        with open(args.bars_log, 'a') as fh:
+            for ln in lines:
+                print(json.dumps(ln), flush=True)
+                fh.write(json.dumps(ln) + '\n')
+        return
 
     if args.refill is not None:
         R, slots = args.prompts, args.refill or eng.BATCH_MAX
