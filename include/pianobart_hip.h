@@ -532,7 +532,28 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   stores pad8[0]: a slot never inherits its previous occupant's stop. pb_batch_decoder_seek does not
  *                                   touch the value (a rewound row keeps its occupant's). Host state only, no device work. Refused (< 0,
  *                                   pb_last_error, nothing changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1,
- *                                   a value outside 0 .. pad8[0]. */
+ *                                   a value outside 0 .. pad8[0].
+ * Time-ordered sampling (an addition to ABI 10): a row whose sampled (bar, position) never goes back. With prev = the row's decoder
+ * input of the position (the SOS row, the prime's last row, else the previous token after forcing) and floor[b] >= 0:
+ *   head 0: the classes c < max(floor[b], prev[0] if prev[0] < pad8[0] else 0) get the quotient -inf in front of the softmax
+ *           (probability exactly 0); every class from there on, the special ids included, stays free;
+ *   head 1: with b0 = head 0's id after forcing, the classes c < prev[1] get -inf if prev[0] < pad8[0], prev[1] < pad8[1] and
+ *           b0 == prev[0]; otherwise head 1 is sampled as ever. Heads 2 .. 7, the given heads and the draws are untouched.
+ *   pb_batch_decoder_order          after pb_batch_decoder_sampler_init, before the first step of the run (pb_batch_decoder_force's window):
+ *                                   floor = (B) host ints, -1 <= floor[b] < pad8[0]; -1 = the row is sampled as ever (what sampler_init sets
+ *                                   for every row). Stored beside the rows' stop bars in decoder-stream order (a small kernel that takes
+ *                                   them by kernarg: the caller's array is free when the call returns); pb_batch_decoder_start keeps them.
+ *                                   Both sampler forms read the row's value with its position (B = 1 included: that run samples on the
+ *                                   device too) and take prev from the row's decoder input on the device, which pb_batch_decoder_start /
+ *                                   _seek / _admit and the sampler itself keep current. Same kernels, same kernarg layouts, same launches
+ *                                   per step; the result stays a prediction the host confirms or rewinds. A value outside -1 .. pad8[0] - 1,
+ *                                   a call before sampler_init, or a call after a step was issued or captured is refused (< 0,
+ *                                   pb_last_error) and changes nothing.
+ *   pb_batch_decoder_admit_order    refill: stages the floor (-1 .. pad8[0] - 1) that the next pb_batch_decoder_admit of `row` stores, in the
+ *                                   same small kernel as the row's position, limit, stop bar and done = 0. An admit without a staged value
+ *                                   stores -1: a slot never inherits its previous occupant's floor. pb_batch_decoder_seek does not touch
+ *                                   the value. Host state only, no device work. Refused (< 0, pb_last_error, nothing changed): not a
+ *                                   dynamic decoder, before sampler_init, row outside 0 .. B - 1, a value outside -1 .. pad8[0] - 1. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -560,6 +581,8 @@ int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int32_t s_enc,
 int pb_batch_decoder_fence(void* dec, void* caller_stream);
 int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar);
 int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_bar);
+int pb_batch_decoder_order(void* dec, const int32_t* floor);
+int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floor);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

@@ -58,6 +58,11 @@ struct BState {
     // row form, the device sampler only: the row is done when head 0 (the bar) of its token is >= stop[b]. pad[0] = no stop beyond the special
     // ids; a lower value is the bar the row stops at (pb_batch_decoder_stop, pb_batch_decoder_admit_stop). Set by sampler_init, start and admit
     int stop[BMAX];
+    // the device sampler, both forms: order[b] >= 0 = the row is time-ordered with that bar floor, -1 = sampled freely
+    // (pb_batch_decoder_order, pb_batch_decoder_admit_order). opad = the first special ids of heads 0 (bar) and 1 (position): the single-row
+    // sampler's kernargs hold no pad. Set by sampler_init, start and admit
+    int order[BMAX];
+    int opad[2];
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -1239,6 +1244,11 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // pad[0], so the one comparison covers the special ids and the bar. It is no template parameter and no kernarg form of its own: one 4-byte
 // load, from the struct done[b] and pos[b] are read from and issued with them, in 1 of the step's launches does not justify doubling the
 // instantiations. The ROWS = false kernels have no done flag and are untouched: the host ends a B = 1 run, as it does for EOS.
+// Time-ordered sampling (pb_batch_decoder_order), both forms: a row with order[b] >= 0 never samples a (bar, position) below its decoder
+// input's -- heads 0 and 1 get -inf quotients for the classes that would go back (the rule: the header), in front of the softmax, and
+// everything behind it is the unordered arithmetic. It is a block-uniform branch on order[b], not a template parameter: the row form
+// mixes ordered and free rows in one launch (one workgroup per row), so a template would still need the per-row test, and four
+// more instantiations would double the captured graphs' variants for code that an unordered row skips with one load and one compare.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1271,52 +1281,17 @@ __device__ __forceinline__ float wave_scan_f(float v, int lane) {
     for (int o = 1; o < 64; o <<= 1) { const float u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
     return v;
 }
-template <bool ROWS, bool FORCED>
-__global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKernArgs<ROWS, FORCED>::type a) {
-    __shared__ __attribute__((aligned(16))) float pn[8][SMP_W];     // normalised probabilities, class order
-    __shared__ float sp[8][SMP_W + 64];   // ... in descending order (heads with p < 1), zero tail
-    __shared__ int si[8][SMP_W];          // class of each sorted entry
-    __shared__ int htok[8];
-    const int b = ROWS ? (int)blockIdx.x : 0;
-    if (ROWS && a.st->done[b]) return;                           // block-uniform
-    const int t = threadIdx.x, lane = t & 63, h = t >> 6;
-    const int pos = a.st->pos[b];
-    [[maybe_unused]] int stop0 = 0;                              // head 0's first id that ends the row: requested with done[b] and pos[b]
-    if constexpr (ROWS) stop0 = a.st->stop[b];
-    const float* logits = a.logits + (size_t)b * a.vocab;
-    float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
-    const int n = a.n[h], off = a.off[h];
-    const float T = a.temp[h];
-    const double u_draw = a.u[((size_t)b * a.S + pos) * 8 + h];  // requested now: a load that depends on pos would otherwise sit at the end of the chain
-    [[maybe_unused]] int f = -1;                                 // the given id of head t & 7 at this position
-    if constexpr (FORCED) {
-        const int16_t* fr = a.force + ((size_t)b * a.S + pos) * 8;
-        const uint4 all = *reinterpret_cast<const uint4*>(fr);   // the 8 entries of the position: 16 bytes, 16-byte aligned
-        f = fr[t & 7];
-        if ((((all.x | all.y) | (all.z | all.w)) & 0x80008000u) == 0) {     // all 8 heads given (block-uniform): nothing to sample
-            if constexpr (ROWS) __syncthreads();                 // every thread has read done[b] before it may change
-            if (t < 8) {
-                a.tok_dev[b * 8 + t] = (int16_t)f;
-                a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)f;
-                if constexpr (ROWS) { if (f >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }
-            }
-            return;
-        }
-    }
-    // softmax(logit / T) of head h (torch.softmax(logit / t, dim=-1), model.py:103-104), then probs /= (sum(probs) + 1e-5) (model.py:85).
-    // The sums here are wave reductions, not numpy's left-to-right ones: a common divisor that differs in its last bit moves every
-    // probability alike, so the order and (but for a 1e-7 neighbourhood of a threshold) the choice stay -- the host checks every position.
-    float y[5], e[5];
+// The three stages of one head, each run by the head's wave (the rank counting of the first pass: by one thread per class). They are
+// functions because the time-ordered form runs them a second time for head 1 (below); inlined, the first pass is the code it was.
+// softmax(y) of the head's n classes (lane l holds classes l, l + 64, ..; -inf = no such class or a masked one) -> pnh[0 .. SMP_W): torch.softmax(logit / t,
+// dim=-1) (model.py:103-104), then probs /= (sum(probs) + 1e-5) (model.py:85). The sums here are wave reductions, not numpy's left-to-right
+// ones: a common divisor that differs in its last bit moves every probability alike, so the order and (but for a 1e-7 neighbourhood of a
+// threshold) the choice stay -- the host checks every position.
+__device__ __forceinline__ void smp_softmax(const float (&y)[5], int n, int lane, float* __restrict__ pnh) {
+    float e[5];
     float mx = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int c = lane + 64 * k;
-        const bool in = c < n;
-        const float lg = in ? logits[off + c] : 0.f;
-        if (in) ROWS ? log_logits[off + c] = lg : a.log_logits[(size_t)pos * a.vocab + off + c] = lg;
-        y[k] = in ? lg / T : -INFINITY;
-        mx = fmaxf(mx, y[k]);
-    }
+    for (int k = 0; k < 5; ++k) mx = fmaxf(mx, y[k]);
     mx = wave_max(mx);
     float s = 0.f;
 #pragma unroll
@@ -1328,39 +1303,30 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const int c = lane + 64 * k;
-        if (c < SMP_W) pn[h][c] = c < n ? e[k] * inv : -1.f;     // -1 behind the head's classes: never ranked in front of a class
+        if (c < SMP_W) pnh[c] = c < n ? e[k] * inv : -1.f;       // -1 behind the head's classes: never ranked in front of a class
     }
-    __syncthreads();
-    // descending order of the heads with p < 1 by rank counting, one thread per (head, class): ties by class index
-    {
-        int hh = -1, c = t;
-        for (int q = 0; q < 8; ++q) {
-            if (a.p[q] < 1.0f) {
-                if (hh < 0 && c < a.n[q]) hh = q;
-                if (hh < 0) c -= a.n[q];
-            }
-        }
-        if (hh >= 0) {
-            const float v = pn[hh][c];
-            int rank = 0;
-#pragma unroll 17                                              // fixed trip count (the tail holds -1: never in front of a class), four independent LDS reads in flight
-            for (int j4 = 0; j4 < SMP_W / 4; ++j4) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(&pn[hh][4 * j4]);
+}
+// class c's place in the descending order of pnh (ties by class index) -> sph / sih
+__device__ __forceinline__ void smp_rank(const float* __restrict__ pnh, int c, float* __restrict__ sph, int* __restrict__ sih) {
+    const float v = pnh[c];
+    int rank = 0;
+#pragma unroll 17                                                  // fixed trip count (the tail holds -1: never in front of a class), four independent LDS reads in flight
+    for (int j4 = 0; j4 < SMP_W / 4; ++j4) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(&pnh[4 * j4]);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) rank += (w[r] > v || (w[r] == v && 4 * j4 + r < c)) ? 1 : 0;
-            }
-            sp[hh][rank] = v; si[hh][rank] = c;
-        }
-        if (t < 8 * 64) sp[t >> 6][SMP_W + (t & 63)] = 0.f;
+        for (int r = 0; r < 4; ++r) rank += (w[r] > v || (w[r] == v && 4 * j4 + r < c)) ? 1 : 0;
     }
-    __syncthreads();
-    const float ph = a.p[h];
-    if (ph < 1.0f) {                                            // wave-uniform; no barrier below
+    sph[rank] = v; sih[rank] = c;
+}
+// nucleus(ph) of the head with the draw u_draw; the id in every lane. ph is wave-uniform; no barrier inside
+__device__ __forceinline__ int smp_pick(float ph, int n, int lane, double u_draw, const float* __restrict__ pnh, const float* __restrict__ sph,
+                                        const int* __restrict__ sih) {
+    if (ph < 1.0f) {
         // lane l owns sorted entries 5 l .. 5 l + 4 (0 behind the head's classes): prefix sums in sorted order
         float v5[5], pre[5];
         float run = 0.f;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) { const int i = 5 * lane + k; v5[k] = i < n ? sp[h][i] : 0.f; run += v5[k]; pre[k] = run; }
+        for (int k = 0; k < 5; ++k) { const int i = 5 * lane + k; v5[k] = i < n ? sph[i] : 0.f; run += v5[k]; pre[k] = run; }
         const float base = wave_scan_f(run, lane) - run;
         int first = 0x7fffffff;                                  // candidates: up to and including the first cumsum > p; none -> top 1
 #pragma unroll
@@ -1380,22 +1346,132 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         for (int k = 4; k >= 0; --k) if (5 * lane + k < kc && base + pre[k] > thr) best = 5 * lane + k;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
-        if (lane == 0) htok[h] = si[h][best];
-    } else {                                                     // p = 1: the cumsum never exceeds it -> the largest probability (lowest class among equals)
-        float bv = -1.f; int bi = 0x7fffffff;
+        return sih[best];
+    }
+    // p = 1: the cumsum never exceeds it -> the largest probability (lowest class among equals)
+    float bv = -1.f; int bi = 0x7fffffff;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int c = lane + 64 * k;
-            if (c < n) { const float v = pn[h][c]; if (v > bv) { bv = v; bi = c; } }
-        }
+    for (int k = 0; k < 5; ++k) {
+        const int c = lane + 64 * k;
+        if (c < n) { const float v = pnh[c]; if (v > bv) { bv = v; bi = c; } }
+    }
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    return bi;
+}
+template <bool ROWS, bool FORCED>
+__global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKernArgs<ROWS, FORCED>::type a) {
+    __shared__ __attribute__((aligned(16))) float pn[8][SMP_W];     // normalised probabilities, class order
+    __shared__ float sp[8][SMP_W + 64];   // ... in descending order (heads with p < 1), zero tail
+    __shared__ int si[8][SMP_W];          // class of each sorted entry
+    __shared__ int htok[8];
+    const int b = ROWS ? (int)blockIdx.x : 0;
+    if (ROWS && a.st->done[b]) return;                           // block-uniform
+    const int t = threadIdx.x, lane = t & 63, h = t >> 6;
+    const int pos = a.st->pos[b];
+    [[maybe_unused]] int stop0 = 0;                              // head 0's first id that ends the row: requested with done[b] and pos[b]
+    if constexpr (ROWS) stop0 = a.st->stop[b];
+    // time-ordered row (order[b] >= 0, block-uniform): low0 = the first bar head 0 may sample; low1 > 0 = the first position head 1 may
+    // sample IF the token's bar stays prev0 (0: head 1 is free whatever the bar). prev = the row's decoder input, read here, in front of
+    // the first barrier; the last stage overwrites it behind the last one.
+    const int ord = a.st->order[b];
+    int low0 = 0, low1 = 0, prev0 = -1;
+    if (ord >= 0) {
+        const int p0 = a.tok_dev[b * 8 + 0], p1 = a.tok_dev[b * 8 + 1];
+        const bool bar = p0 < a.st->opad[0];                     // an ordinary event: not the SOS row
+        low0 = max(ord, bar ? p0 : 0);
+        if (bar && p1 < a.st->opad[1]) { low1 = p1; prev0 = p0; }
+    }
+    const float* logits = a.logits + (size_t)b * a.vocab;
+    float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
+    const int n = a.n[h], off = a.off[h];
+    const float T = a.temp[h];
+    const double u_draw = a.u[((size_t)b * a.S + pos) * 8 + h];  // requested now: a load that depends on pos would otherwise sit at the end of the chain
+    [[maybe_unused]] int f = -1;                                 // the given id of head t & 7 at this position
+    [[maybe_unused]] int f0 = -1, f1 = -1;                       // ... of heads 0 and 1, in every thread
+    if constexpr (FORCED) {
+        const int16_t* fr = a.force + ((size_t)b * a.S + pos) * 8;
+        const uint4 all = *reinterpret_cast<const uint4*>(fr);   // the 8 entries of the position: 16 bytes, 16-byte aligned
+        f = fr[t & 7];
+        f0 = (int16_t)(all.x & 0xffffu); f1 = (int16_t)(all.x >> 16);
+        if ((((all.x | all.y) | (all.z | all.w)) & 0x80008000u) == 0) {     // all 8 heads given (block-uniform): nothing to sample
+            if constexpr (ROWS) __syncthreads();                 // every thread has read done[b] before it may change
+            if (t < 8) {
+                a.tok_dev[b * 8 + t] = (int16_t)f;
+                a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)f;
+                if constexpr (ROWS) { if (f >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }
+            }
+            return;
         }
-        if (lane == 0) htok[h] = bi;
+    }
+    // y = logit / T of head h's classes; a time-ordered row's bars below low0 get -inf here, so their probability is an exact 0: the
+    // rank count puts them behind every positive class and the p = 1 arg-max never picks one (the largest class has e = 1).
+    float y[5];
+    const int lowh = h == 0 ? low0 : 0;                          // wave-uniform
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int c = lane + 64 * k;
+        const bool in = c < n;
+        const float lg = in ? logits[off + c] : 0.f;
+        if (in) ROWS ? log_logits[off + c] = lg : a.log_logits[(size_t)pos * a.vocab + off + c] = lg;
+        y[k] = (in && c >= lowh) ? lg / T : -INFINITY;
+    }
+    smp_softmax(y, n, lane, pn[h]);
+    __syncthreads();
+    // descending order of the heads with p < 1 by rank counting, one thread per (head, class): ties by class index
+    {
+        int hh = -1, c = t;
+        for (int q = 0; q < 8; ++q) {
+            if (a.p[q] < 1.0f) {
+                if (hh < 0 && c < a.n[q]) hh = q;
+                if (hh < 0) c -= a.n[q];
+            }
+        }
+        if (hh >= 0) smp_rank(pn[hh], c, sp[hh], si[hh]);
+        if (t < 8 * 64) sp[t >> 6][SMP_W + (t & 63)] = 0.f;
     }
     __syncthreads();
+    const float ph = a.p[h];
+    {                                                            // wave h = head h; no barrier inside
+        const int id = smp_pick(ph, n, lane, u_draw, pn[h], sp[h], si[h]);
+        if (lane == 0) htok[h] = id;
+    }
+    __syncthreads();
+    // Time-ordered row, head 1: its mask depends on head 0's id AFTER forcing (b0 == prev0: the token stays in the bar of its
+    // predecessor), which exists only now. Wave 1 therefore samples a second time behind the barrier that published htok[0]. The other
+    // way -- both variants in the first pass, one selected here -- would give the masked variant a ninth wave or a second round of wave 1 at
+    // EVERY position of every ordered row, and rows of pn / sp / si of its own; the second pass is paid only where the mask bites
+    // (same bar, predecessor's position > 0, head 1 not given), runs 134 classes on one wave, and leaves the first pass -- all an
+    // unordered row executes -- as it was. Every condition is block-uniform (BState, tok_dev, the force table, htok[0] behind a barrier),
+    // so the barriers below are reached by all 512 threads or by none. Same draw u[1]: the draws do not move.
+    if (low1 > 0) {
+        int b0 = htok[0];
+        if constexpr (FORCED) { if (f0 >= 0) b0 = f0; }
+        if (b0 == prev0 && f1 < 0) {
+            const bool sorted1 = a.p[1] < 1.0f;
+            if (h == 1) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) if (lane + 64 * k < low1) y[k] = -INFINITY;
+                smp_softmax(y, n, lane, pn[1]);
+            }
+            __syncthreads();
+            if (sorted1) {
+                if (h == 1) {
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) { const int c = lane + 64 * k; if (c < n) smp_rank(pn[1], c, sp[1], si[1]); }
+                }
+                __syncthreads();
+            }
+            if (h == 1) {
+                const int id = smp_pick(ph, n, lane, u_draw, pn[1], sp[1], si[1]);
+                if (lane == 0) htok[1] = id;
+            }
+            __syncthreads();
+        }
+    }
     if (t < 8) {
         int id = htok[t];
         if constexpr (FORCED) { if (f >= 0) id = f; }
@@ -1418,10 +1494,16 @@ __global__ __launch_bounds__(64) void dec_stop_kernel(BState* __restrict__ st, c
     const int t = threadIdx.x;
     if (t < BMAX) st->stop[t] = g.stop[t];
 }
+struct OrderArgs { int order[BMAX]; };
+__global__ __launch_bounds__(64) void dec_order_kernel(BState* __restrict__ st, const OrderArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) st->order[t] = g.order[t];
+}
 struct AdmitArgs {
     BState* st; int16_t* tok_dev;
     int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
     int stop;                                // the new occupant's stop bar (pad[0]: none)
+    int order;                               // ... and its bar floor of time-ordered sampling (-1: a free row)
     int16_t tok[8];
 };
 __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
@@ -1429,7 +1511,7 @@ __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
     if (t < 8) a.tok_dev[b * 8 + t] = a.tok[t];
     if (t == 0) {
         a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
-        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop;
+        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop; a.st->order[b] = a.order;
     }
 }
 
@@ -1473,6 +1555,8 @@ struct Decoder {
     bool live[BMAX] = {};                  // the host has started the row and not ended it (pb_batch_decoder_admit refuses a live row)
     StopArgs stop{};                       // host mirror of the rows' stop bars in BState (pb_batch_decoder_start uploads the whole struct)
     int admit_stop[BMAX] = {};             // pb_batch_decoder_admit_stop: the value the row's next admit stores (-1: none staged -> pad[0])
+    OrderArgs order{};                     // host mirror of the rows' bar floors in BState (-1: a free row), valid behind sampler_init
+    int admit_order[BMAX] = {};            // pb_batch_decoder_admit_order: the value the row's next admit stores (-1: none staged -> a free row)
     hipEvent_t ev_fence = nullptr;
     char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
     size_t stage_bytes = 0;
@@ -1863,9 +1947,12 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->limit, limit, BMAX, D->stream));    // every row; pb_batch_decoder_start may set them one by one
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->stop, pad8[0], BMAX, D->stream));   // no row stops at a bar until pb_batch_decoder_stop says so
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->order, -1, BMAX, D->stream));       // every row is sampled freely until pb_batch_decoder_order says otherwise
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[0], pad8[0], 1, D->stream));
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[1], pad8[1], 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
     D->limit = limit;
-    for (int b = 0; b < BMAX; ++b) { D->stop.stop[b] = pad8[0]; D->admit_stop[b] = -1; }
+    for (int b = 0; b < BMAX; ++b) { D->stop.stop[b] = pad8[0]; D->admit_stop[b] = -1; D->order.order[b] = -1; D->admit_order[b] = -1; }
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
     D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
@@ -1919,6 +2006,25 @@ extern "C" int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar) {
     hipLaunchKernelGGL(dec_stop_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
     PB_LAUNCH_CHECK();
     D->stop = g;
+    return 0;
+}
+
+// Time-ordered sampling (see the header): one bar floor per row (-1: a free row), checked whole on the host before anything changes, then
+// stored in decoder-stream order by a small kernel that takes the values by kernarg, as the stop bars are. Unlike them it reaches the
+// single-row sampler too: a B = 1 run samples on the device, and a kernel that did not know the constraint would be rewound wherever it bites.
+extern "C" int pb_batch_decoder_order(void* dec, const int32_t* floor) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && floor, "pb_batch_decoder_order: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_order: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_order: a step was already issued; the rows' bar floors are set before the run's first step");
+    for (int b = 0; b < D->B; ++b)
+        PB_REQUIRE(floor[b] >= -1 && floor[b] < D->sa.pad[0], "pb_batch_decoder_order: row %d: floor %d outside -1..%d (-1 = not ordered)", b, floor[b],
+                   D->sa.pad[0] - 1);
+    OrderArgs g = D->order;
+    for (int b = 0; b < D->B; ++b) g.order[b] = floor[b];
+    hipLaunchKernelGGL(dec_order_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
+    PB_LAUNCH_CHECK();
+    D->order = g;
     return 0;
 }
 
@@ -1994,7 +2100,9 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
         h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt;
         h.s_enc[b] = D->geo.s_enc[b]; h.ck[b] = D->geo.ck[b]; h.kv_row[b] = D->geo.kv_row[b];
         h.stop[b] = D->stop.stop[b];                                  // as sampler_init / pb_batch_decoder_stop left it (unread without a sampler)
+        h.order[b] = D->sampler ? D->order.order[b] : -1;             // ... / pb_batch_decoder_order
     }
+    h.opad[0] = D->sa.pad[0]; h.opad[1] = D->sa.pad[1];
     for (int b = 0; b < B; ++b) {
         PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
         PB_REQUIRE(!limit || (limit[b] >= 0 && limit[b] <= S), "pb_batch_decoder_start: row %d limit %d outside 0..%d", b, limit[b], S);
@@ -2091,6 +2199,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     AdmitArgs a{};
     a.st = D->st; a.tok_dev = D->tok_dev; a.row = row; a.s_enc = s_enc; a.ck = cross_chunk(D, s_enc); a.slice = slice; a.pos = last_pos; a.limit = limit;
     a.stop = D->admit_stop[row] >= 0 ? D->admit_stop[row] : D->sa.pad[0];    // never the previous occupant's
+    a.order = D->admit_order[row];                                           // -1 unless staged: nor its bar floor
     for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
@@ -2109,6 +2218,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     PB_CHECK_HIP(hipEventRecord(D->stage_ev[e], D->stream));
     D->geo.s_enc[row] = s_enc; D->geo.ck[row] = a.ck; D->geo.kv_row[row] = slice; D->ck_cross[row] = a.ck;
     D->stop.stop[row] = a.stop; D->admit_stop[row] = -1;
+    D->order.order[row] = a.order; D->admit_order[row] = -1;
     D->live[row] = true;
     return 0;
 }
@@ -2122,6 +2232,18 @@ extern "C" int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_
     PB_REQUIRE(stop_bar >= 0 && stop_bar <= D->sa.pad[0], "pb_batch_decoder_admit_stop: row %d: bar %d outside 0..%d (%d = no stop)", row, stop_bar,
                D->sa.pad[0], D->sa.pad[0]);
     D->admit_stop[row] = stop_bar;
+    return 0;
+}
+
+// The bar floor of the prompt the next pb_batch_decoder_admit puts into `row` (see the header). Host state only: the store is the admit's.
+extern "C" int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floor) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit_order: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_admit_order: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit_order: row %d of %d", row, D->B);
+    PB_REQUIRE(floor >= -1 && floor < D->sa.pad[0], "pb_batch_decoder_admit_order: row %d: floor %d outside -1..%d (-1 = not ordered)", row, floor,
+               D->sa.pad[0] - 1);
+    D->admit_order[row] = floor;
     return 0;
 }
 

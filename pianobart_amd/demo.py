@@ -24,7 +24,7 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows'):
+                 precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
@@ -32,6 +32,7 @@ class Args:
         self.keep = keep                    # None or 'ATTR[,ATTR...]': attributes of the piece's own rows behind the prime that are kept (needs prime)
         self.bars = bars                    # None or N: finish the bar the prime ends in, write N whole new bars, stop (eval_generation --bars)
         self.infill, self.infill_mode = infill, infill_mode     # None or 'LO:HI': rewrite bars LO .. HI-1 of the piece (eval_generation --infill; needs a seed)
+        self.ordered = ordered              # time-ordered sampling: no sampled (bar, position) goes back (eval_generation --ordered)
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -63,6 +64,8 @@ def get_args(argv=None):
                     'not with --prime, --keep or --bars)')
     ap.add_argument('--infill_mode', type=str, default='rows', choices=['rows', 'span'], help='the encoder sees a MASK row per row of the region (rows) '
                     'or one MASK row for the whole region (span)')
+    ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
+                    '--infill LO:HI and 0 otherwise')
     return ap.parse_args(argv)
 
 
@@ -154,6 +157,7 @@ def demo(args=None):
     if bars is not None:                     # the row finishes the bar its prime ends in and writes `bars` whole new bars
         from .generation import stop_after_bars
         stops = [stop_after_bars(prefix[0, :ks[0]] if ks is not None else None, bars, pianobart.bar_pad_word)]
+    order = [region[0] if region is not None else 0] if getattr(args, 'ordered', False) else None      # the bar floor: the region's first bar, else 0
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
@@ -161,15 +165,20 @@ def demo(args=None):
             from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
                                      decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples,
-                                     decoder_forced=forced, decoder_stop=stops)
+                                     decoder_forced=forced, decoder_stop=stops, decoder_order=order)
         else:
             y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                      decoder_forced=forced, decoder_stop=stops)
+                      decoder_forced=forced, decoder_stop=stops, decoder_order=order)
     if plan is not None:                     # the rows behind the region go back behind the new ones
         from .generation import infill_splice
         spliced = [infill_splice(row, plan['suffix'], args.max_seq_len, pianobart.bar_pad_word) for row in y.cpu()]
         y = torch.as_tensor(np.stack([r for r, _ in spliced])).to(y.dtype)
         print("Truncated pieces:", sum(int(c) for _, c in spliced))
+        if order is not None:
+            from .generation import is_time_ordered
+            for j, row in enumerate(y):
+                if not is_time_ordered(row, start=plan['k'], floor=order[0]):
+                    raise PBError('--ordered --infill: sample %d is not in time order behind its prime of %d rows' % (j, plan['k']))
     for j, path in enumerate(sample_paths(args.output, samples)):
         if Octuple2Midi(y[j:j + 1], path):
             print(f"Saved to {path}")

@@ -36,6 +36,12 @@ pieces, cut at max_seq_len (the number of truncated pieces is printed). The flag
 it excludes --prime, --keep, --bars and --score_dataset; it combines with --samples, --refill, --score and --pick. --score scores the
 generated row before the splice, with start = the prime length, as a primed row is scored.
 
+Time-ordered sampling (--ordered): no sampled (bar, position) goes back in time (PianoBartLM.generate_batch's decoder_order; DESIGN.md
+section 1, "Time-ordered sampling"). The bar floor is 0 with --prime, --bars or neither, and LO with --infill LO:HI, so no new row of an
+infilled region sounds in front of it; the tool then checks generation.is_time_ordered on every spliced piece from its prime on and raises
+PBError where it fails. Combines with --samples, --refill, --keep (a kept bar or position is given, never reordered), --score and --pick; not
+with --score_dataset. Without the flag the output files are byte-identical to a run of a version without it.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -54,7 +60,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import check_refill, infill_plan, infill_splice, keep_mask, parse_keep, sample_seed, stop_after_bars
+from .generation import check_refill, infill_plan, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -102,6 +108,8 @@ def get_args(argv=None):
                     'in front prime the decoder, the region is a MASK for the encoder, the rows behind are spliced back; needs --seed')
     ap.add_argument('--infill_mode', type=str, default='rows', choices=['rows', 'span'], help='the encoder sees a MASK row per row of the region (rows) '
                     'or one MASK row for the whole region (span)')
+    ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
+                    '--infill LO:HI and 0 otherwise')
     return ap.parse_args(argv)
 
 
@@ -181,6 +189,8 @@ def check_args(args):
             raise PBError('--score_dataset generates nothing: it takes no --infill')
     elif getattr(args, 'infill_mode', 'rows') != 'rows':
         raise PBError('--infill_mode %s needs --infill' % args.infill_mode)
+    if getattr(args, 'ordered', False) and getattr(args, 'score_dataset', False):
+        raise PBError('--score_dataset generates nothing: it takes no --ordered')
     if getattr(args, 'keep', None) is not None:
         parse_keep(args.keep)
         if getattr(args, 'prime', None) is None:
@@ -265,11 +275,13 @@ def eval_generation(args=None):
     keep = parse_keep(args.keep) if getattr(args, 'keep', None) is not None else None
     bars, infill, truncated = getattr(args, 'bars', None), parse_infill(getattr(args, 'infill', None), bar_pad), 0
     pad_word = model.pianobart.pad_word_np
+    floor = (infill[0] if infill is not None else 0) if getattr(args, 'ordered', False) else None       # --ordered: every row's bar floor
 
     def inputs(x):
-        """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars
-        and (--infill) the plans."""
+        """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars,
+        (--infill) the plans and (--ordered) the bar floors."""
         prefix = ks = forced = stops = plans = None
+        order = [floor] * len(x) if floor is not None else None
         if infill is not None:
             plans = [infill_plan(p, infill[0], infill[1], model.pianobart.mask_word_np, pad_word, getattr(args, 'infill_mode', 'rows')) for p in x.numpy()]
             ks, stops = [pl['k'] for pl in plans], [pl['stop'] for pl in plans]
@@ -283,7 +295,7 @@ def eval_generation(args=None):
             x, prefix = prime_inputs(x, ks, pad_word)
         if bars is not None:
             stops = [stop_after_bars(prefix[b, :ks[b]] if ks is not None else None, bars, bar_pad) for b in range(len(x))]
-        return x, prefix, ks, forced, stops, plans
+        return x, prefix, ks, forced, stops, plans, order
 
     def splice(y, plans, own):
         """--infill: row r of y (numpy) spliced with the suffix of its piece own[r]; counts the truncated ones."""
@@ -291,6 +303,8 @@ def eval_generation(args=None):
         for r, p in enumerate(own):
             y[r], cut = infill_splice(y[r], plans[p]['suffix'], args.max_seq_len, bar_pad)
             truncated += int(cut)
+            if floor is not None and not is_time_ordered(y[r], start=plans[p]['k'], floor=floor):
+                raise PBError('--ordered --infill: output row %d is not in time order behind its prime of %d rows' % (r, plans[p]['k']))
         return y
     output = np.zeros((N, args.max_seq_len, 8) if samples == 1 else (N, samples, args.max_seq_len, 8), dtype=np.float32)
     do_score = getattr(args, 'score', False)
@@ -323,11 +337,11 @@ def eval_generation(args=None):
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
-            x, prefix, ks, forced, stops, plans = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
                                      device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
-                                     samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
+                                     decoder_order=order, samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
             own = [i - c0 for i, _ in chunk]
             if do_score:
                 sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
@@ -342,15 +356,15 @@ def eval_generation(args=None):
         gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
         for c0 in range(0, N if samples == 1 else 0, gen_rows):
             c1 = min(N, c0 + gen_rows)
-            x, prefix, ks, forced, stops, plans = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
                 y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                          decoder_forced=forced, decoder_stop=stops)
+                          decoder_forced=forced, decoder_stop=stops, decoder_order=order)
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
-                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
+                                         decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops, decoder_order=order,
                                          refill=(refill or True) if refill is not None else False)
             output[c0:c1] = y.float().cpu().numpy() if plans is None else splice(y.float().cpu().numpy(), plans, list(range(c1 - c0)))
             for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):

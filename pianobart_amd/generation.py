@@ -128,6 +128,70 @@ def check_stop(stop, P, pad0, owner=None):
     return vals if owner is None else [vals[p] for p in owner]
 
 
+def check_order(order, P, owner=None):
+    """The argument rules of time-ordered generation, on the host before any device work. order: P ints (list, array or tensor on any
+    device), one per prompt: -1 = row p is sampled as ever, 0 .. ORDER_MAX = row p is time-ordered with that bar floor (0: ordered, no
+    extra floor). owner (row -> prompt, check_samples): the list is expanded to one entry per output row. Returns a list of ints, P or R
+    long; None for order=None or a list that is -1 everywhere (no order: the caller runs what it ran before). Raises PBError for a
+    wrong length, a non-integer or a value outside -1 .. ORDER_MAX."""
+    if order is None:
+        return None
+    try:
+        vals = order.tolist() if hasattr(order, 'tolist') else list(order)
+    except TypeError:
+        raise PBError('order must be a sequence of %d bar floors, one per prompt (got %r)' % (P, order))
+    if not isinstance(vals, list) or len(vals) != P:
+        raise PBError('order has %d entries for %d prompt(s)' % (len(vals) if isinstance(vals, list) else 1, P))
+    for p, v in enumerate(vals):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise PBError('order[%d] = %r is not an integer' % (p, v))
+        if not -1 <= v <= ORDER_MAX:
+            raise PBError('order[%d] = %d outside -1 .. %d (a bar floor; -1 = not ordered)' % (p, v, ORDER_MAX))
+    if all(int(v) == -1 for v in vals):
+        return None
+    vals = [int(v) for v in vals]
+    return vals if owner is None else [vals[p] for p in owner]
+
+
+ORDER_MAX = 255                    # the last bar id: for heads 0 and 1 the ids ARE the values (Bar k = k, Position k/64 = k in octuple_vocab.json)
+
+
+def ordered_token(frow, sample, floor, prev, pad):
+    """The token of ONE position under the time-ordered contract, for every decode path: the reference's `current_output = self.sample(x,
+    i)` (model.py:46) becomes the ordered sample, followed by forced_token's overwrite of the given heads. floor: the row's bar floor (None
+    or -1: the row is not ordered -- forced_token(frow, sample), nothing else); prev: the 8 ids of the decoder's input row at this position
+    (the SOS row, the prime's last row, else the previous position's token after forcing); pad: the first special id per head.
+    sample(order=(low, prev0, low1, given0)) is the path's own sampling of the position with the mask described by the tuple
+    (PianoBartLM.sample_row): head 0's classes below low = max(floor, prev[0] if ordinary) are impossible; head 1's classes below low1 =
+    prev[1] are impossible if the token's bar after forcing (given0 where forced gives one, else the sample) equals prev0 -- low1 is 0 (no
+    mask) unless prev[0] and prev[1] are both ordinary. Given heads are never masked or changed, and the draws are forced_token's."""
+    if floor is None or int(floor) < 0:
+        return forced_token(frow, sample)
+    p0, p1 = int(prev[0]), int(prev[1])
+    bar = p0 < int(pad[0])
+    low = max(int(floor), p0 if bar else 0)
+    low1 = p1 if bar and p1 < int(pad[1]) else 0
+    given0 = int(frow[0]) if frow is not None else -1
+    return forced_token(frow, lambda: sample(order=(low, p0, low1, given0)))
+
+
+def is_time_ordered(rows, start=0, floor=0):
+    """Whether the emitted rows of a piece are in time order from `start` on (host, numpy). rows (S, 8) Octuple ids; the emitted rows are
+    those in front of the first row whose bar id is special (>= 256: EOS or PAD). True iff the pairs (bar, position) of rows start - 1,
+    start, .. (from row `start` itself for start = 0) are non-decreasing in lexicographic order and every bar of the rows from `start` on
+    is >= floor."""
+    x = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    x = x.astype(np.int64)
+    special = np.flatnonzero(x[:, 0] > ORDER_MAX)
+    e = int(special[0]) if len(special) else len(x)
+    if start >= e:
+        return True
+    if (x[start:e, 0] < floor).any():
+        return False
+    t = x[max(start - 1, 0):e, 0] * 1024 + x[max(start - 1, 0):e, 1]      # position ids stay below 1024
+    return not (np.diff(t) < 0).any()
+
+
 def stop_vector(pad_cpu, s):
     """The 8 thresholds of ONE row's stop test, for every decode path: the reference's `(current_output >= pad).any()` (model.py:47)
     becomes `(current_output >= stop_vector(pad, s)).any()` -- pad with its head 0 lowered to the row's stop bar s, so the one comparison
@@ -317,7 +381,7 @@ def sample_seed(seed, j, i, N):
 
 class GenerationMixin:
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -339,21 +403,28 @@ class GenerationMixin:
         forcing; the token that trips it is not written (result[0, i:] stays PAD) and its draws are consumed; positions below k are not
         tested; max_new and the window still apply. pad[0] (256), or None: no stop, the call without the argument. A call that
         passes `stop` (256 included) finds last_decode['ended']: what ended the row, 'special', 'bar' or 'limit'; a call without the
-        argument leaves the record it always left."""
+        argument leaves the record it always left.
+        order (an int, or a sequence of one; check_order): time-ordered sampling -- the reference loop with `current_output =
+        self.sample(x, i)` replaced by the ordered sample (ordered_token; DESIGN.md section 1, "Time-ordered sampling"): with prev = the
+        decoder's input row at position i, bars below max(order, prev's bar) and, inside prev's bar, positions below prev's position get
+        probability 0. Forcing, the stop test, the draws and what is written are unchanged. `sample_row` must then take the keyword
+        `order` (PianoBartLM.sample_row does). -1, or None: not ordered, the call without the argument."""
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
         forced = check_forced(forced, 1, S, ops.SEG_SIZES, ks)
         stop = check_stop([stop] if isinstance(stop, (int, np.integer)) and not isinstance(stop, bool) else stop, 1, int(self.pb.pad_word_np[0]))
         sb = stop[0] if stop is not None else None
+        order = check_order([order] if isinstance(order, (int, np.integer)) and not isinstance(order, bool) else order, 1)
+        ob = order[0] if order is not None else None
         fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -362,11 +433,12 @@ class GenerationMixin:
             if run.dec is not None:
                 if sampler is not None and _DECODE_SPEC:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
-                    info = self._decode_device_sampled(run.dec, 1, S, lambda b, row: sample_row(row), [np.random.get_state()], sampler,
-                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop)
+                    info = self._decode_device_sampled(run.dec, 1, S, lambda b, row, **kw: sample_row(row, **kw), [np.random.get_state()], sampler,
+                                                       res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop,
+                                                       order=order)
                     info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0], ended=info['ended'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb)
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob)
                 self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()))
                 if not with_ended:
                     del self.last_decode['ended']
@@ -379,13 +451,14 @@ class GenerationMixin:
                 tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
                 logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
                 sv = stop_vector(pad_cpu, sb)
+                prev = pre[k - 1] if k else torch.from_numpy(self.pb.sos_word_np)
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
-                    tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_pin))
+                    tok = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ob, prev, pad_cpu)
                     if (tok >= sv).any():
                         break
-                    res_cpu[0, i] = tok
+                    res_cpu[0, i] = prev = tok
                     tok_pin.copy_(tok)
                     tok16.copy_(tok_pin, non_blocking=True)                     # stream-ordered before the next step's kernels
         return res_cpu.to(enc_ids.device)
@@ -554,10 +627,11 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
         k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
-        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector)."""
+        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
+        (ordered_token; prev is tok_np, the decoder's input)."""
         import ctypes
         sv, ended = stop_vector(pad_cpu, stop), 'limit'
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
@@ -571,7 +645,7 @@ class GenerationMixin:
         for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
-            tok = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logit_cpu))
+            tok = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), order, tok_np, pad_cpu)
             if (tok >= sv).any():
                 ended = end_reason(tok, pad_cpu)
                 break
@@ -584,7 +658,7 @@ class GenerationMixin:
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
     def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
-                       refill=False, stop=None):
+                       refill=False, stop=None, order=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -614,7 +688,12 @@ class GenerationMixin:
         (pb_batch_decoder_stop; a refilled slot gets its row's value with the hand-over, pb_batch_decoder_admit_stop), so a stopped row
         frees its place at once; the host's verification decides, as for every token. None, or pad[0] everywhere: the call without the
         argument. A call that passes `stop` finds last_decode['ended'][b]: 'special', 'bar' or 'limit', for every row of the call; a call
-        without the argument leaves the record it always left."""
+        without the argument leaves the record it always left.
+        order (B ints, check_order): time-ordered sampling, row b under `generate`'s contract with order[b]; -1 = not ordered, so one
+        batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder's device sampler applies the same
+        mask (pb_batch_decoder_order; a refilled slot gets its row's floor with the hand-over, pb_batch_decoder_admit_order), so its
+        prediction holds where the constraint bites; the host's verification decides, as for every token. None, or -1 everywhere: the
+        call without the argument."""
         def done(out, with_ended=stop is not None):      # every path below records `ended`; a call without `stop` keeps the record it had
             if not with_ended and self.last_decode is not None:
                 self.last_decode.pop('ended', None)
@@ -626,6 +705,7 @@ class GenerationMixin:
         forced = check_forced(forced, P, int(enc_ids.shape[1]), ops.SEG_SIZES, ks)
         pad0 = int(self.pb.pad_word_np[0])
         stop = check_stop(stop, P, pad0, owner if samples is not None else None)         # one entry per output row
+        order = check_order(order, P, owner if samples is not None else None)            # ... and here
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -634,10 +714,10 @@ class GenerationMixin:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop))
-            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop))
+                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order))
+            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order))
         if slots and R > slots:
-            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop)
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order)
             if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
                 return done(out)
         outs, ended = [], []
@@ -645,41 +725,45 @@ class GenerationMixin:
             own = owner[c0:c0 + self.BATCH_MAX]
             st = stop[c0:c0 + len(own)] if stop is not None else None
             st = st if st is not None and any(v != pad0 for v in st) else None     # a chunk without a real stop is today's chunk
+            od = order[c0:c0 + len(own)] if order is not None else None
+            od = od if od is not None and any(v != -1 for v in od) else None       # ... and one without an ordered row
             p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
             outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
                                                    groups=[p - p0 for p in own] if samples is not None else None,
-                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st))
+                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st, order=od))
             ended += (self.last_decode or {}).get('ended') or [None] * len(own)
         if len(outs) > 1 and self.last_decode is not None:                # last_decode describes the last chunk; `ended` covers every row
             self.last_decode['ended'] = ended
         return done(torch.cat(outs, 0))
 
-    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None):
+    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None, order=None):
         """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt. stop: one
-        entry per ROW (check_stop expands it), or None."""
+        entry per ROW (check_stop expands it), or None; order likewise (check_order)."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
                                          max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
-                                         forced[idx.numpy()] if forced is not None else None, stop)
+                                         forced[idx.numpy()] if forced is not None else None, stop, order)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None):
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None, order=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
         caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
-        checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None."""
+        checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None; order: one bar floor per row
+        (check_order) or None."""
         saved = np.random.get_state()
         outs, ended, pad0 = [], [], int(self.pb.pad_word_np[0])
         try:
             for b in range(int(enc_ids.shape[0])):
                 np.random.set_state(rngs[b].get_state())
                 pre = rows[b:b + 1, :ks[b]] if rows is not None and ks[b] else None
-                outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r: sample_row(r, None),
+                outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r, **kw: sample_row(r, None, **kw),
                                           max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None,
-                                          stop=stop[b] if stop is not None else pad0))        # 256: no stop, and the row's `ended`
+                                          stop=stop[b] if stop is not None else pad0,         # 256: no stop, and the row's `ended`
+                                          order=order[b] if order is not None else None))
                 ended.append((self.last_decode or {}).get('ended'))
                 rngs[b].set_state(np.random.get_state())
         finally:
@@ -687,22 +771,24 @@ class GenerationMixin:
         self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended)
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None):
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None, order=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
-        loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None."""
+        loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None;
+        order: one bar floor per ROW, or None."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
-            info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row: sample_row(row, rngs[b]), [r.get_state() for r in rngs], sampler,
-                                               run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
-                                               forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop)
+            info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row, **kw: sample_row(row, rngs[b], **kw), [r.get_state() for r in rngs],
+                                               sampler, run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
+                                               forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop,
+                                               order=order)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None):
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None):
         """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
         waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
         in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
@@ -713,7 +799,8 @@ class GenerationMixin:
         SLOT: an occupant's log rows are read before the next one is admitted) and rewinds a row alone. Each row's draws are made at its
         admission from a copy of rngs[r] (forced_draws). stop (R stop bars or None): the first n rows' values go up as a chunk's do
         (pb_batch_decoder_stop), a later row's is staged in front of its admission (pb_batch_decoder_admit_stop); a row without a stop
-        stages nothing and its slot gets pad[0], never the previous occupant's value. Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        stages nothing and its slot gets pad[0], never the previous occupant's value. order (R bar floors or None) travels the same way
+        (pb_batch_decoder_order, pb_batch_decoder_admit_order; a free row stages nothing and its slot gets -1). Returns the (R, S, 8) result, or None -- before any encoder work -- where
         pb_batch_decoder_create declines the shape."""
         R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
@@ -729,11 +816,11 @@ class GenerationMixin:
                 return None
             try:
                 return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
-                                        pad_cpu, stop).to(dev)
+                                        pad_cpu, stop, order).to(dev)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
-    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None):
+    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None, order=None):
         """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
         import ctypes
         from collections import deque
@@ -804,6 +891,9 @@ class GenerationMixin:
         ended = ['limit'] * R
         if stop is not None and any(v != pad0 for v in stop[:n]):
             LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop[:n], dtype=np.int32).ctypes.data)
+        if order is not None and any(v != -1 for v in order[:n]):
+            LIB.call('pb_batch_decoder_order', dec, np.asarray(order[:n], dtype=np.int32).ctypes.data)
+        sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (n * S * vocab)).from_address(lp.value)).reshape(n, S, vocab))
@@ -852,6 +942,8 @@ class GenerationMixin:
                 fr = np.ascontiguousarray(forced[r]) if forced is not None and (forced[r] != -1).any() else None
                 if stop is not None and stop[r] != pad0:                   # stored by the admit's kernel, with the row's position and done = 0
                     LIB.call('pb_batch_decoder_admit_stop', dec, s, stop[r])
+                if order is not None and order[r] != -1:                   # likewise; a free successor of an ordered row gets -1
+                    LIB.call('pb_batch_decoder_admit_order', dec, s, order[r])
                 LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
                          fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
                 counts['admissions'] += 1
@@ -880,7 +972,8 @@ class GenerationMixin:
 
         def verify(s, r, a, e):                    # positions a .. e-1 of row r in slot s, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(a, e):
-                tok = forced_token(forced[r, i] if forced is not None else None, lambda: sample_row(log_logits[s, i], rngs[r]))
+                tok = ordered_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
+                                    order[r] if order is not None else None, res_cpu[r, i - 1] if i else sos, pad_cpu)
                 tokens[r] += 1
                 if (tok >= svs[r]).any():
                     ended[r] = end_reason(tok, pad_cpu)
@@ -933,7 +1026,8 @@ class GenerationMixin:
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
         return res_cpu
 
-    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None):
+    def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None,
+                               order=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -954,7 +1048,11 @@ class GenerationMixin:
         stop (B stop bars, check_stop) or None: the values go to the device sampler behind sampler_init and force (pb_batch_decoder_stop: its
         done test of head 0 then compares against the row's bar) and the host's stop test uses the row's stop_vector. The device's done
         flag stays a prediction: where it stopped a row the host does not stop, or the other way round, the tokens differ and the rewind
-        below handles it. Returns `ended` per row: 'special', 'bar' or 'limit', as the host decided."""
+        below handles it. Returns `ended` per row: 'special', 'bar' or 'limit', as the host decided.
+        order (B bar floors, check_order) or None: the values go to the device sampler too (pb_batch_decoder_order: it masks heads 0 and 1
+        against the row's decoder input on the device) and the host samples every position through ordered_token, with prev = the row's
+        previous result row (the prefix's last row at k_b, the SOS row at 0). A device that ignored the mask would be rewound wherever it
+        bites; one that applies it differs from the host as rarely as the unordered sampler does."""
         import contextlib
         import ctypes
         from collections import deque
@@ -980,6 +1078,9 @@ class GenerationMixin:
         ended = ['limit'] * B
         if stop is not None:
             LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop, dtype=np.int32).ctypes.data)
+        if order is not None:
+            LIB.call('pb_batch_decoder_order', dec, np.asarray(order, dtype=np.int32).ctypes.data)
+        sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
         log_logits = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * (B * S * vocab)).from_address(lp.value)).reshape(B, S, vocab))
@@ -1013,7 +1114,8 @@ class GenerationMixin:
 
         def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(s, e):
-                tok = forced_token(forced[b, i] if forced is not None else None, lambda: sample(b, log_logits[b, i]))
+                tok = ordered_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
+                                    order[b] if order is not None else None, res_cpu[b, i - 1] if i else sos, pad_cpu)
                 tokens[b] += 1
                 if (tok >= svs[b]).any():
                     ended[b] = end_reason(tok, pad_cpu)
@@ -1054,12 +1156,12 @@ class GenerationMixin:
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
                     device_sampler=True, tokens_per_graph_replay=K, ended=ended)
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
         rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
         fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads.
-        stop: the row's stop bar or None (stop_vector)."""
+        stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None (ordered_token; prev is `cur`, the step's input)."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
@@ -1111,17 +1213,19 @@ class GenerationMixin:
                 frow = fr[i] if fr is not None else None
                 if frow is None or (frow < 0).any():
                     ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
-                tok = forced_token(frow, lambda: sample_row(logits[0].cpu()))
+                tok = ordered_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), order,
+                                    cur.reshape(8).cpu() if order is not None else None, pad_cpu)
                 if (tok >= sv).any():
                     break
                 result[:, i, :] = tok.to(dev)
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
         cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
-        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector)."""
+        fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
+        (ordered_token; prev is decoder input i, which the loop wrote at i - 1)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -1144,7 +1248,8 @@ class GenerationMixin:
                 dec16 = ops.ids_to_i16(dec)
                 dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
                 logits = self.heads_forward(dec_h)
-                cur = forced_token(fr[i] if fr is not None else None, lambda: sample_row(logits[i].float().cpu()))
+                cur = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), order,
+                                    dec[0, i].cpu() if order is not None else None, pad_cpu)
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)
                     dmask[:, i + 1] += 1

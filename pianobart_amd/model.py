@@ -344,7 +344,8 @@ class PianoBartLM(nn.Module):
         return self._engine
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
-                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None):
+                decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None,
+                decoder_order=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
         position k on (Engine.generate's `prefix`).
         decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
@@ -357,7 +358,13 @@ class PianoBartLM(nn.Module):
         decoder_stop (a bar id 0 .. 256, or a sequence of one; generate=True only): stop at a bar -- the reference loop with its stop test
         `(current_output >= pad).any()` replaced by `(current_output >= pad).any() or current_output[0] >= decoder_stop`. The test sees the
         token after forcing; the token that trips it is not written and its draws are consumed; positions inside decoder_prefix are not
-        tested (generation.stop_after_bars turns "n more bars" into the bar id). 256 (the bar head's PAD id), or None: no stop."""
+        tested (generation.stop_after_bars turns "n more bars" into the bar id). 256 (the bar head's PAD id), or None: no stop.
+        decoder_order (-1 .. 255, or a sequence of one; generate=True only): time-ordered sampling -- the reference loop with `current_output
+        = self.sample(x, i)` replaced by a sample whose (bar, position) never goes back. With prev = the decoder's input row of position i
+        (the SOS row, the prefix's last row, else the previous token after forcing): bars below max(decoder_order, prev's bar) have
+        probability 0, and so have positions below prev's position while the bar (after forcing) stays prev's. Special ids stay
+        reachable, heads 2 .. 7 and given heads are untouched, and the draws are those of the unordered call. 0 = ordered without an
+        extra bar floor; -1, or None: not ordered. DESIGN.md section 1, "Time-ordered sampling"."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
@@ -366,6 +373,8 @@ class PianoBartLM(nn.Module):
                 raise PBError('decoder_forced gives tokens of a generated piece: it needs generate=True')
             if decoder_stop is not None:
                 raise PBError('decoder_stop ends a generated piece at a bar: it needs generate=True')
+            if decoder_order is not None:
+                raise PBError('decoder_order constrains what a generated piece samples: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             return [logits[..., ops.SEG_OFF[i]:ops.SEG_OFF[i + 1]] for i in range(8)]
@@ -373,13 +382,13 @@ class PianoBartLM(nn.Module):
             print("ERROR")
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
-                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop)
+                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
                        decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False,
-                       decoder_stop=None):
+                       decoder_stop=None, decoder_order=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -398,7 +407,10 @@ class PianoBartLM(nn.Module):
         they stop (Engine.generate_batch's `refill`); the result is that of refill=False. Not with samples_per_prompt.
         decoder_stop (B bar ids 0 .. 256): prompt b under forward(generate=True, decoder_stop=...)'s contract with its own bar; 256 = no
         stop, so one batch may mix both. With samples_per_prompt it describes the P prompts. The fused decoder's device sampler makes the
-        test too, so a stopped row leaves the batch (or frees its slot under refill) at once."""
+        test too, so a stopped row leaves the batch (or frees its slot under refill) at once.
+        decoder_order (B ints -1 .. 255): prompt b under forward(generate=True, decoder_order=...)'s contract with its own bar floor; -1 = not
+        ordered, so one batch may mix both. With samples_per_prompt it describes the P prompts. The fused decoder's device sampler
+        applies the same mask, so an ordered batch keeps the batched decode's launches per step and its rewind rate."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -415,7 +427,7 @@ class PianoBartLM(nn.Module):
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
-                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop)
+                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):
@@ -443,17 +455,23 @@ class PianoBartLM(nn.Module):
     SAMPLE_T =[1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
-    def sample_row(self, row_logits, rng=None):
+    def sample_row(self, row_logits, rng=None, order=None):
         """row_logits: (1280,) f32 CPU tensor of one position; returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
         on the host row -- the division by the temperature (one call with a per-element temperature vector: the same quotients) and a
         1-D softmax per head -- then nucleus() for all 8 heads in one native call (pb_nucleus_rows: numpy's arithmetic order and
         precision; ties among candidates go back to the numpy code), fed the 8 uniform draws np.random.choice would have made. Checked
         draw for draw and RNG state for RNG state against sampling() in tests/test_model_cpu.py. 0.31 -> 0.1 ms of host time per
         generated position, which sits in series with the GPU's ~0.3 ms. rng: a numpy RandomState to draw the 8 uniforms from instead of
-        the global stream (generate_batch: one generator per prompt)."""
+        the global stream (generate_batch: one generator per prompt).
+        order = (low, prev0, low1, given0) (generation.ordered_token), or None: the time-ordered sample. The quotients of head 0's
+        classes below `low` are set to -inf in front of the softmax (probability exactly 0). If low1 > 0 and head 0's id after forcing
+        (given0 if >= 0, else the id just sampled) equals prev0, head 1's classes below low1 are masked the same way and head 1 is sampled
+        again with the same u[1]. One random_sample(8) either way; without `order` the arithmetic and the native call are unchanged."""
         tab = _sample_tables()
         y = row_logits / tab['tvec']
         probs = tab['probs']
+        if order is not None and order[0] > 0:
+            y[ops.SEG_OFF[0]:ops.SEG_OFF[0] + order[0]] = -np.inf
         for j in range(8):                                           # 1-D calls: a 2-D softmax would open an OpenMP region per position
             torch.softmax(y[ops.SEG_OFF[j]:ops.SEG_OFF[j + 1]], dim=-1, out=probs[j, :tab['n'][j]])
         # the 8 draws np.random.choice would make, in head order (RandomState fills a request sequentially: the same stream as 8 calls)
@@ -465,6 +483,14 @@ class PianoBartLM(nn.Module):
             for j in range(8):
                 if tie[0] >> j & 1:
                     out[j] = _nucleus_with_draw(pn[j, :tab['n'][j]], self.SAMPLE_P[j], u[j])
+        if order is not None and order[2] > 0 and (order[3] if order[3] >= 0 else int(out[0])) == order[1]:
+            # the token stays in its predecessor's bar: head 1 again, from the masked quotients, with the draw it had (the other rows of
+            # `probs` are untouched, so their ids come out as they did)
+            y[ops.SEG_OFF[1]:ops.SEG_OFF[1] + order[2]] = -np.inf
+            torch.softmax(y[ops.SEG_OFF[1]:ops.SEG_OFF[2]], dim=-1, out=probs[1, :tab['n'][1]])
+            head1 = out.copy()
+            LIB.call('pb_nucleus_rows', probs.data_ptr(), probs.shape[1], tab['n_p'], tab['p_p'], u.ctypes.data, 8, head1.ctypes.data, tie.ctypes.data)
+            out[1] = _nucleus_with_draw(probs.numpy()[1, :tab['n'][1]], self.SAMPLE_P[1], u[1]) if tie[0] >> 1 & 1 else head1[1]
         return torch.from_numpy(out.astype(np.int64))
 
     def sample(self, x, index):

@@ -4,10 +4,14 @@ positions). Prints ONE JSON line: per B in --batches, aggregate tokens/s, ms per
 verification ms per step and an HBM-bytes estimate per step (decoder + LM-head weights once, plus each row's cross K/V over its visible
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
-    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]] [--bars N]
+    python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]] [--bars N] [--ordered]
 
 --keep pitch,velocity: forced tokens -- the named attributes of synthetic pieces are given at every position (generation.keep_mask) and the
 model samples the others, at the largest B of --batches: ms per step and rewinds per row, beside the unforced run of the same process.
+
+--ordered: time-ordered sampling -- the same prompts and seeds with and without the constraint (order = 0 for every row) at the largest B of
+--batches, in this process: ms per step and rewinds per row for both, and at how many positions per row the unordered run goes back in
+time (where a device sampler that did not know the constraint would be rewound).
 
 --samples n: n samples of ONE prompt instead. Three runs alternate in this process, --reps times: "grouped" (samples=n: one encoder pass,
 one (1, S, 2d) cross cache per layer, the grouped cross-attention kernel), "indirect" (the same with PB_DECODE_CROSS_GROUPED=0: the per-row
@@ -61,6 +65,8 @@ def main(argv=None):
     ap.add_argument('--log', type=str, default=os.path.join(ROOT, 'profiles', 'refill_b16.jsonl'), help='--refill: the file the lines are appended to')
     ap.add_argument('--bars', type=int, default=None, metavar='N', help='time bar-bounded generation (N new bars per primed row), refilled and chunked, '
                     'against the same prompts decoded without the stop and cut afterwards')
+    ap.add_argument('--ordered', action='store_true', help='also time time-ordered generation at the largest batch, beside the unordered run of the same '
+                    'prompts and seeds')
     ap.add_argument('--bars_log', type=str, default=os.path.join(ROOT, 'profiles', 'bar_stop_b16.jsonl'), help='--bars: the file the lines are appended to')
     args = ap.parse_args(argv)
 
@@ -354,6 +360,25 @@ def main(argv=None):
                            tokens=sum(info['tokens']), launches_per_step=info['launches_per_token'], graph=info['graph'],
                            host_ms_per_step=info['host_ms'] / max(1, info['steps']))
         out['forced'] = dict(keep=args.keep, batch=B, **by)
+    if args.ordered:
+        # time-ordered sampling: every row with floor 0; same launches per step, the sampler masks heads 0 and 1 on the device
+        from pianobart_amd.generation import is_time_ordered
+        B = Bmax
+        by, ys = {}, {}
+        for tag, order in (('unordered', None), ('ordered', [0] * B)):
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=16, sampler=sampler, order=order)     # warm-up (capture)
+            torch.cuda.synchronize()
+            rngs = [np.random.RandomState(b) for b in range(B)]
+            ys[tag] = eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=steps, sampler=sampler, order=order).cpu().numpy()
+            torch.cuda.synchronize()
+            info = eng.last_decode
+            by[tag] = dict(ms_per_step=info['loop_ms'] / max(1, info['steps']), rewinds_per_row=sum(info['rewinds']) / B, steps=info['steps'],
+                           tokens=sum(info['tokens']), launches_per_step=info['launches_per_token'], graph=info['graph'],
+                           host_ms_per_step=info['host_ms'] / max(1, info['steps']),
+                           rows_in_time_order=sum(bool(is_time_ordered(ys[tag][b])) for b in range(B)))
+        t = ys['unordered'][:, :steps, 0].astype(np.int64) * 1024 + ys['unordered'][:, :steps, 1].astype(np.int64)
+        out['ordered'] = dict(batch=B, positions_going_back_per_row_unordered=float((np.diff(t, axis=1) < 0).sum() / B), **by)
     print(json.dumps(out), flush=True)
 
 
