@@ -347,7 +347,8 @@ int64_t pb_corrupt_replay_stride(int32_t S);
  * pb_eltwise_bwd: dx = dy * mask * act'(.) with the derivative taken from the PRE-dropout output `y` (op 5: y = x, also dx2).
  * pb_softmax_dim1_*: F.softmax(x, dim=1) of x (B, S, R) and its backward (model.py:140).
  * pb_ce_rows: loss[row] = CrossEntropy(logits[row, :C], target[row]) (reduction='none'), argmax[row] (first maximum, may be
- *   NULL) and, if dlogits != NULL, dlogits = (softmax - onehot) * coef[0] * weight[row] (weight / coef may be NULL = 1). */
+ *   NULL) and, if dlogits != NULL, dlogits = (softmax - onehot) * coef[0] * weight[row] (weight / coef may be NULL = 1).
+ *   A target outside [0, C) (nn.CrossEntropyLoss's ignore_index = -100) gives loss 0 and an all-zero dlogits row; argmax is written. */
 int pb_eltwise_fwd(int32_t op, const float* x, const float* x2, float* y, int64_t n, uint64_t seed, uint32_t site, float p_drop, void* stream);
 int pb_eltwise_bwd(int32_t op, const float* y, const float* x2, const float* dy, float* dx, float* dx2, int64_t n, uint64_t seed,
                    uint32_t site, float p_drop, void* stream);

@@ -109,6 +109,7 @@ __global__ __launch_bounds__(64) void softmax_dim1_bwd_kernel(const float* __res
 
 // nn.CrossEntropyLoss(reduction='none') on rows of C <= 1024 classes + its gradient scaled by coef[0] * weight[row]:
 // loss[row] = logsumexp - logit[target]; dlogits = (softmax - onehot) * w. One wave per row. argmax (first maximum) too.
+// A target outside [0, C) (the loss's ignore_index = -100) is a row without loss: loss 0 AND an all-zero gradient row; argmax is still written.
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ target, const float* __restrict__ weight,
                                                      const float* __restrict__ coef, float* __restrict__ loss, float* __restrict__ dlogits,
                                                      int32_t* __restrict__ argmax, long rows, int C) {
@@ -126,15 +127,16 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     for (int c = lane; c < C; c += 64) sum += __expf(lr[c] - wm);
     sum = wave_sum(sum);
     const int t = target[row];
+    const bool valid = t >= 0 && t < C;
     const float w = (weight ? weight[row] : 1.0f);
     if (lane == 0) {
-        loss[row] = (t >= 0 && t < C) ? (wm + __logf(sum) - lr[t]) : 0.f;
+        loss[row] = valid ? (wm + __logf(sum) - lr[t]) : 0.f;
         if (argmax) argmax[row] = cand;
     }
     if (dlogits) {
         const float k = (coef ? coef[0] : 1.0f) * w / sum;
         const float kt = (coef ? coef[0] : 1.0f) * w;
-        for (int c = lane; c < C; c += 64) dlogits[row * C + c] = __expf(lr[c] - wm) * k - (c == t ? kt : 0.f);
+        for (int c = lane; c < C; c += 64) dlogits[row * C + c] = valid ? __expf(lr[c] - wm) * k - (c == t ? kt : 0.f) : 0.f;
     }
 }
 

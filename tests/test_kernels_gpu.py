@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.philox_ref import drop_mask
+
 pytestmark = pytest.mark.gpu
 
 
@@ -116,16 +118,18 @@ def test_add_ln_fwd_bwd(ops, dt, d, p):
     mean = torch.empty(T, device='cuda'); rstd = torch.empty(T, device='cuda')
     seed, site = 1234567, 5
     ops.add_ln_fwd(res, a, w, b, y, mean, rstd, 1e-5, seed, site, p)
-    # recover the dropout mask by running the same site on (0, ones) with identity LN statistics
+    # the dropout mask is the Philox stream of the host reference (tests/philox_ref.py); the kernel's own mask, recovered by running the
+    # same site on (0, ones) with identity LN statistics, must be that one
     if p > 0:
         ones = torch.ones(T, d, device='cuda', dtype=dt); zeros = torch.zeros_like(ones)
         y1 = torch.empty_like(ones); m1 = torch.empty(T, device='cuda'); r1 = torch.empty(T, device='cuda')
         ops.add_ln_fwd(zeros, ones, torch.ones(d, device='cuda'), torch.zeros(d, device='cuda'), y1, m1, r1, 1e-5, seed, site, p)
         # z = mask/(1-p); y1 = (z-mean)*rstd  -> z = y1/rstd + mean
         z = y1.float() / r1[:, None] + m1[:, None]
-        mask = (z > 0.5).double() / (1 - p)
-        frac = float((mask == 0).double().mean())
+        frac = float((z <= 0.5).double().mean())
         assert abs(frac - p) < 0.01
+        mask = torch.from_numpy(drop_mask(seed, site, p, T * d)).cuda().reshape(T, d).double()
+        assert torch.equal(z > 0.5, mask != 0)
     else:
         mask = torch.ones(T, d, device='cuda', dtype=torch.double)
     rd = res.double().requires_grad_(True); ad = a.double().requires_grad_(True)
@@ -878,3 +882,113 @@ def test_flash_attention_x3_two_tiles_per_wave_changes_no_bit(ops, hd, causal):
     for b in range(B):
         o1, l1, g1 = run(qkv[b:b + 1].contiguous(), km[b:b + 1].contiguous(), dout[b:b + 1].contiguous(), 1)
         assert torch.equal(o1[0], out[b]) and torch.equal(l1[0], lse[b]) and torch.equal(g1[0], dqkv[b]), b
+
+
+@pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('N', [4, 252, 256, 260, 1280])
+@pytest.mark.parametrize('T', [0, 1, 63, 64, 65, 301, 8193])
+def test_colsum(ops, T, N, dt):
+    """pb_colsum (every bias gradient of the step): out += column sums of the stored values, against float64. One row block per 64 rows up to
+    128 of them (T = 65: blocks of 33 and 32 rows; 8193: 128 blocks of 65 = four trips of the 16-row unrolled loop and one of its 4-row
+    remainder per wave), a lane per 4 columns (N = 252 / 260: a ragged last column block). Accumulates; deterministic; T = 0 is a no-op."""
+    g = torch.Generator(device='cuda').manual_seed(T * 3 + N)
+    dy = torch.randn(T, N, device='cuda', generator=g).to(dt)
+    out0 = 0.5 + 0.01 * torch.arange(N, device='cuda', dtype=torch.float32)
+    partials = torch.empty(int(ops.LIB.query('pb_colsum_partials_floats', N)), device='cuda')
+    runs = []
+    for _ in range(2):
+        out = out0.clone()
+        ops.colsum(dy, out, partials, T, N)
+        runs.append(out)
+    assert torch.equal(runs[0], runs[1])
+    if T == 0:
+        assert torch.equal(runs[0], out0)
+    assert _rel(runs[0], out0.double() + dy.double().sum(0)) < 2e-5
+
+
+@pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16])
+def test_colsum_of_a_column_slice(ops, dt):
+    """ld > N: the sums of a column slice of a wider matrix, as the engine takes a layer's K | V bias gradient out of the stacked projection.
+    The slice starts 8 columns in and its neighbours hold 1e6; the output vector is in turn not 16-byte aligned."""
+    from pianobart_amd._lib import PBError
+    T, N, W, off = 301, 252, 272, 8
+    g = torch.Generator(device='cuda').manual_seed(1)
+    wide = torch.full((T, W), 1e6, device='cuda', dtype=dt)
+    wide[:, off:off + N] = torch.randn(T, N, device='cuda', generator=g).to(dt)
+    view = wide[:, off:off + N]
+    partials = torch.empty(int(ops.LIB.query('pb_colsum_partials_floats', N)), device='cuda')
+    for shift in (0, 1):
+        buf = torch.full((N + 4,), 0.25, device='cuda')
+        out = buf[shift:shift + N]
+        ops.colsum(view, out, partials, T, N, ld=W)
+        assert _rel(out, 0.25 + view.double().sum(0)) < 2e-5
+        assert bool((buf[shift + N:] == 0.25).all()) and bool((buf[:shift] == 0.25).all())
+    out = torch.full((8,), 0.25, device='cuda')
+    with pytest.raises(PBError, match='pb_colsum'):                      # N = 6 is no multiple of 4: refused before any launch
+        ops.colsum(wide, out, partials, T, 6, ld=W)
+    torch.cuda.synchronize()
+    assert bool((out == 0.25).all())
+
+
+@pytest.mark.parametrize('n', [1, 3, 1023, 1025, 262144 + 1030])
+def test_l2_penalty_kernel(ops, n):
+    """pb_l2_penalty on its own: loss_acc += w * ||p||, g += w * p / ||p|| against float64, on views 1 and 3 floats into their buffers
+    ("any alignment"), accumulating onto non-zero values, with either output absent, for an all-zero p (adds exactly nothing) and n = 0.
+    The last n is beyond 256 blocks x 1024 elements: both kernels stride."""
+    g_ = torch.Generator(device='cuda').manual_seed(n)
+    w = 0.37
+    p = torch.randn(n + 8, device='cuda', generator=g_)[1:1 + n]
+    g0 = torch.randn(n + 8, device='cuda', generator=g_)
+    scratch = torch.empty(int(ops.LIB.query('pb_l2_penalty_scratch_floats')), device='cuda')
+    nrm = p.double().norm()
+    loss_ref = 2.5 + w * float(nrm)
+    g_ref = g0[3:3 + n].double() + w * p.double() / nrm
+
+    def run(p_, with_g=True, with_loss=True):
+        gbuf = g0.clone(); loss = torch.tensor([2.5], device='cuda')
+        ops.l2_penalty(p_, gbuf[3:3 + n] if with_g else None, w, scratch, loss if with_loss else None)
+        assert torch.equal(gbuf[:3], g0[:3]) and torch.equal(gbuf[3 + n:], g0[3 + n:])
+        return gbuf[3:3 + n], float(loss)
+    g, loss = run(p)
+    assert _rel(g, g_ref) < 2e-5 and abs(loss - loss_ref) / loss_ref < 1e-6
+    g, loss = run(p, with_g=False)                                        # value only
+    assert torch.equal(g, g0[3:3 + n]) and abs(loss - loss_ref) / loss_ref < 1e-6
+    g, loss = run(p, with_loss=False)                                     # gradient only
+    assert _rel(g, g_ref) < 2e-5 and loss == 2.5
+    g, loss = run(torch.zeros(n + 8, device='cuda')[1:1 + n])             # ||p|| = 0: torch's norm backward gives 0
+    assert torch.equal(g, g0[3:3 + n]) and loss == 2.5
+    gbuf = g0.clone(); lacc = torch.tensor([2.5], device='cuda')          # n = 0 with valid pointers
+    ops.LIB.call('pb_l2_penalty', ops._p(p), ops._p(gbuf), 0, w, ops._p(scratch), ops._p(lacc), ops._stream())
+    assert torch.equal(gbuf, g0) and float(lacc) == 2.5
+
+
+def test_ids_check_kernel(ops):
+    """pb_ids_check on its own: clean ids raise no flag and stay; an id at or beyond its column's limit, or -1 (what ids_to_i16 leaves of a
+    value that is no int16), raises the flag and becomes 0, every other entry stays; the flag is only ever ORed into."""
+    from pianobart_amd._lib import PBError
+    g = torch.Generator(device='cuda').manual_seed(6)
+    T = 1000
+    ids = torch.stack([torch.randint(0, n, (T,), device='cuda', generator=g) for n in ops.SEG_SIZES], dim=1)
+    ids[5, 0], ids[T - 1, 7] = ops.SEG_SIZES[0] - 1, ops.SEG_SIZES[7] - 1  # the largest valid ids
+    limits = torch.tensor(ops.SEG_SIZES, dtype=torch.int32, device='cuda')
+    flag = torch.zeros(1, dtype=torch.int32, device='cuda')
+    ids16 = ops.ids_to_i16(ids)
+    ops.ids_check(ids16, limits, flag)
+    assert int(flag) == 0 and torch.equal(ids16.long(), ids)
+    assert ops.ids_to_i16(torch.tensor([40000, -5, 32767], device='cuda')).tolist() == [-1, -1, 32767]
+    planted = {(0, 0): -1, (10, 0): ops.SEG_SIZES[0], (500, 7): ops.SEG_SIZES[7] + 5, (T - 1, 3): -1, (T - 1, 7): ops.SEG_SIZES[7],
+               (T - 1, 0): ops.SEG_SIZES[0] + 5, (321, 5): ops.SEG_SIZES[5]}
+    bad = ids16.clone()
+    want = ids.clone()
+    for (t, c), v in planted.items():
+        bad[t, c] = v
+        want[t, c] = 0
+    ops.ids_check(bad, limits, flag)
+    assert int(flag) == 1 and torch.equal(bad.long(), want)
+    ops.ids_check(ids16, limits, flag)                                    # a clean call never lowers a raised flag
+    assert int(flag) == 1 and torch.equal(ids16.long(), ids)
+    flag.zero_()
+    short = ids16.reshape(-1)[:12].clone()
+    with pytest.raises(PBError, match='pb_ids_check'):                   # 12 ids are no whole tokens
+        ops.ids_check(short, limits, flag)
+    assert int(flag) == 0 and torch.equal(short, ids16.reshape(-1)[:12])
