@@ -148,6 +148,10 @@ int pb_add_ln_bwd_packed(const void* dy, const void* res, const void* a, const f
 int64_t pb_colsum_partials_floats(int32_t N);
 int pb_colsum(const void* dy, int64_t ld, float* out, float* partials, int32_t T, int32_t N, int32_t dtype,
               int32_t src_f32, void* stream);
+/* pb_colsum for any N and ld (an addition to ABI 10; pb_colsum itself needs multiples of 4: a lane owns 4 adjacent columns): a thread
+ * owns one column. The head-bias gradient of a dictionary whose vocabulary total is no multiple of 4. Same workspace, accumulates alike. */
+int pb_colsum_any(const void* dy, int64_t ld, float* out, float* partials, int32_t T, int32_t N, int32_t dtype,
+                  int32_t src_f32, void* stream);
 
 /* ---- K4 (unfused form, both dtypes): masked softmax over key axis -------------------------------
  * scores (B,H,Sq,Sk) f32 = q.k^T (unscaled); P = softmax(scale*scores + mask); a query row with no
@@ -270,7 +274,8 @@ int pb_loss_coef(const float* counts, const float* w /*device 8*/, float* coef, 
  *   rank    int16 columns of the head that beat the target: a greater logit, or an equal one at a lower index -- rank == 0 iff the
  *                 target is the first maximum, the argmax of pb_ce_fwd_bwd
  * A position with mask == 0 gets logp = 0, entropy = 0, rank = -1 and neither its logits nor its target are read. entropy and rank may
- * be NULL. Heads of 1 .. 320 classes (the register-resident row layout of K9); a target outside its head scores a logit of 0 as in K9.
+ * be NULL. Heads of 1 .. 1088 classes: up to 320 the register-resident row layout of K9, above it a wide form that holds one head's
+ * 17 classes per lane at a time (same arithmetic and summation order); a target outside its head scores a logit of 0 as in K9.
  * pb_seq_scores: out (B,4,8) f32 = per sequence and head {sum mask*logp, sum mask*entropy, sum mask*[rank == 0], sum mask} over the S
  * positions of sequence b (rows b*S .. b*S + S - 1 of the (B*S,8) arrays); entropy / rank NULL leave their plane 0. One workgroup per
  * sequence, fixed summation order, no atomics (bit-reproducible). */
@@ -554,7 +559,14 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   same small kernel as the row's position, limit, stop bar and done = 0. An admit without a staged value
  *                                   stores -1: a slot never inherits its previous occupant's floor. pb_batch_decoder_seek does not touch
  *                                   the value. Host state only, no device work. Refused (< 0, pb_last_error, nothing changed): not a
- *                                   dynamic decoder, before sampler_init, row outside 0 .. B - 1, a value outside -1 .. pad8[0] - 1. */
+ *                                   dynamic decoder, before sampler_init, row outside 0 .. B - 1, a value outside -1 .. pad8[0] - 1.
+ * Vocabulary layout (an addition to ABI 10): nothing about the dictionary is compiled in. plan.vocab / plan.tab_off and sampler_init's
+ * n8 / off8 / pad8 describe it; a head has 1 .. 1088 (64 x 17) classes. sampler_init picks one of two sampler forms from n8 and p8:
+ * narrow while every head has <= 272 classes AND the heads with p < 1 hold at most 512 classes together (5 classes per lane, static
+ * LDS, one thread per ranked class), else wide (17 classes per lane, ~104 KB of dynamic LDS, the rank counting in rounds of 512
+ * threads): every dictionary inside the head limit is served. Both run the same steps in the same order,
+ * take the same kernargs and honour forced ids, stop bars and bar floors alike.
+ *   pb_batch_decoder_sampler_form   0 = the narrow sampler (also before sampler_init), 1 = the wide one. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -584,6 +596,7 @@ int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar);
 int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_bar);
 int pb_batch_decoder_order(void* dec, const int32_t* floor);
 int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floor);
+int pb_batch_decoder_sampler_form(void* dec);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

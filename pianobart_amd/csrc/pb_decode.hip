@@ -1274,7 +1274,16 @@ template <bool ROWS> struct ForcedSampleArgs : SampleArgs<ROWS> {
 };
 template <bool ROWS, bool FORCED> struct SampleKernArgs { using type = SampleArgs<ROWS>; };
 template <bool ROWS> struct SampleKernArgs<ROWS, true> { using type = ForcedSampleArgs<ROWS>; };
-constexpr int SMP_W = 272;                // >= the largest head (262), multiple of 16
+// Two forms of the sampler, chosen by sampler_init from the decoder's heads (wide: a head over SMP_W classes, or more than 512 classes under the
+// heads with p < 1, which the narrow form ranks with one thread each): the narrow one (K = SMP_K = 5 classes per lane, rows of
+// SMP_W = 272 floats in static LDS; the default dictionary's heads are <= 262) and the wide one (K = SMP_KW = 17, rows of 64 * 17 = 1088, the
+// three arrays in ~104 KB of dynamic LDS). Same steps in the same order; K is a template parameter so that the narrow form keeps its
+// registers and its LDS.
+constexpr int SMP_K = 5, SMP_W = 272;     // narrow: SMP_W >= the largest head, a multiple of 16 (the rank loop's f32x4 reads)
+constexpr int SMP_KW = 17;                // wide: heads up to 64 * SMP_KW classes (ops.Layout's limit)
+template <int K> struct SmpForm { static constexpr int W = 64 * K; };
+template <> struct SmpForm<SMP_K> { static constexpr int W = SMP_W; };
+constexpr size_t smp_lds_bytes(int K) { return K == SMP_K ? 0 : sizeof(float) * 8 * (size_t)(64 * K) * 2 + sizeof(float) * 8 * 64 + sizeof(int) * 8 * (size_t)(64 * K); }
 // inclusive prefix sums over a wave (lane order), by shuffles
 __device__ __forceinline__ float wave_scan_f(float v, int lane) {
 #pragma unroll
@@ -1287,31 +1296,34 @@ __device__ __forceinline__ float wave_scan_f(float v, int lane) {
 // dim=-1) (model.py:103-104), then probs /= (sum(probs) + 1e-5) (model.py:85). The sums here are wave reductions, not numpy's left-to-right
 // ones: a common divisor that differs in its last bit moves every probability alike, so the order and (but for a 1e-7 neighbourhood of a
 // threshold) the choice stay -- the host checks every position.
-__device__ __forceinline__ void smp_softmax(const float (&y)[5], int n, int lane, float* __restrict__ pnh) {
-    float e[5];
+template <int K>
+__device__ __forceinline__ void smp_softmax(const float (&y)[K], int n, int lane, float* __restrict__ pnh) {
+    constexpr int W = SmpForm<K>::W;
+    float e[K];
     float mx = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) mx = fmaxf(mx, y[k]);
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, y[k]);
     mx = wave_max(mx);
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) { e[k] = (lane + 64 * k < n) ? expf(y[k] - mx) : 0.f; s += e[k]; }
+    for (int k = 0; k < K; ++k) { e[k] = (lane + 64 * k < n) ? expf(y[k] - mx) : 0.f; s += e[k]; }
     s = wave_sum(s);
     // probs = e / s, then probs /= (sum(probs) + 1e-5) with sum(probs) = 1 to rounding: one division by s (1 + 1e-5). A common factor a few ulps off
     // numpy's moves every probability alike (same order, same candidates but for a 1e-6 neighbourhood of the threshold): the host checks.
     const float inv = 1.0f / (s * 1.00001f);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < K; ++k) {
         const int c = lane + 64 * k;
-        if (c < SMP_W) pnh[c] = c < n ? e[k] * inv : -1.f;       // -1 behind the head's classes: never ranked in front of a class
+        if (c < W) pnh[c] = c < n ? e[k] * inv : -1.f;       // -1 behind the head's classes: never ranked in front of a class
     }
 }
 // class c's place in the descending order of pnh (ties by class index) -> sph / sih
+template <int W>
 __device__ __forceinline__ void smp_rank(const float* __restrict__ pnh, int c, float* __restrict__ sph, int* __restrict__ sih) {
     const float v = pnh[c];
     int rank = 0;
 #pragma unroll 17                                                  // fixed trip count (the tail holds -1: never in front of a class), four independent LDS reads in flight
-    for (int j4 = 0; j4 < SMP_W / 4; ++j4) {
+    for (int j4 = 0; j4 < W / 4; ++j4) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(&pnh[4 * j4]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) rank += (w[r] > v || (w[r] == v && 4 * j4 + r < c)) ? 1 : 0;
@@ -1319,18 +1331,19 @@ __device__ __forceinline__ void smp_rank(const float* __restrict__ pnh, int c, f
     sph[rank] = v; sih[rank] = c;
 }
 // nucleus(ph) of the head with the draw u_draw; the id in every lane. ph is wave-uniform; no barrier inside
+template <int K>
 __device__ __forceinline__ int smp_pick(float ph, int n, int lane, double u_draw, const float* __restrict__ pnh, const float* __restrict__ sph,
                                         const int* __restrict__ sih) {
     if (ph < 1.0f) {
-        // lane l owns sorted entries 5 l .. 5 l + 4 (0 behind the head's classes): prefix sums in sorted order
-        float v5[5], pre[5];
+        // lane l owns sorted entries K l .. K l + K - 1 (0 behind the head's classes): prefix sums in sorted order
+        float v5[K], pre[K];
         float run = 0.f;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) { const int i = 5 * lane + k; v5[k] = i < n ? sph[i] : 0.f; run += v5[k]; pre[k] = run; }
+        for (int k = 0; k < K; ++k) { const int i = K * lane + k; v5[k] = i < n ? sph[i] : 0.f; run += v5[k]; pre[k] = run; }
         const float base = wave_scan_f(run, lane) - run;
         int first = 0x7fffffff;                                  // candidates: up to and including the first cumsum > p; none -> top 1
 #pragma unroll
-        for (int k = 4; k >= 0; --k) if (5 * lane + k < n && base + pre[k] > ph) first = 5 * lane + k;
+        for (int k = K - 1; k >= 0; --k) if (K * lane + k < n && base + pre[k] > ph) first = K * lane + k;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
         const int kc = first == 0x7fffffff ? 1 : first + 1;
@@ -1338,12 +1351,12 @@ __device__ __forceinline__ int smp_pick(float ph, int n, int lane, double u_draw
         // (numpy renormalises in f32 and accumulates the cdf in f64: a relative 1e-7 against a uniform u)
         float myqs = 0.f;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) if (5 * lane + k == kc - 1) myqs = base + pre[k];
+        for (int k = 0; k < K; ++k) if (K * lane + k == kc - 1) myqs = base + pre[k];
         const float qs = wave_sum(myqs);                         // exactly one lane holds a non-zero term
         const float thr = (float)(u_draw * (double)qs);
         int best = kc - 1;                                       // first candidate whose running sum exceeds u times the candidates' total
 #pragma unroll
-        for (int k = 4; k >= 0; --k) if (5 * lane + k < kc && base + pre[k] > thr) best = 5 * lane + k;
+        for (int k = K - 1; k >= 0; --k) if (K * lane + k < kc && base + pre[k] > thr) best = K * lane + k;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
         return sih[best];
@@ -1351,7 +1364,7 @@ __device__ __forceinline__ int smp_pick(float ph, int n, int lane, double u_draw
     // p = 1: the cumsum never exceeds it -> the largest probability (lowest class among equals)
     float bv = -1.f; int bi = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < K; ++k) {
         const int c = lane + 64 * k;
         if (c < n) { const float v = pnh[c]; if (v > bv) { bv = v; bi = c; } }
     }
@@ -1362,11 +1375,17 @@ __device__ __forceinline__ int smp_pick(float ph, int n, int lane, double u_draw
     }
     return bi;
 }
-template <bool ROWS, bool FORCED>
+template <bool ROWS, bool FORCED, int K = SMP_K>
 __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKernArgs<ROWS, FORCED>::type a) {
-    __shared__ __attribute__((aligned(16))) float pn[8][SMP_W];     // normalised probabilities, class order
-    __shared__ float sp[8][SMP_W + 64];   // ... in descending order (heads with p < 1), zero tail
-    __shared__ int si[8][SMP_W];          // class of each sorted entry
+    constexpr int W = SmpForm<K>::W;
+    constexpr bool WIDE = K != SMP_K;     // the wide form's three arrays are dynamic LDS (smp_lds_bytes, over the 64 KB a kernel has without the opt-in)
+    __shared__ __attribute__((aligned(16))) float pn_s[WIDE ? 1 : 8][WIDE ? 4 : W];   // normalised probabilities, class order
+    __shared__ float sp_s[WIDE ? 1 : 8][WIDE ? 1 : W + 64];                            // ... in descending order (heads with p < 1), zero tail
+    __shared__ int si_s[WIDE ? 1 : 8][WIDE ? 1 : W];                                   // class of each sorted entry
+    extern __shared__ __attribute__((aligned(16))) char smp_dyn[];
+    float (*pn)[W] = reinterpret_cast<float (*)[W]>(WIDE ? (void*)smp_dyn : (void*)pn_s);
+    float (*sp)[W + 64] = reinterpret_cast<float (*)[W + 64]>(WIDE ? (void*)(smp_dyn + sizeof(float) * 8 * W) : (void*)sp_s);
+    int (*si)[W] = reinterpret_cast<int (*)[W]>(WIDE ? (void*)(smp_dyn + sizeof(float) * 8 * (2 * W + 64)) : (void*)si_s);
     __shared__ int htok[8];
     const int b = ROWS ? (int)blockIdx.x : 0;
     if (ROWS && a.st->done[b]) return;                           // block-uniform
@@ -1409,10 +1428,10 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     }
     // y = logit / T of head h's classes; a time-ordered row's bars below low0 get -inf here, so their probability is an exact 0: the
     // rank count puts them behind every positive class and the p = 1 arg-max never picks one (the largest class has e = 1).
-    float y[5];
+    float y[K];
     const int lowh = h == 0 ? low0 : 0;                          // wave-uniform
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < K; ++k) {
         const int c = lane + 64 * k;
         const bool in = c < n;
         const float lg = in ? logits[off + c] : 0.f;
@@ -1423,20 +1442,25 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     __syncthreads();
     // descending order of the heads with p < 1 by rank counting, one thread per (head, class): ties by class index
     {
-        int hh = -1, c = t;
-        for (int q = 0; q < 8; ++q) {
-            if (a.p[q] < 1.0f) {
-                if (hh < 0 && c < a.n[q]) hh = q;
-                if (hh < 0) c -= a.n[q];
+        // narrow: at most 512 such classes (sampler_init), one round; wide: rounds of 512 until every class of those heads had its thread
+        int tot = 0;                                             // wide only: the classes under heads with p < 1 (block-uniform)
+        if constexpr (WIDE) { for (int q = 0; q < 8; ++q) tot += a.p[q] < 1.0f ? a.n[q] : 0; }
+        for (int c0 = t; WIDE ? c0 < tot : c0 == t; c0 += 512) {
+            int hh = -1, c = c0;
+            for (int q = 0; q < 8; ++q) {
+                if (a.p[q] < 1.0f) {
+                    if (hh < 0 && c < a.n[q]) hh = q;
+                    if (hh < 0) c -= a.n[q];
+                }
             }
+            if (hh >= 0) smp_rank<W>(pn[hh], c, sp[hh], si[hh]);
         }
-        if (hh >= 0) smp_rank(pn[hh], c, sp[hh], si[hh]);
-        if (t < 8 * 64) sp[t >> 6][SMP_W + (t & 63)] = 0.f;
+        if (t < 8 * 64) sp[t >> 6][W + (t & 63)] = 0.f;
     }
     __syncthreads();
     const float ph = a.p[h];
     {                                                            // wave h = head h; no barrier inside
-        const int id = smp_pick(ph, n, lane, u_draw, pn[h], sp[h], si[h]);
+        const int id = smp_pick<K>(ph, n, lane, u_draw, pn[h], sp[h], si[h]);
         if (lane == 0) htok[h] = id;
     }
     __syncthreads();
@@ -1454,19 +1478,19 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
             const bool sorted1 = a.p[1] < 1.0f;
             if (h == 1) {
 #pragma unroll
-                for (int k = 0; k < 5; ++k) if (lane + 64 * k < low1) y[k] = -INFINITY;
+                for (int k = 0; k < K; ++k) if (lane + 64 * k < low1) y[k] = -INFINITY;
                 smp_softmax(y, n, lane, pn[1]);
             }
             __syncthreads();
             if (sorted1) {
                 if (h == 1) {
 #pragma unroll
-                    for (int k = 0; k < 5; ++k) { const int c = lane + 64 * k; if (c < n) smp_rank(pn[1], c, sp[1], si[1]); }
+                    for (int k = 0; k < K; ++k) { const int c = lane + 64 * k; if (c < n) smp_rank<W>(pn[1], c, sp[1], si[1]); }
                 }
                 __syncthreads();
             }
             if (h == 1) {
-                const int id = smp_pick(ph, n, lane, u_draw, pn[1], sp[1], si[1]);
+                const int id = smp_pick<K>(ph, n, lane, u_draw, pn[1], sp[1], si[1]);
                 if (lane == 0) htok[1] = id;
             }
             __syncthreads();
@@ -1533,6 +1557,7 @@ struct Decoder {
     int16_t* log_tok = nullptr;            // pinned (B, S, 8)
     SampleArgs<true> sa{};                 // the sampler constants (the single-row kernel takes its subset)
     bool sampler = false;
+    bool wide = false;                     // sampler_init: a head over SMP_W classes -> the wide sampler (K = SMP_KW, dynamic LDS)
     int16_t* force_dev = nullptr;          // pb_batch_decoder_force: (B, S, 8) given ids, -1 = free; the steps then end with the FORCED sampler
     hipGraph_t graph[N_GRAPHS] = {};
     hipGraphExec_t exec[N_GRAPHS] = {};
@@ -1690,9 +1715,11 @@ static int step_issue(Decoder* D, bool sample) {
                 ForcedSampleArgs<true> sf{};
                 static_cast<SampleArgs<true>&>(sf) = D->sa;
                 sf.force = D->force_dev;
-                hipLaunchKernelGGL((dec_sample_kernel<true, true>), dim3(B), dim3(512), 0, st, sf);
+                if (D->wide) hipLaunchKernelGGL((dec_sample_kernel<true, true, SMP_KW>), dim3(B), dim3(512), smp_lds_bytes(SMP_KW), st, sf);
+                else hipLaunchKernelGGL((dec_sample_kernel<true, true>), dim3(B), dim3(512), 0, st, sf);
             } else {
-                hipLaunchKernelGGL((dec_sample_kernel<true, false>), dim3(B), dim3(512), 0, st, D->sa);
+                if (D->wide) hipLaunchKernelGGL((dec_sample_kernel<true, false, SMP_KW>), dim3(B), dim3(512), smp_lds_bytes(SMP_KW), st, D->sa);
+                else hipLaunchKernelGGL((dec_sample_kernel<true, false>), dim3(B), dim3(512), 0, st, D->sa);
             }
         } else {
             SampleArgs<false> s1{};
@@ -1703,9 +1730,11 @@ static int step_issue(Decoder* D, bool sample) {
                 ForcedSampleArgs<false> sf{};
                 static_cast<SampleArgs<false>&>(sf) = s1;
                 sf.force = D->force_dev;
-                hipLaunchKernelGGL((dec_sample_kernel<false, true>), dim3(1), dim3(512), 0, st, sf);
+                if (D->wide) hipLaunchKernelGGL((dec_sample_kernel<false, true, SMP_KW>), dim3(1), dim3(512), smp_lds_bytes(SMP_KW), st, sf);
+                else hipLaunchKernelGGL((dec_sample_kernel<false, true>), dim3(1), dim3(512), 0, st, sf);
             } else {
-                hipLaunchKernelGGL((dec_sample_kernel<false, false>), dim3(1), dim3(512), 0, st, s1);
+                if (D->wide) hipLaunchKernelGGL((dec_sample_kernel<false, false, SMP_KW>), dim3(1), dim3(512), smp_lds_bytes(SMP_KW), st, s1);
+                else hipLaunchKernelGGL((dec_sample_kernel<false, false>), dim3(1), dim3(512), 0, st, s1);
             }
         }
         PB_LAUNCH_CHECK(); ++n;
@@ -1927,14 +1956,24 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     const size_t S = (size_t)D->bp.plan.S, B = (size_t)D->B, vocab = (size_t)D->bp.plan.vocab;
     PB_REQUIRE(n_u >= (int64_t)(B * S * 8), "pb_batch_decoder_sampler_init: %lld draws for %d rows x %d positions x 8 heads", (long long)n_u, D->B, (int)S);
     PB_REQUIRE(limit >= 0 && limit <= (int)S, "pb_batch_decoder_sampler_init: limit %d outside 0..%d", limit, (int)S);
+    bool wide = false;
     for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(n8[h] > 0 && n8[h] <= SMP_W && n8[h] <= 320 && off8[h] >= 0 && off8[h] + n8[h] <= (int)vocab && temps8[h] > 0.f,
+        wide = wide || n8[h] > SMP_W;
+        PB_REQUIRE(n8[h] > 0 && n8[h] <= 64 * SMP_KW && off8[h] >= 0 && off8[h] + n8[h] <= (int)vocab && temps8[h] > 0.f,
                    "pb_batch_decoder_sampler_init: head %d (n %d, offset %d, temperature %g)", h, n8[h], off8[h], (double)temps8[h]);
         D->sa.n[h] = n8[h]; D->sa.off[h] = off8[h]; D->sa.temp[h] = temps8[h]; D->sa.p[h] = p8[h]; D->sa.pad[h] = pad8[h];
     }
     int sorted = 0;
     for (int h = 0; h < 8; ++h) if (p8[h] < 1.0f) sorted += n8[h];
-    PB_REQUIRE(sorted <= 512, "pb_batch_decoder_sampler_init: %d classes under heads with p < 1 (one thread each, 512 threads)", sorted);
+    wide = wide || sorted > 512;                                        // the narrow form ranks with one thread per class under a head with p < 1: 512 of them; the wide form takes rounds
+    if (wide) {                                                         // ~104 KB of dynamic LDS: over the default limit, so every wide instantiation opts in
+        const int lds = (int)smp_lds_bytes(SMP_KW);
+        PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_sample_kernel<true, true, SMP_KW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_sample_kernel<true, false, SMP_KW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_sample_kernel<false, true, SMP_KW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        PB_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_sample_kernel<false, false, SMP_KW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    D->wide = wide;
     if (!D->u_dev) {
         if (hipMalloc(&D->u_dev, sizeof(double) * B * S * 8) != hipSuccess ||
             hipHostMalloc(&D->log_logits, sizeof(float) * B * S * vocab, hipHostMallocDefault) != hipSuccess ||
@@ -1959,6 +1998,13 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     drop_graphs(D);                                                     // captured with the previous constants
     D->sampler = true;
     return 0;
+}
+
+// Which sampler the decoder's steps end with (behind sampler_init): 0 = narrow (every head <= 272 classes and at most 512 classes under the
+// heads with p < 1), 1 = wide.
+extern "C" int32_t pb_batch_decoder_sampler_form(void* dec) {
+    Decoder* D = (Decoder*)dec;
+    return (D && D->sampler && D->wide) ? 1 : 0;
 }
 
 // Forced tokens (see the header): the (B, S, 8) table of given ids goes up once, into memory the decoder owns. Every value is checked on

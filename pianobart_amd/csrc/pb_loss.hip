@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
         partials[(size_t)blockIdx.x * 24 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// Register-resident form for heads of at most 64 * CE_K classes (the Octuple heads: <= 262): the row's logits are loaded ONCE, all
+// Register-resident form for heads of at most 64 * CE_K classes (the default dictionary's heads: <= 262; a dictionary with a larger head
+// runs the generic kernel above): the row's logits are loaded ONCE, all
 // loads of a row in flight together, lane l holding classes l, l + 64, ... of every head; max / first-argmax / sum-exp are VALU-only
 // wave reductions (DPP + permlane swaps). The generic kernel above re-reads the row three times behind dependent LDS-routed
 // shuffles and was pure latency: 310 us for the 168 MB of cfg-2 logits (0.8 TB/s). Same per-lane summation order -> same bits.

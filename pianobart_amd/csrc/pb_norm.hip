@@ -368,6 +368,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ dy, l
     if (cc < N) partials[(size_t)blockIdx.y * N + cc] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+// Any N and ld (the head-bias gradient of a dictionary whose vocabulary total is no multiple of 4): a thread owns one column and sums the
+// block's rows in order; same grid over the rows and the same partials layout as above.
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_any_kernel(const T* __restrict__ dy, long ld, float* __restrict__ partials, int rows, int N, int rows_per_blk) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    const int r0 = blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
+    float s = 0.f;
+    for (int r = r0; r < r1; ++r) s += to_f(dy[(long)r * ld + c]);
+    partials[(size_t)blockIdx.y * N + c] = s;
+}
+
 int ln_grid(int rows) { return max(1, min((rows + LN_WAVES - 1) / LN_WAVES, LN_MAX_BLOCKS)); }        // kernels that write per-block partials
 int ln_grid_fwd(int rows) { return max(1, min((rows + LN_WAVES - 1) / LN_WAVES, 2048)); }
 
@@ -642,6 +654,23 @@ extern "C" int pb_colsum(const void* dy, int64_t ld, float* out, float* partials
         hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, stream, (const float*)dy, (long)ld, partials, T, N, rpb);
     else
         hipLaunchKernelGGL((colsum_kernel<bf16_t>), grid, dim3(256), 0, stream, (const bf16_t*)dy, (long)ld, partials, T, N, rpb);
+    PB_LAUNCH_CHECK();
+    return launch_finalize(partials, nrb, 1, N, out, nullptr, nullptr, nullptr, stream);
+}
+
+// pb_colsum without its multiple-of-4 rule (the one-column kernel): same arguments, workspace and result
+extern "C" int pb_colsum_any(const void* dy, int64_t ld, float* out, float* partials, int32_t T, int32_t N, int32_t dtype,
+                             int32_t src_f32, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    PB_REQUIRE(dy && out && partials && T >= 0 && N > 0 && ld >= N, "pb_colsum_any: T=%d, N=%d, ld=%ld", T, N, (long)ld);
+    if (T == 0) return 0;
+    const int nrb = max(1, min(128, (T + 63) / 64));
+    const int rpb = (T + nrb - 1) / nrb;
+    dim3 grid((N + 255) / 256, nrb);
+    if (src_f32 || dtype == PB_F32)
+        hipLaunchKernelGGL((colsum_any_kernel<float>), grid, dim3(256), 0, stream, (const float*)dy, (long)ld, partials, T, N, rpb);
+    else
+        hipLaunchKernelGGL((colsum_any_kernel<bf16_t>), grid, dim3(256), 0, stream, (const bf16_t*)dy, (long)ld, partials, T, N, rpb);
     PB_LAUNCH_CHECK();
     return launch_finalize(partials, nrb, 1, N, out, nullptr, nullptr, nullptr, stream);
 }

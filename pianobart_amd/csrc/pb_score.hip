@@ -10,7 +10,8 @@
 namespace {
 
 struct Seg9 { int off[9]; };
-constexpr int SC_K = 5;                     // heads of at most 64 * SC_K classes (the Octuple heads: <= 262)
+constexpr int SC_K = 5;                     // the register form: heads of at most 64 * SC_K = 320 classes (the default dictionary's: <= 262)
+constexpr int SC_KW = 17;                   // the wide form: heads of at most 64 * SC_KW = 1088 classes (ops.Layout's limit)
 constexpr int SC_MAX_BLOCKS = 4096;
 
 // FULL = false: logp only (entropy and rank both NULL)
@@ -92,6 +93,74 @@ __global__ __launch_bounds__(256) void token_scores_kernel(const float* __restri
     }
 }
 
+// The wide form, for a dictionary with a head of 321 .. 64 * SC_KW classes: the same per-head arithmetic and summation order (lane l holds
+// classes l, l + 64, ...; sums over k in order, then the wave), but one head's SC_KW values in registers at a time instead of the whole
+// row's 8 x SC_K -- the register form above keeps its 40 values and is launched for every dictionary it covers.
+template <bool FULL>
+__global__ __launch_bounds__(256) void token_scores_wide_kernel(const float* __restrict__ logits, const int16_t* __restrict__ target,
+        const float* __restrict__ mask, const Seg9 so, float* __restrict__ logp, float* __restrict__ entropy,
+        int16_t* __restrict__ rank, int rows, int V) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+        if (mask[row] == 0.f) {                                     // wave-uniform; neither the logits nor the target of the row are read
+            if (lane < 8) {
+                logp[row * 8 + lane] = 0.f;
+                if (FULL && entropy) entropy[row * 8 + lane] = 0.f;
+                if (FULL && rank) rank[row * 8 + lane] = (int16_t)-1;
+            }
+            continue;
+        }
+        const float* x = logits + row * V;
+        const int my_t = lane < 8 ? (int)target[row * 8 + lane] : 0;
+        float r_lp = 0.f, r_en = 0.f;
+        int r_rk = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int o = so.off[i], n = so.off[i + 1] - o;
+            float v[SC_KW];
+#pragma unroll
+            for (int k = 0; k < SC_KW; ++k) {
+                const int c = lane + 64 * k;
+                v[k] = c < n ? x[o + c] : -INFINITY;                // tail lanes: -inf to the maximum, 0 to the sums
+            }
+            const int tgt = __builtin_amdgcn_readlane(my_t, i);
+            float mx = v[0];
+#pragma unroll
+            for (int k = 1; k < SC_KW; ++k) mx = fmaxf(mx, v[k]);
+            mx = wave_max(mx);
+            float se = 0.f, sed = 0.f;
+#pragma unroll
+            for (int k = 0; k < SC_KW; ++k) {
+                const float dlt = v[k] - mx;
+                const float e = lane + 64 * k < n ? __expf(dlt) : 0.f;
+                se += e;
+                if (FULL) sed += e > 0.f ? e * dlt : 0.f;
+            }
+            se = wave_sum(se);
+            if (FULL) sed = wave_sum(sed);
+            const bool in = tgt >= 0 && tgt < n;                    // wave-uniform; a target outside its head scores a logit of 0
+            const float xt = in ? x[o + tgt] : 0.f;                 // the value lane tgt & 63 holds in v[tgt >> 6]: the same bits
+            const float lg = __logf(se);
+            const float lp = (xt - mx) - lg;
+            const float en = FULL ? lg - sed / se : 0.f;
+            int rk = 0;
+            if (FULL) {
+#pragma unroll
+                for (int k = 0; k < SC_KW; ++k) {
+                    const int c = lane + 64 * k;
+                    rk += __popcll(__ballot(v[k] > xt || (v[k] == xt && c < tgt)));
+                }
+            }
+            if (lane == i) { r_lp = lp; r_en = en; r_rk = rk; }
+        }
+        if (lane < 8) {
+            logp[row * 8 + lane] = r_lp;
+            if (FULL && entropy) entropy[row * 8 + lane] = r_en;
+            if (FULL && rank) rank[row * 8 + lane] = (int16_t)r_rk;
+        }
+    }
+}
+
 // One workgroup per sequence: thread t sums head t & 7 over positions (t >> 3) + 32 j in order, then a fixed-order sum over the 32
 // position groups. No atomics: two runs give the same bits.
 __global__ __launch_bounds__(256) void seq_scores_kernel(const float* __restrict__ logp, const float* __restrict__ entropy,
@@ -129,11 +198,19 @@ extern "C" int pb_token_scores(const float* logits, const int16_t* target, const
     PB_REQUIRE(seg_off[8] == V && seg_off[0] == 0, "pb_token_scores: segment offsets do not cover V=%d", V);
     Seg9 so;
     for (int i = 0; i < 9; ++i) so.off[i] = seg_off[i];
-    for (int i = 0; i < 8; ++i)
-        PB_REQUIRE(so.off[i + 1] > so.off[i] && so.off[i + 1] - so.off[i] <= 64 * SC_K, "pb_token_scores: head %d has %d classes (1 .. %d)", i,
-                   so.off[i + 1] - so.off[i], 64 * SC_K);
+    bool wide = false;
+    for (int i = 0; i < 8; ++i) {
+        PB_REQUIRE(so.off[i + 1] > so.off[i] && so.off[i + 1] - so.off[i] <= 64 * SC_KW, "pb_token_scores: head %d has %d classes (1 .. %d)", i,
+                   so.off[i + 1] - so.off[i], 64 * SC_KW);
+        wide = wide || so.off[i + 1] - so.off[i] > 64 * SC_K;
+    }
     const int grid = max(1, min(SC_MAX_BLOCKS, (T + 3) / 4));
-    if (entropy || rank)
+    if (wide) {
+        if (entropy || rank)
+            hipLaunchKernelGGL((token_scores_wide_kernel<true>), dim3(grid), dim3(256), 0, stream, logits, target, mask, so, logp, entropy, rank, T, V);
+        else
+            hipLaunchKernelGGL((token_scores_wide_kernel<false>), dim3(grid), dim3(256), 0, stream, logits, target, mask, so, logp, entropy, rank, T, V);
+    } else if (entropy || rank)
         hipLaunchKernelGGL((token_scores_kernel<true>), dim3(grid), dim3(256), 0, stream, logits, target, mask, so, logp, entropy, rank, T, V);
     else
         hipLaunchKernelGGL((token_scores_kernel<false>), dim3(grid), dim3(256), 0, stream, logits, target, mask, so, logp, entropy, rank, T, V);

@@ -94,6 +94,21 @@ def check_keep_args(keep, prime):
     return heads
 
 
+def check_dictionary(e2w):
+    """demo() converts MIDI <-> Octuple with octuple_midi, which is the DEFAULT dictionary's codec: its PAD_ROW / EOS_ROW are that
+    dictionary's ids. The model itself takes any legal dictionary (ops.Layout); a piece encoded under another one would be read and
+    written with the wrong ids here, so the demo refuses it. Raises PBError naming the first head that differs."""
+    from . import octuple_midi as OM
+    from .ops import CLASS_NAMES, Layout
+    lay = Layout.from_dict(e2w)
+    for h, name in enumerate(CLASS_NAMES):
+        if lay.sizes[h] != OM.PAD_ROW[h] + 6 or lay.pad8[h] != OM.PAD_ROW[h] or lay.specials[h][3] != OM.EOS_ROW[h]:
+            raise PBError('demo: the dictionary\'s head %d (%s) has %d ids with <PAD> = %d; the MIDI codec (octuple_midi) is written for %d ids with '
+                          '<PAD> = %d. MIDI conversion exists for the default dictionary only: generate with eval_generation on encoded data'
+                          % (h, name, lay.sizes[h], lay.pad8[h], OM.PAD_ROW[h] + 6, OM.PAD_ROW[h]))
+    return lay
+
+
 def check_bar_args(bars, infill, prime, keep, seed):
     """The --bars and --infill rules (eval_generation's); raises PBError. Returns (lo, hi) or None."""
     from .eval_generation import parse_infill
@@ -126,6 +141,7 @@ def demo(args=None):
     from .pretrain import _load_vocab
     print("Loading Dictionary")
     e2w, w2e = _load_vocab(args.dict_file)
+    check_dictionary(e2w)
     print("\nBuilding BART model")
     shape = dict(max_position_embeddings=args.max_seq_len, d_model=args.hs)
     for side in ('encoder', 'decoder'):

@@ -98,6 +98,7 @@ class Engine(GenerationMixin, ScoringMixin):
         if precision not in ('bf16', 'fp32', 'bf16x3'):
             raise PBError('precision must be "bf16", "fp32" or "bf16x3"')
         self.pb, self.mlm = pianobart, mask_lm
+        self.lay = pianobart.layout           # the dictionary's vocabulary layout (ops.Layout): every size and offset below comes from it
         for mod in (pianobart, mask_lm):
             if mod is not None and hasattr(mod, 'register_state_dict_pre_hook'):         # a checkpoint must not read parameters a pipelined update is still writing
                 mod.register_state_dict_pre_hook(lambda *a, **k: self.finish_updates())
@@ -156,7 +157,7 @@ class Engine(GenerationMixin, ScoringMixin):
             cur[0] += _r4(int(np.prod(shape)))
 
         # region A: matrices whose gradients are OVERWRITTEN by one wgrad GEMM each step
-        add('emb', ops.TAB_TOTAL, 256)                 # 8 slots of 264 rows (pad rows stay zero: zero grad, zero decay)
+        add('emb', self.lay.tab_total, 256)                 # 8 slots of 264 rows (pad rows stay zero: zero grad, zero decay)
         add('lin.w', d, 2048)
         for l in range(self.NE):
             p = 'enc.%d.' % l
@@ -171,7 +172,7 @@ class Engine(GenerationMixin, ScoringMixin):
         if self.ND:
             add('dec.wkv_all', self.ND * 2 * d, d)
         if self.mlm is not None:
-            add('head.w', ops.VOCAB, d)
+            add('head.w', self.lay.vocab, d)
         self.n_matrix = cur[0]
         # region B: vectors / tables whose gradients are ACCUMULATED (zeroed at the start of each backward)
         add('lin.b', d)
@@ -186,7 +187,7 @@ class Engine(GenerationMixin, ScoringMixin):
         if self.ND:
             add('dec.bkv_all', self.ND * 2 * d)
         if self.mlm is not None:
-            add('head.b', ops.VOCAB)
+            add('head.b', self.lay.vocab)
         self.n_total = cur[0]
         self.slots = slots
 
@@ -196,7 +197,7 @@ class Engine(GenerationMixin, ScoringMixin):
         out = []
         off = 0
         for i in range(8):
-            out.append((pb.word_emb[i].lut.weight, 'emb', ops.TAB_OFF[i]))
+            out.append((pb.word_emb[i].lut.weight, 'emb', self.lay.tab_off[i]))
         out.append((pb.encoder_linear.weight, 'lin.w', 0)); out.append((pb.encoder_linear.bias, 'lin.b', 0))
         for side, stack, n in (('enc', pb.bart.encoder, self.NE), ('dec', pb.bart.decoder, self.ND)):
             out.append((stack.embed_positions.weight, side + '.pos', 0))
@@ -221,7 +222,7 @@ class Engine(GenerationMixin, ScoringMixin):
             off = 0
             for i in range(8):
                 out.append((self.mlm.proj[i].weight, 'head.w', off)); out.append((self.mlm.proj[i].bias, 'head.b', off))
-                off += ops.SEG_SIZES[i]
+                off += self.lay.sizes[i]
         return out
 
     def _elem_off(self, slot, row):
@@ -284,9 +285,9 @@ class Engine(GenerationMixin, ScoringMixin):
         self.opt_m = self.opt_v = None
         self._versions = None
         self._ws_cache = {}
-        self.ptab = torch.zeros(ops.TAB_TOTAL, self.d, dtype=torch.float32, device=device)
-        self.dptab = torch.zeros(ops.TAB_TOTAL, self.d, dtype=torch.float32, device=device)
-        npart = max(int(LIB.query('pb_ln_partials_floats', self.d)), int(LIB.query('pb_colsum_partials_floats', max(3 * self.d, self.fe, self.fd, ops.VOCAB))),
+        self.ptab = torch.zeros(self.lay.tab_total, self.d, dtype=torch.float32, device=device)
+        self.dptab = torch.zeros(self.lay.tab_total, self.d, dtype=torch.float32, device=device)
+        npart = max(int(LIB.query('pb_ln_partials_floats', self.d)), int(LIB.query('pb_colsum_partials_floats', max(3 * self.d, self.fe, self.fd, self.lay.vocab))),
                     int(LIB.query('pb_ce_partials_floats')), int(LIB.query('pb_norm_partials_floats')))
         self.partials = torch.empty(npart, dtype=torch.float32, device=device)
         self.scal = torch.zeros(64, dtype=torch.float32, device=device)    # [0:24] ce sums, [24:32] counts, [32:40] coef, [40] sq, [41] clip
@@ -364,12 +365,12 @@ class Engine(GenerationMixin, ScoringMixin):
                   x_enc=e(T, d), me=f(T), re=f(T), x_dec=e(T, d), md=f(T), rd=f(T),
                   kvc_all=e(T, max(1, self.ND) * 2 * d), dkv_all=e(T, max(1, self.ND) * 2 * d),      # cross-attention K | V of every decoder layer side by side, and their gradients
                   enc=[layer(False) for _ in range(self.NE)], dec=[layer(True) for _ in range(self.ND)],
-                  logits=f(T, ops.VOCAB) if self.mlm is not None else None,
+                  logits=f(T, self.lay.vocab) if self.mlm is not None else None,
                   scores=None if self.use_flash else f(B, H, S, S), dS=None if self.use_flash else e(B, H, S, S), delta=f(B, H, S),
                   gy=[e(T, d), e(T, d)], gA=e(T, d), gB=e(T, d), gC=e(T, d), dqkv=e(T, 3 * d), dq=e(T, d),
-                  du=e(T, max(self.fe, self.fd)), genc=e(T, d), dlogits=e(T, ops.VOCAB) if self.mlm is not None else None,
+                  du=e(T, max(self.fe, self.fd)), genc=e(T, d), dlogits=e(T, self.lay.vocab) if self.mlm is not None else None,
                   dz=e(2 * T, d) if (self.code == PB_BF16 or self.x3) else None,
-                  onehot=torch.empty(2 * T, ops.TAB_TOTAL, dtype=torch.bfloat16, device=self.device) if (self.code == PB_BF16 or self.x3) else None,
+                  onehot=torch.empty(2 * T, self.lay.tab_total, dtype=torch.bfloat16, device=self.device) if (self.code == PB_BF16 or self.x3) else None,
                   dz_planes=torch.empty(2, 2 * T, d, dtype=torch.bfloat16, device=self.device) if self.x3 else None)    # bf16x3: dz cut into (hi, lo) for the one-hot GEMMs
         ws['Te'] = ws['Td'] = T
         self._ws_cache = {key: ws}          # keep one shape resident
@@ -489,7 +490,7 @@ class Engine(GenerationMixin, ScoringMixin):
 
     def build_ptab(self):
         """P[off_i + v] = 16 * E_i[v] @ W_lin[:, 256 i : 256 i + 256]^T in exact f32 (PianoBart.py:16,67-71)."""
-        R = ops.TAB_ROWS
+        R = self.lay.tab_rows
         ops.gemm(self.wf['emb'], self.wf['lin.w'], self.ptab, M=R, N=self.d, K=256, dtype=PB_F32, lda=256, ldb=2048, ldc=self.d, alpha=16.0,
                  c_f32=True, nb1=8, sA=(R * 256, 0), sB=(256, 0), sC=(R * self.d, 0))
 
@@ -526,7 +527,7 @@ class Engine(GenerationMixin, ScoringMixin):
         x = ws['x_enc']
         if not reuse_encoder:
             ops.embed_ln_fwd(enc16, self.ptab, wf['lin.b'], wf['enc.pos'], wf['enc.lne.w'], wf['enc.lne.b'], x, ws['me'], ws['re'], S,
-                             LN_EPS, seed, self._site('enc_emb'), p, padded=True, row_ids=ids_e)
+                             LN_EPS, seed, self._site('enc_emb'), p, padded=True, layout=self.lay, row_ids=ids_e)
         T = Te
         for l in range(self.NE if not reuse_encoder else 0):
             L, pf = ws['enc'][l], 'enc.%d.' % l
@@ -549,7 +550,7 @@ class Engine(GenerationMixin, ScoringMixin):
         T = Td
         if dec_embeds is None:
             ops.embed_ln_fwd(dec16, self.ptab, wf['lin.b'], wf['dec.pos'], wf['dec.lne.w'], wf['dec.lne.b'], y, ws['md'], ws['rd'], S,
-                             LN_EPS, seed, self._site('dec_emb'), p, padded=True, row_ids=ids_d)
+                             LN_EPS, seed, self._site('dec_emb'), p, padded=True, layout=self.lay, row_ids=ids_d)
         else:
             # decoder_inputs_embeds supplied by the caller (velocity task's label embedding, PianoBart.py:65-66): BART adds the
             # learned positions (offset 2), applies layernorm_embedding, then dropout (modeling_bart.py, BartDecoder.forward)
@@ -618,7 +619,7 @@ class Engine(GenerationMixin, ScoringMixin):
         ws = self._cur_ws
         T = dec_hidden.shape[0]
         logits = ws['logits'][:T]
-        ops.gemm(dec_hidden, self.w['head.w'], logits, M=T, N=ops.VOCAB, K=self.d, dtype=self.gcode, bias=self.wf['head.b'], c_f32=True)
+        ops.gemm(dec_hidden, self.w['head.w'], logits, M=T, N=self.lay.vocab, K=self.d, dtype=self.gcode, bias=self.wf['head.b'], c_f32=True)
         return logits
 
     # ------------------------------------------------------------------ backward
@@ -925,14 +926,14 @@ class Engine(GenerationMixin, ScoringMixin):
             else:
                 ops.embed_ln_bwd(cur, sv['dec16'], self.ptab, wf['lin.b'], wf['dec.pos'], wf['dec.lne.w'], ws['md'], ws['rd'], self.dptab,
                                  g['dec.pos'], g['lin.b'], g['dec.lne.w'], g['dec.lne.b'], self.partials, S, seed, self._site('dec_emb'), p,
-                                 dz_out=ws['dz'][Te:Te + Td] if onehot_route else None, padded=True, row_ids=pack.src_d if pack is not None else None)
+                                 dz_out=ws['dz'][Te:Te + Td] if onehot_route else None, padded=True, layout=self.lay, row_ids=pack.src_d if pack is not None else None)
                 if onehot_route and pack is not None:
                     ops.pos_grad_packed(ws['dz'][Te:Te + Td], pack.inv_d, g['dec.pos'][2:2 + S], B, S)
                 elif onehot_route:
                     ops.batch_sum(ws['dz'][T:], g['dec.pos'][2:2 + S], B, S * d)
                 if onehot_route:
                     # the decoder tokens' half of dP = Onehot^T dz is ready now: on the second stream, beside the encoder's backward
-                    ops.onehot_build(sv['dec16'], ws['onehot'][Te:Te + Td], padded=True)
+                    ops.onehot_build(sv['dec16'], ws['onehot'][Te:Te + Td], padded=True, layout=self.lay)
                     dec_tab_done = self._onehot_gemm(ws['onehot'][Te:Te + Td], ws['dz'][Te:Te + Td], Td, False, side=True)
             cur = genc
             if gy_enc_extra is not None:
@@ -967,20 +968,20 @@ class Engine(GenerationMixin, ScoringMixin):
                 self._side_last = self._event()
         ops.embed_ln_bwd(cur, sv['enc16'], self.ptab, wf['lin.b'], wf['enc.pos'], wf['enc.lne.w'], ws['me'], ws['re'], self.dptab,
                          g['enc.pos'], g['lin.b'], g['enc.lne.w'], g['enc.lne.b'], self.partials, S, seed, self._site('enc_emb'), p,
-                         dz_out=ws['dz'][:Te] if onehot_route else None, padded=True, row_ids=pack.src_e if pack is not None else None)
+                         dz_out=ws['dz'][:Te] if onehot_route else None, padded=True, layout=self.lay, row_ids=pack.src_e if pack is not None else None)
         if onehot_route:
             # dP = Onehot^T dz over the encoder AND decoder tokens in one split-K MFMA GEMM (K = Te + Td): no atomics
             if pack is not None:
                 ops.pos_grad_packed(ws['dz'][:Te], pack.inv_e, g['enc.pos'][2:2 + S], B, S)
             else:
                 ops.batch_sum(ws['dz'][:T], g['enc.pos'][2:2 + S], B, S * d)
-            ops.onehot_build(sv['enc16'], ws['onehot'][:Te], padded=True)
+            ops.onehot_build(sv['enc16'], ws['onehot'][:Te], padded=True, layout=self.lay)
             # the encoder tokens' half, added to the decoder's (a caller-supplied decoder embedding has no Octuple rows to scatter into)
             if dec_tab_done is not None:
                 dec_tab_done.wait_on(torch.cuda.current_stream())
             self._onehot_gemm(ws['onehot'][:Te], ws['dz'][:Te], Te, dec_tab_done is not None, side=False)
         # projected-table gradient -> embedding tables and the shared merge Linear (exact f32)
-        E, W, R = self.wf['emb'], self.wf['lin.w'], ops.TAB_ROWS
+        E, W, R = self.wf['emb'], self.wf['lin.w'], self.lay.tab_rows
         lin_w = lambda: ops.gemm(self.dptab, E, g['lin.w'], M=d, N=256, K=R, dtype=PB_F32, a_kc=False, b_kc=False, lda=d, ldb=256, ldc=2048, alpha=16.0,
                                  c_f32=True, nb1=8, sA=(R * d, 0), sB=(R * 256, 0), sC=(256, 0))
         if side_tail:                                           # two small f32 GEMMs that both read dP: one per stream
@@ -1004,10 +1005,10 @@ class Engine(GenerationMixin, ScoringMixin):
         """dP (+)= Onehot^T dz over K token rows: one split-K MFMA GEMM (no atomics). side: on the second stream; returns its event."""
         d = self.d
         which = 1 if side else 0
-        need = 16 * ops.TAB_TOTAL * d
+        need = 16 * self.lay.tab_total * d
         if self._slabs_oh[which] is None:
             self._slabs_oh[which] = torch.empty(need, dtype=torch.float32, device=self.device)
-        one = lambda b, acc: ops.gemm(onehot, b, self.dptab, M=ops.TAB_TOTAL, N=d, K=K, dtype=PB_BF16, a_kc=False, b_kc=False, lda=ops.TAB_TOTAL, ldb=d,
+        one = lambda b, acc: ops.gemm(onehot, b, self.dptab, M=self.lay.tab_total, N=d, K=K, dtype=PB_BF16, a_kc=False, b_kc=False, lda=self.lay.tab_total, ldb=d,
                                       dbg=self._bwd_dbg(), ldc=d, c_f32=True, accum=acc, splitk=16, slabs=self._slabs_oh[which], tile256=True)
         if self.x3:
             # the one-hot matrix is exact in bf16, so the split-bf16 product is Onehot^T dz_hi + Onehot^T dz_lo: two bf16 GEMMs over dz's two planes (the exact-f32
@@ -1041,10 +1042,10 @@ class Engine(GenerationMixin, ScoringMixin):
         """dlogits (T,1280) storage dtype -> head grads + grad wrt decoder hidden (returned in ws['gy'][0])."""
         ws, g, T, d = self._cur_ws, self.g, dlogits.shape[0], self.d
         self._ensure_wT()
-        ops.colsum(dlogits, g['head.b'], self.partials, T, ops.VOCAB)
-        self._wgrad(dlogits, dec_hidden, 'head.w', ops.VOCAB, d, T)
+        (ops.colsum if self.lay.vocab % 4 == 0 else ops.colsum_any)(dlogits, g['head.b'], self.partials, T, self.lay.vocab)   # a total that is no multiple of 4: one column per thread
+        self._wgrad(dlogits, dec_hidden, 'head.w', self.lay.vocab, d, T)
         gy = ws['gy'][0][:T]
-        self._dgrad(dlogits, 'head.w', gy, T, d, ops.VOCAB, False)
+        self._dgrad(dlogits, 'head.w', gy, T, d, self.lay.vocab, False)
         self._ready('head.w')
         return gy
 
@@ -1119,7 +1120,7 @@ class Engine(GenerationMixin, ScoringMixin):
             ids16 = ids16.clone()
         if getattr(self, '_id_flag', None) is None or self._id_flag.device != ids16.device:
             self._id_flag = torch.zeros(1, dtype=torch.int32, device=ids16.device)
-            self._id_lim = torch.tensor(ops.SEG_SIZES, dtype=torch.int32, device=ids16.device)
+            self._id_lim = torch.tensor(list(self.lay.sizes), dtype=torch.int32, device=ids16.device)
         ops.ids_check(ids16, self._id_lim, self._id_flag)
         return ids16
 
@@ -1137,7 +1138,7 @@ class Engine(GenerationMixin, ScoringMixin):
                 dist.all_reduce(self._id_flag, op=dist.ReduceOp.MAX)
         if getattr(self, '_id_flag', None) is not None and int(self._id_flag.item()) != 0:
             self._id_flag.zero_()
-            raise IndexError('index out of range in self: an Octuple id lies outside its embedding table (sizes %s)' % ops.SEG_SIZES)
+            raise IndexError('index out of range in self: an Octuple id lies outside its embedding table (sizes %s)' % list(self.lay.sizes))
 
     def _queue_id_verdict(self):
         """The fused step does not drain the stream: the mark of note_ids travels to pinned memory behind an event and is read by
@@ -1166,7 +1167,7 @@ class Engine(GenerationMixin, ScoringMixin):
             if int(pin[0]) != 0:
                 q.clear()
                 self._id_flag.zero_()
-                raise IndexError('index out of range in self: an Octuple id lies outside its embedding table (sizes %s)' % ops.SEG_SIZES)
+                raise IndexError('index out of range in self: an Octuple id lies outside its embedding table (sizes %s)' % list(self.lay.sizes))
 
     def _next_seed(self):
         self._seed = (self._seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
@@ -1239,7 +1240,7 @@ class Engine(GenerationMixin, ScoringMixin):
             count_hook(counts)
         ops.loss_coef(counts, self.loss_w if head_w is None else head_w, coef, w_scale)
         dlogits = ws['dlogits'][:logits.shape[0]] if train else None
-        ops.ce_fwd_bwd(logits, tgt, lm, sums, self.partials, coef, dlogits, argmax_out)
+        ops.ce_fwd_bwd(logits, tgt, lm, sums, self.partials, coef, dlogits, argmax_out, layout=self.lay)
         if train:
             self._micro = micro
             try:
@@ -1381,7 +1382,7 @@ class _LMFn(torch.autograd.Function):
         logits = eng.heads_forward(dec_h)
         eng._fwd_token += 1
         ctx.eng, ctx.token = eng, eng._fwd_token
-        out = logits.view(B, S, ops.VOCAB)
+        out = logits.view(B, S, eng.lay.vocab)
         return out.clone()        # the workspace buffer is overwritten by the next forward
 
     @staticmethod
@@ -1395,7 +1396,7 @@ class _LMFn(torch.autograd.Function):
         p0 = eng.params[0]
         alias = p0.grad is not None and p0.grad.data_ptr() == eng.grad_views[0].data_ptr()
         eng._select_grads(alias)
-        dl = dlogits.reshape(T, ops.VOCAB).contiguous()
+        dl = dlogits.reshape(T, eng.lay.vocab).contiguous()
         if eng.xdt == torch.float32:
             dlx = dl.float()
         else:

@@ -25,7 +25,7 @@ the other attributes (generation.keep_mask with start = k_b -> PianoBartLM.gener
 shape and dtype it has without the flag, and without the flag it is byte-identical. --score still scores all 8 heads of a position.
 
 Bar-bounded generation (--bars N): every row also stops at a bar -- generation.stop_after_bars of its prime (q = the bar of the prime's last
-row, -1 without --prime; the stop bar is min(q + 1 + N, 256)), so the row finishes the bar it is in and writes N whole new bars
+row, -1 without --prime; the stop bar is min(q + 1 + N, the bar PAD id), 256 in the default dictionary), so the row finishes the bar it is in and writes N whole new bars
 (PianoBartLM.generate_batch's decoder_stop). Works with and without --prime and with --keep, --samples, --refill, --score and --pick.
 
 Infilling (--infill LO:HI [--infill_mode rows|span], needs --seed): bars LO .. HI-1 of every piece are rewritten and the rest is left alone.
@@ -135,7 +135,8 @@ def parse_prime(value):
 
 
 def parse_infill(value, bar_pad=256):
-    """--infill -> None or (lo, hi) with 0 <= lo < hi <= bar_pad; PBError otherwise."""
+    """--infill -> None or (lo, hi) with 0 <= lo < hi <= bar_pad; PBError otherwise. bar_pad: the bar head's PAD id of the dictionary in use
+    (model.pianobart.bar_pad_word; 256 = the default dictionary's); None = no upper bound (check_args, before the dictionary is read)."""
     if value is None:
         return None
     parts = str(value).split(':')
@@ -143,8 +144,8 @@ def parse_infill(value, bar_pad=256):
         lo, hi = (int(v) for v in parts) if len(parts) == 2 else (-1, -1)
     except ValueError:
         lo, hi = -1, -1
-    if not 0 <= lo < hi <= bar_pad:
-        raise PBError('--infill takes LO:HI, two bar ids with 0 <= LO < HI <= %d (got %r)' % (bar_pad, value))
+    if not 0 <= lo < hi or (bar_pad is not None and hi > bar_pad):
+        raise PBError('--infill takes LO:HI, two bar ids with 0 <= LO < HI <= %s (got %r)' % ('the bar PAD id' if bar_pad is None else '%d' % bar_pad, value))
     return lo, hi
 
 
@@ -179,7 +180,7 @@ def check_args(args):
     if getattr(args, 'bars', None) is not None and getattr(args, 'score_dataset', False):
         raise PBError('--score_dataset generates nothing: it takes no --bars')
     if getattr(args, 'infill', None) is not None:
-        parse_infill(args.infill)
+        parse_infill(args.infill, None)                  # the form; run() checks the bars against the dictionary's bar PAD id
         if args.seed is None:
             raise PBError('--infill needs --seed: the pieces are generated side by side, each from its own RandomState(seed + i)')
         for flag in ('prime', 'keep', 'bars'):

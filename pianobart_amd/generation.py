@@ -128,14 +128,16 @@ def check_stop(stop, P, pad0, owner=None):
     return vals if owner is None else [vals[p] for p in owner]
 
 
-def check_order(order, P, owner=None):
+def check_order(order, P, owner=None, order_max=None):
     """The argument rules of time-ordered generation, on the host before any device work. order: P ints (list, array or tensor on any
-    device), one per prompt: -1 = row p is sampled as ever, 0 .. ORDER_MAX = row p is time-ordered with that bar floor (0: ordered, no
-    extra floor). owner (row -> prompt, check_samples): the list is expanded to one entry per output row. Returns a list of ints, P or R
-    long; None for order=None or a list that is -1 everywhere (no order: the caller runs what it ran before). Raises PBError for a
-    wrong length, a non-integer or a value outside -1 .. ORDER_MAX."""
+    device), one per prompt: -1 = row p is sampled as ever, 0 .. order_max = row p is time-ordered with that bar floor (0: ordered, no
+    extra floor). order_max = the dictionary's last bar id, pad[0] - 1 (None: ORDER_MAX, the default dictionary's). owner (row -> prompt,
+    check_samples): the list is expanded to one entry per output row. Returns a list of ints, P or R long; None for order=None or a list
+    that is -1 everywhere (no order: the caller runs what it ran before). Raises PBError for a wrong length, a non-integer or a value
+    outside -1 .. order_max."""
     if order is None:
         return None
+    order_max = ORDER_MAX if order_max is None else int(order_max)
     try:
         vals = order.tolist() if hasattr(order, 'tolist') else list(order)
     except TypeError:
@@ -145,15 +147,15 @@ def check_order(order, P, owner=None):
     for p, v in enumerate(vals):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise PBError('order[%d] = %r is not an integer' % (p, v))
-        if not -1 <= v <= ORDER_MAX:
-            raise PBError('order[%d] = %d outside -1 .. %d (a bar floor; -1 = not ordered)' % (p, v, ORDER_MAX))
+        if not -1 <= v <= order_max:
+            raise PBError('order[%d] = %d outside -1 .. %d (a bar floor; -1 = not ordered)' % (p, v, order_max))
     if all(int(v) == -1 for v in vals):
         return None
     vals = [int(v) for v in vals]
     return vals if owner is None else [vals[p] for p in owner]
 
 
-ORDER_MAX = 255                    # the last bar id: for heads 0 and 1 the ids ARE the values (Bar k = k, Position k/64 = k in octuple_vocab.json)
+ORDER_MAX = 255                    # the default dictionary's last bar id: for heads 0 and 1 the ids ARE the values (Bar k = k, Position k/64 = k in octuple_vocab.json)
 
 
 def ordered_token(frow, sample, floor, prev, pad):
@@ -379,7 +381,24 @@ def sample_seed(seed, j, i, N):
     return int(seed) + int(j) * int(N) + int(i)
 
 
+def sampler_form_for(sizes, p):
+    """The rule of pb_batch_decoder_sampler_init, stated on the host: which device sampler a decoder with these 8 head sizes and nucleus
+    thresholds gets. 'narrow' while every head has <= 272 classes (its LDS rows) AND the heads with p < 1 hold at most 512 classes together
+    (it ranks them with one thread each), else 'wide' (heads up to 1088 classes, the rank counting in rounds of 512 threads). Every legal
+    dictionary (ops.Layout) gets one of the two: none is refused at generation time."""
+    ranked = sum(int(n) for n, q in zip(sizes, p) if float(q) < 1.0)
+    return 'wide' if max(int(n) for n in sizes) > 272 or ranked > 512 else 'narrow'
+
+
 class GenerationMixin:
+    last_sampler_form = None            # 'narrow' / 'wide': the device sampler of the last device-sampled decode (None: there was none yet)
+
+    def _note_sampler_form(self, dec):
+        """Which device sampler the decoder's steps ended with: 'narrow' (the default dictionary) or 'wide' (sampler_form_for's rule). Kept
+        in `last_sampler_form`; `last_decode` names it only when it is the wide one, so the default dictionary's record keeps its keys."""
+        self.last_sampler_form = 'wide' if int(LIB.query('pb_batch_decoder_sampler_form', dec)) else 'narrow'
+        return dict(sampler_form='wide') if self.last_sampler_form == 'wide' else {}
+
     # ------------------------------------------------------------------ generate (model.py:28-66)
     def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
@@ -412,10 +431,10 @@ class GenerationMixin:
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
-        forced = check_forced(forced, 1, S, ops.SEG_SIZES, ks)
+        forced = check_forced(forced, 1, S, list(self.lay.sizes) if forced is not None else None, ks)
         stop = check_stop([stop] if isinstance(stop, (int, np.integer)) and not isinstance(stop, bool) else stop, 1, int(self.pb.pad_word_np[0]))
         sb = stop[0] if stop is not None else None
-        order = check_order([order] if isinstance(order, (int, np.integer)) and not isinstance(order, bool) else order, 1)
+        order = check_order([order] if isinstance(order, (int, np.integer)) and not isinstance(order, bool) else order, 1, order_max=int(self.pb.pad_word_np[0]) - 1)
         ob = order[0] if order is not None else None
         fr = forced[0] if forced is not None else None
         k = ks[0]
@@ -449,7 +468,7 @@ class GenerationMixin:
                 if k:
                     tok16.copy_(pre[k - 1].to(torch.int16))                     # the input of position k: the prefix's last row
                 tok_pin = torch.empty(8, dtype=torch.int16).pin_memory()         # one small H2D per position; the result goes up once at the end
-                logit_pin = torch.empty(ops.VOCAB, dtype=torch.float32).pin_memory()
+                logit_pin = torch.empty(self.lay.vocab, dtype=torch.float32).pin_memory()
                 sv = stop_vector(pad_cpu, sb)
                 prev = pre[k - 1] if k else torch.from_numpy(self.pb.sos_word_np)
                 for i in range(k, S):
@@ -586,13 +605,13 @@ class GenerationMixin:
         e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
         bufs = dict(kvc=[e(B if G is None else G, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
                     rows={n: e(B, d) for n in ('x', 'y1', 'yc', 'y2', 'q', 'ctx', 'a')}, g=e(B, ff), stat=e(8, dt=torch.float32),
-                    logits=e(B, ops.VOCAB, dt=torch.float32), tok16=torch.tensor(self.pb.sos_word_np, dtype=torch.int16, device=dev),
+                    logits=e(B, self.lay.vocab, dt=torch.float32), tok16=torch.tensor(self.pb.sos_word_np, dtype=torch.int16, device=dev),
                     attn_part=e(B * self.H * 16 * (self.hd + 4), dt=torch.float32))      # PB_DECODE_MAX_SPLITS records per (row, head)
         bp = DecodeBatch()
         plan = bp.plan
-        plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), self.ND, ops.VOCAB
+        plan.dtype, plan.d, plan.H, plan.ffn, plan.S, plan.S_enc, plan.n_layers, plan.vocab = self.code, d, self.H, ff, S, max(s_enc), self.ND, self.lay.vocab
         for k in range(9):
-            plan.tab_off[k] = ops.TAB_OFF[k]
+            plan.tab_off[k] = self.lay.tab_off[k]
         P = lambda t: t.data_ptr()
         plan.tok16, plan.ptab, plan.lin_b, plan.pos = P(bufs['tok16']), P(self.ptab), P(wf['lin.b']), P(wf['dec.pos'])
         plan.lne_w, plan.lne_b, plan.enc_mask = P(wf['dec.lne.w']), P(wf['dec.lne.b']), (P(em) if em is not None else None)
@@ -638,7 +657,7 @@ class GenerationMixin:
         if k:
             last = np.asarray([k - 1], dtype=np.int32)
             LIB.call('pb_batch_decoder_start', dec, last.ctypes.data, tok_np.ctypes.data, None)
-        logit_cpu = torch.empty(ops.VOCAB, dtype=torch.float32)
+        logit_cpu = torch.empty(self.lay.vocab, dtype=torch.float32)
         tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
         n = 0
         t_loop = time.perf_counter()
@@ -702,10 +721,10 @@ class GenerationMixin:
         slots = check_refill(refill, samples, self.BATCH_MAX)
         owner = check_samples(samples, P, len(rngs)) if samples is not None else list(range(P))        # row -> prompt
         ks, rows = check_prefix(prefix, prefix_len, P, int(enc_ids.shape[1]), self.pb.pad_word_np)
-        forced = check_forced(forced, P, int(enc_ids.shape[1]), ops.SEG_SIZES, ks)
+        forced = check_forced(forced, P, int(enc_ids.shape[1]), list(self.lay.sizes) if forced is not None else None, ks)
         pad0 = int(self.pb.pad_word_np[0])
         stop = check_stop(stop, P, pad0, owner if samples is not None else None)         # one entry per output row
-        order = check_order(order, P, owner if samples is not None else None)            # ... and here
+        order = check_order(order, P, owner if samples is not None else None, order_max=pad0 - 1)            # ... and here
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -827,7 +846,7 @@ class GenerationMixin:
         from concurrent.futures import ThreadPoolExecutor
         from .refill import RefillSchedule
         R, S, dev = int(enc16.shape[0]), int(enc16.shape[1]), enc16.device
-        K, vocab = 8, ops.VOCAB
+        K, vocab = 8, self.lay.vocab
         LIB.call('pb_batch_decoder_dynamic', dec, NS)
         sched = RefillSchedule(R, n, NS)
         res_cpu = pad_cpu.repeat(R, S, 1)
@@ -877,8 +896,8 @@ class GenerationMixin:
             return np.ascontiguousarray((res_cpu[r, ks[r] - 1].numpy() if ks[r] else np.asarray(self.pb.sos_word_np)).astype(np.int16))
 
         fault = getattr(self, 'decode_fault_row', None) or (-1, 0)         # tests: the device's choice of one SLOT corrupted
-        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
-        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
+        n8 = np.asarray(self.lay.sizes, dtype=np.int32)
+        off8 = np.asarray(self.lay.seg_off[:8], dtype=np.int32)
         pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
         t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
         U = np.ascontiguousarray(np.stack([draws(r) for r in range(n)]))
@@ -1020,7 +1039,7 @@ class GenerationMixin:
         assert sched.done(), (sched.finished, R)
         self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                                 tokens=tokens, rewinds=rewinds, steps=stat['steps'], row_steps=stat['row_steps'], loop_ms=(time.perf_counter() - t_loop) * 1e3,
-                                host_ms=stat['host_s'] * 1e3, device_sampler=True, tokens_per_graph_replay=K, refill=n, slices=NS,
+                                host_ms=stat['host_s'] * 1e3, device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, refill=n, slices=NS,
                                 admissions=counts['admissions'], row_slot=row_slot, encoder_passes=counts['encoder_passes'], s_enc=s_enc, batched=True, batch=n,
                                 prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms, ended=ended,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
@@ -1057,7 +1076,7 @@ class GenerationMixin:
         import ctypes
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
-        K, vocab = 8, ops.VOCAB
+        K, vocab = 8, self.lay.vocab
         starts = list(starts) if starts is not None else [0] * B
         lim = [S if max_new is None else max(0, min(S, k + int(max_new))) for k in starts]
         limit = max(lim)
@@ -1066,8 +1085,8 @@ class GenerationMixin:
             ahead = np.random.RandomState()
             ahead.set_state(states[b])
             U[b] = forced_draws(ahead, forced[b] if forced is not None else None, starts[b], S).reshape(-1)
-        n8 = np.asarray([ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)], dtype=np.int32)
-        off8 = np.asarray(ops.SEG_OFF[:8], dtype=np.int32)
+        n8 = np.asarray(self.lay.sizes, dtype=np.int32)
+        off8 = np.asarray(self.lay.seg_off[:8], dtype=np.int32)
         pad8 = np.asarray(self.pb.pad_word_np, dtype=np.int32)
         t8, p8 = np.asarray(sampler['T'], dtype=np.float32), np.asarray(sampler['P'], dtype=np.float32)
         LIB.call('pb_batch_decoder_sampler_init', dec, t8.ctypes.data, p8.ctypes.data, n8.ctypes.data, off8.ctypes.data, pad8.ctypes.data,
@@ -1154,7 +1173,7 @@ class GenerationMixin:
                             sp[b][0] = sp[b][1] = i + 1
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
-                    device_sampler=True, tokens_per_graph_replay=K, ended=ended)
+                    device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, ended=ended)
 
     def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
@@ -1181,13 +1200,13 @@ class GenerationMixin:
             x, q, ctx, a, y1, qc, ctxc, yc, y2 = (e(1, d) for _ in range(9))
             u, g = e(1, ff), e(1, ff)
             mr = f(8)
-            logits = f(1, ops.VOCAB)
+            logits = f(1, self.lay.vocab)
             save = dict(lse=f(1, H, 1)) if self.use_flash else dict(P=e(1, H, 1, S))
             cur = torch.tensor(pb.sos_word_np, device=dev).reshape(1, 1, 8)
             for i in range(S):
                 tok16 = ops.ids_to_i16(cur)
                 ops.embed_ln_fwd(tok16.reshape(1, 8), self.ptab, wf['lin.b'], wf['dec.pos'][i:], wf['dec.lne.w'], wf['dec.lne.b'], x,
-                                 mr[0:1], mr[1:2], 1, LN_EPS, 0, 0, 0.0, padded=True)
+                                 mr[0:1], mr[1:2], 1, LN_EPS, 0, 0, 0.0, padded=True, layout=self.lay)
                 h = x
                 for l in range(self.ND):
                     pf = 'dec.%d.' % l
@@ -1212,7 +1231,7 @@ class GenerationMixin:
                     continue
                 frow = fr[i] if fr is not None else None
                 if frow is None or (frow < 0).any():
-                    ops.gemm(h, self.w['head.w'], logits, M=1, N=ops.VOCAB, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
+                    ops.gemm(h, self.w['head.w'], logits, M=1, N=self.lay.vocab, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
                 tok = ordered_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), order,
                                     cur.reshape(8).cpu() if order is not None else None, pad_cpu)
                 if (tok >= sv).any():

@@ -169,6 +169,8 @@ class PianoBart(nn.Module):
     def __init__(self, bartConfig, e2w, w2e, precision='bf16'):
         super().__init__()
         _check_cfg(bartConfig)
+        # the vocabulary layout is the dictionary's (ops.Layout): an illegal dictionary is refused here, by head and rule, before any device work
+        object.__setattr__(self, 'layout', ops.Layout.from_dict(e2w))
         self.bart = _BartParams(bartConfig)
         self.hidden_size = bartConfig.d_model
         self.bartConfig = bartConfig
@@ -176,8 +178,6 @@ class PianoBart(nn.Module):
         self.classes = list(CLASSES)
         for key in self.classes:
             self.n_tokens.append(len(e2w[key]))
-        if self.n_tokens != ops.SEG_SIZES:
-            raise PBError('vocabulary sizes %s differ from the Octuple layout compiled into the kernels' % self.n_tokens)
         self.emb_sizes = [256] * 8
         self.e2w = e2w
         self.w2e = w2e
@@ -235,7 +235,7 @@ class PianoBart(nn.Module):
 
 
 class MLM(nn.Module):
-    """model.py:109-126 (parameter holder; the 8 heads run as one fused d x 1280 GEMM)."""
+    """model.py:109-126 (parameter holder; the 8 heads run as one fused d x vocab GEMM, vocab = 1280 for the default dictionary)."""
 
     def __init__(self, e2w, n_tokens, hidden_size):
         super().__init__()
@@ -272,13 +272,18 @@ def nucleus(probs, p):
 _SAMPLE_TLS = threading.local()
 
 
-def _sample_tables():
-    """Constants and scratch of PianoBartLM.sample_row: per-element temperatures, the (8, 272) probability rows, the native call's arrays.
-    One set per thread: Engine.generate_batch verifies the rows of a batch on a small thread pool."""
-    tab = getattr(_SAMPLE_TLS, 'tab', None)
+def _sample_tables(layout=None):
+    """Constants and scratch of PianoBartLM.sample_row for one vocabulary layout: per-element temperatures, the (8, width) probability rows
+    (width = the largest head rounded up to 16: 272 for the default dictionary), the native call's arrays. One set per thread and layout:
+    Engine.generate_batch verifies the rows of a batch on a small thread pool."""
+    layout = layout or ops.DEFAULT_LAYOUT
+    tabs = getattr(_SAMPLE_TLS, 'tabs', None)
+    if tabs is None:
+        tabs = _SAMPLE_TLS.tabs = {}
+    tab = tabs.get(layout)
     if tab is None:
-        tab = _SAMPLE_TLS.tab = {}
-        n = [ops.SEG_OFF[j + 1] - ops.SEG_OFF[j] for j in range(8)]
+        tab = tabs[layout] = {}
+        n = list(layout.sizes)
         width = (max(n) + 15) // 16 * 16
         n_a, p_a = np.asarray(n, dtype=np.int32), np.asarray(PianoBartLM.SAMPLE_P, dtype=np.float32)
         tab.update(n_a=n_a, p_a=p_a, n_p=n_a.ctypes.data, p_p=p_a.ctypes.data, out=np.zeros(8, dtype=np.int32), tie=np.zeros(1, dtype=np.int32))
@@ -355,11 +360,11 @@ class PianoBartLM(nn.Module):
         special); a position with a free head draws its 8 uniforms as ever (the draws of its given heads are consumed and unused), a
         position whose 8 heads are given draws nothing; a given id may be any id of its head's table (IndexError otherwise); positions
         inside decoder_prefix must be -1 (PBError). None, or -1 everywhere, is the call without the argument.
-        decoder_stop (a bar id 0 .. 256, or a sequence of one; generate=True only): stop at a bar -- the reference loop with its stop test
+        decoder_stop (a bar id 0 .. the bar head's PAD id, 256 in the default dictionary, or a sequence of one; generate=True only): stop at a bar -- the reference loop with its stop test
         `(current_output >= pad).any()` replaced by `(current_output >= pad).any() or current_output[0] >= decoder_stop`. The test sees the
         token after forcing; the token that trips it is not written and its draws are consumed; positions inside decoder_prefix are not
         tested (generation.stop_after_bars turns "n more bars" into the bar id). 256 (the bar head's PAD id), or None: no stop.
-        decoder_order (-1 .. 255, or a sequence of one; generate=True only): time-ordered sampling -- the reference loop with `current_output
+        decoder_order (-1 .. the bar head's PAD id - 1, 255 in the default dictionary, or a sequence of one; generate=True only): time-ordered sampling -- the reference loop with `current_output
         = self.sample(x, i)` replaced by a sample whose (bar, position) never goes back. With prev = the decoder's input row of position i
         (the SOS row, the prefix's last row, else the previous token after forcing): bars below max(decoder_order, prev's bar) have
         probability 0, and so have positions below prev's position while the bar (after forcing) stays prev's. Special ids stay
@@ -377,7 +382,8 @@ class PianoBartLM(nn.Module):
                 raise PBError('decoder_order constrains what a generated piece samples: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
-            return [logits[..., ops.SEG_OFF[i]:ops.SEG_OFF[i + 1]] for i in range(8)]
+            off = self.pianobart.layout.seg_off
+            return [logits[..., off[i]:off[i + 1]] for i in range(8)]
         if input_ids_encoder.shape[0] != 1:
             print("ERROR")
             exit(-1)
@@ -456,7 +462,7 @@ class PianoBartLM(nn.Module):
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
     def sample_row(self, row_logits, rng=None, order=None):
-        """row_logits: (1280,) f32 CPU tensor of one position; returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
+        """row_logits: (vocab,) f32 CPU tensor of one position (1280 for the default dictionary); returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
         on the host row -- the division by the temperature (one call with a per-element temperature vector: the same quotients) and a
         1-D softmax per head -- then nucleus() for all 8 heads in one native call (pb_nucleus_rows: numpy's arithmetic order and
         precision; ties among candidates go back to the numpy code), fed the 8 uniform draws np.random.choice would have made. Checked
@@ -467,13 +473,15 @@ class PianoBartLM(nn.Module):
         classes below `low` are set to -inf in front of the softmax (probability exactly 0). If low1 > 0 and head 0's id after forcing
         (given0 if >= 0, else the id just sampled) equals prev0, head 1's classes below low1 are masked the same way and head 1 is sampled
         again with the same u[1]. One random_sample(8) either way; without `order` the arithmetic and the native call are unchanged."""
-        tab = _sample_tables()
+        lay = getattr(getattr(self, 'pianobart', None), 'layout', None) or ops.DEFAULT_LAYOUT      # called on the class itself: the default dictionary
+        tab = _sample_tables(lay)
+        off = lay.seg_off
         y = row_logits / tab['tvec']
         probs = tab['probs']
         if order is not None and order[0] > 0:
-            y[ops.SEG_OFF[0]:ops.SEG_OFF[0] + order[0]] = -np.inf
+            y[off[0]:off[0] + order[0]] = -np.inf
         for j in range(8):                                           # 1-D calls: a 2-D softmax would open an OpenMP region per position
-            torch.softmax(y[ops.SEG_OFF[j]:ops.SEG_OFF[j + 1]], dim=-1, out=probs[j, :tab['n'][j]])
+            torch.softmax(y[off[j]:off[j + 1]], dim=-1, out=probs[j, :tab['n'][j]])
         # the 8 draws np.random.choice would make, in head order (RandomState fills a request sequentially: the same stream as 8 calls)
         u = np.random.random_sample(8) if rng is None else rng.random_sample(8)
         out, tie = tab['out'], tab['tie']
@@ -486,8 +494,8 @@ class PianoBartLM(nn.Module):
         if order is not None and order[2] > 0 and (order[3] if order[3] >= 0 else int(out[0])) == order[1]:
             # the token stays in its predecessor's bar: head 1 again, from the masked quotients, with the draw it had (the other rows of
             # `probs` are untouched, so their ids come out as they did)
-            y[ops.SEG_OFF[1]:ops.SEG_OFF[1] + order[2]] = -np.inf
-            torch.softmax(y[ops.SEG_OFF[1]:ops.SEG_OFF[2]], dim=-1, out=probs[1, :tab['n'][1]])
+            y[off[1]:off[1] + order[2]] = -np.inf
+            torch.softmax(y[off[1]:off[2]], dim=-1, out=probs[1, :tab['n'][1]])
             head1 = out.copy()
             LIB.call('pb_nucleus_rows', probs.data_ptr(), probs.shape[1], tab['n_p'], tab['p_p'], u.ctypes.data, 8, head1.ctypes.data, tie.ctypes.data)
             out[1] = _nucleus_with_draw(probs.numpy()[1, :tab['n'][1]], self.SAMPLE_P[1], u[1]) if tie[0] >> 1 & 1 else head1[1]

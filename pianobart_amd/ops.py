@@ -9,18 +9,113 @@ import torch
 from ._lib import (LIB, PB_BF16, PB_F32, PB_F32X3, AttnDesc, GemmDesc, PBError, GEMM_ACCUM, GEMM_C_F32, GEMM_GELU,
                    GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS)
 
-SEG_SIZES = [262, 134, 135, 262, 134, 38, 260, 55]          # PianoBart.classes order
-SEG_OFF = [0]
-for _n in SEG_SIZES:
-    SEG_OFF.append(SEG_OFF[-1] + _n)
-VOCAB = SEG_OFF[-1]                                         # 1280
-_SEG9 = (ctypes.c_int32 * 9)(*SEG_OFF)
+CLASS_NAMES = ('Bar', 'Position', 'Instrument', 'Pitch', 'Duration', 'Velocity', 'TimeSig', 'Tempo')   # PianoBart.classes order
+SPECIAL_TAGS = ('PAD', 'MASK', 'SOS', 'EOS', 'CLS', 'SEP')  # the six special ids of a head: its last six, in this order
+HEAD_MIN, HEAD_MAX = 7, 64 * 17                             # six specials and one class .. the wide sampler / score kernels' 17 classes per lane
+
+
+class Layout:
+    """The vocabulary layout of one Octuple dictionary: a property of the model, handed to the kernels at run time (they take segment
+    offsets, sizes and pad ids as arguments). sizes: the 8 head sizes in CLASS_NAMES order; specials: per head the six special ids
+    (SPECIAL_TAGS order), None = the last six of the head. Immutable. A head outside HEAD_MIN .. HEAD_MAX classes, or specials that
+    are not the head's last six ids with PAD first, raise PBError here: on the host, before any device work.
+      seg_off[9]   start of every head in a logits row (seg_off[8] = vocab, the row's width and stride)
+      tab_rows     rows of one slot of the projected Octuple table: the largest head rounded up to a multiple of 8, so the per-stream
+                   table GEMMs are ONE batched launch with uniform strides; tab_off[9] / tab_total = 8 such slots
+      pad8         the first special id of every head (an id >= pad8[h] ends a generated piece)
+      seg9 / tab9  seg_off / tab_off as ctypes int32[9]"""
+    _FIELDS = ('sizes', 'specials', 'seg_off', 'vocab', 'tab_rows', 'tab_off', 'tab_total', 'pad8', 'seg9', 'tab9')
+    __slots__ = _FIELDS + ('_hash',)
+
+    def __init__(self, sizes, specials=None):
+        try:
+            sizes = tuple(int(n) for n in sizes)
+        except (TypeError, ValueError):
+            raise PBError('Layout: sizes must be 8 integers (got %r)' % (sizes,))
+        if len(sizes) != 8:
+            raise PBError('Layout: %d heads; the Octuple layout has 8 (%s)' % (len(sizes), ', '.join(CLASS_NAMES)))
+        for h, n in enumerate(sizes):
+            if not HEAD_MIN <= n <= HEAD_MAX:
+                raise PBError('Layout: head %d (%s) has %d classes; a head needs %d .. %d (its six special ids and at least one class; '
+                              'the kernels hold at most 64 x 17 classes of a head)' % (h, CLASS_NAMES[h], n, HEAD_MIN, HEAD_MAX))
+        if specials is None:
+            specials = [range(n - 6, n) for n in sizes]
+        specials = tuple(tuple(int(v) for v in sp) for sp in specials)
+        if len(specials) != 8:
+            raise PBError('Layout: special ids of %d heads for 8' % len(specials))
+        for h, (n, sp) in enumerate(zip(sizes, specials)):
+            if sp != tuple(range(n - 6, n)):
+                raise PBError('Layout: head %d (%s): the special ids <%s> = %s must be the last six ids of the head, %d .. %d in this order '
+                              '(the stop rule is "an id >= <PAD>")' % (h, CLASS_NAMES[h], '> <'.join(SPECIAL_TAGS), list(sp), n - 6, n - 1))
+        seg_off = [0]
+        for n in sizes:
+            seg_off.append(seg_off[-1] + n)
+        tab_rows = (max(sizes) + 7) // 8 * 8
+        tab_off = tuple(tab_rows * i for i in range(9))
+        for k, v in zip(self._FIELDS, (sizes, specials, tuple(seg_off), seg_off[-1], tab_rows, tab_off, tab_off[8], tuple(sp[0] for sp in specials),
+                                       (ctypes.c_int32 * 9)(*seg_off), (ctypes.c_int32 * 9)(*tab_off))):
+            object.__setattr__(self, k, v)
+        object.__setattr__(self, '_hash', hash((sizes, specials)))      # a layout keys per-thread scratch on the sampling path
+
+    @classmethod
+    def from_dict(cls, e2w):
+        """The layout of a dictionary's event -> word half (the reference's e2w): 8 classes under the reference's names, each with its six
+        special words '<class> <TAG>'. PBError names the class and the rule that a dictionary breaks."""
+        try:
+            keys = list(e2w.keys())
+        except AttributeError:
+            raise PBError('Layout: the dictionary must map class names to {word: id} tables (got %s)' % type(e2w).__name__)
+        if len(keys) != 8 or set(keys) != set(CLASS_NAMES):
+            raise PBError('Layout: the dictionary has the classes %s; the Octuple layout needs exactly %s' % (keys, list(CLASS_NAMES)))
+        sizes, specials = [], []
+        for h, name in enumerate(CLASS_NAMES):
+            tab = e2w[name]
+            sizes.append(len(tab))
+            sp = []
+            for tag in SPECIAL_TAGS:
+                word = '%s <%s>' % (name, tag)
+                if word not in tab:
+                    raise PBError('Layout: head %d (%s) has no special word %r (every head needs <%s>)' % (h, name, word, '> <'.join(SPECIAL_TAGS)))
+                sp.append(int(tab[word]))
+            specials.append(sp)
+        return cls(sizes, specials)
+
+    def __setattr__(self, k, v):
+        raise AttributeError('Layout is immutable')
+
+    __delattr__ = __setattr__
+
+    def __reduce__(self):                # copy / pickle rebuild it (the ctypes arrays do not pickle)
+        return (Layout, (self.sizes, self.specials))
+
+    def __eq__(self, other):
+        return isinstance(other, Layout) and self.sizes == other.sizes and self.specials == other.specials
+
+    def __hash__(self):
+        return self._hash
+
+    def __repr__(self):
+        return 'Layout(sizes=%s)' % list(self.sizes)
+
+
+# Today's dictionary (data/octuple_vocab.json). The module globals below are its fields under their earlier names: the `layout=None` of
+# every wrapper means this one.
+DEFAULT_LAYOUT = Layout([262, 134, 135, 262, 134, 38, 260, 55])
+SEG_SIZES = list(DEFAULT_LAYOUT.sizes)                      # PianoBart.classes order
+SEG_OFF = list(DEFAULT_LAYOUT.seg_off)
+VOCAB = DEFAULT_LAYOUT.vocab                                # 1280
+_SEG9 = DEFAULT_LAYOUT.seg9
 # the projected Octuple table keeps every stream in a fixed 264-row slot (max vocabulary 262, padded to a multiple of 8) so the
 # per-stream table GEMMs are ONE batched launch with uniform strides
-TAB_ROWS = 264
-TAB_OFF = [TAB_ROWS * i for i in range(9)]
-TAB_TOTAL = TAB_OFF[8]                                      # 2112
-_TAB9 = (ctypes.c_int32 * 9)(*TAB_OFF)
+TAB_ROWS = DEFAULT_LAYOUT.tab_rows                          # 264
+TAB_OFF = list(DEFAULT_LAYOUT.tab_off)
+TAB_TOTAL = DEFAULT_LAYOUT.tab_total                        # 2112
+_TAB9 = DEFAULT_LAYOUT.tab9
+
+
+def _off9(layout, padded):
+    layout = layout or DEFAULT_LAYOUT
+    return layout.tab9 if padded else layout.seg9
 
 
 def seg_array(offsets):
@@ -117,25 +212,25 @@ def ids_check(ids16, limits, flag):
     LIB.call('pb_ids_check', _p(ids16), ids16.numel(), _p(limits), _p(flag), _stream())
 
 
-def embed_ln_fwd(ids16, P, lin_bias, pos, ln_w, ln_b, y, mean, rstd, S, eps, seed, site, p_drop, padded=False, row_ids=None):
+def embed_ln_fwd(ids16, P, lin_bias, pos, ln_w, ln_b, y, mean, rstd, S, eps, seed, site, p_drop, padded=False, row_ids=None, layout=None):
     T, d = y.shape
     if row_ids is not None:
-        LIB.call('pb_embed_ln_fwd_packed', _p(ids16), _p(row_ids), _p(P), _TAB9 if padded else _SEG9, _p(lin_bias), _p(pos), _p(ln_w), _p(ln_b),
+        LIB.call('pb_embed_ln_fwd_packed', _p(ids16), _p(row_ids), _p(P), _off9(layout, padded), _p(lin_bias), _p(pos), _p(ln_w), _p(ln_b),
                  _p(y), _p(mean), _p(rstd), T, S, d, dtype_code(y.dtype), eps, seed, site, p_drop, _stream())
         return
-    LIB.call('pb_embed_ln_fwd', _p(ids16), _p(P), _TAB9 if padded else _SEG9, _p(lin_bias), _p(pos), _p(ln_w), _p(ln_b), _p(y), _p(mean),
+    LIB.call('pb_embed_ln_fwd', _p(ids16), _p(P), _off9(layout, padded), _p(lin_bias), _p(pos), _p(ln_w), _p(ln_b), _p(y), _p(mean),
              _p(rstd), T, S, d, dtype_code(y.dtype), eps, seed, site, p_drop, _stream())
 
 
 def embed_ln_bwd(dy, ids16, P, lin_bias, pos, ln_w, mean, rstd, dP, dpos, dbias, dgamma, dbeta, partials, S, seed, site, p_drop,
-                 dz_out=None, padded=False, row_ids=None):
+                 dz_out=None, padded=False, row_ids=None, layout=None):
     T, d = dy.shape
     if row_ids is not None:
-        LIB.call('pb_embed_ln_bwd_packed', _p(dy), _p(ids16), _p(row_ids), _p(P), _TAB9 if padded else _SEG9, _p(lin_bias), _p(pos), _p(ln_w),
+        LIB.call('pb_embed_ln_bwd_packed', _p(dy), _p(ids16), _p(row_ids), _p(P), _off9(layout, padded), _p(lin_bias), _p(pos), _p(ln_w),
                  _p(mean), _p(rstd), _p(dP), _p(dpos), _p(dbias), _p(dgamma), _p(dbeta), _p(partials), _p(dz_out), T, S, d,
                  dtype_code(dy.dtype), seed, site, p_drop, _stream())
         return
-    LIB.call('pb_embed_ln_bwd', _p(dy), _p(ids16), _p(P), _TAB9 if padded else _SEG9, _p(lin_bias), _p(pos), _p(ln_w), _p(mean), _p(rstd),
+    LIB.call('pb_embed_ln_bwd', _p(dy), _p(ids16), _p(P), _off9(layout, padded), _p(lin_bias), _p(pos), _p(ln_w), _p(mean), _p(rstd),
              _p(dP), _p(dpos), _p(dbias), _p(dgamma), _p(dbeta), _p(partials), _p(dz_out), T, S, d, dtype_code(dy.dtype), seed, site,
              p_drop, _stream())
 
@@ -145,8 +240,9 @@ def split_bf16(x, hi, lo):
     LIB.call('pb_split_bf16', _p(x), _p(hi), _p(lo), x.numel(), _stream())
 
 
-def onehot_build(ids16, out, padded=False):
-    LIB.call('pb_onehot_build', _p(ids16), _TAB9 if padded else _SEG9, _p(out), ids16.numel() // 8, TAB_TOTAL if padded else VOCAB, _stream())
+def onehot_build(ids16, out, padded=False, layout=None):
+    layout = layout or DEFAULT_LAYOUT
+    LIB.call('pb_onehot_build', _p(ids16), _off9(layout, padded), _p(out), ids16.numel() // 8, layout.tab_total if padded else layout.vocab, _stream())
 
 
 def batch_sum(x, out, B, Sd):
@@ -180,6 +276,12 @@ def colsum(dy, out, partials, T, N, ld=None):
              PB_F32 if dy.dtype == torch.float32 else PB_BF16, int(dy.dtype == torch.float32), _stream())
 
 
+def colsum_any(dy, out, partials, T, N, ld=None):
+    """colsum for any N and ld (pb_colsum_any: one column per thread); pb_colsum needs multiples of 4."""
+    LIB.call('pb_colsum_any', _p(dy), ld if ld is not None else N, _p(out), _p(partials), T, N,
+             PB_F32 if dy.dtype == torch.float32 else PB_BF16, int(dy.dtype == torch.float32), _stream())
+
+
 def softmax_fwd(scores, key_mask, P, B, H, Sq, Sk, scale, causal):
     LIB.call('pb_softmax_fwd', _p(scores), _p(key_mask), _p(P), B, H, Sq, Sk, scale, int(causal), dtype_code(P.dtype), _stream())
 
@@ -188,17 +290,17 @@ def softmax_bwd(dP, P, dS, rows, Sk, scale):
     LIB.call('pb_softmax_bwd', _p(dP), _p(P), _p(dS), rows, Sk, scale, dtype_code(P.dtype), _stream())
 
 
-def ce_fwd_bwd(logits, target16, loss_mask, sums, partials, coef, dlogits, argmax_out):
+def ce_fwd_bwd(logits, target16, loss_mask, sums, partials, coef, dlogits, argmax_out, layout=None):
     T, V = logits.shape
-    LIB.call('pb_ce_fwd_bwd', _p(logits), _p(target16), _p(loss_mask), _SEG9, _p(sums), _p(partials), _p(coef), _p(dlogits),
+    LIB.call('pb_ce_fwd_bwd', _p(logits), _p(target16), _p(loss_mask), _off9(layout, False), _p(sums), _p(partials), _p(coef), _p(dlogits),
              _p(argmax_out), T, V, dtype_code(dlogits.dtype) if dlogits is not None else PB_F32, _stream())
 
 
-def token_scores(logits, target16, mask, logp, entropy=None, rank=None):
+def token_scores(logits, target16, mask, logp, entropy=None, rank=None, layout=None):
     """pb_token_scores: logits (T, V) f32, target16 (T, 8) int16, mask (T,) f32 of 0 / 1 -> logp / entropy (T, 8) f32, rank (T, 8) int16
     (entropy and rank may be None)."""
     T, V = logits.shape
-    LIB.call('pb_token_scores', _p(logits), _p(target16), _p(mask), _SEG9, _p(logp), _p(entropy), _p(rank), T, V, _stream())
+    LIB.call('pb_token_scores', _p(logits), _p(target16), _p(mask), _off9(layout, False), _p(logp), _p(entropy), _p(rank), T, V, _stream())
 
 
 def seq_scores(logp, entropy, rank, mask, out):

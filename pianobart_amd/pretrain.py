@@ -129,7 +129,7 @@ def _loader_kw(num_workers):
     return kw
 
 
-def make_loaders(X_train, X_val, batch_size, num_workers, seed=None, balance=True):
+def make_loaders(X_train, X_val, batch_size, num_workers, seed=None, balance=True, pad_bar=256):
     """main.py:28-35. One process: the reference's two DataLoaders. Under torchrun `batch_size` stays the GLOBAL batch (what
     nn.DataParallel scatters, pretrain.py:63-65): each rank loads batch_size / world samples per step through a
     DistributedSampler whose per-epoch permutation is seeded identically on every rank (seed drawn on rank 0)."""
@@ -150,7 +150,7 @@ def make_loaders(X_train, X_val, batch_size, num_workers, seed=None, balance=Tru
         if balance:
             # the same global batches, dealt to the ranks by sequence length: the packed step's time follows the kept rows, and the
             # ranks meet at every bucket exchange (data.BalancedDistributedSampler)
-            sampler = BalancedDistributedSampler(sequence_lengths(ds.data), world, rank, batch_size, shuffle=shuffle, seed=seed)
+            sampler = BalancedDistributedSampler(sequence_lengths(ds.data, pad_bar), world, rank, batch_size, shuffle=shuffle, seed=seed)
         else:
             sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed)
         loaders.append(DataLoader(ds, batch_size=batch_size // world, sampler=sampler, **_loader_kw(num_workers)))
@@ -492,7 +492,7 @@ def pretrain(argv=None):
     e2w, w2e = _load_vocab(args.dict_file)
     print("\nLoading Dataset", args.datasets)
     X_train, X_val = load_data_pretrain(datasets=args.datasets, mode="pretrain", root=args.data_root)
-    train_loader, valid_loader = make_loaders(X_train, X_val, args.batch_size, args.num_workers)
+    train_loader, valid_loader = make_loaders(X_train, X_val, args.batch_size, args.num_workers, pad_bar=int(e2w['Bar']['Bar <PAD>']))
     print("   len of train_loader", len(train_loader))
     print("   len of valid_loader", len(valid_loader))
     print("\nBuilding BART model")

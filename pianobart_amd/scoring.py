@@ -123,7 +123,7 @@ class ScoringMixin:
             entropy = torch.empty(B, S, 8, dtype=torch.float32, device=dev)
             rank = torch.empty(B, S, 8, dtype=torch.int16, device=dev)
             sums = torch.empty(B, 4, 8, dtype=torch.float32, device=dev)
-            ops.token_scores(logits, tgt16.view(B * S, 8), mask.view(B * S), logp, entropy, rank)
+            ops.token_scores(logits, tgt16.view(B * S, 8), mask.view(B * S), logp, entropy, rank, layout=self.lay)
             ops.seq_scores(logp, entropy, rank, mask, sums)
         self.check_ids(collective=False)          # a rank may score by itself: local verdict (synchronises; an offending id was read as 0)
         return SimpleNamespace(logp=logp, entropy=entropy, rank=rank, sum_logp=sums[:, 0], sum_entropy=sums[:, 1], hits=sums[:, 2],

@@ -67,6 +67,8 @@ def main(argv=None):
                     'against the same prompts decoded without the stop and cut afterwards')
     ap.add_argument('--ordered', action='store_true', help='also time time-ordered generation at the largest batch, beside the unordered run of the same '
                     'prompts and seeds')
+    ap.add_argument('--sizes', type=int, nargs=8, default=None, metavar='N', help='the 8 head sizes of another dictionary (PianoBart.classes order), e.g. '
+                    '1030 134 135 518 300 38 260 55: a head over 272 classes selects the wide device sampler. Plain --batches runs only')
     ap.add_argument('--bars_log', type=str, default=os.path.join(ROOT, 'profiles', 'bar_stop_b16.jsonl'), help='--bars: the file the lines are appended to')
     args = ap.parse_args(argv)
 
@@ -76,26 +78,34 @@ def main(argv=None):
     from tests.golden_util import load_vocab, synth_octuple_batch
     dev = torch.device('cuda', 0)
     e2w, w2e = load_vocab()
+    sizes = [262, 134, 135, 262, 134, 38, 260, 55]
+    if args.sizes is not None:
+        if args.refill is not None or args.bars is not None or args.samples or args.prime or args.keep or args.ordered:
+            raise SystemExit('--sizes times the plain --batches runs only')
+        from tests.vocab_layout_util import make_dict, synth_batch
+        sizes = list(args.sizes)
+        e2w, w2e = make_dict(sizes)
+    pads = [n - 6 for n in sizes]
     S, d, L, f = args.seq, args.hs, args.layers, args.ffn
     cfg = BartConfig(max_position_embeddings=S, d_model=d, encoder_layers=L, decoder_layers=L, encoder_ffn_dim=f, decoder_ffn_dim=f,
                      encoder_attention_heads=args.heads, decoder_attention_heads=args.heads, dropout=0.0)
     torch.manual_seed(0)
     model = PianoBartLM(PianoBart(cfg, e2w, w2e, precision='bf16')).to(dev).eval()
     with torch.no_grad():
-        for i, p0 in enumerate([256, 128, 129, 256, 128, 32, 254, 49]):
+        for i, p0 in enumerate(pads):
             model.mask_lm.proj[i].bias[p0:] = -30.0
     eng = model._get_engine()
     eng.bind(dev)
     sampler = dict(T=model.SAMPLE_T, P=model.SAMPLE_P)
     Bmax = max(args.batches) if args.refill is None and args.bars is None else args.prompts
-    enc = synth_octuple_batch(Bmax, S, seed=7, min_len=S // 2)[5].to(dev)     # S/2 .. S visible rows, as bench.py's decode prompt
-    emask = (enc[:, :, 0] != 256).float()
+    enc = (synth_octuple_batch(Bmax, S, seed=7, min_len=S // 2) if args.sizes is None else synth_batch(sizes, Bmax, S, seed=7, min_len=S // 2))[5].to(dev)     # S/2 .. S visible rows, as bench.py's decode prompt
+    emask = (enc[:, :, 0] != pads[0]).float()
     steps = min(args.steps, S)
     vis = [int(v) for v in emask.sum(1).tolist()]
 
     # weight bytes a step streams once (bf16): per layer q|k|v, out, q_c, out_c, fc1, fc2; the LM head
     w_layer = (3 * d * d + d * d + d * d + d * d + 2 * d * f) * 2
-    w_bytes = L * w_layer + 1280 * d * 2
+    w_bytes = L * w_layer + sum(sizes) * d * 2
 
     def kv_bytes(rows):                                     # cross K/V over the visible rows + self K/V at the mean position
         return sum(L * (vis[b] + steps / 2) * 2 * d * 2 for b in range(rows))

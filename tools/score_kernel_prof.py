@@ -5,7 +5,8 @@
 
 Both kernels read the row's 5 KB once (one wave per row, register-resident); the score kernel writes 48 B per row (logp, entropy, rank)
 against the ce kernel's 16 B argmax row. The two are launched alternately, every position live (mask of ones), after warm-up launches of
-each; the trace's token_scores_kernel<true> and ce_rows_reg_kernel<float> rows are the comparison (profiles/score_kernel_stats.txt)."""
+each; the trace's token_scores_kernel<true> and ce_rows_reg_kernel<float> rows are the comparison (profiles/score_kernel_stats.txt).
+--sizes N x 8: another dictionary's logits rows (profiles/vocab_layout_kernel_stats.txt: the wide score kernel beside the general ce kernel)."""
 import argparse
 import os
 import sys
@@ -22,13 +23,16 @@ def main():
     ap.add_argument('--rows', type=int, default=16384)
     ap.add_argument('--launches', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--sizes', type=int, nargs=8, default=None, metavar='N', help='the 8 head sizes of another dictionary, e.g. 1030 134 135 518 300 38 260 55: '
+                    'a head over 320 classes selects token_scores_wide_kernel and the general ce_kernel')
     a = ap.parse_args()
+    lay = ops.Layout(a.sizes) if a.sizes else ops.DEFAULT_LAYOUT
     if not torch.cuda.is_available():
         raise SystemExit('score_kernel_prof needs an MI355X: there is no CPU path')
     T = a.rows
     g = torch.Generator(device='cuda').manual_seed(0)
-    logits = 2.0 * torch.randn(T, ops.VOCAB, generator=g, device='cuda')
-    tgt = torch.stack([torch.randint(0, n, (T,), generator=g, device='cuda') for n in ops.SEG_SIZES], 1).to(torch.int16)
+    logits = 2.0 * torch.randn(T, lay.vocab, generator=g, device='cuda')
+    tgt = torch.stack([torch.randint(0, n, (T,), generator=g, device='cuda') for n in lay.sizes], 1).to(torch.int16)
     mask = torch.ones(T, device='cuda')
     loss_mask = torch.ones(T, 8, device='cuda')
     logp, ent = torch.empty(T, 8, device='cuda'), torch.empty(T, 8, device='cuda')
@@ -37,8 +41,8 @@ def main():
     sums = torch.zeros(24, device='cuda')
     partials = torch.empty(int(LIB.query('pb_ce_partials_floats')), device='cuda')
     for _ in range(a.warmup + a.launches):
-        ops.ce_fwd_bwd(logits, tgt, loss_mask, sums, partials, None, None, argmax)
-        ops.token_scores(logits, tgt, mask, logp, ent, rank)
+        ops.ce_fwd_bwd(logits, tgt, loss_mask, sums, partials, None, None, argmax, layout=lay)
+        ops.token_scores(logits, tgt, mask, logp, ent, rank, layout=lay)
     torch.cuda.synchronize()
     hits = int((rank == 0).sum())
     assert hits == int((argmax == tgt).sum())                 # the two kernels agree on what a hit is
