@@ -566,7 +566,27 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  * LDS, one thread per ranked class), else wide (17 classes per lane, ~104 KB of dynamic LDS, the rank counting in rounds of 512
  * threads): every dictionary inside the head limit is served. Both run the same steps in the same order,
  * take the same kernargs and honour forced ids, stop bars and bar floors alike.
- *   pb_batch_decoder_sampler_form   0 = the narrow sampler (also before sampler_init), 1 = the wide one. */
+ *   pb_batch_decoder_sampler_form   0 = the narrow sampler (also before sampler_init), 1 = the wide one.
+ * Allowed classes (an addition to ABI 10): a row may carry an allow mask, one bit per vocabulary column (bit c & 31 of word c >> 5 =
+ * column c of plan.vocab, model order). A class whose bit is 0 gets the quotient -inf in front of the softmax of its head (probability
+ * exactly 0: never a nucleus candidate, never the arg-max of a p = 1 head); the draws, the temperatures, the nucleus rule, the given
+ * heads, the stop test and the logged (raw) logits are untouched. A row that is time-ordered too loses the classes either rule removes,
+ * and head 1's second pass keeps the allow mask. The caller keeps every head's special ids set, so a row can always end.
+ *   pb_batch_decoder_allow          after pb_batch_decoder_sampler_init, before the first step of the run (pb_batch_decoder_order's window):
+ *                                   masks = (n_masks, words) host words, words = ceil(plan.vocab / 32); row_mask = (B) host ints, the
+ *                                   index of row b's mask, -1 = every class allowed (what sampler_init sets for every row). The table is
+ *                                   copied to device memory the decoder owns (the caller's arrays are free when the call returns) and
+ *                                   the indices are stored beside the rows' bar floors in decoder-stream order; pb_batch_decoder_start
+ *                                   keeps them. Both sampler forms and both widths read the row's index with its position (B = 1
+ *                                   included). Same kernels, same kernarg layouts, same launches per step. Refused (< 0, pb_last_error,
+ *                                   nothing changed): before sampler_init, after a step was issued or captured, n_masks < 1, words !=
+ *                                   ceil(vocab / 32), an index outside -1 .. n_masks - 1. A later sampler_init frees every row again.
+ *   pb_batch_decoder_admit_allow    refill: stages the mask index (-1 .. n_masks - 1 of the table pb_batch_decoder_allow uploaded, which
+ *                                   therefore holds the masks of ALL rows of the call from the start) that the next
+ *                                   pb_batch_decoder_admit of `row` stores, in the same small kernel as the row's position, limit, stop
+ *                                   bar, bar floor and done = 0. An admit without a staged value stores -1: a slot never inherits its
+ *                                   previous occupant's mask. Host state only, no device work. Refused (< 0, pb_last_error, nothing
+ *                                   changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1, an index outside the table. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -597,6 +617,8 @@ int pb_batch_decoder_admit_stop(void* dec, int32_t row, int32_t stop_bar);
 int pb_batch_decoder_order(void* dec, const int32_t* floor);
 int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floor);
 int pb_batch_decoder_sampler_form(void* dec);
+int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t n_masks, int32_t words, const int32_t* row_mask);
+int pb_batch_decoder_admit_allow(void* dec, int32_t row, int32_t mask_index);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

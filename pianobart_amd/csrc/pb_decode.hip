@@ -61,8 +61,15 @@ struct BState {
     // the device sampler, both forms: order[b] >= 0 = the row is time-ordered with that bar floor, -1 = sampled freely
     // (pb_batch_decoder_order, pb_batch_decoder_admit_order). opad = the first special ids of heads 0 (bar) and 1 (position): the single-row
     // sampler's kernargs hold no pad. Set by sampler_init, start and admit
-    int order[BMAX];
+    // ... and rule[b].allow >= 0 = the row samples only the classes whose bit is set in mask allow of the table amask ((n_masks, awords)
+    // uint32 words in device memory the decoder owns, bit c & 31 of word c >> 5 = vocabulary column c), -1 = every class is allowed
+    // (pb_batch_decoder_allow, pb_batch_decoder_admit_allow). The two per-row rules sit side by side: the sampler reads them with ONE
+    // 8-byte load, so a free row's requests are those of a sampler that knew the bar floor alone
+    struct RowRule { int order, allow; };
+    RowRule rule[BMAX];
     int opad[2];
+    int awords;
+    const uint32_t* amask;
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -1249,6 +1256,12 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // everything behind it is the unordered arithmetic. It is a block-uniform branch on order[b], not a template parameter: the row form
 // mixes ordered and free rows in one launch (one workgroup per row), so a template would still need the per-row test, and four
 // more instantiations would double the captured graphs' variants for code that an unordered row skips with one load and one compare.
+// Allowed classes (pb_batch_decoder_allow), both forms and both widths: a row with allow[b] >= 0 carries one bit per vocabulary column; a
+// class whose bit is 0 gets the quotient -inf in the expression that forms y, beside the bar floor, so the softmax, the ranking, the
+// nucleus rule, the arg-max of a p = 1 head and head 1's second pass (which reuses y) never see it. The logged logits stay the raw ones:
+// the host masks its own copy. The bit of class c of head h is bit off[h] + c of the row's mask -- the heads' offsets are no multiples
+// of 32, so the word is indexed by column. Block-uniform on the row's index and no template parameter, for order[b]'s reasons: a free
+// row pays one compare and 4 more bytes in the load that brings its bar floor, a masked row K loads of words its wave shares.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1396,7 +1409,8 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     // time-ordered row (order[b] >= 0, block-uniform): low0 = the first bar head 0 may sample; low1 > 0 = the first position head 1 may
     // sample IF the token's bar stays prev0 (0: head 1 is free whatever the bar). prev = the row's decoder input, read here, in front of
     // the first barrier; the last stage overwrites it behind the last one.
-    const int ord = a.st->order[b];
+    const BState::RowRule rule = a.st->rule[b];                  // one 8-byte load: the bar floor and the allow mask (below) of the row
+    const int ord = rule.order, alw = rule.allow;
     int low0 = 0, low1 = 0, prev0 = -1;
     if (ord >= 0) {
         const int p0 = a.tok_dev[b * 8 + 0], p1 = a.tok_dev[b * 8 + 1];
@@ -1404,6 +1418,11 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         low0 = max(ord, bar ? p0 : 0);
         if (bar && p1 < a.st->opad[1]) { low1 = p1; prev0 = p0; }
     }
+    // allowed classes (rule[b].allow >= 0, block-uniform): the row's mask, one bit per vocabulary column
+    // The address is formed whether the row has a mask or not (index 0 for a free row; never read then): with a branch of its own here
+    // the compiler requests pos[b] a scalar-load round trip later than it did, which every free row would pay (1 us per launch, measured).
+    const bool masked = alw >= 0;
+    const uint32_t* amask = a.st->amask + (size_t)max(alw, 0) * a.st->awords;
     const float* logits = a.logits + (size_t)b * a.vocab;
     float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
     const int n = a.n[h], off = a.off[h];
@@ -1427,16 +1446,28 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         }
     }
     // y = logit / T of head h's classes; a time-ordered row's bars below low0 get -inf here, so their probability is an exact 0: the
-    // rank count puts them behind every positive class and the p = 1 arg-max never picks one (the largest class has e = 1).
+    // rank count puts them behind every positive class and the p = 1 arg-max never picks one (the largest class has e = 1). The classes
+    // a row's allow mask removes get -inf the same way (column off + c <= vocab - 1: inside the mask's ceil(vocab / 32) words).
     float y[K];
     const int lowh = h == 0 ? low0 : 0;                          // wave-uniform
+    // bit k of `allowed` = the lane's class k may be sampled. A masked row reads its K bits here, behind one block-uniform branch and in
+    // front of the loop, so that the loop below keeps the free row's shape: its K logits loads in flight together, no branch per class.
+    unsigned allowed = ~0u;
+    if (masked) {
+        allowed = 0u;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {                            // every lane reads a word of the mask (the column clamped into it; `in` below decides): K loads in flight
+            const int col = min(off + lane + 64 * k, a.vocab - 1);
+            allowed |= ((amask[col >> 5] >> (col & 31)) & 1u) << k;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int c = lane + 64 * k;
         const bool in = c < n;
         const float lg = in ? logits[off + c] : 0.f;
         if (in) ROWS ? log_logits[off + c] = lg : a.log_logits[(size_t)pos * a.vocab + off + c] = lg;
-        y[k] = (in && c >= lowh) ? lg / T : -INFINITY;
+        y[k] = (in && c >= lowh && ((allowed >> k) & 1u)) ? lg / T : -INFINITY;
     }
     smp_softmax(y, n, lane, pn[h]);
     __syncthreads();
@@ -1521,13 +1552,20 @@ __global__ __launch_bounds__(64) void dec_stop_kernel(BState* __restrict__ st, c
 struct OrderArgs { int order[BMAX]; };
 __global__ __launch_bounds__(64) void dec_order_kernel(BState* __restrict__ st, const OrderArgs g) {
     const int t = threadIdx.x;
-    if (t < BMAX) st->order[t] = g.order[t];
+    if (t < BMAX) st->rule[t].order = g.order[t];
+}
+struct AllowArgs { int allow[BMAX]; int words; const uint32_t* table; };
+__global__ __launch_bounds__(64) void dec_allow_kernel(BState* __restrict__ st, const AllowArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) st->rule[t].allow = g.allow[t];
+    if (t == 0) { st->awords = g.words; st->amask = g.table; }
 }
 struct AdmitArgs {
     BState* st; int16_t* tok_dev;
     int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
     int stop;                                // the new occupant's stop bar (pad[0]: none)
     int order;                               // ... and its bar floor of time-ordered sampling (-1: a free row)
+    int allow;                               // ... and the index of its allow mask in the decoder's table (-1: every class allowed)
     int16_t tok[8];
 };
 __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
@@ -1535,7 +1573,8 @@ __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
     if (t < 8) a.tok_dev[b * 8 + t] = a.tok[t];
     if (t == 0) {
         a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
-        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop; a.st->order[b] = a.order;
+        a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop;
+        a.st->rule[b].order = a.order; a.st->rule[b].allow = a.allow;
     }
 }
 
@@ -1582,6 +1621,10 @@ struct Decoder {
     int admit_stop[BMAX] = {};             // pb_batch_decoder_admit_stop: the value the row's next admit stores (-1: none staged -> pad[0])
     OrderArgs order{};                     // host mirror of the rows' bar floors in BState (-1: a free row), valid behind sampler_init
     int admit_order[BMAX] = {};            // pb_batch_decoder_admit_order: the value the row's next admit stores (-1: none staged -> a free row)
+    AllowArgs allow{};                     // host mirror of the rows' mask indices in BState (-1: every class allowed) and of the table's address
+    int admit_allow[BMAX] = {};            // pb_batch_decoder_admit_allow: the index the row's next admit stores (-1: none staged -> a free row)
+    uint32_t* allow_dev = nullptr;         // pb_batch_decoder_allow: (n_allow, allow.words) masks, one bit per vocabulary column
+    int n_allow = 0;                       // masks in allow_dev; 0 behind sampler_init until pb_batch_decoder_allow
     hipEvent_t ev_fence = nullptr;
     char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
     size_t stage_bytes = 0;
@@ -1850,6 +1893,7 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     for (int i = 0; i < SPEC_EVENTS; ++i) if (D->evs[i]) (void)hipEventDestroy(D->evs[i]);
     if (D->u_dev) (void)hipFree(D->u_dev);
     if (D->force_dev) (void)hipFree(D->force_dev);
+    if (D->allow_dev) (void)hipFree(D->allow_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
     for (int i = 0; i < N_STAGE; ++i) if (D->stage_ev[i]) (void)hipEventDestroy(D->stage_ev[i]);
@@ -1986,12 +2030,14 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->limit, limit, BMAX, D->stream));    // every row; pb_batch_decoder_start may set them one by one
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->stop, pad8[0], BMAX, D->stream));   // no row stops at a bar until pb_batch_decoder_stop says so
-    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->order, -1, BMAX, D->stream));       // every row is sampled freely until pb_batch_decoder_order says otherwise
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->rule, -1, 2 * BMAX, D->stream));    // every row is sampled freely, from every class, until pb_batch_decoder_order / _allow say otherwise
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[0], pad8[0], 1, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[1], pad8[1], 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
     D->limit = limit;
     for (int b = 0; b < BMAX; ++b) { D->stop.stop[b] = pad8[0]; D->admit_stop[b] = -1; D->order.order[b] = -1; D->admit_order[b] = -1; }
+    for (int b = 0; b < BMAX; ++b) { D->allow.allow[b] = -1; D->admit_allow[b] = -1; }
+    D->n_allow = 0;                                                     // the previous run's table (if any) stays allocated and unread: no row points into it
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
     D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
@@ -2074,6 +2120,47 @@ extern "C" int pb_batch_decoder_order(void* dec, const int32_t* floor) {
     return 0;
 }
 
+// Allowed classes (see the header): the table of distinct masks goes up once, into memory the decoder owns, and one index per row is stored
+// beside the rows' bar floors in decoder-stream order by a small kernel that takes them by kernarg. Everything is checked on the host
+// before anything changes. Like the bar floors it reaches the single-row sampler too.
+extern "C" int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t n_masks, int32_t words, const int32_t* row_mask) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && masks && row_mask, "pb_batch_decoder_allow: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_allow: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_allow: a step was already issued; the rows' allow masks are set before the run's first step");
+    PB_REQUIRE(n_masks > 0 && n_masks <= 65536, "pb_batch_decoder_allow: %d masks (1 .. 65536)", n_masks);
+    PB_REQUIRE(words == (D->sa.vocab + 31) / 32, "pb_batch_decoder_allow: %d words per mask for %d vocabulary columns (%d)", words, D->sa.vocab,
+               (D->sa.vocab + 31) / 32);
+    for (int b = 0; b < D->B; ++b)
+        PB_REQUIRE(row_mask[b] >= -1 && row_mask[b] < n_masks, "pb_batch_decoder_allow: row %d: mask index %d outside -1..%d (-1 = every class allowed)", b,
+                   row_mask[b], n_masks - 1);
+    const size_t bytes = sizeof(uint32_t) * (size_t)n_masks * (size_t)words;
+    uint32_t* tab = nullptr;
+    if (hipMalloc(&tab, bytes) != hipSuccess) {
+        pb_set_error("pb_batch_decoder_allow: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    if (hipMemcpyAsync(tab, masks, bytes, hipMemcpyHostToDevice, D->stream) != hipSuccess ||
+        hipStreamSynchronize(D->stream) != hipSuccess) {         // `masks` may be pageable: the copy is done when we return
+        pb_set_error("pb_batch_decoder_allow: upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(tab);
+        return -1;
+    }
+    AllowArgs g = D->allow;
+    for (int b = 0; b < D->B; ++b) g.allow[b] = row_mask[b];
+    g.words = words; g.table = tab;
+    hipLaunchKernelGGL(dec_allow_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
+    if (hipGetLastError() != hipSuccess) {
+        pb_set_error("pb_batch_decoder_allow: launch failed");
+        (void)hipFree(tab);
+        return -1;
+    }
+    if (D->allow_dev) (void)hipFree(D->allow_dev);               // the previous table: no row has pointed into it since sampler_init (hipFree drains the device)
+    D->allow_dev = tab; D->n_allow = n_masks;
+    D->allow = g;
+    return 0;
+}
+
 // Enqueue `ntok` steps; first_tok ((B, 8) host ids, may be NULL) is copied up in front as the rows' decoder inputs. Row form: a row stops
 // by itself at the limit; B == 1: the steps must stay within it. Returns a ticket >= 0 for pb_batch_decoder_wait, < 0 on error.
 extern "C" int pb_batch_decoder_launch(void* dec, int32_t ntok, const int16_t* first_tok) {
@@ -2146,9 +2233,11 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
         h.pos[b] = -1; h.done[b] = 0; h.limit[b] = dflt;
         h.s_enc[b] = D->geo.s_enc[b]; h.ck[b] = D->geo.ck[b]; h.kv_row[b] = D->geo.kv_row[b];
         h.stop[b] = D->stop.stop[b];                                  // as sampler_init / pb_batch_decoder_stop left it (unread without a sampler)
-        h.order[b] = D->sampler ? D->order.order[b] : -1;             // ... / pb_batch_decoder_order
+        h.rule[b].order = D->sampler ? D->order.order[b] : -1;        // ... / pb_batch_decoder_order
+        h.rule[b].allow = D->sampler ? D->allow.allow[b] : -1;        // ... / pb_batch_decoder_allow
     }
     h.opad[0] = D->sa.pad[0]; h.opad[1] = D->sa.pad[1];
+    h.awords = D->allow.words; h.amask = D->n_allow ? D->allow_dev : nullptr;
     for (int b = 0; b < B; ++b) {
         PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
         PB_REQUIRE(!limit || (limit[b] >= 0 && limit[b] <= S), "pb_batch_decoder_start: row %d limit %d outside 0..%d", b, limit[b], S);
@@ -2246,6 +2335,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     a.st = D->st; a.tok_dev = D->tok_dev; a.row = row; a.s_enc = s_enc; a.ck = cross_chunk(D, s_enc); a.slice = slice; a.pos = last_pos; a.limit = limit;
     a.stop = D->admit_stop[row] >= 0 ? D->admit_stop[row] : D->sa.pad[0];    // never the previous occupant's
     a.order = D->admit_order[row];                                           // -1 unless staged: nor its bar floor
+    a.allow = D->admit_allow[row];                                           // ... nor its allow mask
     for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
@@ -2265,6 +2355,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     D->geo.s_enc[row] = s_enc; D->geo.ck[row] = a.ck; D->geo.kv_row[row] = slice; D->ck_cross[row] = a.ck;
     D->stop.stop[row] = a.stop; D->admit_stop[row] = -1;
     D->order.order[row] = a.order; D->admit_order[row] = -1;
+    D->allow.allow[row] = a.allow; D->admit_allow[row] = -1;
     D->live[row] = true;
     return 0;
 }
@@ -2290,6 +2381,19 @@ extern "C" int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floo
     PB_REQUIRE(floor >= -1 && floor < D->sa.pad[0], "pb_batch_decoder_admit_order: row %d: floor %d outside -1..%d (-1 = not ordered)", row, floor,
                D->sa.pad[0] - 1);
     D->admit_order[row] = floor;
+    return 0;
+}
+
+// The allow mask (an index into pb_batch_decoder_allow's table) of the prompt the next pb_batch_decoder_admit puts into `row` (see the
+// header). Host state only: the store is the admit's.
+extern "C" int pb_batch_decoder_admit_allow(void* dec, int32_t row, int32_t mask_index) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit_allow: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_admit_allow: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit_allow: row %d of %d", row, D->B);
+    PB_REQUIRE(mask_index >= -1 && mask_index < D->n_allow, "pb_batch_decoder_admit_allow: row %d: mask index %d outside -1..%d (-1 = every class allowed; the "
+               "table is pb_batch_decoder_allow's)", row, mask_index, D->n_allow - 1);
+    D->admit_allow[row] = mask_index;
     return 0;
 }
 

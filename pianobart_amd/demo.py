@@ -24,7 +24,8 @@ class Args:
 
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
-                 precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False):
+                 precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False,
+                 key=None, pitch_range=None, instruments=None, tempo=None, max_duration=None, velocity=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
@@ -33,6 +34,8 @@ class Args:
         self.bars = bars                    # None or N: finish the bar the prime ends in, write N whole new bars, stop (eval_generation --bars)
         self.infill, self.infill_mode = infill, infill_mode     # None or 'LO:HI': rewrite bars LO .. HI-1 of the piece (eval_generation --infill; needs a seed)
         self.ordered = ordered              # time-ordered sampling: no sampled (bar, position) goes back (eval_generation --ordered)
+        # allowed classes (eval_generation --key / --pitch_range / --instruments / --tempo / --max_duration / --velocity): one mask for the piece
+        self.key, self.pitch_range, self.instruments, self.tempo, self.max_duration, self.velocity = key, pitch_range, instruments, tempo, max_duration, velocity
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -66,6 +69,8 @@ def get_args(argv=None):
                     'or one MASK row for the whole region (span)')
     ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
                     '--infill LO:HI and 0 otherwise')
+    from .generation import add_allow_flags
+    add_allow_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -174,6 +179,9 @@ def demo(args=None):
         from .generation import stop_after_bars
         stops = [stop_after_bars(prefix[0, :ks[0]] if ks is not None else None, bars, pianobart.bar_pad_word)]
     order = [region[0] if region is not None else 0] if getattr(args, 'ordered', False) else None      # the bar floor: the region's first bar, else 0
+    from .generation import allow_from_args
+    amask = allow_from_args(args, e2w)       # --key / --pitch_range / ..: what the free heads may sample (None: no flag)
+    allow = [amask] if amask is not None else None
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
@@ -181,10 +189,10 @@ def demo(args=None):
             from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
                                      decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples,
-                                     decoder_forced=forced, decoder_stop=stops, decoder_order=order)
+                                     decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
         else:
             y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                      decoder_forced=forced, decoder_stop=stops, decoder_order=order)
+                      decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
     if plan is not None:                     # the rows behind the region go back behind the new ones
         from .generation import infill_splice
         spliced = [infill_splice(row, plan['suffix'], args.max_seq_len, pianobart.bar_pad_word) for row in y.cpu()]

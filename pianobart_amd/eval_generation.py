@@ -42,6 +42,13 @@ infilled region sounds in front of it; the tool then checks generation.is_time_o
 PBError where it fails. Combines with --samples, --refill, --keep (a kept bar or position is given, never reordered), --score and --pick; not
 with --score_dataset. Without the flag the output files are byte-identical to a run of a version without it.
 
+Allowed classes (--key C:major, --pitch_range LO:HI, --instruments 0,1, --tempo LO:HI, --max_duration N, --velocity LO:HI): what a free head
+may sample is restricted to the named classes (PianoBartLM.generate_batch's decoder_allow; DESIGN.md section 1, "Allowed classes"). One
+mask, built by generation.allow_mask from the model's own dictionary, is used for every row; the flags of one head intersect. The tool
+checks generation.is_allowed on every output row behind its prime (kept attributes are given, not tested) and raises PBError where it
+fails. Combines with --prime, --keep, --bars, --infill, --ordered, --samples, --refill, --score and --pick; not with --score_dataset. Without
+the flags the output files are byte-identical to a run of a version without them.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -60,7 +67,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import check_refill, infill_plan, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
+from .generation import add_allow_flags, allow_flags_given, allow_from_args, check_refill, infill_plan, is_allowed, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -110,6 +117,7 @@ def get_args(argv=None):
                     'or one MASK row for the whole region (span)')
     ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
                     '--infill LO:HI and 0 otherwise')
+    add_allow_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -192,6 +200,8 @@ def check_args(args):
         raise PBError('--infill_mode %s needs --infill' % args.infill_mode)
     if getattr(args, 'ordered', False) and getattr(args, 'score_dataset', False):
         raise PBError('--score_dataset generates nothing: it takes no --ordered')
+    if allow_flags_given(args) and getattr(args, 'score_dataset', False):
+        raise PBError('--score_dataset generates nothing: it takes no --%s' % allow_flags_given(args)[0])
     if getattr(args, 'keep', None) is not None:
         parse_keep(args.keep)
         if getattr(args, 'prime', None) is None:
@@ -277,12 +287,21 @@ def eval_generation(args=None):
     bars, infill, truncated = getattr(args, 'bars', None), parse_infill(getattr(args, 'infill', None), bar_pad), 0
     pad_word = model.pianobart.pad_word_np
     floor = (infill[0] if infill is not None else 0) if getattr(args, 'ordered', False) else None       # --ordered: every row's bar floor
+    amask = allow_from_args(args, e2w)                   # --key / --pitch_range / ..: the one allow mask of every row (None: no flag)
+
+    def allowed(y, ks, forced, own):
+        """The allow flags: every output row of y (row r belongs to piece own[r] of the call) stays inside the mask behind its prime."""
+        for r, p in enumerate(own if amask is not None else []):
+            k = ks[p] if ks is not None else 0
+            if not is_allowed(y[r], amask, start=k, forced=forced[p] if forced is not None else None, layout=model.pianobart.layout):
+                raise PBError('--%s: output row %d leaves the allowed classes behind its prime of %d rows' % (allow_flags_given(args)[0], r, k))
 
     def inputs(x):
         """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars,
         (--infill) the plans and (--ordered) the bar floors."""
         prefix = ks = forced = stops = plans = None
         order = [floor] * len(x) if floor is not None else None
+        allow = [amask] * len(x) if amask is not None else None
         if infill is not None:
             plans = [infill_plan(p, infill[0], infill[1], model.pianobart.mask_word_np, pad_word, getattr(args, 'infill_mode', 'rows')) for p in x.numpy()]
             ks, stops = [pl['k'] for pl in plans], [pl['stop'] for pl in plans]
@@ -296,7 +315,7 @@ def eval_generation(args=None):
             x, prefix = prime_inputs(x, ks, pad_word)
         if bars is not None:
             stops = [stop_after_bars(prefix[b, :ks[b]] if ks is not None else None, bars, bar_pad) for b in range(len(x))]
-        return x, prefix, ks, forced, stops, plans, order
+        return x, prefix, ks, forced, stops, plans, order, allow
 
     def splice(y, plans, own):
         """--infill: row r of y (numpy) spliced with the suffix of its piece own[r]; counts the truncated ones."""
@@ -338,12 +357,14 @@ def eval_generation(args=None):
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
-            x, prefix, ks, forced, stops, plans, order = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
                                      device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
-                                     decoder_order=order, samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
+                                     decoder_order=order, decoder_allow=allow,
+                                     samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
             own = [i - c0 for i, _ in chunk]
+            allowed(y, ks, forced, own)
             if do_score:
                 sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
             y = y.float().cpu().numpy()
@@ -357,16 +378,17 @@ def eval_generation(args=None):
         gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
         for c0 in range(0, N if samples == 1 else 0, gen_rows):
             c1 = min(N, c0 + gen_rows)
-            x, prefix, ks, forced, stops, plans, order = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
                 y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                          decoder_forced=forced, decoder_stop=stops, decoder_order=order)
+                          decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
                                          decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops, decoder_order=order,
-                                         refill=(refill or True) if refill is not None else False)
+                                         decoder_allow=allow, refill=(refill or True) if refill is not None else False)
+            allowed(y, ks, forced, list(range(c1 - c0)))
             output[c0:c1] = y.float().cpu().numpy() if plans is None else splice(y.float().cpu().numpy(), plans, list(range(c1 - c0)))
             for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):
                 s1 = min(c1 - c0, s0 + args.batch_size)

@@ -194,6 +194,285 @@ def is_time_ordered(rows, start=0, floor=0):
     return not (np.diff(t) < 0).any()
 
 
+def _as_numpy(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _layout_of(layout_or_e2w):
+    if layout_or_e2w is None:
+        return ops.DEFAULT_LAYOUT, None
+    if isinstance(layout_or_e2w, ops.Layout):
+        return layout_or_e2w, None
+    return ops.Layout.from_dict(layout_or_e2w), layout_or_e2w
+
+
+def check_allow(allow, P, layout=None, owner=None):
+    """The argument rules of allowed-class generation, on the host before any device work. allow: one mask per prompt -- a bool array or
+    tensor (P, V), a list of P entries each a (V,) bool mask or None (= the row is free), or, for P = 1, one (V,) mask; V = layout.vocab,
+    columns in model order (ops.Layout offsets), True = the class may be sampled. The six special ids of every head are set here (a row
+    can always end); a head left without an ordinary class raises PBError naming it. owner (row -> prompt, check_samples): the indices are
+    expanded to one per output row. Returns None for allow=None or masks that are True everywhere (the caller runs what it ran before),
+    else (masks, index): the distinct masks packed to uint32 words, (n, ceil(V / 32)), bit c & 31 of word c >> 5 = column c, and one int per
+    row, the row's mask or -1 = free. Equal masks share an entry."""
+    if allow is None:
+        return None
+    lay = layout if layout is not None else ops.DEFAULT_LAYOUT
+    V = int(lay.vocab)
+    if isinstance(allow, (list, tuple)):
+        entries = list(allow)
+    else:
+        a = _as_numpy(allow)
+        if a.ndim == 1 and P == 1:
+            entries = [a]
+        elif a.ndim == 2:
+            entries = list(a)
+        else:
+            raise PBError('allow of shape %s: expected (%d, %d) bools for %d prompt(s)%s' % (tuple(a.shape), P, V, P, ', or (%d,)' % V if P == 1 else ''))
+    if len(entries) != P:
+        raise PBError('allow has %d entries for %d prompt(s)' % (len(entries), P))
+    keys, masks, index = {}, [], []
+    for p, m in enumerate(entries):
+        if m is None:
+            index.append(-1)
+            continue
+        try:
+            m = _as_numpy(m)
+        except Exception:
+            raise PBError('allow[%d] = %r is neither None nor a bool mask' % (p, m))
+        if m.dtype != np.bool_:
+            raise PBError('allow[%d] must be a bool mask (got %s)' % (p, m.dtype))
+        if m.shape != (V,):
+            raise PBError('allow[%d] of shape %s: expected (%d,), one bool per vocabulary column' % (p, tuple(m.shape), V))
+        m = m.copy()
+        for h in range(8):
+            o, n, pad = lay.seg_off[h], lay.sizes[h], lay.pad8[h]
+            if not m[o:o + pad].any():
+                raise PBError('allow[%d] leaves head %d (%s) without an ordinary class' % (p, h, ops.CLASS_NAMES[h]))
+            m[o + pad:o + n] = True
+        if m.all():
+            index.append(-1)
+            continue
+        key = m.tobytes()
+        if key not in keys:
+            keys[key] = len(masks)
+            masks.append(m)
+        index.append(keys[key])
+    if not masks:
+        return None
+    words = (V + 31) // 32
+    bits = np.zeros((len(masks), words * 32), dtype=np.uint8)
+    bits[:, :V] = np.stack(masks)
+    packed = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder='little')).view('<u4').astype(np.uint32).reshape(len(masks), words)
+    return packed, (index if owner is None else [index[p] for p in owner])
+
+
+def unpack_allow(allow, vocab):
+    """The masks of check_allow's result as bool tensors: one (vocab,) torch.bool per ROW (True = allowed), None for a free row."""
+    if allow is None:
+        return None
+    packed, index = allow
+    bits = np.unpackbits(np.ascontiguousarray(packed).astype('<u4').view(np.uint8), axis=1, bitorder='little')[:, :vocab].astype(bool)
+    ms = [torch.from_numpy(np.ascontiguousarray(b)) for b in bits]
+    return [ms[i] if i >= 0 else None for i in index]
+
+
+def _slice_allow(allow, a, b):
+    """check_allow's result for the rows a .. b - 1 (the table stays whole); None where they are all free."""
+    if allow is None or all(i < 0 for i in allow[1][a:b]):
+        return None
+    return allow[0], list(allow[1][a:b])
+
+
+_SCALES = dict(major=(0, 2, 4, 5, 7, 9, 11), minor=(0, 2, 3, 5, 7, 8, 10))
+_TONICS = {'C': 0, 'C#': 1, 'Db': 1, 'D': 2, 'D#': 3, 'Eb': 3, 'E': 4, 'F': 5, 'F#': 6, 'Gb': 6, 'G': 7, 'G#': 8, 'Ab': 8, 'A': 9, 'A#': 10, 'Bb': 10, 'B': 11}
+
+
+def _range2(name, r):
+    try:
+        lo, hi = r
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise PBError('allow_mask: %s must be a pair (lo, hi) of numbers (got %r)' % (name, r))
+    if not lo < hi:
+        raise PBError('allow_mask: %s = %r is an empty range (lo <= value < hi)' % (name, r))
+    return lo, hi
+
+
+def allow_mask(layout_or_e2w=None, key=None, pitch_range=None, instruments=None, velocity=None, tempo=None, max_duration=None, timesig=None,
+               heads=None):
+    """One (V,) bool allow mask (check_allow's input) built from a dictionary's NAMES (host, numpy). layout_or_e2w: the dictionary's event ->
+    word half (the reference's e2w: {class: {word: id}}; PianoBart.e2w), so any legal dictionary works; an ops.Layout (or None: the default
+    one) serves the raw form `heads` only, since a layout has no names. A head without a rule stays free; several rules on one head
+    intersect; the special ids of every head are always set.
+      key='C:major'        tonic C, C#, Db, D, .. B and mode major or minor (natural minor): the melodic 'Pitch k' with k % 12 in the scale
+      pitch_range=(lo, hi) the melodic 'Pitch k' with lo <= k < hi. key and pitch_range both remove the 'Pitch percussion k' classes
+      instruments={..}     a set of 'Instrument <x>' words given by <x> (0, '0', 'percussion') or in full
+      timesig={..}         a set of 'TimeSig <x>' words given by <x> ('4/4') or in full; an int is the id itself
+      velocity=(lo, hi)    the 'Velocity v' with lo <= v < hi;  tempo=(lo, hi): the 'Tempo t' with lo <= t < hi (beats per minute)
+      max_duration=N       the duration ids 0 .. N
+      heads={h: ids}       the raw form: head h admits exactly these ordinary ids
+    PBError: an unknown tonic, mode, word or head, an id outside its head, an empty range, or a head left without an ordinary class."""
+    lay, e2w = _layout_of(layout_or_e2w)
+    ok = [np.ones(lay.pad8[h], dtype=bool) for h in range(8)]
+
+    def names(h):
+        if e2w is None:
+            raise PBError('allow_mask: the rule on %s needs the dictionary\'s names: pass e2w (PianoBart.e2w), not a Layout' % ops.CLASS_NAMES[h])
+        cls = ops.CLASS_NAMES[h]
+        return [(w[len(cls) + 1:], int(i)) for w, i in e2w[cls].items() if int(i) < lay.pad8[h]]
+
+    def numbered(h):
+        out = []
+        for rest, i in names(h):
+            try:
+                out.append((float(rest), i))
+            except ValueError:
+                pass
+        return out
+
+    def keep(h, ids, what):
+        m = np.zeros(lay.pad8[h], dtype=bool)
+        m[list(ids)] = True
+        ok[h] &= m
+        if not ok[h].any():
+            raise PBError('allow_mask: %s leaves head %d (%s) without an ordinary class' % (what, h, ops.CLASS_NAMES[h]))
+
+    def named_set(h, items, what):
+        tab = dict(names(h))
+        cls = ops.CLASS_NAMES[h]
+        try:
+            items = list(items) if not isinstance(items, (str, int, np.integer)) else [items]
+        except TypeError:
+            raise PBError('allow_mask: %s must be a set of names or numbers (got %r)' % (what, items))
+        if not items:
+            raise PBError('allow_mask: %s is empty' % what)
+        ids = []
+        for it in items:
+            if h == 6 and isinstance(it, (int, np.integer)) and not isinstance(it, bool):
+                if not 0 <= int(it) < lay.pad8[h]:
+                    raise PBError('allow_mask: %s: id %d outside 0 .. %d' % (what, int(it), lay.pad8[h] - 1))
+                ids.append(int(it))
+                continue
+            w = str(it)
+            w = w[len(cls) + 1:] if w.startswith(cls + ' ') else w
+            if w not in tab:
+                raise PBError('allow_mask: %s: the dictionary has no word %r' % (what, '%s %s' % (cls, w)))
+            ids.append(tab[w])
+        keep(h, ids, what)
+
+    if key is not None:
+        try:
+            tonic, mode = str(key).split(':')
+        except ValueError:
+            raise PBError('allow_mask: key %r is not TONIC:MODE (C:major, A:minor, ..)' % (key,))
+        if tonic not in _TONICS:
+            raise PBError('allow_mask: unknown tonic %r (%s)' % (tonic, ', '.join(_TONICS)))
+        if mode not in _SCALES:
+            raise PBError('allow_mask: unknown mode %r (major, minor)' % mode)
+        pcs = {(_TONICS[tonic] + d) % 12 for d in _SCALES[mode]}
+        keep(3, [i for rest, i in names(3) if rest.isdigit() and int(rest) % 12 in pcs], 'key %s' % key)
+    if pitch_range is not None:
+        lo, hi = _range2('pitch_range', pitch_range)
+        keep(3, [i for rest, i in names(3) if rest.isdigit() and lo <= int(rest) < hi], 'pitch_range %r' % (pitch_range,))
+    if instruments is not None:
+        named_set(2, instruments, 'instruments')
+    if timesig is not None:
+        named_set(6, timesig, 'timesig')
+    if velocity is not None:
+        lo, hi = _range2('velocity', velocity)
+        keep(5, [i for v, i in numbered(5) if lo <= v < hi], 'velocity %r' % (velocity,))
+    if tempo is not None:
+        lo, hi = _range2('tempo', tempo)
+        keep(7, [i for v, i in numbered(7) if lo <= v < hi], 'tempo %r' % (tempo,))
+    if max_duration is not None:
+        if isinstance(max_duration, bool) or not isinstance(max_duration, (int, np.integer)) or max_duration < 0:
+            raise PBError('allow_mask: max_duration must be a duration id >= 0 (got %r)' % (max_duration,))
+        keep(4, range(min(int(max_duration) + 1, lay.pad8[4])), 'max_duration %d' % max_duration)
+    if heads is not None:
+        for h, ids in dict(heads).items():
+            if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 0 <= h < 8:
+                raise PBError('allow_mask: heads: %r is not a head 0 .. 7' % (h,))
+            ids = [int(v) for v in _as_numpy(ids).reshape(-1)]
+            if any(not 0 <= v < lay.pad8[h] for v in ids):
+                raise PBError('allow_mask: heads[%d]: an id outside the ordinary ids 0 .. %d of %s' % (h, lay.pad8[h] - 1, ops.CLASS_NAMES[h]))
+            if not ids:
+                raise PBError('allow_mask: heads[%d] is empty: it leaves head %d (%s) without an ordinary class' % (h, h, ops.CLASS_NAMES[h]))
+            keep(int(h), ids, 'heads[%d]' % h)
+    mask = np.ones(lay.vocab, dtype=bool)
+    for h in range(8):
+        mask[lay.seg_off[h]:lay.seg_off[h] + lay.pad8[h]] = ok[h]
+    return mask
+
+
+def add_allow_flags(ap):
+    """The command-line form of allow_mask, shared by eval_generation, demo and tools/decode_batch_bench.py: one mask for every row."""
+    ap.add_argument('--key', type=str, default=None, metavar='TONIC:MODE', help='allowed classes: melodic pitches of this key only (C:major, A:minor, ..)')
+    ap.add_argument('--pitch_range', type=str, default=None, metavar='LO:HI', help='allowed classes: melodic pitches LO <= k < HI only')
+    ap.add_argument('--instruments', type=str, default=None, metavar='I[,I...]', help='allowed classes: these instruments only (numbers or "percussion")')
+    ap.add_argument('--tempo', type=str, default=None, metavar='LO:HI', help='allowed classes: tempo classes with LO <= beats per minute < HI only')
+    ap.add_argument('--max_duration', type=int, default=None, metavar='N', help='allowed classes: duration ids 0 .. N only')
+    ap.add_argument('--velocity', type=str, default=None, metavar='LO:HI', help='allowed classes: velocity classes with LO <= velocity < HI only')
+
+
+ALLOW_FLAGS = ('key', 'pitch_range', 'instruments', 'tempo', 'max_duration', 'velocity')
+
+
+def allow_flags_given(args):
+    """The allow flags (add_allow_flags) the arguments set, by name."""
+    return [f for f in ALLOW_FLAGS if getattr(args, f, None) is not None]
+
+
+def allow_from_args(args, e2w):
+    """The one (V,) allow mask the flags of add_allow_flags describe, built from the dictionary e2w; None where no flag is given. PBError
+    for a flag that is not of its form, and allow_mask's."""
+    if not allow_flags_given(args):
+        return None
+
+    def pair(flag):
+        v = getattr(args, flag, None)
+        if v is None:
+            return None
+        try:
+            lo, hi = (float(t) for t in str(v).split(':'))
+        except ValueError:
+            raise PBError('--%s takes LO:HI, two numbers (got %r)' % (flag, v))
+        return lo, hi
+    inst = getattr(args, 'instruments', None)
+    return allow_mask(e2w, key=getattr(args, 'key', None), pitch_range=pair('pitch_range'), tempo=pair('tempo'), velocity=pair('velocity'),
+                      instruments=[t.strip() for t in str(inst).split(',') if t.strip()] if inst is not None else None,
+                      max_duration=getattr(args, 'max_duration', None))
+
+
+def allowed_token(frow, sample, allow, floor, prev, pad):
+    """The token of ONE position under the allowed-class contract, for every decode path: ordered_token (and through it forced_token) with
+    the path's sample() given the row's mask. allow: the row's (V,) bool mask, True = the class may be sampled (None: the row is free --
+    ordered_token(frow, sample, floor, prev, pad), nothing else). sample(allow=mask[, order=...]) is the path's own sampling of the position
+    with the masked columns at -inf in front of the softmax (PianoBartLM.sample_row). Given heads are written as given, inside the mask or
+    not; a position whose 8 heads are given draws nothing; the draws are forced_token's."""
+    if allow is None:
+        return ordered_token(frow, sample, floor, prev, pad)
+    return ordered_token(frow, lambda **kw: sample(allow=allow, **kw), floor, prev, pad)
+
+
+def is_allowed(rows, mask, start=0, forced=None, layout=None):
+    """Whether every emitted, non-given head of the rows from `start` on is inside the mask (host, numpy). rows (S, 8) Octuple ids; the
+    emitted rows are those in front of the first row whose bar id is special. mask (V,) bools in model column order (special ids count as
+    allowed, as check_allow sets them); forced (S, 8) or None: the row's forced table -- a given head (>= 0) is not tested."""
+    lay = layout if layout is not None else ops.DEFAULT_LAYOUT
+    x = _as_numpy(rows).astype(np.int64)
+    m = _as_numpy(mask).astype(bool)
+    special = np.flatnonzero(x[:, 0] >= lay.pad8[0])
+    e = int(special[0]) if len(special) else len(x)
+    if start >= e:
+        return True
+    x = x[start:e]
+    off, pad = np.asarray(lay.seg_off[:8], dtype=np.int64), np.asarray(lay.pad8, dtype=np.int64)
+    ok = m[np.clip(x, 0, np.asarray(lay.sizes) - 1) + off] | (x >= pad)
+    if forced is not None:
+        ok |= _as_numpy(forced)[start:e] >= 0
+    return bool(ok.all())
+
+
 def stop_vector(pad_cpu, s):
     """The 8 thresholds of ONE row's stop test, for every decode path: the reference's `(current_output >= pad).any()` (model.py:47)
     becomes `(current_output >= stop_vector(pad, s)).any()` -- pad with its head 0 lowered to the row's stop bar s, so the one comparison
@@ -400,7 +679,7 @@ class GenerationMixin:
         return dict(sampler_form='wide') if self.last_sampler_form == 'wide' else {}
 
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None, allow=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -427,7 +706,12 @@ class GenerationMixin:
         self.sample(x, i)` replaced by the ordered sample (ordered_token; DESIGN.md section 1, "Time-ordered sampling"): with prev = the
         decoder's input row at position i, bars below max(order, prev's bar) and, inside prev's bar, positions below prev's position get
         probability 0. Forcing, the stop test, the draws and what is written are unchanged. `sample_row` must then take the keyword
-        `order` (PianoBartLM.sample_row does). -1, or None: not ordered, the call without the argument."""
+        `order` (PianoBartLM.sample_row does). -1, or None: not ordered, the call without the argument.
+        allow ((V,) bools, or a sequence of one; check_allow): allowed classes -- the reference loop with sampling(logit, p, t) seeing -inf
+        in place of every logit whose bit is 0 (allowed_token; DESIGN.md section 1, "Allowed classes"). The mask is constant over the
+        positions; the special ids stay reachable; forcing, the stop test, the draws and what is written are unchanged; an ordered row
+        loses the classes either rule removes. `sample_row` must then take the keyword `allow`. None, or True everywhere: the call
+        without the argument."""
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
@@ -436,14 +720,16 @@ class GenerationMixin:
         sb = stop[0] if stop is not None else None
         order = check_order([order] if isinstance(order, (int, np.integer)) and not isinstance(order, bool) else order, 1, order_max=int(self.pb.pad_word_np[0]) - 1)
         ob = order[0] if order is not None else None
+        allow = check_allow(allow, 1, self.lay if allow is not None else None)
+        ab = unpack_allow(allow, self.lay.vocab)[0] if allow is not None else None
         fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -454,10 +740,10 @@ class GenerationMixin:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                     info = self._decode_device_sampled(run.dec, 1, S, lambda b, row, **kw: sample_row(row, **kw), [np.random.get_state()], sampler,
                                                        res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop,
-                                                       order=order)
+                                                       order=order, allow=allow)
                     info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0], ended=info['ended'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob)
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob, ab)
                 self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()))
                 if not with_ended:
                     del self.last_decode['ended']
@@ -474,7 +760,7 @@ class GenerationMixin:
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
-                    tok = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ob, prev, pad_cpu)
+                    tok = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ab, ob, prev, pad_cpu)
                     if (tok >= sv).any():
                         break
                     res_cpu[0, i] = prev = tok
@@ -646,11 +932,11 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None, allow=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
         k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
-        (ordered_token; prev is tok_np, the decoder's input)."""
+        (ordered_token; prev is tok_np, the decoder's input). allow: the row's (V,) bool mask or None (allowed_token)."""
         import ctypes
         sv, ended = stop_vector(pad_cpu, stop), 'limit'
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
@@ -664,7 +950,7 @@ class GenerationMixin:
         for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
-            tok = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), order, tok_np, pad_cpu)
+            tok = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), allow, order, tok_np, pad_cpu)
             if (tok >= sv).any():
                 ended = end_reason(tok, pad_cpu)
                 break
@@ -677,7 +963,7 @@ class GenerationMixin:
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
     def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
-                       refill=False, stop=None, order=None):
+                       refill=False, stop=None, order=None, allow=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -712,7 +998,11 @@ class GenerationMixin:
         batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder's device sampler applies the same
         mask (pb_batch_decoder_order; a refilled slot gets its row's floor with the hand-over, pb_batch_decoder_admit_order), so its
         prediction holds where the constraint bites; the host's verification decides, as for every token. None, or -1 everywhere: the
-        call without the argument."""
+        call without the argument.
+        allow ((B, V) bools, or a list of B masks / None; check_allow): allowed classes, row b under `generate`'s contract with allow[b];
+        None = a free row, so one batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder's device
+        sampler tests the same bits (pb_batch_decoder_allow uploads the distinct masks once; a refilled slot gets its row's mask index
+        with the hand-over, pb_batch_decoder_admit_allow). None, or True everywhere: the call without the argument."""
         def done(out, with_ended=stop is not None):      # every path below records `ended`; a call without `stop` keeps the record it had
             if not with_ended and self.last_decode is not None:
                 self.last_decode.pop('ended', None)
@@ -725,6 +1015,7 @@ class GenerationMixin:
         pad0 = int(self.pb.pad_word_np[0])
         stop = check_stop(stop, P, pad0, owner if samples is not None else None)         # one entry per output row
         order = check_order(order, P, owner if samples is not None else None, order_max=pad0 - 1)            # ... and here
+        allow = check_allow(allow, P, self.lay if allow is not None else None, owner if samples is not None else None)   # ... and here: (distinct masks, one index per row)
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -733,10 +1024,10 @@ class GenerationMixin:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order))
-            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order))
+                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order, allow))
+            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order, allow))
         if slots and R > slots:
-            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order)
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order, allow)
             if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
                 return done(out)
         outs, ended = [], []
@@ -746,35 +1037,40 @@ class GenerationMixin:
             st = st if st is not None and any(v != pad0 for v in st) else None     # a chunk without a real stop is today's chunk
             od = order[c0:c0 + len(own)] if order is not None else None
             od = od if od is not None and any(v != -1 for v in od) else None       # ... and one without an ordered row
+            al = _slice_allow(allow, c0, c0 + len(own))                           # ... and one without a masked row
             p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
             outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
                                                    groups=[p - p0 for p in own] if samples is not None else None,
-                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st, order=od))
+                                                   forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st, order=od,
+                                                   allow=al))
             ended += (self.last_decode or {}).get('ended') or [None] * len(own)
         if len(outs) > 1 and self.last_decode is not None:                # last_decode describes the last chunk; `ended` covers every row
             self.last_decode['ended'] = ended
         return done(torch.cat(outs, 0))
 
-    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None, order=None):
+    def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None, order=None,
+                                 allow=None):
         """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt. stop: one
-        entry per ROW (check_stop expands it), or None; order likewise (check_order)."""
+        entry per ROW (check_stop expands it), or None; order likewise (check_order), and allow's indices (check_allow)."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
                                          max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
-                                         forced[idx.numpy()] if forced is not None else None, stop, order)
+                                         forced[idx.numpy()] if forced is not None else None, stop, order, allow)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
-    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None, order=None):
+    def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None, order=None,
+                             allow=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
         caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
         checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None; order: one bar floor per row
-        (check_order) or None."""
+        (check_order) or None; allow: check_allow's result with one index per row, or None."""
         saved = np.random.get_state()
         outs, ended, pad0 = [], [], int(self.pb.pad_word_np[0])
+        masks = unpack_allow(allow, self.lay.vocab)
         try:
             for b in range(int(enc_ids.shape[0])):
                 np.random.set_state(rngs[b].get_state())
@@ -782,7 +1078,8 @@ class GenerationMixin:
                 outs.append(self.generate(enc_ids[b:b + 1], emask[b:b + 1] if emask is not None else None, lambda r, **kw: sample_row(r, None, **kw),
                                           max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None,
                                           stop=stop[b] if stop is not None else pad0,         # 256: no stop, and the row's `ended`
-                                          order=order[b] if order is not None else None))
+                                          order=order[b] if order is not None else None,
+                                          allow=masks[b].numpy() if masks is not None and masks[b] is not None else None))
                 ended.append((self.last_decode or {}).get('ended'))
                 rngs[b].set_state(np.random.get_state())
         finally:
@@ -790,24 +1087,25 @@ class GenerationMixin:
         self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended)
         return torch.cat(outs, 0)
 
-    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None, order=None):
+    def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None, order=None,
+                              allow=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
         loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None;
-        order: one bar floor per ROW, or None."""
+        order: one bar floor per ROW, or None; allow: check_allow's result with one index per ROW, or None."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order, allow)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
             info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row, **kw: sample_row(row, rngs[b], **kw), [r.get_state() for r in rngs],
                                                sampler, run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
                                                forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop,
-                                               order=order)
+                                               order=order, allow=allow)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None):
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None, allow=None):
         """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
         waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
         in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
@@ -819,7 +1117,9 @@ class GenerationMixin:
         admission from a copy of rngs[r] (forced_draws). stop (R stop bars or None): the first n rows' values go up as a chunk's do
         (pb_batch_decoder_stop), a later row's is staged in front of its admission (pb_batch_decoder_admit_stop); a row without a stop
         stages nothing and its slot gets pad[0], never the previous occupant's value. order (R bar floors or None) travels the same way
-        (pb_batch_decoder_order, pb_batch_decoder_admit_order; a free row stages nothing and its slot gets -1). Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        (pb_batch_decoder_order, pb_batch_decoder_admit_order; a free row stages nothing and its slot gets -1), and so does allow (check_allow's
+        result for the R rows: the table of ALL rows' masks goes up at the start, pb_batch_decoder_allow, and a later row's index is staged,
+        pb_batch_decoder_admit_allow). Returns the (R, S, 8) result, or None -- before any encoder work -- where
         pb_batch_decoder_create declines the shape."""
         R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
@@ -835,11 +1135,12 @@ class GenerationMixin:
                 return None
             try:
                 return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
-                                        pad_cpu, stop, order).to(dev)
+                                        pad_cpu, stop, order, allow).to(dev)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
-    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None, order=None):
+    def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None, order=None,
+                    allow=None):
         """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
         import ctypes
         from collections import deque
@@ -912,6 +1213,10 @@ class GenerationMixin:
             LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop[:n], dtype=np.int32).ctypes.data)
         if order is not None and any(v != -1 for v in order[:n]):
             LIB.call('pb_batch_decoder_order', dec, np.asarray(order[:n], dtype=np.int32).ctypes.data)
+        if allow is not None:                                              # the masks of ALL rows: a later row's index points into this table
+            LIB.call('pb_batch_decoder_allow', dec, allow[0].ctypes.data, allow[0].shape[0], allow[0].shape[1],
+                     np.asarray(allow[1][:n], dtype=np.int32).ctypes.data)
+        masks = unpack_allow(allow, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
@@ -963,6 +1268,8 @@ class GenerationMixin:
                     LIB.call('pb_batch_decoder_admit_stop', dec, s, stop[r])
                 if order is not None and order[r] != -1:                   # likewise; a free successor of an ordered row gets -1
                     LIB.call('pb_batch_decoder_admit_order', dec, s, order[r])
+                if allow is not None and allow[1][r] != -1:                # likewise; a free successor of a masked row gets -1
+                    LIB.call('pb_batch_decoder_admit_allow', dec, s, allow[1][r])
                 LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
                          fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
                 counts['admissions'] += 1
@@ -991,8 +1298,9 @@ class GenerationMixin:
 
         def verify(s, r, a, e):                    # positions a .. e-1 of row r in slot s, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(a, e):
-                tok = ordered_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
-                                    order[r] if order is not None else None, res_cpu[r, i - 1] if i else sos, pad_cpu)
+                tok = allowed_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
+                                    masks[r] if masks is not None else None, order[r] if order is not None else None,
+                                    res_cpu[r, i - 1] if i else sos, pad_cpu)
                 tokens[r] += 1
                 if (tok >= svs[r]).any():
                     ended[r] = end_reason(tok, pad_cpu)
@@ -1046,7 +1354,7 @@ class GenerationMixin:
         return res_cpu
 
     def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None,
-                               order=None):
+                               order=None, allow=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -1071,7 +1379,10 @@ class GenerationMixin:
         order (B bar floors, check_order) or None: the values go to the device sampler too (pb_batch_decoder_order: it masks heads 0 and 1
         against the row's decoder input on the device) and the host samples every position through ordered_token, with prev = the row's
         previous result row (the prefix's last row at k_b, the SOS row at 0). A device that ignored the mask would be rewound wherever it
-        bites; one that applies it differs from the host as rarely as the unordered sampler does."""
+        bites; one that applies it differs from the host as rarely as the unordered sampler does.
+        allow (check_allow's result with B indices) or None: the distinct masks and the rows' indices go to the device sampler
+        (pb_batch_decoder_allow: it tests the class's bit where it forms the quotient) and the host samples every position through
+        allowed_token with the row's mask; the logged logits rows are the raw ones."""
         import contextlib
         import ctypes
         from collections import deque
@@ -1099,6 +1410,10 @@ class GenerationMixin:
             LIB.call('pb_batch_decoder_stop', dec, np.asarray(stop, dtype=np.int32).ctypes.data)
         if order is not None:
             LIB.call('pb_batch_decoder_order', dec, np.asarray(order, dtype=np.int32).ctypes.data)
+        if allow is not None:
+            LIB.call('pb_batch_decoder_allow', dec, allow[0].ctypes.data, allow[0].shape[0], allow[0].shape[1],
+                     np.asarray(allow[1], dtype=np.int32).ctypes.data)
+        masks = unpack_allow(allow, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
@@ -1133,8 +1448,9 @@ class GenerationMixin:
 
         def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(s, e):
-                tok = ordered_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
-                                    order[b] if order is not None else None, res_cpu[b, i - 1] if i else sos, pad_cpu)
+                tok = allowed_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
+                                    masks[b] if masks is not None else None, order[b] if order is not None else None,
+                                    res_cpu[b, i - 1] if i else sos, pad_cpu)
                 tokens[b] += 1
                 if (tok >= svs[b]).any():
                     ended[b] = end_reason(tok, pad_cpu)
@@ -1175,12 +1491,13 @@ class GenerationMixin:
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
                     device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, ended=ended)
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
         rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
         fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads.
-        stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None (ordered_token; prev is `cur`, the step's input)."""
+        stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None (ordered_token; prev is `cur`, the step's input).
+        allow: the row's (V,) bool mask or None (allowed_token)."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
@@ -1232,7 +1549,7 @@ class GenerationMixin:
                 frow = fr[i] if fr is not None else None
                 if frow is None or (frow < 0).any():
                     ops.gemm(h, self.w['head.w'], logits, M=1, N=self.lay.vocab, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
-                tok = ordered_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), order,
+                tok = allowed_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), allow, order,
                                     cur.reshape(8).cpu() if order is not None else None, pad_cpu)
                 if (tok >= sv).any():
                     break
@@ -1240,11 +1557,11 @@ class GenerationMixin:
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
         cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
-        (ordered_token; prev is decoder input i, which the loop wrote at i - 1)."""
+        (ordered_token; prev is decoder input i, which the loop wrote at i - 1). allow: the row's (V,) bool mask or None (allowed_token)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -1267,7 +1584,7 @@ class GenerationMixin:
                 dec16 = ops.ids_to_i16(dec)
                 dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
                 logits = self.heads_forward(dec_h)
-                cur = ordered_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), order,
+                cur = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), allow, order,
                                     dec[0, i].cpu() if order is not None else None, pad_cpu)
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)

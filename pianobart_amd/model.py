@@ -350,7 +350,7 @@ class PianoBartLM(nn.Module):
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
                 decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None,
-                decoder_order=None):
+                decoder_order=None, decoder_allow=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
         position k on (Engine.generate's `prefix`).
         decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
@@ -369,7 +369,14 @@ class PianoBartLM(nn.Module):
         (the SOS row, the prefix's last row, else the previous token after forcing): bars below max(decoder_order, prev's bar) have
         probability 0, and so have positions below prev's position while the bar (after forcing) stays prev's. Special ids stay
         reachable, heads 2 .. 7 and given heads are untouched, and the draws are those of the unordered call. 0 = ordered without an
-        extra bar floor; -1, or None: not ordered. DESIGN.md section 1, "Time-ordered sampling"."""
+        extra bar floor; -1, or None: not ordered. DESIGN.md section 1, "Time-ordered sampling".
+        decoder_allow ((V,) bools in model column order, V = the layout's total, 1280 in the default dictionary, or a sequence of one;
+        generate=True only): allowed classes -- the reference loop with `sampling(logit, p, t)` seeing -inf in place of every logit whose
+        bit is False: such a class has probability exactly 0, is never a nucleus candidate and never the arg-max of a p = 1 head. The
+        mask is constant over the positions; the six special ids of every head are always reachable (generation.check_allow sets them);
+        given heads are written as given; the draws, the stop test and decoder_prefix are untouched; with decoder_order the row loses the
+        classes either rule removes. generation.allow_mask builds a mask from the dictionary's names (key, pitch range, instruments, ..).
+        None, or True everywhere: the call without the argument. DESIGN.md section 1, "Allowed classes"."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
@@ -380,6 +387,8 @@ class PianoBartLM(nn.Module):
                 raise PBError('decoder_stop ends a generated piece at a bar: it needs generate=True')
             if decoder_order is not None:
                 raise PBError('decoder_order constrains what a generated piece samples: it needs generate=True')
+            if decoder_allow is not None:
+                raise PBError('decoder_allow constrains what a generated piece samples: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             off = self.pianobart.layout.seg_off
@@ -388,13 +397,13 @@ class PianoBartLM(nn.Module):
             print("ERROR")
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
-                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order)
+                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order, allow=decoder_allow)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
                        decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False,
-                       decoder_stop=None, decoder_order=None):
+                       decoder_stop=None, decoder_order=None, decoder_allow=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -416,7 +425,11 @@ class PianoBartLM(nn.Module):
         test too, so a stopped row leaves the batch (or frees its slot under refill) at once.
         decoder_order (B ints -1 .. 255): prompt b under forward(generate=True, decoder_order=...)'s contract with its own bar floor; -1 = not
         ordered, so one batch may mix both. With samples_per_prompt it describes the P prompts. The fused decoder's device sampler
-        applies the same mask, so an ordered batch keeps the batched decode's launches per step and its rewind rate."""
+        applies the same mask, so an ordered batch keeps the batched decode's launches per step and its rewind rate.
+        decoder_allow ((B, V) bools, or a list of B entries, each a (V,) mask or None = free): prompt b under forward(generate=True,
+        decoder_allow=...)'s contract with its own mask, so one batch may mix masked and free rows. With samples_per_prompt it describes
+        the P prompts. The fused decoder's device sampler tests the same bits, so a masked batch keeps the batched decode's launches per
+        step and its rewind rate."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -433,7 +446,8 @@ class PianoBartLM(nn.Module):
         eng = self._get_engine()
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
-                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order)
+                                 samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order,
+                                 allow=decoder_allow)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):
@@ -461,7 +475,7 @@ class PianoBartLM(nn.Module):
     SAMPLE_T =[1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
-    def sample_row(self, row_logits, rng=None, order=None):
+    def sample_row(self, row_logits, rng=None, order=None, allow=None):
         """row_logits: (vocab,) f32 CPU tensor of one position (1280 for the default dictionary); returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
         on the host row -- the division by the temperature (one call with a per-element temperature vector: the same quotients) and a
         1-D softmax per head -- then nucleus() for all 8 heads in one native call (pb_nucleus_rows: numpy's arithmetic order and
@@ -472,12 +486,18 @@ class PianoBartLM(nn.Module):
         order = (low, prev0, low1, given0) (generation.ordered_token), or None: the time-ordered sample. The quotients of head 0's
         classes below `low` are set to -inf in front of the softmax (probability exactly 0). If low1 > 0 and head 0's id after forcing
         (given0 if >= 0, else the id just sampled) equals prev0, head 1's classes below low1 are masked the same way and head 1 is sampled
-        again with the same u[1]. One random_sample(8) either way; without `order` the arithmetic and the native call are unchanged."""
+        again with the same u[1]. One random_sample(8) either way; without `order` the arithmetic and the native call are unchanged.
+        allow = a (vocab,) bool tensor or array, True = the class may be sampled (generation.allowed_token), or None: the quotients of
+        the other columns are set to -inf in front of the 8 softmaxes (probability exactly 0), beside the ordered sample's own mask; head
+        1's second pass starts from the masked quotients. The native call and the tie rule are unchanged; without `allow` so is the
+        arithmetic."""
         lay = getattr(getattr(self, 'pianobart', None), 'layout', None) or ops.DEFAULT_LAYOUT      # called on the class itself: the default dictionary
         tab = _sample_tables(lay)
         off = lay.seg_off
         y = row_logits / tab['tvec']
         probs = tab['probs']
+        if allow is not None:
+            y.masked_fill_(~torch.as_tensor(allow), -np.inf)
         if order is not None and order[0] > 0:
             y[off[0]:off[0] + order[0]] = -np.inf
         for j in range(8):                                           # 1-D calls: a 2-D softmax would open an OpenMP region per position
