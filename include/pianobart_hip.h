@@ -318,6 +318,66 @@ int pb_sum_rows_bf16(const void* src, void* dst, int32_t rows, int64_t n, void* 
  * Nothing outside [0, n) is read or written; no atomics (bit-reproducible); n <= 0 is a no-op that returns 0. */
 int pb_accum_f32(float* dst, const float* src, int64_t n, int32_t add, void* stream);
 
+/* ---- K18: checkpoint merging (pb_merge.hip; additions to ABI 10) -----------------------------------------------------
+ * Replaces model_merging_methods/merging_methods.py (average_merging, task_arithmetic, ties_merging, mask_merging) and
+ * mask_weights_utils.py of the reference's tidied tree: N fine-tuned backbones and the pre-trained one, each packed into ONE flat f32
+ * vector in the order of the sorted parameter names, are merged by a handful of streaming passes. All arithmetic is float32, every
+ * operation rounded once in the order DESIGN.md 9 writes it (the file is compiled without contraction: an FMA would break bit parity
+ * with the reference's CPU tensors). Integer counts only, no float atomics: equal inputs give equal bytes.
+ *
+ * pb_merge_kth_abs: *kth_out = the exact k-th smallest (1 <= k <= n) of |x[i] - base[i]| (base != NULL; the difference is rounded once)
+ *   or |x[i]|, i < n, as a radix select over the magnitude's bit pattern (non-negative floats order as unsigned integers): four
+ *   streaming histogram passes over 8 bits each, top down (per-workgroup LDS bins merged by 64-bit integer atomics), a one-workgroup
+ *   kernel between them that picks the bin holding the k-th element and narrows the prefix. The state lives in ws
+ *   (pb_merge_kth_ws_bytes() bytes, 8-byte aligned; free for reuse by the next call on the same stream); no host round trip.
+ *   *flags_out |= 1 when a magnitude has an all-ones exponent (inf / NaN); the caller zeroes and reads the word. Pointers need 4-byte
+ *   alignment only (segments of a flat buffer): 16-byte loads for the body, scalar head and tail; x and base offset differently from
+ *   a 16-byte boundary go scalar throughout.
+ * pb_merge_sign_tally: TIES pass 1. With D_m = model[m] - pre, T_m = D_m where |D_m| >= *thresh[m] (NULL: everywhere) else 0 and
+ *   s = (T_0 + T_1) + ...: tally[0] += #{s > 0}, tally[1] += #{s < 0} (device int64[2], zeroed by the caller). Reads n_models, pre,
+ *   model, thresh and n of the descriptor.
+ * pb_merge_apply: out[i] for i < n in one fused pass: one 16-byte load per input vector and lane, one store, registers in between.
+ *   Element i is element g = g0 + i of the whole flat vector; a call over a segment draws the random mask the whole-vector call draws
+ *   (g0 need not be a multiple of 4). Per model m: kind NONE: W_m = model[m]. Otherwise X = model[m] - pre (format DELTA) or model[m]
+ *   (format FINETUNED); X *= 0 where it is masked -- MAGNITUDE: |X| <= *thresh[m]; RANDOM: word g & 3 of
+ *   philox4x32-7(g >> 2, model_base + m, 0x4D455247, 0) under the key (low, high half of seed) < drop_thresh[m] (= uint32(float32(rate) 2^32), as
+ *   64 bits so that rate 1 drops everything) --; X /= rescale[m] (pass 1 for none); W_m = pre + X (DELTA) or X. Then
+ *     PB_MERGE_AVERAGE   (((0 + W_0) + W_1) + ...) / float(n_models)    (torch's sum starts at +0: all -0.0 gives +0.0; so do the TIES sums)
+ *     PB_MERGE_TASK      pre + lambda * ((W_0 - pre) + (W_1 - pre) + ...)
+ *     PB_MERGE_TIES      T_m as for the tally (every kind must be NONE; thresh[m] is the trim threshold); sign = sgn(s), where s == 0
+ *                        the sign of tally[0] - tally[1]; kept_m = T_m where its sign equals that sign, else T_m * 0;
+ *                        pre + lambda * (((kept_0 + kept_1) + ...) / max(#{kept_m != 0}, 1))
+ *     PB_MERGE_MASKED    W_0 (n_models = 1): the masked model itself, for callers that run TIES over masked models
+ *   2 <= n_models <= PB_MERGE_MAX_MODELS otherwise. out may not alias an input. The descriptor starts zeroed. */
+#define PB_MERGE_MAX_MODELS 8
+#define PB_MERGE_AVERAGE 0
+#define PB_MERGE_TASK 1
+#define PB_MERGE_TIES 2
+#define PB_MERGE_MASKED 3
+#define PB_MERGE_MASK_NONE 0
+#define PB_MERGE_MASK_MAGNITUDE 1
+#define PB_MERGE_MASK_RANDOM 2
+#define PB_MERGE_DELTA 0
+#define PB_MERGE_FINETUNED 1
+typedef struct pb_merge_desc {
+    const float* pre; float* out;
+    const float* model[PB_MERGE_MAX_MODELS];
+    const float* thresh[PB_MERGE_MAX_MODELS];   /* device scalars (pb_merge_kth_abs results) */
+    int64_t* tally;
+    int64_t n, g0;
+    uint64_t seed;
+    uint64_t drop_thresh[PB_MERGE_MAX_MODELS];
+    float rescale[PB_MERGE_MAX_MODELS];
+    int32_t mask_kind[PB_MERGE_MAX_MODELS];
+    int32_t n_models, method, format; float lambda;
+    int32_t model_base, _pad;                   /* index of model[0] in the whole merge: model m draws stream model_base + m */
+} pb_merge_desc;
+int64_t pb_merge_desc_bytes(void);
+int64_t pb_merge_kth_ws_bytes(void);
+int pb_merge_kth_abs(const float* x, const float* base, int64_t n, int64_t k, float* kth_out, int32_t* flags_out, void* ws, void* stream);
+int pb_merge_sign_tally(const pb_merge_desc* d, void* stream);
+int pb_merge_apply(const pb_merge_desc* d, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

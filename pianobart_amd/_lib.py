@@ -81,6 +81,23 @@ class AttnDesc(ctypes.Structure):
     _fields_ = parse_struct('pb_attn_desc')
 
 
+MERGE_MAX_MODELS = 8
+MERGE_AVERAGE, MERGE_TASK, MERGE_TIES, MERGE_MASKED = 0, 1, 2, 3
+MERGE_MASK_NONE, MERGE_MASK_MAGNITUDE, MERGE_MASK_RANDOM = 0, 1, 2
+MERGE_DELTA, MERGE_FINETUNED = 0, 1
+
+
+class MergeDesc(ctypes.Structure):
+    """pb_merge_desc (it holds arrays, which parse_struct does not read; tests/test_merge_cpu.py compares the size with the compiler's)."""
+    _fields_ = [('pre', ctypes.c_void_p), ('out', ctypes.c_void_p),
+                ('model', ctypes.c_void_p * MERGE_MAX_MODELS), ('thresh', ctypes.c_void_p * MERGE_MAX_MODELS), ('tally', ctypes.c_void_p),
+                ('n', ctypes.c_int64), ('g0', ctypes.c_int64), ('seed', ctypes.c_uint64),
+                ('drop_thresh', ctypes.c_uint64 * MERGE_MAX_MODELS), ('rescale', ctypes.c_float * MERGE_MAX_MODELS),
+                ('mask_kind', ctypes.c_int32 * MERGE_MAX_MODELS),
+                ('n_models', ctypes.c_int32), ('method', ctypes.c_int32), ('format', ctypes.c_int32), ('lam', ctypes.c_float),
+                ('model_base', ctypes.c_int32), ('_pad', ctypes.c_int32)]
+
+
 def parse_header(path=HEADER):
     """Returns {name: (restype, [argtypes])} for every function the header declares."""
     src = re.sub(r'typedef\s+struct.*?}\s*\w+\s*;', ' ', _header_source(path), flags=re.S)

@@ -17,6 +17,12 @@ FLAGS = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-ffp-contract=
          '-mllvm', '-amdgpu-mfma-vgpr-form=1'] + os.environ.get('PB_EXTRA_HIPCC_FLAGS', '').split()      # e.g. -DPB_FA1_STAMPS (diagnostic build)
 
 
+# flags of single sources, after FLAGS (the last -ffp-contract wins). pb_merge.hip: bit parity with the reference's CPU tensors needs every float32
+# operation rounded on its own; under -ffp-contract=fast the backend fuses a * b + c whatever the source says (`#pragma clang fp contract(off)` does not
+# reach it, and clang's __fmul_rn / __fadd_rn are plain operators)
+FILE_FLAGS = {'pb_merge.hip': ['-ffp-contract=off']}
+
+
 def _hipcc():
     for c in (os.environ.get('HIPCC'), '/opt/rocm/bin/hipcc', 'hipcc'):
         if c and (os.path.isabs(c) and os.path.exists(c) or not os.path.isabs(c)):
@@ -47,7 +53,7 @@ def build(force=False, verbose=True, jobs=None):
 
     def cc(job):
         src, obj = job
-        cmd = [_hipcc()] + FLAGS + ['-c', src, '-o', obj]
+        cmd = [_hipcc()] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ['-c', src, '-o', obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError('hipcc failed for %s:\n%s' % (src, r.stderr[-4000:]))

@@ -7,7 +7,8 @@ import os
 import torch
 
 from ._lib import (LIB, PB_BF16, PB_F32, PB_F32X3, AttnDesc, GemmDesc, PBError, GEMM_ACCUM, GEMM_C_F32, GEMM_GELU,
-                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS)
+                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS, MergeDesc, MERGE_MAX_MODELS, MERGE_AVERAGE,
+                   MERGE_DELTA, MERGE_MASK_NONE)
 
 CLASS_NAMES = ('Bar', 'Position', 'Instrument', 'Pitch', 'Duration', 'Velocity', 'TimeSig', 'Tempo')   # PianoBart.classes order
 SPECIAL_TAGS = ('PAD', 'MASK', 'SOS', 'EOS', 'CLS', 'SEP')  # the six special ids of a head: its last six, in this order
@@ -348,6 +349,64 @@ def accum_f32(dst, src, add=True):
     if dst.dtype != torch.float32 or src.dtype != torch.float32 or dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
         raise PBError('accum_f32 needs two contiguous f32 tensors of the same size')
     LIB.call('pb_accum_f32', _p(dst), _p(src), dst.numel(), int(bool(add)), _stream())
+
+
+def _flat_f32(t, what):
+    if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+        raise PBError('%s must be a contiguous 1-D f32 tensor' % what)
+    return _p(t).value
+
+
+def merge_kth_ws(device):
+    """The state of one pb_merge_kth_abs call (reusable by the next call on the same stream)."""
+    return torch.empty((LIB.query('pb_merge_kth_ws_bytes') + 7) // 8, dtype=torch.int64, device=device)
+
+
+def merge_kth_abs(x, base, k, kth_out, flags, ws):
+    """kth_out[0] = the exact k-th smallest of |x - base| (base None: |x|), 1 <= k <= x.numel(); x / base are flat f32 tensors or views into
+    them. flags (int32[1], zeroed by the caller) gets bit 0 when a magnitude is inf or NaN. Nothing comes back to the host."""
+    if base is not None and base.numel() != x.numel():
+        raise PBError('merge_kth_abs: x and base differ in size')
+    if kth_out.dtype != torch.float32 or flags.dtype != torch.int32:
+        raise PBError('merge_kth_abs: kth_out is f32, flags int32')
+    LIB.call('pb_merge_kth_abs', _flat_f32(x, 'x'), None if base is None else _flat_f32(base, 'base'), x.numel(), int(k), _p(kth_out), _p(flags), _p(ws), _stream())
+
+
+def merge_desc(pre, models, out=None, *, method=MERGE_AVERAGE, fmt=MERGE_DELTA, lam=1.0, kinds=None, thresh=None, drop_thresh=None,
+               rescale=None, tally=None, seed=0, g0=0, model_base=0):
+    """A pb_merge_desc over flat f32 tensors (or equal views of them: a segment that starts at element g0 of the whole vector). kinds /
+    thresh (one-element f32 device tensors or None) / drop_thresh (ints) / rescale (the divisor float32(1 - rate); 1 = none) are per model;
+    model_base = the index of models[0] in the whole merge (its random mask stream)."""
+    N = len(models)
+    if N > MERGE_MAX_MODELS:
+        raise PBError('merging takes at most %d models at a time (got %d)' % (MERGE_MAX_MODELS, N))
+    d = MergeDesc()
+    d.pre, d.n = _flat_f32(pre, 'pre'), pre.numel()
+    if out is not None:
+        if out.numel() != pre.numel():
+            raise PBError('merge: out and pre differ in size')
+        d.out = _flat_f32(out, 'out')
+    for m, f in enumerate(models):
+        if f.numel() != pre.numel():
+            raise PBError('merge: model %d and pre differ in size' % m)
+        d.model[m] = _flat_f32(f, 'model %d' % m)
+        d.mask_kind[m] = kinds[m] if kinds else MERGE_MASK_NONE
+        d.thresh[m] = _adr(thresh[m]) if thresh and thresh[m] is not None else None
+        d.drop_thresh[m] = int(drop_thresh[m]) if drop_thresh else 0
+        d.rescale[m] = float(rescale[m]) if rescale else 1.0
+    d.tally = _adr(tally)
+    d.g0, d.seed = int(g0), int(seed) & 0xFFFFFFFFFFFFFFFF
+    d.n_models, d.method, d.format, d.lam, d.model_base = N, method, fmt, float(lam), int(model_base)
+    return d
+
+
+def merge_sign_tally(desc):
+    """TIES pass 1: desc.tally (int64[2], zeroed by the caller) += the counts of positive and negative summed signs."""
+    LIB.call('pb_merge_sign_tally', ctypes.byref(desc), _stream())
+
+
+def merge_apply(desc):
+    LIB.call('pb_merge_apply', ctypes.byref(desc), _stream())
 
 
 def transpose_batch_bf16(src, dst, table, n_tiles):

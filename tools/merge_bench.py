@@ -1,0 +1,98 @@
+"""Checkpoint merging at the size of the BASELINE configs[1] backbone (12L / 768d / ffn 3072 / 12 heads, S = 1024) with N = 4 models:
+ms per kernel family, GB/s on the bytes each family moves, the whole merge_flat call of each method, and pb_accum_f32 on the same n in
+the same process as the yardstick of a streaming kernel on the machine.
+
+    python tools/merge_bench.py [--models 4] [--out profiles/merge_kernel_stats.txt]
+
+Each timed call runs once after one warm-up call of the same shape, between device events. Bytes are counted from the shapes:
+accum 12 n; one k-th call 4 passes x 8 n (x and base); tally (N + 1) 4 n; apply (N + 1) 4 n + 4 n. Nothing is asserted."""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def backbone_segments(seq):
+    """The segment table of the configs[1] backbone, from a model built without storage."""
+    from pianobart_amd.merge import segment_table
+    from pianobart_amd.model import BartConfig, PianoBart
+    from tests.golden_util import load_vocab
+    e2w, w2e = load_vocab()
+    cfg = BartConfig(max_position_embeddings=seq, d_model=768, encoder_layers=12, decoder_layers=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072,
+                     encoder_attention_heads=12, decoder_attention_heads=12)
+    m = PianoBart(cfg, e2w, w2e)
+    return segment_table({n: tuple(p.shape) for n, p in m.named_parameters()})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--models', type=int, default=4)
+    ap.add_argument('--seq', type=int, default=1024)
+    ap.add_argument('--out', default='')
+    args = ap.parse_args()
+    from pianobart_amd import ops, _lib
+    from pianobart_amd.merge import MergePlan, drop_threshold, merge_flat, rescale_divisor
+    if not torch.cuda.is_available():
+        raise SystemExit('merge_bench needs a GPU: nothing is measured without one')
+    dev = torch.device('cuda', 0)
+    segs = backbone_segments(args.seq)
+    n, N = segs[-1].offset + segs[-1].numel, args.models
+    g = torch.Generator(device=dev).manual_seed(1234)
+    pre = torch.randn(n, device=dev, generator=g) * 0.02
+    models = [pre + torch.randn(n, device=dev, generator=g) * 0.002 * (m + 1) for m in range(N)]
+    out = torch.empty_like(pre)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    def timed(fn):
+        fn()                                                   # warm-up of the same shape
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def row(name, ms, nbytes=None):
+        say('%-46s %9.3f ms%s' % (name, ms, '' if nbytes is None else '   %8.1f GB/s over %6.2f GB' % (nbytes / ms / 1e6, nbytes / 1e9)))
+
+    say('checkpoint merging, %s, n = %d parameters (%d tensors), N = %d models' % (torch.cuda.get_device_name(0), n, len(segs), N))
+    row('pb_accum_f32 add (yardstick)', timed(lambda: ops.accum_f32(out, pre, add=True)), 12.0 * n)
+    ws, flags, thr = ops.merge_kth_ws(dev), torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(N, device=dev)
+    k = int(n * 0.8)
+    row('pb_merge_kth_abs, whole vector, k = 0.8 n', timed(lambda: ops.merge_kth_abs(models[0], pre, k, thr[0:1], flags, ws)), 4 * 8.0 * n)
+    for m in range(1, N):
+        ops.merge_kth_abs(models[m], pre, k, thr[m:m + 1], flags, ws)
+    tally = torch.zeros(2, dtype=torch.int64, device=dev)
+    th = [thr[m:m + 1] for m in range(N)]
+    d = ops.merge_desc(pre, models, out, method=_lib.MERGE_TIES, lam=1.0, thresh=th, tally=tally)
+    row('pb_merge_sign_tally', timed(lambda: ops.merge_sign_tally(d)), (N + 1) * 4.0 * n)
+    rates = [0.8] * N
+    common = dict(drop_thresh=[drop_threshold(r) for r in rates], rescale=[rescale_divisor(r, True) for r in rates], seed=7)
+    for name, desc in (('average', ops.merge_desc(pre, models, out, method=_lib.MERGE_AVERAGE)),
+                       ('task arithmetic', ops.merge_desc(pre, models, out, method=_lib.MERGE_TASK, lam=0.7)),
+                       ('ties', d),
+                       ('average, random masks', ops.merge_desc(pre, models, out, method=_lib.MERGE_AVERAGE, kinds=[_lib.MERGE_MASK_RANDOM] * N, **common)),
+                       ('average, magnitude masks', ops.merge_desc(pre, models, out, method=_lib.MERGE_AVERAGE, kinds=[_lib.MERGE_MASK_MAGNITUDE] * N, thresh=th, **common))):
+        row('pb_merge_apply: ' + name, timed(lambda: ops.merge_apply(desc)), (N + 2) * 4.0 * n)
+    for name, kw in (('average_merging', dict(method='average_merging')), ('task_arithmetic', dict(method='task_arithmetic', scaling_coefficient=0.7)),
+                     ('ties_merging', dict(method='ties_merging')), ('mask_merging random / average', dict(method='mask_merging')),
+                     ('mask_merging magnitude / average (per tensor)', dict(method='mask_merging', mask_strategy='magnitude')),
+                     ('mask_merging random / ties', dict(method='mask_merging', mask_apply_method='ties_merging'))):
+        plan = MergePlan(N, **kw)
+        row('merge_flat: ' + name, timed(lambda: merge_flat(plan, pre, models, segs)))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
