@@ -378,6 +378,32 @@ int pb_merge_kth_abs(const float* x, const float* base, int64_t n, int64_t k, fl
 int pb_merge_sign_tally(const pb_merge_desc* d, void* stream);
 int pb_merge_apply(const pb_merge_desc* d, void* stream);
 
+/* ---- K19: set metrics for generated pieces (pb_metrics.hip; additions to ABI 10) ----------------------------------------
+ * Per-piece musical features, pairwise feature distances, their moments and a Gaussian kernel density estimate: the device half of
+ * pianobart_amd.metrics. Integer counts and fixed-order floating-point sums only: equal inputs give equal bytes.
+ * Every entry checks its arguments before the first HIP call (-2, pb_last_error names the field).
+ *
+ * pb_piece_features: feat (N, 288) int32 from ids16 (N, S, 8) int16, 16-byte aligned. The notes of piece n are its rows
+ *   start[n] (0 when start is NULL) .. L - 1, L = the first row in which any head's id is >= pad8[h] (S if none). pad8: 8 HOST
+ *   int32, each 1 .. 1082; pitch_of: pad8[3] device int16, the MIDI number of a pitch id or -1 (percussion); dur_pos: pad8[4]
+ *   device int32, the length of a duration id in positions. The columns are the table of DESIGN.md 10. One workgroup per piece, a
+ *   workgroup sweeping over several pieces when they are short or many.
+ * pb_pairwise_l2: D[i, j] = sqrt(sum_f (A[i, f] - B[j, f])^2), A (N, F), B (M, F), D (N, M) f32, 1 <= F <= 144; one f32 chain over
+ *   f = 0 .. F - 1 of the squared differences (never |a|^2 + |b|^2 - 2ab): equal rows give exactly 0.
+ * pb_sample_moments: out[0 .. 5] = n, sum, sum of squares, 0, min, max (device doubles) of the samples of D (N, M) f32: all of it,
+ *   or with upper = 1 (N == M) the strict upper triangle j > i. f64 throughout, fixed-order partials in ws.
+ * pb_kde_eval: dens[g] = 1 / (n h sqrt(2 pi)) sum_s exp(-(grid[g] - s)^2 / (2 h^2)) over the same samples, 1 <= G <= 4096, n >= 1.
+ *   Terms in f32 (one exp2 of (grid[g] - s)^2 * float32(-log2(e) / (2 h^2))), summed in f64: per sample slab one partial row in ws,
+ *   the slabs summed front to back by a second kernel.
+ * pb_metrics_ws_bytes: the bytes of ws (8-byte aligned, free for reuse by the next call on the same stream) that
+ *   pb_sample_moments and pb_kde_eval need for an (N, M) matrix and G grid points. */
+int64_t pb_metrics_ws_bytes(int64_t N, int64_t M, int32_t G);
+int pb_piece_features(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int32_t* dur_pos,
+                      int32_t* feat, int32_t N, int32_t S, void* stream);
+int pb_pairwise_l2(const float* A, const float* B, float* D, int32_t N, int32_t M, int32_t F, void* stream);
+int pb_sample_moments(const float* D, int64_t N, int64_t M, int32_t upper, double* out, void* ws, void* stream);
+int pb_kde_eval(const float* D, int64_t N, int64_t M, int32_t upper, const float* grid, int32_t G, double h, double* dens, void* ws, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

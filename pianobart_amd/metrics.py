@@ -1,0 +1,277 @@
+"""Set metrics for generated pieces: does a generated SET look like the data? The protocol of Yang & Lerch, "On the evaluation of
+generative models in music": per-piece musical features, the pairwise distances inside each set and between the sets, a Gaussian kernel
+density estimate of each distance sample, and from those the KL divergence and the overlapped area of intra-set and inter-set distances.
+
+The features (pb_piece_features), the N x M distances (pb_pairwise_l2), their moments (pb_sample_moments) and the n x G Gaussian terms
+(pb_kde_eval) run in pb_metrics.hip; the host divides integer columns, picks bandwidths and integrates G-point curves.
+There is no CPU path. The reference's own quality line (the `shapesimilarity` "FAD" of its GenerationTrainer) needs a third-party
+package this project does not have and stays `n/a`; this module does not stand in for it, it measures something else."""
+import json
+import os
+import re
+from collections import OrderedDict, namedtuple
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import PBError
+from .octuple_midi import code_to_dur
+
+_VOCAB = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'octuple_vocab.json')
+MAX_PITCH = ops.HEAD_MAX - 1                  # the kernel's pitch bitmap covers 0 .. HEAD_MAX - 1
+
+Tables = namedtuple('Tables', 'pitch_of dur_pos layout')
+
+SCALAR_GROUPS = ('note_count', 'pitch_count', 'pitch_range', 'avg_interval', 'notes_per_bar', 'avg_duration', 'avg_velocity', 'onset_ratio')
+# histogram groups: (first column, width, divisor column)
+HIST_GROUPS = OrderedDict([('pch', (16, 12, 1)), ('pctm', (28, 144, 8)), ('beat_grid', (172, 16, 0)), ('duration_hist', (188, 32, 0)),
+                           ('velocity_hist', (220, 32, 0)), ('bar_density_hist', (252, 32, 2))])
+GROUPS = SCALAR_GROUPS + tuple(HIST_GROUPS)
+
+
+def _default_e2w():
+    return json.load(open(_VOCAB))['e2w']
+
+
+def _words_by_id(e2w, name, n):
+    """The words of ids 0 .. n - 1 of a class; PBError when an id has no word."""
+    by_id = {int(i): w for w, i in e2w[name].items()}
+    missing = [i for i in range(n) if i not in by_id]
+    if missing:
+        raise PBError('metrics: class %s has no word for id %d' % (name, missing[0]))
+    return [by_id[i] for i in range(n)]
+
+
+def tables(e2w=None):
+    """Tables(pitch_of, dur_pos, layout) of a dictionary's event -> word half (None: the default dictionary): pitch_of[id] = k for the word
+    'Pitch k' and -1 for 'Pitch percussion k' (int16, one entry per ordinary pitch id); dur_pos[id] = octuple_midi.code_to_dur(c) for the
+    word 'Duration c' (int32, one entry per ordinary duration id). A word of another form is a PBError that names it."""
+    if e2w is None:
+        e2w = _default_e2w()
+    layout = ops.Layout.from_dict(e2w)
+    pitch_of = np.empty(layout.pad8[3], dtype=np.int16)
+    for i, w in enumerate(_words_by_id(e2w, 'Pitch', layout.pad8[3])):
+        m = re.fullmatch(r'Pitch (percussion )?(\d+)', w)
+        if not m:
+            raise PBError("metrics: pitch word %r (id %d) is neither 'Pitch k' nor 'Pitch percussion k'" % (w, i))
+        k = -1 if m.group(1) else int(m.group(2))
+        if k > MAX_PITCH:
+            raise PBError('metrics: pitch word %r (id %d): the pitch number must lie in 0 .. %d' % (w, i, MAX_PITCH))
+        pitch_of[i] = k
+    dur_pos = np.empty(layout.pad8[4], dtype=np.int32)
+    for i, w in enumerate(_words_by_id(e2w, 'Duration', layout.pad8[4])):
+        m = re.fullmatch(r'Duration (\d+)', w)
+        if not m:
+            raise PBError("metrics: duration word %r (id %d) is not 'Duration c'" % (w, i))
+        dur_pos[i] = code_to_dur(int(m.group(1)))
+    return Tables(pitch_of, dur_pos, layout)
+
+
+def _host_ids(ids, layout):
+    """ids as a host int64 (N, S, 8) array, every id checked against its head's size."""
+    if torch.is_tensor(ids):
+        ops._p(ids)                                   # a host tensor is refused as every op refuses it: there is no CPU path
+        ids = ids.detach().cpu().numpy()
+    a = np.asarray(ids)
+    if a.ndim != 3 or a.shape[2] != 8 or a.shape[1] < 1:
+        raise PBError('metrics: ids must be (N, S, 8) with S >= 1 (got %s)' % (a.shape,))
+    if a.dtype.kind == 'f':
+        r = np.rint(a)
+        if not np.array_equal(r, a):                  # NaN included
+            raise PBError('metrics: ids hold values that are not integers')
+        a = r
+    elif a.dtype.kind not in 'iu':
+        raise PBError('metrics: ids must be integers or integer-valued floats (got %s)' % a.dtype)
+    a = a.astype(np.int64)
+    for h, n in enumerate(layout.sizes):
+        col = a[:, :, h]
+        if col.size and (col.min() < 0 or col.max() >= n):
+            bad = col[(col < 0) | (col >= n)][0]
+            raise PBError('metrics: head %d (%s) holds the id %d; its ids are 0 .. %d' % (h, ops.CLASS_NAMES[h], int(bad), n - 1))
+    return a
+
+
+def _host_start(start, N):
+    """start as a host int32 (N) array: one row index >= 0 for every piece, or one per piece."""
+    if start is None:
+        return None
+    s = np.asarray(start.detach().cpu().numpy() if torch.is_tensor(start) else start)
+    if s.ndim > 1 or (s.ndim == 1 and s.shape[0] != N) or s.dtype.kind not in 'iu' or (s.size and s.min() < 0):
+        raise PBError('metrics: start must be one row index >= 0, or one per piece (%d)' % N)
+    return np.array(np.broadcast_to(s, (N,)), dtype=np.int32)
+
+
+def piece_lengths(ids, layout=None, start=None):
+    """Host: the number of notes of every piece of an (N, S, 8) integer array: L - start with L the first row in which any head's id is
+    >= its PAD id (the generator's stop rule; S if none), floor 0."""
+    layout = layout or ops.DEFAULT_LAYOUT
+    a = np.asarray(ids)
+    special = (a >= np.asarray(layout.pad8)).any(-1)
+    L = np.where(special.any(1), special.argmax(1), a.shape[1])
+    s = 0 if start is None else _host_start(start, a.shape[0])
+    return np.maximum(L - s, 0)
+
+
+def _upload(ids, tab, start, device):
+    """The checked arguments of ops.piece_features on the device."""
+    a = _host_ids(ids, tab.layout)
+    dev = torch.device(device) if device is not None else ids.device if torch.is_tensor(ids) else torch.device('cuda', torch.cuda.current_device())
+    s = _host_start(start, a.shape[0])
+    up = lambda x: torch.from_numpy(x).to(dev)
+    return (up(a.astype(np.int16)), up(tab.pitch_of), up(tab.dur_pos)), dict(start=None if s is None else up(s), layout=tab.layout)
+
+
+def piece_features(ids, e2w=None, start=None, device=None):
+    """The (N, 288) int32 device tensor of pb_piece_features for (N, S, 8) ids: integer or integer-valued float arrays or device tensors
+    (eval_generation writes float32). Every id is checked on the host against its head's size (PBError names the head). start: the
+    first row that counts, one number or one per piece (e.g. the prime length). e2w: a dictionary, None (the default one) or tables()."""
+    args, kw = _upload(ids, e2w if isinstance(e2w, Tables) else tables(e2w), start, device)
+    return ops.piece_features(*args, **kw)
+
+
+def _ratio(num, den):
+    out = np.zeros(np.broadcast(num, den).shape, dtype=np.float64)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+def feature_groups(feat):
+    """(groups, empty): the 14 feature groups of an (N, 288) feature tensor or array as float32 arrays, (n,) for the scalar groups and
+    (n, width) for the histograms, over the n pieces that hold a note; empty = the number of pieces left out. Divisions in float64,
+    a zero divisor gives zeros."""
+    f = (feat.detach().cpu().numpy() if torch.is_tensor(feat) else np.asarray(feat)).astype(np.float64)
+    if f.ndim != 2 or f.shape[1] != ops.FEATURE_COLS:
+        raise PBError('feature_groups: need an (N, %d) feature array (got %s)' % (ops.FEATURE_COLS, f.shape))
+    keep = f[:, 0] > 0
+    empty = int((~keep).sum())
+    f = f[keep]
+    c = lambda i: f[:, i]
+    g = OrderedDict()
+    g['note_count'] = c(0)
+    g['pitch_count'] = c(4)
+    g['pitch_range'] = np.where(c(1) > 0, c(6) - c(5), 0.0)
+    g['avg_interval'] = _ratio(c(7), c(8))
+    g['notes_per_bar'] = _ratio(c(0), c(2))
+    g['avg_duration'] = _ratio(c(11), c(0))
+    g['avg_velocity'] = _ratio(c(12), c(0))
+    g['onset_ratio'] = _ratio(c(9), c(0))
+    for name, (col, width, div) in HIST_GROUPS.items():
+        g[name] = _ratio(f[:, col:col + width], f[:, div:div + 1])
+    return OrderedDict((k, v.astype(np.float32)) for k, v in g.items()), empty
+
+
+def overlap_and_kl(p, q, dx):
+    """Host, float64, trapezoid rule on a uniform grid of spacing dx: (oa, kl) with oa = the integral of min(p, q) and
+    kl = KL(p || q) = the integral of p log(p / q), q floored at 1e-300 and points with p = 0 contributing nothing."""
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    if p.shape != q.shape or p.ndim != 1:
+        raise PBError('overlap_and_kl: two curves on one grid (got %s and %s)' % (p.shape, q.shape))
+    trap = lambda y: float(dx * (y.sum() - 0.5 * (y[0] + y[-1]))) if y.size > 1 else 0.0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        integrand = np.where(p > 0, p * (np.log(np.where(p > 0, p, 1.0)) - np.log(np.maximum(q, 1e-300))), 0.0)
+    return trap(np.minimum(p, q)), trap(integrand)
+
+
+def sample_stats(mom):
+    """n, mean, std (ddof = 1), min, max of a pb_sample_moments record on the host. std is 0 when min == max, nan below two samples."""
+    n, s, q, _, lo, hi = (float(v) for v in mom)
+    if n < 1:
+        return dict(n=0, mean=float('nan'), std=float('nan'), min=float('nan'), max=float('nan'))
+    mean = s / n
+    std = float('nan') if n < 2 else 0.0 if lo == hi else float(np.sqrt(max(q - s * s / n, 0.0) / (n - 1)))
+    return dict(n=int(n), mean=mean, std=std, min=lo, max=hi)
+
+
+def scott_bandwidth(stat):
+    return stat['std'] * stat['n'] ** -0.2
+
+
+def densities_defined(stats):
+    """The degenerate rule: a density needs at least two samples with some spread, in every one of the samples compared."""
+    return all(st['n'] >= 2 and st['std'] > 0 for st in stats)
+
+
+class _Timer:
+    """Device milliseconds per stage from pairs of events on the current stream, read after one synchronisation at the end."""
+
+    def __init__(self):
+        self.pairs = []
+
+    def run(self, stage, fn, *args, **kw):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn(*args, **kw)
+        b.record()
+        self.pairs.append((stage, a, b))
+        return out
+
+    def totals(self):
+        torch.cuda.synchronize()
+        ms = OrderedDict((stage, 0.0) for stage in ('features', 'distances', 'moments', 'kde'))
+        for stage, a, b in self.pairs:
+            ms[stage] += a.elapsed_time(b)
+        ms['total'] = sum(ms.values())
+        return ms
+
+
+def compare_sets(gen_ids, ref_ids, e2w=None, grid=1024, start=None, device=None):
+    """Compare a generated set with a reference set, both (N, S, 8) ids. Per feature group: the mean and std (numpy's, ddof = 0) of the
+    feature in each set (of the row norm for the histogram groups), the means of the gen-gen, ref-ref and gen-ref distances, and from
+    Gaussian kernel density estimates of the three distance samples (Scott's bandwidth std(ddof = 1) n^(-1/5) each, one common grid of
+    `grid` points over [min - 3 h_max, max + 3 h_max]) kl = KL(intra-ref || inter) and oa = the overlapped area of the two (kl_gen, oa_gen:
+    the same for intra-gen). A sample with fewer than two values or no spread gives nan for the group's kl and oa. start: see
+    piece_features (one value or a (gen, ref) pair). Returns {'n_gen', 'n_ref', 'empty_gen', 'empty_ref', 'device_ms', 'groups'}."""
+    G = int(grid)
+    if not 2 <= G <= 4096:
+        raise PBError('compare_sets: grid = %r points; 2 .. 4096' % (grid,))
+    tab = e2w if isinstance(e2w, Tables) else tables(e2w)
+    s_gen, s_ref = start if isinstance(start, tuple) else (start, start)
+    timer = _Timer()
+    feats = []
+    for ids, s in ((gen_ids, s_gen), (ref_ids, s_ref)):
+        args, kw = _upload(ids, tab, s, device)
+        feats.append(timer.run('features', ops.piece_features, *args, **kw))
+    f_gen, f_ref = feats
+    dev = f_gen.device
+    g_gen, empty_gen = feature_groups(f_gen)
+    g_ref, empty_ref = feature_groups(f_ref)
+    n_gen, n_ref = len(g_gen['note_count']), len(g_ref['note_count'])
+    ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
+    groups = OrderedDict()
+    for name in GROUPS:
+        xg, xr = g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1)
+        res = OrderedDict()
+        for tag, x in (('gen', xg), ('ref', xr)):
+            v = np.sqrt((x.astype(np.float64) ** 2).sum(1)) if x.shape[1] > 1 else x[:, 0].astype(np.float64)
+            res['mean_' + tag] = float(v.mean()) if v.size else float('nan')
+            res['std_' + tag] = float(v.std()) if v.size else float('nan')
+        for k in ('dist_gen', 'dist_ref', 'dist_inter', 'kl', 'oa', 'kl_gen', 'oa_gen'):
+            res[k] = float('nan')
+        groups[name] = res
+        if n_gen < 1 or n_ref < 1:
+            continue
+        tg, tr = torch.from_numpy(np.ascontiguousarray(xg)).to(dev), torch.from_numpy(np.ascontiguousarray(xr)).to(dev)
+        samples = OrderedDict()                       # name -> (distance matrix, upper)
+        if n_gen >= 2:
+            samples['gen'] = (timer.run('distances', ops.pairwise_l2, tg, tg), True)
+        if n_ref >= 2:
+            samples['ref'] = (timer.run('distances', ops.pairwise_l2, tr, tr), True)
+        samples['inter'] = (timer.run('distances', ops.pairwise_l2, tg, tr), False)
+        moms = torch.stack([timer.run('moments', ops.sample_moments, D, up, ws) for D, up in samples.values()]).cpu().numpy()
+        stats = OrderedDict((k, sample_stats(m)) for k, m in zip(samples, moms))
+        for k, st in stats.items():
+            res['dist_' + k] = st['mean']
+        if len(stats) < 3 or not densities_defined(stats.values()):
+            continue                                  # no density of a sample without spread: kl and oa stay nan
+        hs = OrderedDict((k, scott_bandwidth(st)) for k, st in stats.items())
+        h_max = max(hs.values())
+        lo, hi = min(st['min'] for st in stats.values()) - 3 * h_max, max(st['max'] for st in stats.values()) + 3 * h_max
+        pts = torch.from_numpy(np.linspace(lo, hi, G).astype(np.float32)).to(dev)
+        dens = torch.stack([timer.run('kde', ops.kde_eval, D, pts, hs[k], up, ws) for k, (D, up) in samples.items()]).cpu().numpy()
+        dx = (hi - lo) / (G - 1)
+        p = dict(zip(samples, dens))
+        res['oa'], res['kl'] = overlap_and_kl(p['ref'], p['inter'], dx)
+        res['oa_gen'], res['kl_gen'] = overlap_and_kl(p['gen'], p['inter'], dx)
+    return OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), ('empty_gen', empty_gen), ('empty_ref', empty_ref),
+                        ('device_ms', timer.totals()), ('groups', groups)])

@@ -409,6 +409,82 @@ def merge_apply(desc):
     LIB.call('pb_merge_apply', ctypes.byref(desc), _stream())
 
 
+FEATURE_COLS = 288                                          # the row of pb_piece_features
+
+
+def _dense(t, dtype, dim, what):
+    if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+        raise PBError('%s must be a contiguous %d-D %s tensor (got %s %s)' % (what, dim, str(dtype).replace('torch.', ''), tuple(t.shape), t.dtype))
+    return _p(t)
+
+
+def piece_features(ids16, pitch_of, dur_pos, start=None, layout=None):
+    """pb_piece_features: the (N, 288) int32 feature rows of ids16 (N, S, 8) int16. pitch_of (int16, layout.pad8[3] entries: the MIDI number
+    of a pitch id, -1 = percussion) and dur_pos (int32, layout.pad8[4] entries) are device tables; start (N) int32 or None = 0."""
+    layout = layout or DEFAULT_LAYOUT
+    p_ids = _dense(ids16, torch.int16, 3, 'piece_features: ids16')
+    if ids16.shape[2] != 8 or ids16.shape[1] < 1:
+        raise PBError('piece_features: ids16 must be (N, S, 8) with S >= 1 (got %s)' % (tuple(ids16.shape),))
+    N, S = ids16.shape[0], ids16.shape[1]
+    p_pitch, p_dur = _dense(pitch_of, torch.int16, 1, 'piece_features: pitch_of'), _dense(dur_pos, torch.int32, 1, 'piece_features: dur_pos')
+    if pitch_of.numel() != layout.pad8[3] or dur_pos.numel() != layout.pad8[4]:
+        raise PBError('piece_features: pitch_of / dur_pos hold %d / %d entries, the layout has %d pitch and %d duration ids'
+                      % (pitch_of.numel(), dur_pos.numel(), layout.pad8[3], layout.pad8[4]))
+    p_start = None
+    if start is not None:
+        p_start = _dense(start, torch.int32, 1, 'piece_features: start')
+        if start.numel() != N:
+            raise PBError('piece_features: start holds %d entries for %d pieces' % (start.numel(), N))
+    feat = torch.empty((N, FEATURE_COLS), dtype=torch.int32, device=ids16.device)
+    LIB.call('pb_piece_features', p_ids, p_start, seg_array(layout.pad8), p_pitch, p_dur, _p(feat), N, S, _stream())
+    return feat
+
+
+def pairwise_l2(A, B, out=None):
+    """pb_pairwise_l2: D (N, M) f32 with D[i, j] = |A[i] - B[j]| for A (N, F), B (M, F) f32, 1 <= F <= 144."""
+    pa, pb = _dense(A, torch.float32, 2, 'pairwise_l2: A'), _dense(B, torch.float32, 2, 'pairwise_l2: B')
+    if A.shape[1] != B.shape[1]:
+        raise PBError('pairwise_l2: A has %d features, B %d' % (A.shape[1], B.shape[1]))
+    D = torch.empty((A.shape[0], B.shape[0]), dtype=torch.float32, device=A.device) if out is None else out
+    if tuple(D.shape) != (A.shape[0], B.shape[0]):
+        raise PBError('pairwise_l2: out is %s for %d x %d rows' % (tuple(D.shape), A.shape[0], B.shape[0]))
+    LIB.call('pb_pairwise_l2', pa, pb, _dense(D, torch.float32, 2, 'pairwise_l2: out'), A.shape[0], B.shape[0], A.shape[1], _stream())
+    return D
+
+
+def metrics_ws(N, M, G, device):
+    """The partial rows of sample_moments / kde_eval over an (N, M) matrix and G grid points (reusable by the next call on the same stream)."""
+    return torch.empty(max(1, (LIB.query('pb_metrics_ws_bytes', int(N), int(M), int(G)) + 7) // 8), dtype=torch.float64, device=device)
+
+
+def _samples_ws(D, G, ws, who):
+    N, M = D.shape
+    need = LIB.query('pb_metrics_ws_bytes', N, M, G)
+    if ws is None:
+        ws = metrics_ws(N, M, G, D.device)
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() * 8 < need:
+        raise PBError('%s: ws must be a contiguous f64 tensor of at least %d bytes (metrics_ws)' % (who, need))
+    return ws
+
+
+def sample_moments(D, upper=False, ws=None):
+    """pb_sample_moments: a device f64[6] = n, sum, sum of squares, 0, min, max of D (N, M) f32, or of its strict upper triangle (upper)."""
+    pd = _dense(D, torch.float32, 2, 'sample_moments: D')
+    ws = _samples_ws(D, 1, ws, 'sample_moments')
+    out = torch.empty(6, dtype=torch.float64, device=D.device)
+    LIB.call('pb_sample_moments', pd, D.shape[0], D.shape[1], int(bool(upper)), _p(out), _p(ws), _stream())
+    return out
+
+
+def kde_eval(D, grid, h, upper=False, ws=None):
+    """pb_kde_eval: the Gaussian kernel density (bandwidth h) of the samples of D (as sample_moments) at the f32 grid points, a device f64 (G)."""
+    pd, pg = _dense(D, torch.float32, 2, 'kde_eval: D'), _dense(grid, torch.float32, 1, 'kde_eval: grid')
+    ws = _samples_ws(D, grid.numel(), ws, 'kde_eval')
+    dens = torch.empty(grid.numel(), dtype=torch.float64, device=D.device)
+    LIB.call('pb_kde_eval', pd, D.shape[0], D.shape[1], int(bool(upper)), pg, grid.numel(), float(h), _p(dens), _p(ws), _stream())
+    return dens
+
+
 def transpose_batch_bf16(src, dst, table, n_tiles):
     LIB.call('pb_transpose_batch_bf16', _p(src), _p(dst), _p(table), table.shape[0], n_tiles, _stream())
 
