@@ -404,6 +404,31 @@ int pb_pairwise_l2(const float* A, const float* B, float* D, int32_t N, int32_t 
 int pb_sample_moments(const float* D, int64_t N, int64_t M, int32_t upper, double* out, void* ws, void* stream);
 int pb_kde_eval(const float* D, int64_t N, int64_t M, int32_t upper, const float* grid, int32_t G, double h, double* dens, void* ws, void* stream);
 
+/* ---- K20: copy detection (pb_runs.hip; additions to ABI 10) -----------------------------------------------------------------
+ * The longest run of consecutive notes that a generated piece shares with a corpus piece: the device half of pianobart_amd.novelty
+ * (DESIGN.md 11). Integers and integer maxima only: equal inputs give equal bytes, whatever the order of workgroups or chunks.
+ * Every entry checks its arguments before the first HIP call (-2, pb_last_error names the field).
+ *
+ * pb_piece_keys: keys (N, S) uint32 and klen (N) int32 from ids16 (N, S, 8) int16, 16-byte aligned, 1 <= S <= 4096. The notes of a
+ *   piece, start, pad8 and pitch_of are those of pb_piece_features. A piece of n notes has K = max(n - 1, 0) keys; key t - 1
+ *   describes note t relative to note t - 1: bits 0..11 the pitch field (mode 0, exact: the pitch id; mode 1, interval:
+ *   1088 + pitch_of[id_t] - pitch_of[id_t-1] when both are >= 0, else 2304 + the pitch id), bits 12..22 the position id, bits 23..24
+ *   the bar step (0, 1, 2; 3 = anything else), bits 25..31 zero. keys[n][K ..] = 0xFFFFFFFF ("no key").
+ * pb_shared_runs: A (N, Sa) with alen (N), B (M, Sb) with blen (M): key rows and their lengths (clamped to 0 .. Sa / Sb), 1 <= Sa, Sb
+ *   <= 4096, min_run >= 1. A value with bit 31 set is "no key" and matches nothing. run(p, q) = A[p] == B[q] ? run(p - 1, q - 1) + 1 : 0.
+ *   R[i][j] (N, M; may be NULL) = max over p, q of run(p, q); run_end[i][p] (N, Sa) = max over j, q of run(p, q) where that is
+ *   >= min_run, else 0; best[i] (N, int64) = (max_j R[i][j]) << 32 | (0xFFFFFFFF - (j* + j_base)), j* the smallest j that attains the
+ *   maximum, 0 when the maximum is 0. exclude_self = 1 (N == M): the pair i == j + j_base contributes nothing. accumulate = 0 clears
+ *   run_end and best on the stream first; accumulate = 1 maxes into them: a corpus fed in chunks of M pieces, j_base = the chunk's
+ *   first piece. R is always written whole. N = 0 or M = 0 is no error.
+ * pb_runs_tile: the corpus pieces one workgroup of pb_shared_runs takes. */
+int pb_runs_tile(void);
+int pb_piece_keys(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, uint32_t* keys, int32_t* klen,
+                  int32_t N, int32_t S, int32_t mode, void* stream);
+int pb_shared_runs(const uint32_t* A, const int32_t* alen, int32_t N, int32_t Sa, const uint32_t* B, const int32_t* blen, int32_t M, int32_t Sb,
+                   int32_t min_run, int32_t exclude_self, int32_t j_base, int32_t* R, int32_t* run_end, int64_t* best, int32_t accumulate,
+                   void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

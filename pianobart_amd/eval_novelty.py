@@ -1,0 +1,92 @@
+"""python -m pianobart_amd.eval_novelty: did the generator copy its training data? (pianobart_amd.novelty)
+
+  --generated g.npy   what eval_generation wrote: (N, S, 8), or (N, n, S, 8) with --samples n (the samples are flattened to N * n pieces)
+  --corpus train.npy  the pieces to look the generated ones up in, e.g. the training split: (M, S', 8), whole pieces
+  --self              no corpus: compare --generated with itself, a piece never with itself (the diversity of one set; duplicates in a corpus)
+  --skip K            the first K rows of every GENERATED piece do not count (a prime of K rows taken from the data is a copy by construction)
+  --min_run R         a shared run counts towards coverage from R keys on (R + 1 notes; default 8)
+  --transpose         interval keys: a copy moved to another key is still found
+  --max_pieces N      the first N pieces of each file only
+  --output n.json     the result of novelty.compare_to_corpus as JSON (nan is written as null)
+
+A key holds a note's pitch (or interval), its position in the bar and the bar step from the note before: the identity tested is "the
+same pitches at the same places in the bar". Instrument, duration, velocity, time signature and tempo are not compared."""
+import argparse
+import json
+import os
+
+import numpy as np
+
+from . import novelty
+from ._lib import PBError
+from .eval_metrics import _json_safe, load_pieces
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_VOCAB = os.path.join(_HERE, 'data', 'octuple_vocab.json')
+
+
+def get_args(argv=None):
+    ap = argparse.ArgumentParser(description='')
+    ap.add_argument('--generated', type=str, required=True)
+    ap.add_argument('--corpus', type=str, default=None)
+    ap.add_argument('--self', dest='self_', action='store_true')
+    ap.add_argument('--dict_file', type=str, default=_VOCAB)
+    ap.add_argument('--skip', type=int, default=0, metavar='K')
+    ap.add_argument('--min_run', type=int, default=8, metavar='R')
+    ap.add_argument('--transpose', action='store_true')
+    ap.add_argument('--max_pieces', type=int, default=None, metavar='N')
+    ap.add_argument('--output', type=str, default='./novelty.json')
+    ap.add_argument('--cpu', action='store_true')
+    return ap.parse_args(argv)
+
+
+def _listed(v):
+    if isinstance(v, dict):
+        return {k: _listed(x) for k, x in v.items()}
+    if isinstance(v, np.ndarray):
+        return _listed(v.tolist())
+    if isinstance(v, list):
+        return [_listed(x) for x in v]
+    return _json_safe(v)
+
+
+def main(argv=None):
+    args = get_args(argv)
+    if args.cpu:
+        raise PBError('--cpu: copy detection runs in HIP kernels (pb_runs.hip); there is no CPU path')
+    if args.skip < 0 or (args.max_pieces is not None and args.max_pieces < 1):
+        raise PBError('--skip takes a number of rows >= 0 and --max_pieces a number of pieces >= 1')
+    if args.min_run < 1:
+        raise PBError('--min_run takes a number of keys >= 1 (got %d)' % args.min_run)
+    if args.self_ and args.corpus is not None:
+        raise PBError('--self compares --generated with itself; it takes no --corpus')
+    if not args.self_ and args.corpus is None:
+        raise PBError('--corpus (or --self) is required')
+    gen = load_pieces(args.generated, '--generated', args.max_pieces)
+    cor = gen if args.self_ else load_pieces(args.corpus, '--corpus', args.max_pieces)
+    for what, a in (('--generated', gen), ('--corpus', cor)):
+        if a.shape[1] > novelty.ops.RUNS_MAX_S:
+            raise PBError('%s holds pieces of %d rows; copy detection takes 1 .. %d' % (what, a.shape[1], novelty.ops.RUNS_MAX_S))
+    from .pretrain import _load_vocab
+    if not os.path.isfile(args.dict_file):
+        raise PBError('--dict_file: no file %r' % args.dict_file)
+    tab = novelty.metrics.tables(_load_vocab(args.dict_file)[0])
+    res = novelty.compare_to_corpus(gen, cor, tab, start=(args.skip, 0), min_run=args.min_run, transpose=args.transpose, exclude_self=args.self_)
+    with open(args.output, 'w') as f:
+        json.dump(_listed(res), f, indent=1)
+    tag = '   [novelty]'
+    print('%s %d generated pieces against %s, %s keys, runs from %d keys on; %.2f ms on the device'
+          % (tag, res['n_gen'], 'themselves' if args.self_ else '%d corpus pieces' % res['n_corpus'], 'interval' if args.transpose else 'exact',
+             args.min_run, res['device_ms']['total']))
+    print('%s longest shared run: mean %.2f  median %.1f  max %d keys' % (tag, res['longest_mean'], res['longest_median'], res['longest_max']))
+    print('%s coverage: mean %.4f | pieces at least half covered %.4f | pieces with a run >= %d keys %.4f'
+          % (tag, res['coverage_mean'], res['share_half_covered'], args.min_run, res['share_with_run']))
+    if res['n_gen'] and res['longest_max'] > 0:
+        i = int(np.argmax(res['longest']))
+        print('%s most copied: generated piece %d shares %d keys with piece %d' % (tag, i, res['longest'][i], res['nearest'][i]))
+    print('%s -> %s' % (tag, args.output))
+    return res
+
+
+if __name__ == '__main__':
+    main()

@@ -485,6 +485,63 @@ def kde_eval(D, grid, h, upper=False, ws=None):
     return dens
 
 
+RUNS_TILE = 32                                              # corpus pieces per workgroup of pb_shared_runs (pb_runs_tile)
+RUNS_MAX_S = 4096                                           # rows of a piece / keys of a row that pb_piece_keys and pb_shared_runs take
+NO_KEY = 0xFFFFFFFF
+assert HEAD_MAX == 1088                                     # the key's interval field: 1088 + difference, 2304 + id, both below 4096
+
+
+def piece_keys(ids16, pitch_of, start=None, layout=None, mode=0):
+    """pb_piece_keys: (keys (N, S) int32 holding the uint32 keys, klen (N) int32) of ids16 (N, S, 8) int16, S <= 4096. mode 0 = exact pitch,
+    1 = interval to the note before. pitch_of and start as in piece_features. Key rows behind klen hold NO_KEY (-1 as int32)."""
+    layout = layout or DEFAULT_LAYOUT
+    p_ids = _dense(ids16, torch.int16, 3, 'piece_keys: ids16')
+    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
+        raise PBError('piece_keys: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    if mode not in (0, 1):
+        raise PBError('piece_keys: mode = %r (0 = exact, 1 = interval)' % (mode,))
+    N, S = ids16.shape[0], ids16.shape[1]
+    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_keys: pitch_of')
+    if pitch_of.numel() != layout.pad8[3]:
+        raise PBError('piece_keys: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
+    p_start = None
+    if start is not None:
+        p_start = _dense(start, torch.int32, 1, 'piece_keys: start')
+        if start.numel() != N:
+            raise PBError('piece_keys: start holds %d entries for %d pieces' % (start.numel(), N))
+    keys = torch.empty((N, S), dtype=torch.int32, device=ids16.device)
+    klen = torch.empty((N,), dtype=torch.int32, device=ids16.device)
+    LIB.call('pb_piece_keys', p_ids, p_start, seg_array(layout.pad8), p_pitch, _p(keys), _p(klen), N, S, int(mode), _stream())
+    return keys, klen
+
+
+def shared_runs(A, alen, B, blen, min_run=8, exclude_self=False, j_base=0, want_matrix=True, run_end=None, best=None):
+    """pb_shared_runs: (R, run_end, best) for key rows A (N, Sa) / B (M, Sb) int32 with lengths alen (N) / blen (M) int32. R (N, M) int32 is
+    None without want_matrix. Given run_end (N, Sa) int32 and best (N) int64 are maxed into (a corpus fed in chunks, j_base = the
+    chunk's first piece); otherwise they are new tensors."""
+    pa, pb = _dense(A, torch.int32, 2, 'shared_runs: A'), _dense(B, torch.int32, 2, 'shared_runs: B')
+    pal, pbl = _dense(alen, torch.int32, 1, 'shared_runs: alen'), _dense(blen, torch.int32, 1, 'shared_runs: blen')
+    (N, Sa), (M, Sb) = A.shape, B.shape
+    if alen.numel() != N or blen.numel() != M:
+        raise PBError('shared_runs: alen / blen hold %d / %d entries for %d / %d rows' % (alen.numel(), blen.numel(), N, M))
+    if not (1 <= Sa <= RUNS_MAX_S and 1 <= Sb <= RUNS_MAX_S):
+        raise PBError('shared_runs: rows of %d and %d keys; 1 .. %d' % (Sa, Sb, RUNS_MAX_S))
+    if (run_end is None) != (best is None):
+        raise PBError('shared_runs: run_end and best are given together (accumulate) or not at all')
+    accumulate = run_end is not None
+    if accumulate:
+        if tuple(run_end.shape) != (N, Sa) or tuple(best.shape) != (N,):
+            raise PBError('shared_runs: run_end %s / best %s for %d rows of %d keys' % (tuple(run_end.shape), tuple(best.shape), N, Sa))
+    else:
+        run_end = torch.empty((N, Sa), dtype=torch.int32, device=A.device)
+        best = torch.empty((N,), dtype=torch.int64, device=A.device)
+    p_re, p_best = _dense(run_end, torch.int32, 2, 'shared_runs: run_end'), _dense(best, torch.int64, 1, 'shared_runs: best')
+    R = torch.empty((N, M), dtype=torch.int32, device=A.device) if want_matrix else None
+    LIB.call('pb_shared_runs', pa, pal, N, Sa, pb, pbl, M, Sb, int(min_run), int(bool(exclude_self)), int(j_base), _p(R), p_re, p_best,
+             int(accumulate), _stream())
+    return R, run_end, best
+
+
 def transpose_batch_bf16(src, dst, table, n_tiles):
     LIB.call('pb_transpose_batch_bf16', _p(src), _p(dst), _p(table), table.shape[0], n_tiles, _stream())
 
