@@ -1,5 +1,5 @@
 """GPU: every HIP kernel of libpianobart_hip.so against a plain PyTorch fp32/fp64 reference of the
-same op (called through the C ABI via pianobart_amd.ops)."""
+same op (called through the C ABI via pianobart_amd.ops). The GEMM family's exact tile / split / epilogue-edge suite is tests/test_gemm_kernels_gpu.py."""
 import math
 
 import numpy as np
