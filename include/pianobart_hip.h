@@ -429,6 +429,33 @@ int pb_shared_runs(const uint32_t* A, const int32_t* alen, int32_t N, int32_t Sa
                    int32_t min_run, int32_t exclude_self, int32_t j_base, int32_t* R, int32_t* run_end, int64_t* best, int32_t accumulate,
                    void* stream);
 
+/* ---- K21: copy detection that survives edits (pb_align.hip; additions to ABI 10) ---------------------------------------------------
+ * Smith-Waterman local alignment with a linear gap penalty over the keys of pb_piece_keys: the device half of
+ * pianobart_amd.novelty.local_alignments. Integers and integer maxima only: equal inputs give equal bytes, whatever
+ * the order of lanes, waves, workgroups or chunks. The arguments are checked before the first HIP call (-2, pb_last_error names the
+ * field).
+ *
+ * pb_local_align: A, alen, N, Sa, B, blen, M, Sb as in pb_shared_runs (lengths clamped to 0 .. Sa / Sb, 1 <= Sa, Sb <= 4096, a value
+ *   with bit 31 set matches nothing, not even itself). Penalties are positive numbers: match 1 .. 8, mismatch 1 .. 16, gap 1 .. 16;
+ *   min_score >= 1. For a pair, cell (p, q) holds P = H << 12 | (4095 - start), H the score of the best local alignment that ends
+ *   there, start the A index of its first matched key, P = 0 "no alignment ends here":
+ *     s = (A[p] == B[q]) ? +match : -mismatch
+ *     d = max(P(p - 1, q - 1), 4095 - p) + (s << 12)
+ *     r = max(d, P(p - 1, q) - (gap << 12), P(p, q - 1) - (gap << 12))
+ *     P(p, q) = r >= 4096 ? r : 0,   P(-1, .) = P(., -1) = 0
+ *   Among alignments of equal score the smallest start is kept. Only match cells (A[p] == B[q]) are recorded:
+ *   score[i][j] (N, M; may be NULL) = max over match cells of H; align_end[i][p] (N, Sa) = max over j and over match cells (p, q) of
+ *   P(p, q) where its H >= min_score, else 0 (H = v >> 12, start = 4095 - (v & 4095): the aligned region that ends at key p covers
+ *   the keys start .. p); best[i] (N, int64) = (max_j score[i][j]) << 32 | (0xFFFFFFFF - (j* + j_base)), j* the smallest j that
+ *   attains the maximum, 0 when the maximum is 0 (the packing of pb_shared_runs). exclude_self, j_base and accumulate as in
+ *   pb_shared_runs: accumulate = 0 clears align_end and best on the stream first, accumulate = 1 maxes into them. score is always
+ *   written whole. N = 0 or M = 0 is no error.
+ * pb_align_block: the B columns one sweep of a wave covers. */
+int pb_align_block(void);
+int pb_local_align(const uint32_t* A, const int32_t* alen, int32_t N, int32_t Sa, const uint32_t* B, const int32_t* blen, int32_t M, int32_t Sb,
+                   int32_t match, int32_t mismatch, int32_t gap, int32_t min_score, int32_t exclude_self, int32_t j_base,
+                   int32_t* score, int32_t* align_end, int64_t* best, int32_t accumulate, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

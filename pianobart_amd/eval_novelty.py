@@ -6,6 +6,10 @@
   --skip K            the first K rows of every GENERATED piece do not count (a prime of K rows taken from the data is a copy by construction)
   --min_run R         a shared run counts towards coverage from R keys on (R + 1 notes; default 8)
   --transpose         interval keys: a copy moved to another key is still found
+  --align             also align the keys locally (Smith-Waterman, linear gaps): a copy with edits is found whole
+  --align_scores M,X,G  the reward of a match and the penalties of a mismatch and of a gap, positive numbers (default 1,2,2; M 1 .. 8,
+                      X and G 1 .. 16); implies --align
+  --min_score H       an aligned region counts towards align_coverage from score H on (default 8); implies --align
   --max_pieces N      the first N pieces of each file only
   --output n.json     the result of novelty.compare_to_corpus as JSON (nan is written as null)
 
@@ -34,6 +38,9 @@ def get_args(argv=None):
     ap.add_argument('--skip', type=int, default=0, metavar='K')
     ap.add_argument('--min_run', type=int, default=8, metavar='R')
     ap.add_argument('--transpose', action='store_true')
+    ap.add_argument('--align', action='store_true')
+    ap.add_argument('--align_scores', type=str, default=None, metavar='M,X,G')
+    ap.add_argument('--min_score', type=int, default=None, metavar='H')
     ap.add_argument('--max_pieces', type=int, default=None, metavar='N')
     ap.add_argument('--output', type=str, default='./novelty.json')
     ap.add_argument('--cpu', action='store_true')
@@ -50,6 +57,25 @@ def _listed(v):
     return _json_safe(v)
 
 
+def _align_arg(args):
+    """None without the alignment flags, else the dict compare_to_corpus takes; values out of range are refused here."""
+    if not (args.align or args.align_scores is not None or args.min_score is not None):
+        return None
+    par = dict(novelty.ALIGN_DEFAULTS)
+    if args.align_scores is not None:
+        try:
+            vals = [int(v) for v in args.align_scores.split(',')]
+        except ValueError:
+            vals = []
+        if len(vals) != 3:
+            raise PBError('--align_scores takes three integers M,X,G (got %r)' % args.align_scores)
+        par.update(zip(('match', 'mismatch', 'gap'), vals))
+    if args.min_score is not None:
+        par['min_score'] = args.min_score
+    novelty.ops.align_params(who='--align_scores M,X,G / --min_score H', **par)
+    return par
+
+
 def main(argv=None):
     args = get_args(argv)
     if args.cpu:
@@ -62,6 +88,7 @@ def main(argv=None):
         raise PBError('--self compares --generated with itself; it takes no --corpus')
     if not args.self_ and args.corpus is None:
         raise PBError('--corpus (or --self) is required')
+    align = _align_arg(args)
     gen = load_pieces(args.generated, '--generated', args.max_pieces)
     cor = gen if args.self_ else load_pieces(args.corpus, '--corpus', args.max_pieces)
     for what, a in (('--generated', gen), ('--corpus', cor)):
@@ -71,7 +98,8 @@ def main(argv=None):
     if not os.path.isfile(args.dict_file):
         raise PBError('--dict_file: no file %r' % args.dict_file)
     tab = novelty.metrics.tables(_load_vocab(args.dict_file)[0])
-    res = novelty.compare_to_corpus(gen, cor, tab, start=(args.skip, 0), min_run=args.min_run, transpose=args.transpose, exclude_self=args.self_)
+    kw = {} if align is None else {'align': align}
+    res = novelty.compare_to_corpus(gen, cor, tab, start=(args.skip, 0), min_run=args.min_run, transpose=args.transpose, exclude_self=args.self_, **kw)
     with open(args.output, 'w') as f:
         json.dump(_listed(res), f, indent=1)
     tag = '   [novelty]'
@@ -84,6 +112,12 @@ def main(argv=None):
     if res['n_gen'] and res['longest_max'] > 0:
         i = int(np.argmax(res['longest']))
         print('%s most copied: generated piece %d shares %d keys with piece %d' % (tag, i, res['longest'][i], res['nearest'][i]))
+    if align is not None:
+        print('%s local alignment (match %d, mismatch %d, gap %d): best score mean %.2f  median %.1f  max %d; %.2f ms on the device'
+              % (tag, align['match'], align['mismatch'], align['gap'], res['align_score_mean'], res['align_score_median'], res['align_score_max'],
+                 res['device_ms']['align']))
+        print('%s aligned coverage: mean %.4f | pieces at least half aligned %.4f | pieces with an alignment >= %d %.4f'
+              % (tag, res['align_coverage_mean'], res['share_half_aligned'], align['min_score'], res['share_with_alignment']))
     print('%s -> %s' % (tag, args.output))
     return res
 

@@ -542,6 +542,55 @@ def shared_runs(A, alen, B, blen, min_run=8, exclude_self=False, j_base=0, want_
     return R, run_end, best
 
 
+ALIGN_BLOCK = 256                                           # B columns one sweep of a wave of pb_local_align covers (pb_align_block)
+ALIGN_TILE = RUNS_TILE                                      # corpus pieces per workgroup of pb_local_align: the tile of pb_shared_runs
+ALIGN_RANGES = (('match', 1, 8), ('mismatch', 1, 16), ('gap', 1, 16))
+
+
+def align_params(match=1, mismatch=2, gap=2, min_score=8, who='local_align'):
+    """The four integers of pb_local_align, checked against their ranges (match 1 .. 8, mismatch and gap 1 .. 16, min_score >= 1)."""
+    vals = {'match': match, 'mismatch': mismatch, 'gap': gap, 'min_score': min_score}
+    for name, v in vals.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise PBError('%s: %s = %r is not an integer' % (who, name, v))
+    for name, lo, hi in ALIGN_RANGES:
+        if not lo <= int(vals[name]) <= hi:
+            raise PBError('%s: %s = %d out of range (%d .. %d)' % (who, name, int(vals[name]), lo, hi))
+    if not 1 <= int(min_score) < 2 ** 31:
+        raise PBError('%s: min_score = %d must be >= 1' % (who, int(min_score)))
+    return int(match), int(mismatch), int(gap), int(min_score)
+
+
+def local_align(A, alen, B, blen, match=1, mismatch=2, gap=2, min_score=8, exclude_self=False, j_base=0, want_matrix=True, align_end=None,
+                best=None):
+    """pb_local_align: (score, align_end, best) for key rows A (N, Sa) / B (M, Sb) int32 with lengths alen (N) / blen (M) int32. score
+    (N, M) int32 is None without want_matrix. Given align_end (N, Sa) int32 and best (N) int64 are maxed into (a corpus fed in chunks,
+    j_base = the chunk's first piece); otherwise they are new tensors."""
+    match, mismatch, gap, min_score = align_params(match, mismatch, gap, min_score)
+    pa, pb = _dense(A, torch.int32, 2, 'local_align: A'), _dense(B, torch.int32, 2, 'local_align: B')
+    pal, pbl = _dense(alen, torch.int32, 1, 'local_align: alen'), _dense(blen, torch.int32, 1, 'local_align: blen')
+    assert LIB.query('pb_align_block') == ALIGN_BLOCK, 'ops.ALIGN_BLOCK and the library disagree'
+    (N, Sa), (M, Sb) = A.shape, B.shape
+    if alen.numel() != N or blen.numel() != M:
+        raise PBError('local_align: alen / blen hold %d / %d entries for %d / %d rows' % (alen.numel(), blen.numel(), N, M))
+    if not (1 <= Sa <= RUNS_MAX_S and 1 <= Sb <= RUNS_MAX_S):
+        raise PBError('local_align: rows of %d and %d keys; 1 .. %d' % (Sa, Sb, RUNS_MAX_S))
+    if (align_end is None) != (best is None):
+        raise PBError('local_align: align_end and best are given together (accumulate) or not at all')
+    accumulate = align_end is not None
+    if accumulate:
+        if tuple(align_end.shape) != (N, Sa) or tuple(best.shape) != (N,):
+            raise PBError('local_align: align_end %s / best %s for %d rows of %d keys' % (tuple(align_end.shape), tuple(best.shape), N, Sa))
+    else:
+        align_end = torch.empty((N, Sa), dtype=torch.int32, device=A.device)
+        best = torch.empty((N,), dtype=torch.int64, device=A.device)
+    p_ae, p_best = _dense(align_end, torch.int32, 2, 'local_align: align_end'), _dense(best, torch.int64, 1, 'local_align: best')
+    score = torch.empty((N, M), dtype=torch.int32, device=A.device) if want_matrix else None
+    LIB.call('pb_local_align', pa, pal, N, Sa, pb, pbl, M, Sb, match, mismatch, gap, min_score, int(bool(exclude_self)), int(j_base), _p(score),
+             p_ae, p_best, int(accumulate), _stream())
+    return score, align_end, best
+
+
 def transpose_batch_bf16(src, dst, table, n_tiles):
     LIB.call('pb_transpose_batch_bf16', _p(src), _p(dst), _p(table), table.shape[0], n_tiles, _stream())
 

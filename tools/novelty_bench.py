@@ -3,10 +3,14 @@
 with a few planted copies whose lengths the tool checks in the result.
 
     python tools/novelty_bench.py [--numpy 64] [--out profiles/novelty_kernel_stats.txt]
+    python tools/novelty_bench.py --align --numpy 0 [--out profiles/align_kernel_stats.txt]
 
 Each stage (pb_piece_keys over both sets; pb_shared_runs, no matrix) runs three times between device events on data already on the
 device; the third run is reported, with rows/s for the keys and cells/s (K_a x K_b summed over all pairs) for the runs. --numpy P times
 the numpy restatement (tests/novelty_ref.py) on P x P pieces of the first shape on this host and scales it by the cell count; 0 skips it.
+--align also times pb_local_align (csrc/pb_align.hip, default scoring 1 / 2 / 2, min_score 8, no matrix) on the same keys in the same
+process, the same way, and checks that the planted copies score at least their length; with --numpy it times the numpy restatement
+(tests/align_ref.py) on ONE pair of the first shape and scales it by the pair count.
 Nothing is asserted but the planted copies."""
 import argparse
 import os
@@ -37,6 +41,7 @@ def synth(N, S, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--numpy', type=int, default=64)
+    ap.add_argument('--align', action='store_true')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
     from pianobart_amd import metrics, novelty, ops
@@ -81,6 +86,23 @@ def main():
         say('  pb_piece_keys  (both sets)   %9.3f ms   %10.4g rows/s' % (ms_keys, (N + M) * S / ms_keys * 1e3))
         say('  pb_shared_runs (no matrix)   %9.3f ms   %10.4g cells/s' % (ms_runs, cells / ms_runs * 1e3))
         say('  longest shared run: median %d, max %d keys; mean coverage %.4f' % (np.median(longest), longest.max(), np.nanmean(cov)))
+        if args.align:
+            (_, align_end, abest), ms_align = third(lambda: ops.local_align(ka, la, kb, lb, want_matrix=False))
+            ascore, anearest = novelty.split_best(abest)
+            for i, j, n in PLANTED:
+                n = n or S
+                assert ascore[i] >= n - 1 and (anearest[i] == j or ascore[i] > n - 1), (i, j, n, ascore[i], anearest[i])
+            acov = novelty.align_coverage(align_end, la)
+            say('  pb_local_align (no matrix)   %9.3f ms   %10.4g cells/s   (%.1f x pb_shared_runs)' % (ms_align, cells / ms_align * 1e3, ms_align / ms_runs))
+            say('  best alignment score: median %d, max %d; mean aligned coverage %.4f' % (np.median(ascore), ascore.max(), np.nanmean(acov)))
+            if args.numpy > 0 and S == SHAPES[0][2]:
+                from tests import align_ref
+                a, b = ka[0].cpu().numpy().view(np.uint32)[:int(la[0])], kb[0].cpu().numpy().view(np.uint32)[:int(lb[0])]
+                t0 = time.perf_counter()
+                align_ref.pair_fast(a, b)
+                sec = time.perf_counter() - t0
+                say('  numpy restatement of the alignment, one pair on this host: %.4f s = %.4g cells/s; SCALED by the pair count to %d x %d: %.0f s'
+                    % (sec, len(a) * len(b) / sec, N, M, sec * N * M))
         if args.numpy > 0 and S == SHAPES[0][2]:
             from tests import novelty_ref as R
             P = args.numpy
