@@ -456,6 +456,26 @@ int pb_local_align(const uint32_t* A, const int32_t* alen, int32_t N, int32_t Sa
                    int32_t match, int32_t mismatch, int32_t gap, int32_t min_score, int32_t exclude_self, int32_t j_base,
                    int32_t* score, int32_t* align_end, int64_t* best, int32_t accumulate, void* stream);
 
+/* ---- K22: repetition structure of a piece (pb_structure.hip; additions to ABI 10) ------------------------------------------------------
+ * How much of a bar returns 1 .. 64 bars later: the device half of pianobart_amd.structure. Integers and integer sums
+ * only: equal inputs give equal bytes, and a permutation of a piece's note rows gives the same row. The arguments are checked before
+ * the first HIP call (-2, pb_last_error names the field).
+ *
+ * pb_piece_structure: out (N, 264) int32 from ids16 (N, S, 8) int16, 16-byte aligned, 1 <= S <= 4096. The notes of a piece, start,
+ *   pad8 and pitch_of are those of pb_piece_features. A note has its bar id b (head 0), its position id p (head 1) and a pitch field
+ *   f: mode 0 (exact) the pitch id (head 3); mode 1 (pitch class) pitch_of[id] % 12 where pitch_of[id] >= 0, else 12 + id. Per bar
+ *   O_b = the set of p and N_b = the set of (p, f) of its notes; a bar id without a note between the smallest and the largest one
+ *   is a bar with empty sets. With W = largest - smallest bar id + 1 and X = O or N, for l = 1 .. 64:
+ *     I_X[l] = sum over the bar pairs (b, b + l) inside the span of |X_b ^ X_{b+l}|,   T_X[l] = sum over the same pairs of |X_b| + |X_{b+l}|
+ *   (both 0 for l >= W). Columns: 0 notes, 1 W (0 without a note), 2 sum_b |O_b|, 3 sum_b |N_b|, 4 distinct bar ids, 5..7 zero,
+ *   8..71 I_O[1..64], 72..135 T_O[1..64], 136..199 I_N[1..64], 200..263 T_N[1..64]. One workgroup per piece, a workgroup sweeping over
+ *   several pieces when they are short or many (at most 1024 workgroups). N = 0 is no error.
+ * pb_structure_lags / pb_structure_cols: 64 and 264. */
+int pb_structure_lags(void);
+int pb_structure_cols(void);
+int pb_piece_structure(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of,
+                       int32_t* out, int32_t N, int32_t S, int32_t mode, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

@@ -195,8 +195,9 @@ def densities_defined(stats):
 class _Timer:
     """Device milliseconds per stage from pairs of events on the current stream, read after one synchronisation at the end."""
 
-    def __init__(self):
+    def __init__(self, first='features'):
         self.pairs = []
+        self.first = first                            # the name of the per-piece stage
 
     def run(self, stage, fn, *args, **kw):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -208,11 +209,49 @@ class _Timer:
 
     def totals(self):
         torch.cuda.synchronize()
-        ms = OrderedDict((stage, 0.0) for stage in ('features', 'distances', 'moments', 'kde'))
+        ms = OrderedDict((stage, 0.0) for stage in (self.first, 'distances', 'moments', 'kde'))
         for stage, a, b in self.pairs:
             ms[stage] += a.elapsed_time(b)
         ms['total'] = sum(ms.values())
         return ms
+
+
+def compare_group(xg, xr, G, ws, timer, dev):
+    """One feature group of compare_sets: xg (n_gen, F) and xr (n_ref, F) float32 host rows -> the record of means, stds, distance means,
+    kl and oa (see compare_sets). ws: ops.metrics_ws for the larger set and G grid points; timer: a _Timer."""
+    n_gen, n_ref = len(xg), len(xr)
+    res = OrderedDict()
+    for tag, x in (('gen', xg), ('ref', xr)):
+        v = np.sqrt((x.astype(np.float64) ** 2).sum(1)) if x.shape[1] > 1 else x[:, 0].astype(np.float64)
+        res['mean_' + tag] = float(v.mean()) if v.size else float('nan')
+        res['std_' + tag] = float(v.std()) if v.size else float('nan')
+    for k in ('dist_gen', 'dist_ref', 'dist_inter', 'kl', 'oa', 'kl_gen', 'oa_gen'):
+        res[k] = float('nan')
+    if n_gen < 1 or n_ref < 1:
+        return res
+    tg, tr = torch.from_numpy(np.ascontiguousarray(xg)).to(dev), torch.from_numpy(np.ascontiguousarray(xr)).to(dev)
+    samples = OrderedDict()                           # name -> (distance matrix, upper)
+    if n_gen >= 2:
+        samples['gen'] = (timer.run('distances', ops.pairwise_l2, tg, tg), True)
+    if n_ref >= 2:
+        samples['ref'] = (timer.run('distances', ops.pairwise_l2, tr, tr), True)
+    samples['inter'] = (timer.run('distances', ops.pairwise_l2, tg, tr), False)
+    moms = torch.stack([timer.run('moments', ops.sample_moments, D, up, ws) for D, up in samples.values()]).cpu().numpy()
+    stats = OrderedDict((k, sample_stats(m)) for k, m in zip(samples, moms))
+    for k, st in stats.items():
+        res['dist_' + k] = st['mean']
+    if len(stats) < 3 or not densities_defined(stats.values()):
+        return res                                    # no density of a sample without spread: kl and oa stay nan
+    hs = OrderedDict((k, scott_bandwidth(st)) for k, st in stats.items())
+    h_max = max(hs.values())
+    lo, hi = min(st['min'] for st in stats.values()) - 3 * h_max, max(st['max'] for st in stats.values()) + 3 * h_max
+    pts = torch.from_numpy(np.linspace(lo, hi, G).astype(np.float32)).to(dev)
+    dens = torch.stack([timer.run('kde', ops.kde_eval, D, pts, hs[k], up, ws) for k, (D, up) in samples.items()]).cpu().numpy()
+    dx = (hi - lo) / (G - 1)
+    p = dict(zip(samples, dens))
+    res['oa'], res['kl'] = overlap_and_kl(p['ref'], p['inter'], dx)
+    res['oa_gen'], res['kl_gen'] = overlap_and_kl(p['gen'], p['inter'], dx)
+    return res
 
 
 def compare_sets(gen_ids, ref_ids, e2w=None, grid=1024, start=None, device=None):
@@ -238,40 +277,6 @@ def compare_sets(gen_ids, ref_ids, e2w=None, grid=1024, start=None, device=None)
     g_ref, empty_ref = feature_groups(f_ref)
     n_gen, n_ref = len(g_gen['note_count']), len(g_ref['note_count'])
     ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
-    groups = OrderedDict()
-    for name in GROUPS:
-        xg, xr = g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1)
-        res = OrderedDict()
-        for tag, x in (('gen', xg), ('ref', xr)):
-            v = np.sqrt((x.astype(np.float64) ** 2).sum(1)) if x.shape[1] > 1 else x[:, 0].astype(np.float64)
-            res['mean_' + tag] = float(v.mean()) if v.size else float('nan')
-            res['std_' + tag] = float(v.std()) if v.size else float('nan')
-        for k in ('dist_gen', 'dist_ref', 'dist_inter', 'kl', 'oa', 'kl_gen', 'oa_gen'):
-            res[k] = float('nan')
-        groups[name] = res
-        if n_gen < 1 or n_ref < 1:
-            continue
-        tg, tr = torch.from_numpy(np.ascontiguousarray(xg)).to(dev), torch.from_numpy(np.ascontiguousarray(xr)).to(dev)
-        samples = OrderedDict()                       # name -> (distance matrix, upper)
-        if n_gen >= 2:
-            samples['gen'] = (timer.run('distances', ops.pairwise_l2, tg, tg), True)
-        if n_ref >= 2:
-            samples['ref'] = (timer.run('distances', ops.pairwise_l2, tr, tr), True)
-        samples['inter'] = (timer.run('distances', ops.pairwise_l2, tg, tr), False)
-        moms = torch.stack([timer.run('moments', ops.sample_moments, D, up, ws) for D, up in samples.values()]).cpu().numpy()
-        stats = OrderedDict((k, sample_stats(m)) for k, m in zip(samples, moms))
-        for k, st in stats.items():
-            res['dist_' + k] = st['mean']
-        if len(stats) < 3 or not densities_defined(stats.values()):
-            continue                                  # no density of a sample without spread: kl and oa stay nan
-        hs = OrderedDict((k, scott_bandwidth(st)) for k, st in stats.items())
-        h_max = max(hs.values())
-        lo, hi = min(st['min'] for st in stats.values()) - 3 * h_max, max(st['max'] for st in stats.values()) + 3 * h_max
-        pts = torch.from_numpy(np.linspace(lo, hi, G).astype(np.float32)).to(dev)
-        dens = torch.stack([timer.run('kde', ops.kde_eval, D, pts, hs[k], up, ws) for k, (D, up) in samples.items()]).cpu().numpy()
-        dx = (hi - lo) / (G - 1)
-        p = dict(zip(samples, dens))
-        res['oa'], res['kl'] = overlap_and_kl(p['ref'], p['inter'], dx)
-        res['oa_gen'], res['kl_gen'] = overlap_and_kl(p['gen'], p['inter'], dx)
+    groups = OrderedDict((name, compare_group(g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1), G, ws, timer, dev)) for name in GROUPS)
     return OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), ('empty_gen', empty_gen), ('empty_ref', empty_ref),
                         ('device_ms', timer.totals()), ('groups', groups)])

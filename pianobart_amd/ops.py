@@ -591,6 +591,35 @@ def local_align(A, alen, B, blen, match=1, mismatch=2, gap=2, min_score=8, exclu
     return score, align_end, best
 
 
+STRUCTURE_LAGS = 64                                         # the lags of pb_piece_structure (pb_structure_lags)
+STRUCTURE_COLS = 8 + 4 * STRUCTURE_LAGS                     # its row: 8 scalar columns, then I_O, T_O, I_N, T_N (pb_structure_cols)
+
+
+def piece_structure(ids16, pitch_of, start=None, layout=None, mode=0):
+    """pb_piece_structure: the (N, 264) int32 lag sums of ids16 (N, S, 8) int16, S <= 4096. mode 0 = exact pitch, 1 = pitch class.
+    pitch_of and start as in piece_features."""
+    layout = layout or DEFAULT_LAYOUT
+    p_ids = _dense(ids16, torch.int16, 3, 'piece_structure: ids16')
+    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
+        raise PBError('piece_structure: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    if mode not in (0, 1):
+        raise PBError('piece_structure: mode = %r (0 = exact pitch, 1 = pitch class)' % (mode,))
+    assert LIB.query('pb_structure_lags') == STRUCTURE_LAGS and LIB.query('pb_structure_cols') == STRUCTURE_COLS, \
+        'ops.STRUCTURE_LAGS / STRUCTURE_COLS and the library disagree'
+    N, S = ids16.shape[0], ids16.shape[1]
+    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_structure: pitch_of')
+    if pitch_of.numel() != layout.pad8[3]:
+        raise PBError('piece_structure: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
+    p_start = None
+    if start is not None:
+        p_start = _dense(start, torch.int32, 1, 'piece_structure: start')
+        if start.numel() != N:
+            raise PBError('piece_structure: start holds %d entries for %d pieces' % (start.numel(), N))
+    out = torch.empty((N, STRUCTURE_COLS), dtype=torch.int32, device=ids16.device)
+    LIB.call('pb_piece_structure', p_ids, p_start, seg_array(layout.pad8), p_pitch, _p(out), N, S, int(mode), _stream())
+    return out
+
+
 def transpose_batch_bf16(src, dst, table, n_tiles):
     LIB.call('pb_transpose_batch_bf16', _p(src), _p(dst), _p(table), table.shape[0], n_tiles, _stream())
 
