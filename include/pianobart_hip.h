@@ -476,6 +476,30 @@ int pb_structure_cols(void);
 int pb_piece_structure(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of,
                        int32_t* out, int32_t N, int32_t S, int32_t mode, void* stream);
 
+/* ---- K23: harmony of a piece (pb_harmony.hip; additions to ABI 10) ----------------------------------------------------------------------
+ * The pitch classes of a piece's bars: the device half of pianobart_amd.harmony. Integers and integer sums only: equal
+ * inputs give equal bytes, and a permutation of a piece's note rows gives the same row. The arguments are checked before the first HIP
+ * call (-2, pb_last_error names the field).
+ *
+ * pb_piece_harmony: out (N, 228) int64 from ids16 (N, S, 8) int16, 16-byte aligned, 1 <= S <= 4096. The notes of a piece, start, pad8
+ *   and pitch_of are those of pb_piece_features; bars and W are those of pb_piece_structure. A note is pitched when
+ *   pitch_of[id of head 3] >= 0, its class is c = pitch_of[id] % 12. h_b[c] = the pitched note rows of bar b with class c (a multiset),
+ *   n_b their number; a window of w bars (w = 1, 4) starting at b = 0 .. W - w has the sum of its bars' histograms. table: device
+ *   int64 (4097), table[k] = round(k log2(k) 2^20), table[0] = table[1] = 0; X(window) = table[n] - sum_c table[h[c]]. D_k = k + {0, 2, 4,
+ *   5, 7, 9, 11} mod 12; best(h) = max_k of the sum of h over D_k, key(h) the smallest k attaining it. For l = 1 .. 64 over the bar
+ *   pairs (b, b + l) inside the span: I_H[l] = sum of sum_c min(h_b[c], h_{b+l}[c]), T_H[l] = sum of n_b + n_{b+l},
+ *   I_X[l] = sum of max over t = 0 .. 11 of sum_c min(h_b[c], h_{b+l}[(c + t) % 12]).
+ *   Columns: 0 notes, 1 W (0 without a note), 2 pitched notes P, 3 percussion notes, 4 bars with n_b > 0, 5 K* = key(g) of the whole
+ *   piece's histogram g, 6 SC = best(g), 7 zero, 8..19 g[0..11], 20..27 the window block of w = 1, 28..35 that of w = 4 (windows,
+ *   non-empty windows, sum n, sum X, sum best, non-empty windows with key == K*, key changes between consecutive non-empty windows,
+ *   sum of the classes present), 36..99 I_H[1..64], 100..163 T_H[1..64], 164..227 I_X[1..64]. One workgroup per piece, a workgroup
+ *   sweeping over several pieces when they are short or many (at most 1024 workgroups). N = 0 is no error.
+ * pb_harmony_lags / pb_harmony_cols: 64 and 228. */
+int pb_harmony_lags(void);
+int pb_harmony_cols(void);
+int pb_piece_harmony(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int64_t* table,
+                     int64_t* out, int32_t N, int32_t S, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

@@ -2,6 +2,7 @@
 device memory and the HIP stream; every op below launches a hand-written gfx950 kernel from
 libpianobart_hip.so on torch's current stream. There is no fallback path."""
 import ctypes
+import math
 import os
 
 import torch
@@ -617,6 +618,55 @@ def piece_structure(ids16, pitch_of, start=None, layout=None, mode=0):
             raise PBError('piece_structure: start holds %d entries for %d pieces' % (start.numel(), N))
     out = torch.empty((N, STRUCTURE_COLS), dtype=torch.int32, device=ids16.device)
     LIB.call('pb_piece_structure', p_ids, p_start, seg_array(layout.pad8), p_pitch, _p(out), N, S, int(mode), _stream())
+    return out
+
+
+HARMONY_LAGS = 64                                           # the lags of pb_piece_harmony (pb_harmony_lags)
+HARMONY_COLS = 36 + 3 * HARMONY_LAGS                        # its row: 36 scalar and window columns, then I_H, T_H, I_X (pb_harmony_cols)
+HARMONY_SHIFT = 20                                          # the entropy sums are bits times 2^20
+_HARMONY_TABLES = {}
+
+
+def harmony_table(device=None):
+    """The int64 table of pb_piece_harmony: TL[k] = round(k log2(k) 2^20) for k = 0 .. 4096, TL[0] = TL[1] = 0, from the plain float64
+    expression (no entry lies closer than 1.47e-4 to a rounding tie, so every correct evaluation gives these integers;
+    tests/test_harmony_cpu.py compares them with a 60-digit evaluation). device=None: the host tensor; else that device's cached copy."""
+    if 'host' not in _HARMONY_TABLES:
+        t = [0, 0] + [int(round(k * math.log2(k) * float(1 << HARMONY_SHIFT))) for k in range(2, RUNS_MAX_S + 1)]
+        _HARMONY_TABLES['host'] = torch.tensor(t, dtype=torch.int64)
+    if device is None:
+        return _HARMONY_TABLES['host']
+    dev = torch.device(device)
+    if dev not in _HARMONY_TABLES:
+        _HARMONY_TABLES[dev] = _HARMONY_TABLES['host'].to(dev)
+    return _HARMONY_TABLES[dev]
+
+
+def piece_harmony(ids16, pitch_of, start=None, layout=None, table=None):
+    """pb_piece_harmony: the (N, 228) int64 harmony columns of ids16 (N, S, 8) int16, S <= 4096. pitch_of and start as in piece_features.
+    table: harmony_table() on the device of ids16 (the default: that device's cached copy)."""
+    layout = layout or DEFAULT_LAYOUT
+    p_ids = _dense(ids16, torch.int16, 3, 'piece_harmony: ids16')
+    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
+        raise PBError('piece_harmony: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    assert LIB.query('pb_harmony_lags') == HARMONY_LAGS and LIB.query('pb_harmony_cols') == HARMONY_COLS, \
+        'ops.HARMONY_LAGS / HARMONY_COLS and the library disagree'
+    N, S = ids16.shape[0], ids16.shape[1]
+    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_harmony: pitch_of')
+    if pitch_of.numel() != layout.pad8[3]:
+        raise PBError('piece_harmony: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
+    if table is None:
+        table = harmony_table(ids16.device)
+    p_table = _dense(table, torch.int64, 1, 'piece_harmony: table')
+    if table.numel() != RUNS_MAX_S + 1:
+        raise PBError('piece_harmony: table holds %d entries; harmony_table() has %d' % (table.numel(), RUNS_MAX_S + 1))
+    p_start = None
+    if start is not None:
+        p_start = _dense(start, torch.int32, 1, 'piece_harmony: start')
+        if start.numel() != N:
+            raise PBError('piece_harmony: start holds %d entries for %d pieces' % (start.numel(), N))
+    out = torch.empty((N, HARMONY_COLS), dtype=torch.int64, device=ids16.device)
+    LIB.call('pb_piece_harmony', p_ids, p_start, seg_array(layout.pad8), p_pitch, p_table, _p(out), N, S, _stream())
     return out
 
 
