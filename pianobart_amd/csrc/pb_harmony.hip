@@ -24,31 +24,20 @@
 // a column below 228 or a lag below 64; every table index is a count of notes of one piece, at most S <= 4096.
 #include "pb_common.h"
 #include "pb_api_internal.h"
+#include "pb_pieces.h"
 #include <algorithm>
 #include <climits>
 
 namespace {
 
 constexpr int HM_WIDE = 1024, HM_NARROW = 256, HM_NARROW_S = 512, HM_LAGS = 64, HM_COLS = 36 + 3 * HM_LAGS;
-constexpr int HM_MAX_S = 4096, HM_IDS = 1088, HM_WORDS = 6;      // ids of a head stay below HEAD_MAX = 1088 (ops.py); six words per bar
-constexpr int HM_GRID = 1024, HM_ROWS_PER_WG = 256;               // a workgroup takes at least this many rows' worth of pieces
+constexpr int HM_MAX_S = 4096, HM_IDS = PIECE_IDS, HM_WORDS = 6;   // the table and the 16-bit counts end at HM_MAX_S; six words per bar
+constexpr int HM_ROWS_PER_WG = 256;                               // a workgroup takes at least this many rows' worth of pieces
 constexpr int HM_GROUP = 8, HM_GROUPS = HM_LAGS / HM_GROUP;       // lags per work item of the pair loop
 constexpr int C_G = 8, C_W1 = 20, C_W4 = 28, C_IH = 36, C_TH = C_IH + HM_LAGS, C_IX = C_TH + HM_LAGS;
 static_assert(HM_WIDE % HM_GROUPS == 0 && HM_NARROW % HM_GROUPS == 0 && HM_GROUPS == 8, "a thread keeps its lag group; the lane exchange below is written for 8 groups");
 
-struct Pad8 { int v[8]; };
 typedef unsigned long long u64;
-
-__device__ __forceinline__ int row_id(const uint4& r, int h) {
-    const uint32_t w = h < 2 ? r.x : h < 4 ? r.y : h < 6 ? r.z : r.w;
-    return (int)((w >> (16 * (h & 1))) & 0xffffu);
-}
-__device__ __forceinline__ bool row_is_special(const uint4& r, const Pad8& pad) {
-    bool sp = false;
-#pragma unroll
-    for (int h = 0; h < 8; ++h) sp |= row_id(r, h) >= pad.v[h];      // unsigned 16 bits: a negative id ends the piece too
-    return sp;
-}
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
@@ -163,13 +152,9 @@ __global__ __launch_bounds__(HM_THREADS) void harmony_kernel(const uint4* __rest
         for (int i = tid; i < HM_COLS; i += HM_THREADS) row[i] = 0ull;
         if (tid == 0) { s_L = S; s_lo = INT_MAX; s_hi = -1; }
         __syncthreads();
-        // L: the first row with a special id in any head
-        int mine = S;
-        for (int r = tid; r < S && mine == S; r += HM_THREADS) if (row_is_special(rows[r], pad)) mine = r;
-        if (mine < S) atomicMin(&s_L, mine);
-        __syncthreads();
-        const int first = start ? max(start[piece], 0) : 0;
-        const int n = max(s_L - first, 0);                                              // notes: rows first .. L - 1, n <= S <= 4096
+        const int L = first_special_row<HM_THREADS>(rows, S, pad, s_L);
+        const int first = first_row(start, piece);
+        const int n = max(L - first, 0);                                                // notes: rows first .. L - 1, n <= S <= 4096
 
         // counts
         int lo = INT_MAX, hi = -1, pitched = 0;
@@ -272,23 +257,12 @@ extern "C" int pb_harmony_cols(void) { return HM_COLS; }
 
 extern "C" int pb_piece_harmony(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int64_t* table,
                                 int64_t* out, int32_t N, int32_t S, void* stream_) {
-    PB_REQUIRE((N == 0 || ids16) && ((uintptr_t)ids16 % 16 == 0), "pb_piece_harmony: ids16 must be a non-NULL 16-byte aligned pointer (rows of 8 int16)");
-    PB_REQUIRE((uintptr_t)start % 4 == 0, "pb_piece_harmony: start must be NULL or an int32 pointer");
-    PB_REQUIRE(pad8, "pb_piece_harmony: pad8 (8 host int32) is required");
-    PB_REQUIRE(pitch_of && ((uintptr_t)pitch_of % 2 == 0), "pb_piece_harmony: pitch_of must be a non-NULL int16 pointer");
+    Pad8 pad;
+    if (int e = check_pieces("pb_piece_harmony", HM_MAX_S, "the per-bar counts are sized for it", ids16, start, pad8, pitch_of, N, S, pad)) return e;
     PB_REQUIRE(table && ((uintptr_t)table % 8 == 0), "pb_piece_harmony: table must be a non-NULL int64 pointer (4097 entries)");
     PB_REQUIRE((N == 0 || out) && ((uintptr_t)out % 8 == 0), "pb_piece_harmony: out must be a non-NULL int64 pointer");
-    PB_REQUIRE(N >= 0 && N <= (1 << 24), "pb_piece_harmony: N = %d out of range (0 .. 2^24)", (int)N);
-    PB_REQUIRE(S >= 1 && S <= HM_MAX_S, "pb_piece_harmony: S = %d out of range (1 .. %d: the table and the 16-bit counts end there)", (int)S, HM_MAX_S);
-    Pad8 pad;
-    for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(pad8[h] >= 1 && pad8[h] <= HM_IDS - 6, "pb_piece_harmony: pad8[%d] = %d out of range (1 .. %d: the per-bar counts are sized for it)", h,
-                   (int)pad8[h], HM_IDS - 6);
-        pad.v[h] = pad8[h];
-    }
     if (N == 0) return 0;
-    const int per_wg = std::max(1, HM_ROWS_PER_WG / S);
-    const int grid = std::min(HM_GRID, (N + per_wg - 1) / per_wg);
+    const int grid = piece_grid(N, S, HM_ROWS_PER_WG);
     if (S <= HM_NARROW_S)
         hipLaunchKernelGGL(harmony_kernel<HM_NARROW>, dim3(grid), dim3(HM_NARROW), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of,
                            (const long long*)table, (long long*)out, (int)N, (int)S);

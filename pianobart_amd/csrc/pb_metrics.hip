@@ -8,29 +8,16 @@
 // an LDS tree, and per-slab / per-workgroup partial rows summed front to back by a second kernel. Equal inputs give equal bytes.
 #include "pb_common.h"
 #include "pb_api_internal.h"
+#include "pb_pieces.h"
 #include <algorithm>
 #include <climits>
 
 namespace {
 
 // ---- piece features ----------------------------------------------------------------------------------------------------------------
-constexpr int FT_THREADS = 256, FT_COLS = 288, FT_IDS = 1088;      // ids of a head stay below HEAD_MAX = 1088 (ops.py)
-constexpr int FT_GRID = 1024, FT_ROWS_PER_WG = 2048;               // a workgroup takes at least this many rows' worth of pieces
+constexpr int FT_THREADS = 256, FT_COLS = 288, FT_IDS = PIECE_IDS;
+constexpr int FT_ROWS_PER_WG = 2048;                               // a workgroup takes at least this many rows' worth of pieces
 constexpr int C_PCH = 16, C_PCTM = 28, C_BEAT = 172, C_DUR = 188, C_VEL = 220, C_BARD = 252;
-
-struct Pad8 { int v[8]; };
-
-__device__ __forceinline__ bool row_is_special(const uint4& r, const Pad8& pad) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-    bool sp = false;
-#pragma unroll
-    for (int h = 0; h < 8; ++h) sp |= (int)((w[h >> 1] >> (16 * (h & 1))) & 0xffffu) >= pad.v[h];   // unsigned: a negative id ends the piece too
-    return sp;
-}
-__device__ __forceinline__ int row_id(const uint4& r, int h) {
-    const uint32_t w = h < 2 ? r.x : h < 4 ? r.y : h < 6 ? r.z : r.w;
-    return (int)((w >> (16 * (h & 1))) & 0xffffu);
-}
 
 __global__ __launch_bounds__(FT_THREADS) void feat_kernel(const uint4* __restrict__ ids, const int32_t* __restrict__ start, const Pad8 pad,
                                                           const int16_t* __restrict__ pitch_of, const int32_t* __restrict__ dur_pos,
@@ -49,13 +36,8 @@ __global__ __launch_bounds__(FT_THREADS) void feat_kernel(const uint4* __restric
         if (tid < FT_IDS / 32) { k_map[tid] = 0u; ins_map[tid] = 0u; }
         if (tid == 0) { s_L = S; s_carry = -1; s_bar_lo = INT_MAX; s_bar_hi = -1; }
         __syncthreads();
-        // L: the first row with a special id in any head
-        int mine = S;
-        for (int r = tid; r < S && mine == S; r += FT_THREADS) if (row_is_special(rows[r], pad)) mine = r;
-        if (mine < S) atomicMin(&s_L, mine);
-        __syncthreads();
-        const int L = s_L;
-        const int first = start ? max(start[piece], 0) : 0;
+        const int L = first_special_row<FT_THREADS>(rows, S, pad, s_L);
+        const int first = first_row(start, piece);
 
         int n_notes = 0, n_pitched = 0, iv_sum = 0, iv_cnt = 0, onsets = 0, back = 0, dur_sum = 0, vel_sum = 0;
         for (int base = first; base < L; base += FT_THREADS) {          // chunks of 256 rows, in row order
@@ -320,24 +302,12 @@ extern "C" int64_t pb_metrics_ws_bytes(int64_t N, int64_t M, int32_t G) {
 
 extern "C" int pb_piece_features(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int32_t* dur_pos,
                                  int32_t* feat, int32_t N, int32_t S, void* stream_) {
-    PB_REQUIRE(ids16 && ((uintptr_t)ids16 % 16 == 0), "pb_piece_features: ids16 must be a non-NULL 16-byte aligned pointer (rows of 8 int16)");
-    PB_REQUIRE((uintptr_t)start % 4 == 0, "pb_piece_features: start must be NULL or an int32 pointer");
-    PB_REQUIRE(pad8, "pb_piece_features: pad8 (8 host int32) is required");
-    PB_REQUIRE(pitch_of && ((uintptr_t)pitch_of % 2 == 0), "pb_piece_features: pitch_of must be a non-NULL int16 pointer");
+    Pad8 pad;
+    if (int e = check_pieces("pb_piece_features", PIECE_MAX_S, "the per-id counters live in LDS", ids16, start, pad8, pitch_of, N, S, pad)) return e;
     PB_REQUIRE(dur_pos && ((uintptr_t)dur_pos % 4 == 0), "pb_piece_features: dur_pos must be a non-NULL int32 pointer");
     PB_REQUIRE(feat && ((uintptr_t)feat % 4 == 0), "pb_piece_features: feat must be a non-NULL int32 pointer");
-    PB_REQUIRE(N >= 0 && N <= (1 << 24), "pb_piece_features: N = %d out of range (0 .. 2^24)", (int)N);
-    PB_REQUIRE(S >= 1 && S <= (1 << 20), "pb_piece_features: S = %d out of range (1 .. 2^20)", (int)S);
-    Pad8 pad;
-    for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(pad8[h] >= 1 && pad8[h] <= FT_IDS - 6, "pb_piece_features: pad8[%d] = %d out of range (1 .. %d: the per-id counters live in LDS)", h, (int)pad8[h],
-                   FT_IDS - 6);
-        pad.v[h] = pad8[h];
-    }
     if (N == 0) return 0;
-    const int per_wg = std::max(1, FT_ROWS_PER_WG / S);
-    const int grid = std::min(FT_GRID, (N + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(feat_kernel, dim3(grid), dim3(FT_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, dur_pos, feat, (int)N, (int)S);
+    hipLaunchKernelGGL(feat_kernel, dim3(piece_grid(N, S, FT_ROWS_PER_WG)), dim3(FT_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, dur_pos, feat, (int)N, (int)S);
     PB_LAUNCH_CHECK();
     return 0;
 }

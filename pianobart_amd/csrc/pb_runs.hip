@@ -13,6 +13,7 @@
 // on no order of threads, workgroups or chunks: equal inputs give equal bytes.
 #include "pb_common.h"
 #include "pb_api_internal.h"
+#include "pb_pieces.h"
 #include <algorithm>
 
 namespace {
@@ -21,20 +22,7 @@ constexpr uint32_t NO_KEY = 0xFFFFFFFFu;        // in A: matches nothing
 constexpr uint32_t STOP = 0xFFFFFFFEu;          // in the LDS image of B: matches nothing (a value with bit 31 set is "no key" on either side)
 
 // ---- keys ------------------------------------------------------------------------------------------------------------------------------
-constexpr int KY_THREADS = 256, KY_GRID = 1024, KY_ROWS_PER_WG = 2048, KY_IDS = 1088;      // ids of a head stay below HEAD_MAX = 1088 (ops.py)
-
-struct Pad8 { int v[8]; };
-
-__device__ __forceinline__ int row_id(const uint4& r, int h) {
-    const uint32_t w = h < 2 ? r.x : h < 4 ? r.y : h < 6 ? r.z : r.w;
-    return (int)((w >> (16 * (h & 1))) & 0xffffu);
-}
-__device__ __forceinline__ bool row_is_special(const uint4& r, const Pad8& pad) {
-    bool sp = false;
-#pragma unroll
-    for (int h = 0; h < 8; ++h) sp |= row_id(r, h) >= pad.v[h];      // unsigned 16 bits: a negative id ends the piece too
-    return sp;
-}
+constexpr int KY_THREADS = 256, KY_ROWS_PER_WG = 2048, KY_IDS = PIECE_IDS;
 
 __global__ __launch_bounds__(KY_THREADS) void keys_kernel(const uint4* __restrict__ ids, const int32_t* __restrict__ start, const Pad8 pad,
                                                           const int16_t* __restrict__ pitch_of, uint32_t* __restrict__ keys, int32_t* __restrict__ klen,
@@ -45,12 +33,8 @@ __global__ __launch_bounds__(KY_THREADS) void keys_kernel(const uint4* __restric
         const uint4* rows = ids + (long)piece * S;
         if (tid == 0) s_L = S;
         __syncthreads();
-        int mine = S;
-        for (int r = tid; r < S && mine == S; r += KY_THREADS) if (row_is_special(rows[r], pad)) mine = r;
-        if (mine < S) atomicMin(&s_L, mine);
-        __syncthreads();
-        const int L = s_L;
-        const int first = start ? max(start[piece], 0) : 0;
+        const int L = first_special_row<KY_THREADS>(rows, S, pad, s_L);
+        const int first = first_row(start, piece);
         const int K = max(L - first - 1, 0);                        // first < L <= S whenever K > 0
         uint32_t* out = keys + (long)piece * S;
         for (int t = tid; t < S; t += KY_THREADS) {
@@ -205,25 +189,13 @@ extern "C" int pb_runs_tile(void) { return RN_TILE; }
 
 extern "C" int pb_piece_keys(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, uint32_t* keys, int32_t* klen,
                              int32_t N, int32_t S, int32_t mode, void* stream_) {
-    PB_REQUIRE((N == 0 || ids16) && ((uintptr_t)ids16 % 16 == 0), "pb_piece_keys: ids16 must be a non-NULL 16-byte aligned pointer (rows of 8 int16)");
-    PB_REQUIRE((uintptr_t)start % 4 == 0, "pb_piece_keys: start must be NULL or an int32 pointer");
-    PB_REQUIRE(pad8, "pb_piece_keys: pad8 (8 host int32) is required");
-    PB_REQUIRE(pitch_of && ((uintptr_t)pitch_of % 2 == 0), "pb_piece_keys: pitch_of must be a non-NULL int16 pointer");
+    Pad8 pad;
+    if (int e = check_pieces("pb_piece_keys", RN_MAX_S, "the key's fields are sized for it", ids16, start, pad8, pitch_of, N, S, pad)) return e;
     PB_REQUIRE((N == 0 || keys) && ((uintptr_t)keys % 4 == 0), "pb_piece_keys: keys must be a non-NULL uint32 pointer");
     PB_REQUIRE((N == 0 || klen) && ((uintptr_t)klen % 4 == 0), "pb_piece_keys: klen must be a non-NULL int32 pointer");
-    PB_REQUIRE(N >= 0 && N <= (1 << 24), "pb_piece_keys: N = %d out of range (0 .. 2^24)", (int)N);
-    PB_REQUIRE(S >= 1 && S <= RN_MAX_S, "pb_piece_keys: S = %d out of range (1 .. %d)", (int)S, RN_MAX_S);
     PB_REQUIRE(mode == 0 || mode == 1, "pb_piece_keys: mode = %d (0 = exact, 1 = interval)", (int)mode);
-    Pad8 pad;
-    for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(pad8[h] >= 1 && pad8[h] <= KY_IDS - 6, "pb_piece_keys: pad8[%d] = %d out of range (1 .. %d: the key's fields are sized for it)", h,
-                   (int)pad8[h], KY_IDS - 6);
-        pad.v[h] = pad8[h];
-    }
     if (N == 0) return 0;
-    const int per_wg = std::max(1, KY_ROWS_PER_WG / S);
-    const int grid = std::min(KY_GRID, (N + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(keys_kernel, dim3(grid), dim3(KY_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, keys, klen, (int)N,
+    hipLaunchKernelGGL(keys_kernel, dim3(piece_grid(N, S, KY_ROWS_PER_WG)), dim3(KY_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, keys, klen, (int)N,
                        (int)S, (int)mode);
     PB_LAUNCH_CHECK();
     return 0;

@@ -22,31 +22,19 @@
 // lag below 64.
 #include "pb_common.h"
 #include "pb_api_internal.h"
+#include "pb_pieces.h"
 #include <algorithm>
 #include <climits>
 
 namespace {
 
 constexpr int ST_THREADS = 1024, ST_WAVES = ST_THREADS / 64, ST_LAGS = 64, ST_COLS = 8 + 4 * ST_LAGS;
-constexpr int ST_MAX_S = 4096, ST_BLOCKS = ST_MAX_S / 64, ST_IDS = 1088;      // ids of a head stay below HEAD_MAX = 1088 (ops.py)
-constexpr int ST_GRID = 1024, ST_ROWS_PER_WG = 256;                // a workgroup takes at least this many rows' worth of pieces
+constexpr int ST_MAX_S = 4096, ST_BLOCKS = ST_MAX_S / 64, ST_IDS = PIECE_IDS;      // the notes of a piece live in LDS
+constexpr int ST_ROWS_PER_WG = 256;                                // a workgroup takes at least this many rows' worth of pieces
 constexpr int C_IO = 8, C_TO = C_IO + ST_LAGS, C_IN = C_TO + ST_LAGS, C_TN = C_IN + ST_LAGS;
 constexpr uint32_t NONE_C = 0xFFFFFFFFu;       // K of a note that represents nothing, read as c: K_c - K_a - 1 >= 2^32 - 2^22 - 2
 constexpr uint32_t NONE_A = 0x80000000u;       // the same note (or no note) held as a: K_c - K_a - 1 >= 2^31 - 1 for every K_c
 constexpr uint32_t FIRST_OF_ONSET = 0x80000000u, FIELD = 0x7FFu;
-
-struct Pad8 { int v[8]; };
-
-__device__ __forceinline__ int row_id(const uint4& r, int h) {
-    const uint32_t w = h < 2 ? r.x : h < 4 ? r.y : h < 6 ? r.z : r.w;
-    return (int)((w >> (16 * (h & 1))) & 0xffffu);
-}
-__device__ __forceinline__ bool row_is_special(const uint4& r, const Pad8& pad) {
-    bool sp = false;
-#pragma unroll
-    for (int h = 0; h < 8; ++h) sp |= row_id(r, h) >= pad.v[h];      // unsigned 16 bits: a negative id ends the piece too
-    return sp;
-}
 
 // pass 1, one earlier note of the tile: the lanes (of `later`: the notes in later rows than it) whose (bar, p) / (bar, p, f) it holds. The masks
 // are wave-uniform: a compare writes its lane mask, and the accumulation is scalar.
@@ -83,13 +71,9 @@ __global__ __launch_bounds__(ST_THREADS) void structure_kernel(const uint4* __re
         if (tid < ST_BLOCKS) { blk_lo[tid] = INT_MAX; blk_hi[tid] = -1; dup_o[tid] = 0ull; dup_n[tid] = 0ull; }
         if (tid == 0) { s_L = S; s_bar_lo = INT_MAX; s_bar_hi = -1; }
         __syncthreads();
-        // L: the first row with a special id in any head
-        int mine = S;
-        for (int r = tid; r < S && mine == S; r += ST_THREADS) if (row_is_special(rows[r], pad)) mine = r;
-        if (mine < S) atomicMin(&s_L, mine);
-        __syncthreads();
-        const int first = start ? max(start[piece], 0) : 0;
-        const int n = max(s_L - first, 0);                                   // notes: rows first .. L - 1, n <= S <= 4096
+        const int L = first_special_row<ST_THREADS>(rows, S, pad, s_L);
+        const int first = first_row(start, piece);
+        const int n = max(L - first, 0);                                     // notes: rows first .. L - 1, n <= S <= 4096
         const int n64 = (n + 63) & ~63, nb = n64 >> 6;                       // blocks of 64 notes, the last one filled with NONE
 
         for (int i = tid; i < n64; i += ST_THREADS) {                        // a wave loads whole blocks
@@ -193,24 +177,12 @@ extern "C" int pb_structure_cols(void) { return ST_COLS; }
 
 extern "C" int pb_piece_structure(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, int32_t* out, int32_t N,
                                   int32_t S, int32_t mode, void* stream_) {
-    PB_REQUIRE((N == 0 || ids16) && ((uintptr_t)ids16 % 16 == 0), "pb_piece_structure: ids16 must be a non-NULL 16-byte aligned pointer (rows of 8 int16)");
-    PB_REQUIRE((uintptr_t)start % 4 == 0, "pb_piece_structure: start must be NULL or an int32 pointer");
-    PB_REQUIRE(pad8, "pb_piece_structure: pad8 (8 host int32) is required");
-    PB_REQUIRE(pitch_of && ((uintptr_t)pitch_of % 2 == 0), "pb_piece_structure: pitch_of must be a non-NULL int16 pointer");
-    PB_REQUIRE((N == 0 || out) && ((uintptr_t)out % 4 == 0), "pb_piece_structure: out must be a non-NULL int32 pointer");
-    PB_REQUIRE(N >= 0 && N <= (1 << 24), "pb_piece_structure: N = %d out of range (0 .. 2^24)", (int)N);
-    PB_REQUIRE(S >= 1 && S <= ST_MAX_S, "pb_piece_structure: S = %d out of range (1 .. %d: the notes of a piece live in LDS)", (int)S, ST_MAX_S);
-    PB_REQUIRE(mode == 0 || mode == 1, "pb_piece_structure: mode = %d (0 = exact pitch, 1 = pitch class)", (int)mode);
     Pad8 pad;
-    for (int h = 0; h < 8; ++h) {
-        PB_REQUIRE(pad8[h] >= 1 && pad8[h] <= ST_IDS - 6, "pb_piece_structure: pad8[%d] = %d out of range (1 .. %d: the note words' fields are sized for it)", h,
-                   (int)pad8[h], ST_IDS - 6);
-        pad.v[h] = pad8[h];
-    }
+    if (int e = check_pieces("pb_piece_structure", ST_MAX_S, "the note words' fields are sized for it", ids16, start, pad8, pitch_of, N, S, pad)) return e;
+    PB_REQUIRE((N == 0 || out) && ((uintptr_t)out % 4 == 0), "pb_piece_structure: out must be a non-NULL int32 pointer");
+    PB_REQUIRE(mode == 0 || mode == 1, "pb_piece_structure: mode = %d (0 = exact pitch, 1 = pitch class)", (int)mode);
     if (N == 0) return 0;
-    const int per_wg = std::max(1, ST_ROWS_PER_WG / S);
-    const int grid = std::min(ST_GRID, (N + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(structure_kernel, dim3(grid), dim3(ST_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, out, (int)N, (int)S,
+    hipLaunchKernelGGL(structure_kernel, dim3(piece_grid(N, S, ST_ROWS_PER_WG)), dim3(ST_THREADS), 0, (hipStream_t)stream_, (const uint4*)ids16, start, pad, pitch_of, out, (int)N, (int)S,
                        (int)mode);
     PB_LAUNCH_CHECK();
     return 0;

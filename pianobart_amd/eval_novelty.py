@@ -15,46 +15,23 @@
 
 A key holds a note's pitch (or interval), its position in the bar and the bar step from the note before: the identity tested is "the
 same pitches at the same places in the bar". Instrument, duration, velocity, time signature and tempo are not compared."""
-import argparse
-import json
-import os
-
 import numpy as np
 
-from . import novelty
+from . import eval_metrics as cli
+from . import novelty, ops
 from ._lib import PBError
-from .eval_metrics import _json_safe, load_pieces
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_VOCAB = os.path.join(_HERE, 'data', 'octuple_vocab.json')
 
 
 def get_args(argv=None):
-    ap = argparse.ArgumentParser(description='')
-    ap.add_argument('--generated', type=str, required=True)
+    ap = cli.parser('./novelty.json')
     ap.add_argument('--corpus', type=str, default=None)
     ap.add_argument('--self', dest='self_', action='store_true')
-    ap.add_argument('--dict_file', type=str, default=_VOCAB)
-    ap.add_argument('--skip', type=int, default=0, metavar='K')
     ap.add_argument('--min_run', type=int, default=8, metavar='R')
     ap.add_argument('--transpose', action='store_true')
     ap.add_argument('--align', action='store_true')
     ap.add_argument('--align_scores', type=str, default=None, metavar='M,X,G')
     ap.add_argument('--min_score', type=int, default=None, metavar='H')
-    ap.add_argument('--max_pieces', type=int, default=None, metavar='N')
-    ap.add_argument('--output', type=str, default='./novelty.json')
-    ap.add_argument('--cpu', action='store_true')
     return ap.parse_args(argv)
-
-
-def _listed(v):
-    if isinstance(v, dict):
-        return {k: _listed(x) for k, x in v.items()}
-    if isinstance(v, np.ndarray):
-        return _listed(v.tolist())
-    if isinstance(v, list):
-        return [_listed(x) for x in v]
-    return _json_safe(v)
 
 
 def _align_arg(args):
@@ -72,16 +49,13 @@ def _align_arg(args):
         par.update(zip(('match', 'mismatch', 'gap'), vals))
     if args.min_score is not None:
         par['min_score'] = args.min_score
-    novelty.ops.align_params(who='--align_scores M,X,G / --min_score H', **par)
+    ops.align_params(who='--align_scores M,X,G / --min_score H', **par)
     return par
 
 
 def main(argv=None):
     args = get_args(argv)
-    if args.cpu:
-        raise PBError('--cpu: copy detection runs in HIP kernels (pb_runs.hip); there is no CPU path')
-    if args.skip < 0 or (args.max_pieces is not None and args.max_pieces < 1):
-        raise PBError('--skip takes a number of rows >= 0 and --max_pieces a number of pieces >= 1')
+    cli.refuse_common(args, 'copy detection runs in HIP kernels (pb_runs.hip)')
     if args.min_run < 1:
         raise PBError('--min_run takes a number of keys >= 1 (got %d)' % args.min_run)
     if args.self_ and args.corpus is not None:
@@ -89,19 +63,13 @@ def main(argv=None):
     if not args.self_ and args.corpus is None:
         raise PBError('--corpus (or --self) is required')
     align = _align_arg(args)
-    gen = load_pieces(args.generated, '--generated', args.max_pieces)
-    cor = gen if args.self_ else load_pieces(args.corpus, '--corpus', args.max_pieces)
-    for what, a in (('--generated', gen), ('--corpus', cor)):
-        if a.shape[1] > novelty.ops.RUNS_MAX_S:
-            raise PBError('%s holds pieces of %d rows; copy detection takes 1 .. %d' % (what, a.shape[1], novelty.ops.RUNS_MAX_S))
-    from .pretrain import _load_vocab
-    if not os.path.isfile(args.dict_file):
-        raise PBError('--dict_file: no file %r' % args.dict_file)
-    tab = novelty.metrics.tables(_load_vocab(args.dict_file)[0])
+    sets = cli.load_sets(args, 'corpus')
+    cli.refuse_long(sets, 'copy detection')
+    tab = cli.load_tables(args.dict_file)
+    gen, cor = sets[0][1], sets[-1][1]                 # --self: the corpus is the generated set
     kw = {} if align is None else {'align': align}
     res = novelty.compare_to_corpus(gen, cor, tab, start=(args.skip, 0), min_run=args.min_run, transpose=args.transpose, exclude_self=args.self_, **kw)
-    with open(args.output, 'w') as f:
-        json.dump(_listed(res), f, indent=1)
+    cli.write_json(res, args.output)
     tag = '   [novelty]'
     print('%s %d generated pieces against %s, %s keys, runs from %d keys on; %.2f ms on the device'
           % (tag, res['n_gen'], 'themselves' if args.self_ else '%d corpus pieces' % res['n_corpus'], 'interval' if args.transpose else 'exact',

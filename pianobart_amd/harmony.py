@@ -12,7 +12,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import metrics, ops
+from . import metrics, ops, pieces
 from ._lib import PBError
 
 LAGS, COLS = ops.HARMONY_LAGS, ops.HARMONY_COLS
@@ -23,42 +23,20 @@ GROUPS = ('pc_entropy_1', 'pc_entropy_4', 'scale_consistency', 'local_scale_1', 
 SCALAR_GROUPS = tuple(g for g in GROUPS if not g.endswith('_profile'))
 
 
-def _upload(ids, tab, start, device):
-    """The checked arguments of ops.piece_harmony on the device."""
-    a = metrics._host_ids(ids, tab.layout)
-    dev = torch.device(device) if device is not None else ids.device if torch.is_tensor(ids) else torch.device('cuda', torch.cuda.current_device())
-    s = metrics._host_start(start, a.shape[0])
-    up = lambda x: torch.from_numpy(x).to(dev)
-    return (up(a.astype(np.int16)), up(tab.pitch_of)), dict(start=None if s is None else up(s), layout=tab.layout)
-
-
-def _tables(e2w):
-    return e2w if isinstance(e2w, metrics.Tables) else metrics.tables(e2w)
-
-
 def piece_harmony(ids, e2w=None, start=None, device=None):
     """The (N, 228) int64 device tensor of pb_piece_harmony for (N, S, 8) ids, S <= 4096: integer or integer-valued float arrays or device
     tensors, checked as metrics.piece_features checks them. start: the first row that counts, one number or one per piece. e2w: a
     dictionary, None (the default one) or metrics.tables()."""
-    args, kw = _upload(ids, _tables(e2w), start, device)
-    return ops.piece_harmony(*args, **kw)
+    return ops.piece_harmony(**pieces.upload(ids, pieces.tables(e2w), start, device))
 
 
 def kept_pieces(ids, tab=None, start=None):
     """Host: per piece of an (N, S, 8) integer array whether harmony_groups keeps it: its notes span two bars or more (W >= 2) and one of
     them at least is pitched (P >= 1)."""
-    tab = _tables(tab)
-    a = np.asarray(ids)
-    special = (a >= np.asarray(tab.layout.pad8)).any(-1)
-    L = np.where(special.any(1), special.argmax(1), a.shape[1])
-    s = np.zeros(a.shape[0], dtype=np.int64) if start is None else metrics._host_start(start, a.shape[0])
-    r = np.arange(a.shape[1])
-    live = (r >= np.asarray(s)[:, None]) & (r < L[:, None])
-    bars = a[:, :, 0].astype(np.int64)
-    hi, lo = np.where(live, bars, -1).max(1), np.where(live, bars, 1 << 40).min(1)
-    pit = np.where(live, a[:, :, 3], 0).astype(np.int64)
-    pitched = live & (np.asarray(tab.pitch_of)[pit] >= 0)
-    return live.any(1) & (hi - lo + 1 >= 2) & pitched.any(1)
+    tab = pieces.tables(tab)
+    live = pieces.live_rows(ids, tab.layout, start)[1]
+    pit = np.where(live, np.asarray(ids)[:, :, 3], 0).astype(np.int64)
+    return (pieces.bar_spans(ids, tab.layout, start) >= 2) & (live & (np.asarray(tab.pitch_of)[pit] >= 0)).any(1)
 
 
 def _columns(cols):
@@ -141,14 +119,8 @@ def describe_set(ids, e2w=None, lags=16, start=None, device=None):
     """One set alone: {'n', 'short', 'device_ms', 'profile' (pooled_profiles), 'means'}: means = the mean over the n kept pieces of the
     scalar groups of harmony_groups (nan when n = 0)."""
     lags = _check_lags(lags)
-    args, kw = _upload(ids, _tables(e2w), start, device)
-    timer = metrics._Timer('harmony')
-    cols = timer.run('harmony', ops.piece_harmony, *args, **kw)
-    ms = timer.totals()
-    g, short = harmony_groups(cols, lags)
-    n = len(g['harmony_mean'])
-    means = OrderedDict((k, float(g[k].astype(np.float64).mean()) if n else float('nan')) for k in SCALAR_GROUPS)
-    return OrderedDict([('n', n), ('short', short), ('device_ms', ms), ('profile', pooled_profiles(cols)), ('means', means)])
+    return metrics.describe_pieces('harmony', ops.piece_harmony, lambda c: harmony_groups(c, lags), SCALAR_GROUPS, pooled_profiles, ids,
+                                   pieces.tables(e2w), start, device)
 
 
 def compare_harmony(gen_ids, ref_ids, e2w=None, lags=16, grid=1024, start=None, device=None):
@@ -156,23 +128,6 @@ def compare_harmony(gen_ids, ref_ids, e2w=None, lags=16, grid=1024, start=None, 
     the kept pieces) the record of metrics.compare_sets: mean_* and std_* (of the row norm for the two profile groups), dist_gen /
     dist_ref / dist_inter, kl, oa, kl_gen, oa_gen, with the same degenerate rule. start: one value or a (gen, ref) pair. Returns
     {'n_gen', 'n_ref', 'short_gen', 'short_ref', 'device_ms', 'profile_gen', 'profile_ref', 'groups'}."""
-    G = int(grid)
-    if not 2 <= G <= 4096:
-        raise PBError('compare_harmony: grid = %r points; 2 .. 4096' % (grid,))
     lags = _check_lags(lags)
-    tab = _tables(e2w)
-    s_gen, s_ref = start if isinstance(start, tuple) else (start, start)
-    timer = metrics._Timer('harmony')
-    cols = []
-    for ids, s in ((gen_ids, s_gen), (ref_ids, s_ref)):
-        args, kw = _upload(ids, tab, s, device)
-        cols.append(timer.run('harmony', ops.piece_harmony, *args, **kw))
-    c_gen, c_ref = cols
-    dev = c_gen.device
-    g_gen, short_gen = harmony_groups(c_gen, lags)
-    g_ref, short_ref = harmony_groups(c_ref, lags)
-    n_gen, n_ref = len(g_gen['harmony_mean']), len(g_ref['harmony_mean'])
-    ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
-    groups = OrderedDict((name, metrics.compare_group(g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1), G, ws, timer, dev)) for name in GROUPS)
-    return OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), ('short_gen', short_gen), ('short_ref', short_ref), ('device_ms', timer.totals()),
-                        ('profile_gen', pooled_profiles(c_gen)), ('profile_ref', pooled_profiles(c_ref)), ('groups', groups)])
+    return metrics.compare_pieces('compare_harmony', 'harmony', ops.piece_harmony, lambda c: harmony_groups(c, lags), GROUPS, gen_ids, ref_ids,
+                                  pieces.tables(e2w), grid, start, device, profile=pooled_profiles)

@@ -6,128 +6,35 @@ The features (pb_piece_features), the N x M distances (pb_pairwise_l2), their mo
 (pb_kde_eval) run in pb_metrics.hip; the host divides integer columns, picks bandwidths and integrates G-point curves.
 There is no CPU path. The reference's own quality line (the `shapesimilarity` "FAD" of its GenerationTrainer) needs a third-party
 package this project does not have and stays `n/a`; this module does not stand in for it, it measures something else."""
-import json
-import os
-import re
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, pieces
 from ._lib import PBError
-from .octuple_midi import code_to_dur
-
-_VOCAB = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'octuple_vocab.json')
-MAX_PITCH = ops.HEAD_MAX - 1                  # the kernel's pitch bitmap covers 0 .. HEAD_MAX - 1
-
-Tables = namedtuple('Tables', 'pitch_of dur_pos layout')
+from .pieces import Tables, tables
+from .pieces import host_start as _host_start      # noqa: F401 (the name metrics has always had for it)
 
 SCALAR_GROUPS = ('note_count', 'pitch_count', 'pitch_range', 'avg_interval', 'notes_per_bar', 'avg_duration', 'avg_velocity', 'onset_ratio')
 # histogram groups: (first column, width, divisor column)
 HIST_GROUPS = OrderedDict([('pch', (16, 12, 1)), ('pctm', (28, 144, 8)), ('beat_grid', (172, 16, 0)), ('duration_hist', (188, 32, 0)),
                            ('velocity_hist', (220, 32, 0)), ('bar_density_hist', (252, 32, 2))])
 GROUPS = SCALAR_GROUPS + tuple(HIST_GROUPS)
-
-
-def _default_e2w():
-    return json.load(open(_VOCAB))['e2w']
-
-
-def _words_by_id(e2w, name, n):
-    """The words of ids 0 .. n - 1 of a class; PBError when an id has no word."""
-    by_id = {int(i): w for w, i in e2w[name].items()}
-    missing = [i for i in range(n) if i not in by_id]
-    if missing:
-        raise PBError('metrics: class %s has no word for id %d' % (name, missing[0]))
-    return [by_id[i] for i in range(n)]
-
-
-def tables(e2w=None):
-    """Tables(pitch_of, dur_pos, layout) of a dictionary's event -> word half (None: the default dictionary): pitch_of[id] = k for the word
-    'Pitch k' and -1 for 'Pitch percussion k' (int16, one entry per ordinary pitch id); dur_pos[id] = octuple_midi.code_to_dur(c) for the
-    word 'Duration c' (int32, one entry per ordinary duration id). A word of another form is a PBError that names it."""
-    if e2w is None:
-        e2w = _default_e2w()
-    layout = ops.Layout.from_dict(e2w)
-    pitch_of = np.empty(layout.pad8[3], dtype=np.int16)
-    for i, w in enumerate(_words_by_id(e2w, 'Pitch', layout.pad8[3])):
-        m = re.fullmatch(r'Pitch (percussion )?(\d+)', w)
-        if not m:
-            raise PBError("metrics: pitch word %r (id %d) is neither 'Pitch k' nor 'Pitch percussion k'" % (w, i))
-        k = -1 if m.group(1) else int(m.group(2))
-        if k > MAX_PITCH:
-            raise PBError('metrics: pitch word %r (id %d): the pitch number must lie in 0 .. %d' % (w, i, MAX_PITCH))
-        pitch_of[i] = k
-    dur_pos = np.empty(layout.pad8[4], dtype=np.int32)
-    for i, w in enumerate(_words_by_id(e2w, 'Duration', layout.pad8[4])):
-        m = re.fullmatch(r'Duration (\d+)', w)
-        if not m:
-            raise PBError("metrics: duration word %r (id %d) is not 'Duration c'" % (w, i))
-        dur_pos[i] = code_to_dur(int(m.group(1)))
-    return Tables(pitch_of, dur_pos, layout)
-
-
-def _host_ids(ids, layout):
-    """ids as a host int64 (N, S, 8) array, every id checked against its head's size."""
-    if torch.is_tensor(ids):
-        ops._p(ids)                                   # a host tensor is refused as every op refuses it: there is no CPU path
-        ids = ids.detach().cpu().numpy()
-    a = np.asarray(ids)
-    if a.ndim != 3 or a.shape[2] != 8 or a.shape[1] < 1:
-        raise PBError('metrics: ids must be (N, S, 8) with S >= 1 (got %s)' % (a.shape,))
-    if a.dtype.kind == 'f':
-        r = np.rint(a)
-        if not np.array_equal(r, a):                  # NaN included
-            raise PBError('metrics: ids hold values that are not integers')
-        a = r
-    elif a.dtype.kind not in 'iu':
-        raise PBError('metrics: ids must be integers or integer-valued floats (got %s)' % a.dtype)
-    a = a.astype(np.int64)
-    for h, n in enumerate(layout.sizes):
-        col = a[:, :, h]
-        if col.size and (col.min() < 0 or col.max() >= n):
-            bad = col[(col < 0) | (col >= n)][0]
-            raise PBError('metrics: head %d (%s) holds the id %d; its ids are 0 .. %d' % (h, ops.CLASS_NAMES[h], int(bad), n - 1))
-    return a
-
-
-def _host_start(start, N):
-    """start as a host int32 (N) array: one row index >= 0 for every piece, or one per piece."""
-    if start is None:
-        return None
-    s = np.asarray(start.detach().cpu().numpy() if torch.is_tensor(start) else start)
-    if s.ndim > 1 or (s.ndim == 1 and s.shape[0] != N) or s.dtype.kind not in 'iu' or (s.size and s.min() < 0):
-        raise PBError('metrics: start must be one row index >= 0, or one per piece (%d)' % N)
-    return np.array(np.broadcast_to(s, (N,)), dtype=np.int32)
+SET_STAGES = ('distances', 'moments', 'kde')     # the timed stages of compare_group, behind a family's per-piece stage
 
 
 def piece_lengths(ids, layout=None, start=None):
-    """Host: the number of notes of every piece of an (N, S, 8) integer array: L - start with L the first row in which any head's id is
-    >= its PAD id (the generator's stop rule; S if none), floor 0."""
-    layout = layout or ops.DEFAULT_LAYOUT
-    a = np.asarray(ids)
-    special = (a >= np.asarray(layout.pad8)).any(-1)
-    L = np.where(special.any(1), special.argmax(1), a.shape[1])
-    s = 0 if start is None else _host_start(start, a.shape[0])
-    return np.maximum(L - s, 0)
-
-
-def _upload(ids, tab, start, device):
-    """The checked arguments of ops.piece_features on the device."""
-    a = _host_ids(ids, tab.layout)
-    dev = torch.device(device) if device is not None else ids.device if torch.is_tensor(ids) else torch.device('cuda', torch.cuda.current_device())
-    s = _host_start(start, a.shape[0])
-    up = lambda x: torch.from_numpy(x).to(dev)
-    return (up(a.astype(np.int16)), up(tab.pitch_of), up(tab.dur_pos)), dict(start=None if s is None else up(s), layout=tab.layout)
+    """Host: the number of notes of every piece of an (N, S, 8) integer array (pieces.live_rows), 0 where start lies at or behind its end."""
+    return pieces.live_rows(ids, layout, start)[1].sum(1)
 
 
 def piece_features(ids, e2w=None, start=None, device=None):
     """The (N, 288) int32 device tensor of pb_piece_features for (N, S, 8) ids: integer or integer-valued float arrays or device tensors
     (eval_generation writes float32). Every id is checked on the host against its head's size (PBError names the head). start: the
     first row that counts, one number or one per piece (e.g. the prime length). e2w: a dictionary, None (the default one) or tables()."""
-    args, kw = _upload(ids, e2w if isinstance(e2w, Tables) else tables(e2w), start, device)
-    return ops.piece_features(*args, **kw)
+    tab = tables(e2w)
+    return ops.piece_features(**pieces.upload(ids, tab, start, device, dur_pos=tab.dur_pos))
 
 
 def _ratio(num, den):
@@ -192,33 +99,9 @@ def densities_defined(stats):
     return all(st['n'] >= 2 and st['std'] > 0 for st in stats)
 
 
-class _Timer:
-    """Device milliseconds per stage from pairs of events on the current stream, read after one synchronisation at the end."""
-
-    def __init__(self, first='features'):
-        self.pairs = []
-        self.first = first                            # the name of the per-piece stage
-
-    def run(self, stage, fn, *args, **kw):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn(*args, **kw)
-        b.record()
-        self.pairs.append((stage, a, b))
-        return out
-
-    def totals(self):
-        torch.cuda.synchronize()
-        ms = OrderedDict((stage, 0.0) for stage in (self.first, 'distances', 'moments', 'kde'))
-        for stage, a, b in self.pairs:
-            ms[stage] += a.elapsed_time(b)
-        ms['total'] = sum(ms.values())
-        return ms
-
-
 def compare_group(xg, xr, G, ws, timer, dev):
     """One feature group of compare_sets: xg (n_gen, F) and xr (n_ref, F) float32 host rows -> the record of means, stds, distance means,
-    kl and oa (see compare_sets). ws: ops.metrics_ws for the larger set and G grid points; timer: a _Timer."""
+    kl and oa (see compare_sets). ws: ops.metrics_ws for the larger set and G grid points; timer: a pieces.Timer with SET_STAGES."""
     n_gen, n_ref = len(xg), len(xr)
     res = OrderedDict()
     for tag, x in (('gen', xg), ('ref', xr)):
@@ -254,6 +137,42 @@ def compare_group(xg, xr, G, ws, timer, dev):
     return res
 
 
+def compare_pieces(who, stage, op, grouping, names, gen_ids, ref_ids, tab, grid, start, device, left_out='short', profile=None, **arrays):
+    """The set comparison every family ends in. Per piece of both sets op(**pieces.upload(..)) (timed as `stage`) gives integer columns,
+    grouping(columns) = (groups, pieces left out) turns them into float32 groups, and compare_group compares each group of `names`.
+    start: one value or a (gen, ref) pair; arrays: see pieces.upload. Returns {'n_gen', 'n_ref', left_out + '_gen', left_out + '_ref',
+    'device_ms', ['profile_gen', 'profile_ref': profile(columns),] 'groups'}."""
+    G = int(grid)
+    if not 2 <= G <= 4096:
+        raise PBError('%s: grid = %r points; 2 .. 4096' % (who, grid))
+    s_gen, s_ref = start if isinstance(start, tuple) else (start, start)
+    timer = pieces.Timer((stage,) + SET_STAGES)
+    c_gen, c_ref = (timer.run(stage, op, **pieces.upload(ids, tab, s, device, **arrays)) for ids, s in ((gen_ids, s_gen), (ref_ids, s_ref)))
+    dev = c_gen.device
+    g_gen, out_gen = grouping(c_gen)
+    g_ref, out_ref = grouping(c_ref)
+    n_gen, n_ref = len(g_gen[names[0]]), len(g_ref[names[0]])
+    ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
+    groups = OrderedDict((name, compare_group(g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1), G, ws, timer, dev)) for name in names)
+    res = OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), (left_out + '_gen', out_gen), (left_out + '_ref', out_ref), ('device_ms', timer.totals())])
+    if profile is not None:
+        res.update([('profile_gen', profile(c_gen)), ('profile_ref', profile(c_ref))])
+    res['groups'] = groups
+    return res
+
+
+def describe_pieces(stage, op, grouping, names, profile, ids, tab, start, device, **arrays):
+    """One set alone, the sibling of compare_pieces: {'n', 'short', 'device_ms', 'profile': profile(columns), 'means'}: means = the mean
+    over the n kept pieces of the groups of `names` (nan when n = 0)."""
+    timer = pieces.Timer((stage,) + SET_STAGES)
+    cols = timer.run(stage, op, **pieces.upload(ids, tab, start, device, **arrays))
+    ms = timer.totals()
+    g, short = grouping(cols)
+    n = len(g[names[0]])
+    means = OrderedDict((k, float(g[k].astype(np.float64).mean()) if n else float('nan')) for k in names)
+    return OrderedDict([('n', n), ('short', short), ('device_ms', ms), ('profile', profile(cols)), ('means', means)])
+
+
 def compare_sets(gen_ids, ref_ids, e2w=None, grid=1024, start=None, device=None):
     """Compare a generated set with a reference set, both (N, S, 8) ids. Per feature group: the mean and std (numpy's, ddof = 0) of the
     feature in each set (of the row norm for the histogram groups), the means of the gen-gen, ref-ref and gen-ref distances, and from
@@ -261,22 +180,6 @@ def compare_sets(gen_ids, ref_ids, e2w=None, grid=1024, start=None, device=None)
     `grid` points over [min - 3 h_max, max + 3 h_max]) kl = KL(intra-ref || inter) and oa = the overlapped area of the two (kl_gen, oa_gen:
     the same for intra-gen). A sample with fewer than two values or no spread gives nan for the group's kl and oa. start: see
     piece_features (one value or a (gen, ref) pair). Returns {'n_gen', 'n_ref', 'empty_gen', 'empty_ref', 'device_ms', 'groups'}."""
-    G = int(grid)
-    if not 2 <= G <= 4096:
-        raise PBError('compare_sets: grid = %r points; 2 .. 4096' % (grid,))
-    tab = e2w if isinstance(e2w, Tables) else tables(e2w)
-    s_gen, s_ref = start if isinstance(start, tuple) else (start, start)
-    timer = _Timer()
-    feats = []
-    for ids, s in ((gen_ids, s_gen), (ref_ids, s_ref)):
-        args, kw = _upload(ids, tab, s, device)
-        feats.append(timer.run('features', ops.piece_features, *args, **kw))
-    f_gen, f_ref = feats
-    dev = f_gen.device
-    g_gen, empty_gen = feature_groups(f_gen)
-    g_ref, empty_ref = feature_groups(f_ref)
-    n_gen, n_ref = len(g_gen['note_count']), len(g_ref['note_count'])
-    ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
-    groups = OrderedDict((name, compare_group(g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1), G, ws, timer, dev)) for name in GROUPS)
-    return OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), ('empty_gen', empty_gen), ('empty_ref', empty_ref),
-                        ('device_ms', timer.totals()), ('groups', groups)])
+    tab = tables(e2w)
+    return compare_pieces('compare_sets', 'features', ops.piece_features, feature_groups, GROUPS, gen_ids, ref_ids, tab, grid, start, device,
+                          left_out='empty', dur_pos=tab.dur_pos)

@@ -16,29 +16,18 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import metrics, ops
+from . import ops, pieces
 from ._lib import PBError
 
 STAGES = ('keys', 'runs')
 ALIGN_DEFAULTS = OrderedDict([('match', 1), ('mismatch', 2), ('gap', 2), ('min_score', 8)])
 
 
-def _tables(e2w):
-    return e2w if isinstance(e2w, metrics.Tables) else metrics.tables(e2w)
-
-
 def piece_keys(ids, e2w=None, start=None, transpose=False, device=None):
     """(keys, klen): the (N, S) int32 device tensor of uint32 keys and the (N) int32 key counts of (N, S, 8) ids (integer or
     integer-valued float arrays or device tensors; every id is checked against its head's size as the set metrics check it), S <= 4096.
     start: the first row that counts, one number or one per piece. transpose: interval keys, which a transposed copy keeps."""
-    tab = _tables(e2w)
-    a = metrics._host_ids(ids, tab.layout)
-    if a.shape[1] > ops.RUNS_MAX_S:
-        raise PBError('novelty: pieces of %d rows; the kernels take 1 .. %d' % (a.shape[1], ops.RUNS_MAX_S))
-    dev = torch.device(device) if device is not None else ids.device if torch.is_tensor(ids) else torch.device('cuda', torch.cuda.current_device())
-    s = metrics._host_start(start, a.shape[0])
-    up = lambda x: torch.from_numpy(x).to(dev)
-    return ops.piece_keys(up(a.astype(np.int16)), up(tab.pitch_of), start=None if s is None else up(s), layout=tab.layout, mode=int(bool(transpose)))
+    return ops.piece_keys(mode=int(bool(transpose)), **pieces.upload(ids, pieces.tables(e2w), start, device, max_S=ops.RUNS_MAX_S))
 
 
 def shared_runs(keys_a, klen_a, keys_b, klen_b, min_run=8, exclude_self=False, chunk=4096, want_matrix=False):
@@ -134,18 +123,6 @@ def split_best(best):
     return longest, nearest
 
 
-class _Timer(metrics._Timer):
-    stages = STAGES
-
-    def totals(self):
-        torch.cuda.synchronize()
-        ms = OrderedDict((stage, 0.0) for stage in self.stages)
-        for stage, a, b in self.pairs:
-            ms[stage] += a.elapsed_time(b)
-        ms['total'] = sum(ms.values())
-        return ms
-
-
 def _align_params(align):
     """None, or the four parameters of local_alignments as an ordered dict: True = the defaults, a dict overrides some of them."""
     if align is None or align is False:
@@ -172,18 +149,17 @@ def compare_to_corpus(gen_ids, corpus_ids, e2w=None, start=None, min_run=8, tran
     (the share of its keys inside aligned regions of at least min_score, edited keys included) and `align_span` (the keys of the longest
     such region); set lines align_score_mean / _median / _max, align_coverage_mean, share_half_aligned, share_with_alignment
     (align_score >= min_score); device_ms['align']; with want_matrix `align_matrix`, the (N, M) scores."""
-    tab = _tables(e2w)
+    tab = pieces.tables(e2w)
     par = _align_params(align)
     s_gen, s_cor = start if isinstance(start, tuple) else (start, start)
     for ids in (gen_ids, corpus_ids):
         if torch.is_tensor(ids):
             ops._p(ids)                               # a host tensor is refused before the first device call
-    timer = _Timer()
+    timer = pieces.Timer(STAGES + (('align',) if par is not None else ()))
     ka, la = timer.run('keys', piece_keys, gen_ids, tab, s_gen, transpose)
     kb, lb = (ka, la) if exclude_self else timer.run('keys', piece_keys, corpus_ids, tab, s_cor, transpose, ka.device)
     R, run_end, best = timer.run('runs', shared_runs, ka, la, kb, lb, min_run, exclude_self, chunk, want_matrix)
     if par is not None:
-        timer.stages = STAGES + ('align',)
         al_score, al_end, al_best = timer.run('align', local_alignments, ka, la, kb, lb, par['match'], par['mismatch'], par['gap'], par['min_score'],
                                               exclude_self, chunk, want_matrix)
     ms = timer.totals()

@@ -419,25 +419,35 @@ def _dense(t, dtype, dim, what):
     return _p(t)
 
 
+def _pieces(who, max_S, ids16, pitch_of, start, layout):
+    """The arguments the four piece_* wrappers share, checked: (ids16, start, pad8, pitch_of) as the entries take them, then N and S.
+    who: the wrapper's name; max_S: its largest S (None: no limit of its own)."""
+    layout = layout or DEFAULT_LAYOUT
+    p_ids = _dense(ids16, torch.int16, 3, who + ': ids16')
+    N, S = ids16.shape[0], ids16.shape[1]
+    if ids16.shape[2] != 8 or S < 1 or (max_S is not None and S > max_S):
+        raise PBError('%s: ids16 must be (N, S, 8) with %s (got %s)' % (who, 'S >= 1' if max_S is None else '1 <= S <= %d' % max_S, tuple(ids16.shape)))
+    p_pitch = _dense(pitch_of, torch.int16, 1, who + ': pitch_of')
+    if pitch_of.numel() != layout.pad8[3]:
+        raise PBError('%s: pitch_of holds %d entries, the layout has %d pitch ids' % (who, pitch_of.numel(), layout.pad8[3]))
+    p_start = None
+    if start is not None:
+        p_start = _dense(start, torch.int32, 1, who + ': start')
+        if start.numel() != N:
+            raise PBError('%s: start holds %d entries for %d pieces' % (who, start.numel(), N))
+    return (p_ids, p_start, seg_array(layout.pad8), p_pitch), N, S
+
+
 def piece_features(ids16, pitch_of, dur_pos, start=None, layout=None):
     """pb_piece_features: the (N, 288) int32 feature rows of ids16 (N, S, 8) int16. pitch_of (int16, layout.pad8[3] entries: the MIDI number
     of a pitch id, -1 = percussion) and dur_pos (int32, layout.pad8[4] entries) are device tables; start (N) int32 or None = 0."""
-    layout = layout or DEFAULT_LAYOUT
-    p_ids = _dense(ids16, torch.int16, 3, 'piece_features: ids16')
-    if ids16.shape[2] != 8 or ids16.shape[1] < 1:
-        raise PBError('piece_features: ids16 must be (N, S, 8) with S >= 1 (got %s)' % (tuple(ids16.shape),))
-    N, S = ids16.shape[0], ids16.shape[1]
-    p_pitch, p_dur = _dense(pitch_of, torch.int16, 1, 'piece_features: pitch_of'), _dense(dur_pos, torch.int32, 1, 'piece_features: dur_pos')
-    if pitch_of.numel() != layout.pad8[3] or dur_pos.numel() != layout.pad8[4]:
-        raise PBError('piece_features: pitch_of / dur_pos hold %d / %d entries, the layout has %d pitch and %d duration ids'
-                      % (pitch_of.numel(), dur_pos.numel(), layout.pad8[3], layout.pad8[4]))
-    p_start = None
-    if start is not None:
-        p_start = _dense(start, torch.int32, 1, 'piece_features: start')
-        if start.numel() != N:
-            raise PBError('piece_features: start holds %d entries for %d pieces' % (start.numel(), N))
+    shared, N, S = _pieces('piece_features', None, ids16, pitch_of, start, layout)
+    p_dur = _dense(dur_pos, torch.int32, 1, 'piece_features: dur_pos')
+    n_dur = (layout or DEFAULT_LAYOUT).pad8[4]
+    if dur_pos.numel() != n_dur:
+        raise PBError('piece_features: dur_pos holds %d entries, the layout has %d duration ids' % (dur_pos.numel(), n_dur))
     feat = torch.empty((N, FEATURE_COLS), dtype=torch.int32, device=ids16.device)
-    LIB.call('pb_piece_features', p_ids, p_start, seg_array(layout.pad8), p_pitch, p_dur, _p(feat), N, S, _stream())
+    LIB.call('pb_piece_features', *shared, p_dur, _p(feat), N, S, _stream())
     return feat
 
 
@@ -495,24 +505,12 @@ assert HEAD_MAX == 1088                                     # the key's interval
 def piece_keys(ids16, pitch_of, start=None, layout=None, mode=0):
     """pb_piece_keys: (keys (N, S) int32 holding the uint32 keys, klen (N) int32) of ids16 (N, S, 8) int16, S <= 4096. mode 0 = exact pitch,
     1 = interval to the note before. pitch_of and start as in piece_features. Key rows behind klen hold NO_KEY (-1 as int32)."""
-    layout = layout or DEFAULT_LAYOUT
-    p_ids = _dense(ids16, torch.int16, 3, 'piece_keys: ids16')
-    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
-        raise PBError('piece_keys: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    shared, N, S = _pieces('piece_keys', RUNS_MAX_S, ids16, pitch_of, start, layout)
     if mode not in (0, 1):
         raise PBError('piece_keys: mode = %r (0 = exact, 1 = interval)' % (mode,))
-    N, S = ids16.shape[0], ids16.shape[1]
-    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_keys: pitch_of')
-    if pitch_of.numel() != layout.pad8[3]:
-        raise PBError('piece_keys: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
-    p_start = None
-    if start is not None:
-        p_start = _dense(start, torch.int32, 1, 'piece_keys: start')
-        if start.numel() != N:
-            raise PBError('piece_keys: start holds %d entries for %d pieces' % (start.numel(), N))
     keys = torch.empty((N, S), dtype=torch.int32, device=ids16.device)
     klen = torch.empty((N,), dtype=torch.int32, device=ids16.device)
-    LIB.call('pb_piece_keys', p_ids, p_start, seg_array(layout.pad8), p_pitch, _p(keys), _p(klen), N, S, int(mode), _stream())
+    LIB.call('pb_piece_keys', *shared, _p(keys), _p(klen), N, S, int(mode), _stream())
     return keys, klen
 
 
@@ -599,25 +597,13 @@ STRUCTURE_COLS = 8 + 4 * STRUCTURE_LAGS                     # its row: 8 scalar 
 def piece_structure(ids16, pitch_of, start=None, layout=None, mode=0):
     """pb_piece_structure: the (N, 264) int32 lag sums of ids16 (N, S, 8) int16, S <= 4096. mode 0 = exact pitch, 1 = pitch class.
     pitch_of and start as in piece_features."""
-    layout = layout or DEFAULT_LAYOUT
-    p_ids = _dense(ids16, torch.int16, 3, 'piece_structure: ids16')
-    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
-        raise PBError('piece_structure: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    shared, N, S = _pieces('piece_structure', RUNS_MAX_S, ids16, pitch_of, start, layout)
     if mode not in (0, 1):
         raise PBError('piece_structure: mode = %r (0 = exact pitch, 1 = pitch class)' % (mode,))
     assert LIB.query('pb_structure_lags') == STRUCTURE_LAGS and LIB.query('pb_structure_cols') == STRUCTURE_COLS, \
         'ops.STRUCTURE_LAGS / STRUCTURE_COLS and the library disagree'
-    N, S = ids16.shape[0], ids16.shape[1]
-    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_structure: pitch_of')
-    if pitch_of.numel() != layout.pad8[3]:
-        raise PBError('piece_structure: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
-    p_start = None
-    if start is not None:
-        p_start = _dense(start, torch.int32, 1, 'piece_structure: start')
-        if start.numel() != N:
-            raise PBError('piece_structure: start holds %d entries for %d pieces' % (start.numel(), N))
     out = torch.empty((N, STRUCTURE_COLS), dtype=torch.int32, device=ids16.device)
-    LIB.call('pb_piece_structure', p_ids, p_start, seg_array(layout.pad8), p_pitch, _p(out), N, S, int(mode), _stream())
+    LIB.call('pb_piece_structure', *shared, _p(out), N, S, int(mode), _stream())
     return out
 
 
@@ -645,28 +631,16 @@ def harmony_table(device=None):
 def piece_harmony(ids16, pitch_of, start=None, layout=None, table=None):
     """pb_piece_harmony: the (N, 228) int64 harmony columns of ids16 (N, S, 8) int16, S <= 4096. pitch_of and start as in piece_features.
     table: harmony_table() on the device of ids16 (the default: that device's cached copy)."""
-    layout = layout or DEFAULT_LAYOUT
-    p_ids = _dense(ids16, torch.int16, 3, 'piece_harmony: ids16')
-    if ids16.shape[2] != 8 or not 1 <= ids16.shape[1] <= RUNS_MAX_S:
-        raise PBError('piece_harmony: ids16 must be (N, S, 8) with 1 <= S <= %d (got %s)' % (RUNS_MAX_S, tuple(ids16.shape)))
+    shared, N, S = _pieces('piece_harmony', RUNS_MAX_S, ids16, pitch_of, start, layout)
     assert LIB.query('pb_harmony_lags') == HARMONY_LAGS and LIB.query('pb_harmony_cols') == HARMONY_COLS, \
         'ops.HARMONY_LAGS / HARMONY_COLS and the library disagree'
-    N, S = ids16.shape[0], ids16.shape[1]
-    p_pitch = _dense(pitch_of, torch.int16, 1, 'piece_harmony: pitch_of')
-    if pitch_of.numel() != layout.pad8[3]:
-        raise PBError('piece_harmony: pitch_of holds %d entries, the layout has %d pitch ids' % (pitch_of.numel(), layout.pad8[3]))
     if table is None:
         table = harmony_table(ids16.device)
     p_table = _dense(table, torch.int64, 1, 'piece_harmony: table')
     if table.numel() != RUNS_MAX_S + 1:
         raise PBError('piece_harmony: table holds %d entries; harmony_table() has %d' % (table.numel(), RUNS_MAX_S + 1))
-    p_start = None
-    if start is not None:
-        p_start = _dense(start, torch.int32, 1, 'piece_harmony: start')
-        if start.numel() != N:
-            raise PBError('piece_harmony: start holds %d entries for %d pieces' % (start.numel(), N))
     out = torch.empty((N, HARMONY_COLS), dtype=torch.int64, device=ids16.device)
-    LIB.call('pb_piece_harmony', p_ids, p_start, seg_array(layout.pad8), p_pitch, p_table, _p(out), N, S, _stream())
+    LIB.call('pb_piece_harmony', *shared, p_table, _p(out), N, S, _stream())
     return out
 
 

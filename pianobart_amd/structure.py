@@ -6,12 +6,14 @@ pairs a lag apart. The definition is this project's own, in the f
 The lag sums (pb_piece_structure) run in pb_structure.hip, the set comparison in the kernels of pianobart_amd.metrics; the host divides
 integer columns. There is no CPU path."""
 from collections import OrderedDict
+from functools import partial
 
 import numpy as np
 import torch
 
-from . import metrics, ops
+from . import metrics, ops, pieces
 from ._lib import PBError
+from .pieces import bar_spans
 
 LAGS, COLS = ops.STRUCTURE_LAGS, ops.STRUCTURE_COLS
 C_IO, C_TO, C_IN, C_TN = 8, 8 + LAGS, 8 + 2 * LAGS, 8 + 3 * LAGS
@@ -19,39 +21,15 @@ GROUPS = ('groove_profile', 'repeat_profile', 'groove_mean', 'repeat_mean', 'rep
 SCALAR_GROUPS = GROUPS[2:]
 
 
-def _upload(ids, tab, start, device, pitch_class):
-    """The checked arguments of ops.piece_structure on the device."""
-    a = metrics._host_ids(ids, tab.layout)
-    dev = torch.device(device) if device is not None else ids.device if torch.is_tensor(ids) else torch.device('cuda', torch.cuda.current_device())
-    s = metrics._host_start(start, a.shape[0])
-    up = lambda x: torch.from_numpy(x).to(dev)
-    return (up(a.astype(np.int16)), up(tab.pitch_of)), dict(start=None if s is None else up(s), layout=tab.layout, mode=int(bool(pitch_class)))
-
-
-def _tables(e2w):
-    return e2w if isinstance(e2w, metrics.Tables) else metrics.tables(e2w)
+def _op(pitch_class):
+    return partial(ops.piece_structure, mode=int(bool(pitch_class)))
 
 
 def piece_structure(ids, e2w=None, start=None, device=None, pitch_class=False):
     """The (N, 264) int32 device tensor of pb_piece_structure for (N, S, 8) ids, S <= 4096: integer or integer-valued float arrays or device
     tensors, checked as metrics.piece_features checks them. start: the first row that counts, one number or one per piece. e2w: a
     dictionary, None (the default one) or metrics.tables(). pitch_class: a note is (position, pitch class), percussion stays itself."""
-    args, kw = _upload(ids, _tables(e2w), start, device, pitch_class)
-    return ops.piece_structure(*args, **kw)
-
-
-def bar_spans(ids, layout=None, start=None):
-    """Host: W of every piece of an (N, S, 8) integer array, the largest minus the smallest bar id of its notes plus one (0 without a note)."""
-    layout = layout or ops.DEFAULT_LAYOUT
-    a = np.asarray(ids)
-    special = (a >= np.asarray(layout.pad8)).any(-1)
-    L = np.where(special.any(1), special.argmax(1), a.shape[1])
-    s = np.zeros(a.shape[0], dtype=np.int64) if start is None else metrics._host_start(start, a.shape[0])
-    r = np.arange(a.shape[1])
-    live = (r >= np.asarray(s)[:, None]) & (r < L[:, None])
-    bars = a[:, :, 0].astype(np.int64)
-    hi, lo = np.where(live, bars, -1).max(1), np.where(live, bars, 1 << 40).min(1)
-    return np.where(live.any(1), hi - lo + 1, 0)
+    return _op(pitch_class)(**pieces.upload(ids, pieces.tables(e2w), start, device))
 
 
 def _columns(cols):
@@ -118,14 +96,8 @@ def describe_set(ids, e2w=None, lags=16, start=None, device=None, pitch_class=Fa
     """One set alone: {'n', 'short', 'device_ms', 'profile' (pooled_profiles), 'means'}: means = the mean over the n pieces of W >= 2 of the
     scalar groups of structure_groups (nan when n = 0)."""
     lags = _check_lags(lags)
-    args, kw = _upload(ids, _tables(e2w), start, device, pitch_class)
-    timer = metrics._Timer('structure')
-    cols = timer.run('structure', ops.piece_structure, *args, **kw)
-    ms = timer.totals()
-    g, short = structure_groups(cols, lags)
-    n = len(g['groove_mean'])
-    means = OrderedDict((k, float(g[k].astype(np.float64).mean()) if n else float('nan')) for k in SCALAR_GROUPS)
-    return OrderedDict([('n', n), ('short', short), ('device_ms', ms), ('profile', pooled_profiles(cols)), ('means', means)])
+    return metrics.describe_pieces('structure', _op(pitch_class), lambda c: structure_groups(c, lags), SCALAR_GROUPS, pooled_profiles, ids,
+                                   pieces.tables(e2w), start, device)
 
 
 def compare_structure(gen_ids, ref_ids, e2w=None, lags=16, grid=1024, start=None, device=None, pitch_class=False):
@@ -133,23 +105,6 @@ def compare_structure(gen_ids, ref_ids, e2w=None, lags=16, grid=1024, start=None
     structure_groups (over the pieces of W >= 2) the record of metrics.compare_sets: mean_* and std_* (of the row norm for the two
     profile groups), dist_gen / dist_ref / dist_inter, kl, oa, kl_gen, oa_gen, with the same degenerate rule. start: one value or a
     (gen, ref) pair. Returns {'n_gen', 'n_ref', 'short_gen', 'short_ref', 'device_ms', 'profile_gen', 'profile_ref', 'groups'}."""
-    G = int(grid)
-    if not 2 <= G <= 4096:
-        raise PBError('compare_structure: grid = %r points; 2 .. 4096' % (grid,))
     lags = _check_lags(lags)
-    tab = _tables(e2w)
-    s_gen, s_ref = start if isinstance(start, tuple) else (start, start)
-    timer = metrics._Timer('structure')
-    cols = []
-    for ids, s in ((gen_ids, s_gen), (ref_ids, s_ref)):
-        args, kw = _upload(ids, tab, s, device, pitch_class)
-        cols.append(timer.run('structure', ops.piece_structure, *args, **kw))
-    c_gen, c_ref = cols
-    dev = c_gen.device
-    g_gen, short_gen = structure_groups(c_gen, lags)
-    g_ref, short_ref = structure_groups(c_ref, lags)
-    n_gen, n_ref = len(g_gen['groove_mean']), len(g_ref['groove_mean'])
-    ws = ops.metrics_ws(max(n_gen, n_ref, 1), max(n_gen, n_ref, 1), G, dev)
-    groups = OrderedDict((name, metrics.compare_group(g_gen[name].reshape(n_gen, -1), g_ref[name].reshape(n_ref, -1), G, ws, timer, dev)) for name in GROUPS)
-    return OrderedDict([('n_gen', n_gen), ('n_ref', n_ref), ('short_gen', short_gen), ('short_ref', short_ref), ('device_ms', timer.totals()),
-                        ('profile_gen', pooled_profiles(c_gen)), ('profile_ref', pooled_profiles(c_ref)), ('groups', groups)])
+    return metrics.compare_pieces('compare_structure', 'structure', _op(pitch_class), lambda c: structure_groups(c, lags), GROUPS, gen_ids, ref_ids,
+                                  pieces.tables(e2w), grid, start, device, profile=pooled_profiles)
