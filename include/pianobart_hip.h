@@ -500,6 +500,30 @@ int pb_harmony_cols(void);
 int pb_piece_harmony(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int64_t* table,
                      int64_t* out, int32_t N, int32_t S, void* stream);
 
+/* ---- K24: texture of a piece (pb_texture.hip; additions to ABI 10) ----------------------------------------------------------------------
+ * How many pitches sound at once, in absolute time: the device half of pianobart_amd.texture. Integers and integer sums
+ * only: equal inputs give equal bytes, and a permutation of a piece's note rows gives the same row. The arguments are checked before
+ * the first HIP call (-2, pb_last_error names the field).
+ *
+ * pb_piece_texture: out (N, 64) int32 from ids16 (N, S, 8) int16, 16-byte aligned, 1 <= S <= 4096. The notes of a piece, start, pad8,
+ *   pitch_of and dur_pos are those of pb_piece_features; bar ids, b_lo and W those of pb_piece_structure. bar_pos: device int32
+ *   (pad8[6]), the positions of a bar of a time-signature id; the kernel clamps it to 1 .. 1024 and a duration to 1 .. 4096. Bar index
+ *   b = bar id - b_lo; ts(b) = the time-signature id (head 6) of the note row of bar b with the smallest (position id, time-signature
+ *   id), of bar b - 1 for a bar without a note; len(b) = bar_pos[ts(b)]; B(b) = the sum of len over the bars before b. A pitched note
+ *   (k = pitch_of[id of head 3] >= 0) has its onset t = B(b) + position id, its length d = max(dur_pos[id of head 4], 1) and its end
+ *   e = t + d. Pitch k sounds at step tau if one of its notes has t <= tau < e; c(tau) = the number of pitches that sound.
+ *   Columns: 0 notes, 1 pitched notes P, 2 W; with P = 0 the others are 0. 3 T = max e - min t, 4 / 5 the steps of [min t, max e) with
+ *   c >= 1 / c >= 2, 6 A = the sum of c over the steps, 7 max c, 8 D = the sum of d, 9 X = the distinct (k, t) for which a note of the
+ *   same k has t' < t < e', 10 Y = P - G, 11 O = distinct t, 12 notes with e > B(b) + len(b) of their own bar, 13 notes with position
+ *   id >= len(b), 14 G = distinct (k, t), 15 zero, 16..32 the steps with c = 0, 1, .., 15, >= 16 (sum T), 33..41 the onsets at which
+ *   1, .., 8, >= 9 distinct k start (sum O), 42..57 the gaps g between consecutive distinct onsets by min(floor(log2 g), 15)
+ *   (sum O - 1), 58..63 zero. One workgroup per piece, a workgroup sweeping over several pieces when they are short or many (at most
+ *   1024 workgroups). N = 0 is no error.
+ * pb_texture_cols: 64. */
+int pb_texture_cols(void);
+int pb_piece_texture(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int32_t* dur_pos,
+                     const int32_t* bar_pos, int32_t* out, int32_t N, int32_t S, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

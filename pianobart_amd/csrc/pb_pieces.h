@@ -1,5 +1,5 @@
 // The front end of the kernels that read pieces as (N, S, 8) int16 id rows (pb_piece_features, pb_piece_keys, pb_piece_structure,
-// pb_piece_harmony): which rows of a piece are its notes, and the entry checks and launch grid that go with them.
+// pb_piece_harmony, pb_piece_texture): which rows of a piece are its notes, and the entry checks and launch grid that go with them.
 //   A row is one 16-byte word of eight unsigned 16-bit ids. A piece ends at L, its first row with a special id (>= pad8[h]) in any
 //   head (S if none); its notes are the rows first .. L - 1 with first = max(start[piece], 0), or 0 without start.
 #pragma once

@@ -11,7 +11,7 @@ One line per feature group is printed: the feature's mean in both sets, the mean
 the intra-reference from the inter-set distances and their overlapped area (1 = the sets are told apart by nothing this feature sees).
 The reference's "FAD" lines of finetune_generation stay n/a: they need the third-party `shapesimilarity`, and this is another measure.
 
-This module also holds what the four eval_* tools (metrics, novelty, structure, harmony) share: their common arguments and refusals, the
+This module also holds what the five eval_* tools (metrics, novelty, structure, harmony, texture) share: their common arguments and refusals, the
 loading of pieces, the checks on a loaded set, the line of a compared group and the JSON writer."""
 import argparse
 import json

@@ -420,7 +420,7 @@ def _dense(t, dtype, dim, what):
 
 
 def _pieces(who, max_S, ids16, pitch_of, start, layout):
-    """The arguments the four piece_* wrappers share, checked: (ids16, start, pad8, pitch_of) as the entries take them, then N and S.
+    """The arguments the five piece_* wrappers share, checked: (ids16, start, pad8, pitch_of) as the entries take them, then N and S.
     who: the wrapper's name; max_S: its largest S (None: no limit of its own)."""
     layout = layout or DEFAULT_LAYOUT
     p_ids = _dense(ids16, torch.int16, 3, who + ': ids16')
@@ -641,6 +641,25 @@ def piece_harmony(ids16, pitch_of, start=None, layout=None, table=None):
         raise PBError('piece_harmony: table holds %d entries; harmony_table() has %d' % (table.numel(), RUNS_MAX_S + 1))
     out = torch.empty((N, HARMONY_COLS), dtype=torch.int64, device=ids16.device)
     LIB.call('pb_piece_harmony', *shared, p_table, _p(out), N, S, _stream())
+    return out
+
+
+TEXTURE_COLS = 64                                           # the row of pb_piece_texture (pb_texture_cols)
+
+
+def piece_texture(ids16, pitch_of, dur_pos, bar_pos, start=None, layout=None):
+    """pb_piece_texture: the (N, 64) int32 texture columns of ids16 (N, S, 8) int16, S <= 4096. pitch_of, dur_pos and start as in
+    piece_features; bar_pos (int32, layout.pad8[6] entries: the positions of a bar of a time-signature id) is a device table."""
+    shared, N, S = _pieces('piece_texture', RUNS_MAX_S, ids16, pitch_of, start, layout)
+    assert LIB.query('pb_texture_cols') == TEXTURE_COLS, 'ops.TEXTURE_COLS and the library disagree'
+    p_dur, p_bar = _dense(dur_pos, torch.int32, 1, 'piece_texture: dur_pos'), _dense(bar_pos, torch.int32, 1, 'piece_texture: bar_pos')
+    pad8 = (layout or DEFAULT_LAYOUT).pad8
+    if dur_pos.numel() != pad8[4]:
+        raise PBError('piece_texture: dur_pos holds %d entries, the layout has %d duration ids' % (dur_pos.numel(), pad8[4]))
+    if bar_pos.numel() != pad8[6]:
+        raise PBError('piece_texture: bar_pos holds %d entries, the layout has %d time-signature ids' % (bar_pos.numel(), pad8[6]))
+    out = torch.empty((N, TEXTURE_COLS), dtype=torch.int32, device=ids16.device)
+    LIB.call('pb_piece_texture', *shared, p_dur, p_bar, _p(out), N, S, _stream())
     return out
 
 

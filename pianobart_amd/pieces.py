@@ -1,4 +1,4 @@
-"""The host front end of the evaluation families (metrics, novelty, structure, harmony): what they all do with a set of pieces before a
+"""The host front end of the evaluation families (metrics, novelty, structure, harmony, texture): what they all do with a set of pieces before a
 kernel sees it. The tables of a dictionary, the checks of an (N, S, 8) id array and of `start`, the upload, the host
 statement of which rows of a piece are its notes, and the stage timer. csrc/pb_pieces.h is the device half of the same rules."""
 import json
@@ -15,8 +15,9 @@ from .octuple_midi import code_to_dur
 
 VOCAB = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'octuple_vocab.json')
 MAX_PITCH = ops.HEAD_MAX - 1                  # the kernel's pitch bitmap covers 0 .. HEAD_MAX - 1
+MAX_BAR_POS = 1024                            # the positions of a bar at most: a position id is a 10-bit field of the bar keys
 
-Tables = namedtuple('Tables', 'pitch_of dur_pos layout')
+Tables = namedtuple('Tables', 'pitch_of dur_pos layout bar_pos')
 
 
 def _words_by_id(e2w, name, n):
@@ -29,10 +30,12 @@ def _words_by_id(e2w, name, n):
 
 
 def tables(e2w=None):
-    """Tables(pitch_of, dur_pos, layout) of a dictionary's event -> word half (None: the default dictionary; a Tables is returned as it
-    is): pitch_of[id] = k for the word 'Pitch k' and -1 for 'Pitch percussion k' (int16, one entry per ordinary pitch id); dur_pos[id] =
-    octuple_midi.code_to_dur(c) for the word 'Duration c' (int32, one entry per ordinary duration id). A word of another form is a PBError
-    that names it."""
+    """Tables(pitch_of, dur_pos, layout, bar_pos) of a dictionary's event -> word half (None: the default dictionary; a Tables is returned
+    as it is): pitch_of[id] = k for the word 'Pitch k' and -1 for 'Pitch percussion k' (int16, one entry per ordinary pitch id); dur_pos[id] =
+    octuple_midi.code_to_dur(c) for the word 'Duration c' (int32, one entry per ordinary duration id). A pitch or duration word of another
+    form is a PBError that names it. bar_pos[id] = n * 64 // d, the positions of a bar (octuple_midi.bar_length: 16 per beat), for the
+    word 'TimeSig n/d' (int32, one entry per ordinary time-signature id), and 0 for a word of another form or a length outside 1 .. 1024:
+    only the texture family needs bar lengths, and it refuses a table that holds a 0."""
     if isinstance(e2w, Tables):
         return e2w
     if e2w is None:
@@ -53,7 +56,12 @@ def tables(e2w=None):
         if not m:
             raise PBError("pieces: duration word %r (id %d) is not 'Duration c'" % (w, i))
         dur_pos[i] = code_to_dur(int(m.group(1)))
-    return Tables(pitch_of, dur_pos, layout)
+    bar_pos = np.zeros(layout.pad8[6], dtype=np.int32)
+    for i, w in enumerate(_words_by_id(e2w, 'TimeSig', layout.pad8[6])):
+        m = re.fullmatch(r'TimeSig (\d+)/(\d+)', w)
+        if m and int(m.group(2)) > 0 and 1 <= int(m.group(1)) * 64 // int(m.group(2)) <= MAX_BAR_POS:
+            bar_pos[i] = int(m.group(1)) * 64 // int(m.group(2))
+    return Tables(pitch_of, dur_pos, layout, bar_pos)
 
 
 def host_ids(ids, layout):
