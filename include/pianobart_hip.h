@@ -378,6 +378,44 @@ int pb_merge_kth_abs(const float* x, const float* base, int64_t n, int64_t k, fl
 int pb_merge_sign_tally(const pb_merge_desc* d, void* stream);
 int pb_merge_apply(const pb_merge_desc* d, void* stream);
 
+/* ---- K25: Fisher merging (pb_fisher.hip; additions to ABI 10) ------------------------------------------------------------
+ * The reference's fisher_merging (model_merging_methods/merging_methods.py:82-264): fine-tuned weights averaged element by element,
+ * each model weighted by the diagonal of its own task's empirical Fisher information. Float32, every operation rounded once in the
+ * order DESIGN.md 9 writes it (the file is compiled without contraction). No float atomics: equal inputs give equal bytes. Every entry
+ * checks its arguments before the first HIP call (-2, pb_last_error names the field). Pointers need 4-byte alignment only (segments of
+ * a flat buffer): 16-byte accesses for the body, scalar head and tail; pointers of one call that are offset differently from a
+ * 16-byte boundary go scalar throughout.
+ *
+ * pb_fisher_rows: per row of logits (rows, C), C >= 1, with p = softmax(logits[row]): e_out[row] = sum_c sqrt(p_c) log p_c (log p = z -
+ *   logsumexp; a class whose p underflows to 0 adds 0). dlogits != NULL: dlogits[row][j] = weight[row] (sqrt(p_j) - p_j sum_c sqrt(p_c)),
+ *   the gradient of e_out[row] with sqrt(p) held constant, as the reference detaches it; weight NULL = 1, weight 0 = a row of zeros.
+ *   One wave per row, 4 rows per workgroup.
+ * pb_fisher_accum: F[i] = F[i] + g[i] * g[i], i < n (a product and a sum, each rounded): one streaming pass per batch over the engine's
+ *   flat gradient buffer.
+ * pb_fisher_finish: F[i] = F[i] / float(divisor), an IEEE division (1 <= divisor <= 2^24: the examples computed); *flags |= 1 where a
+ *   result is not finite (the caller zeroes and reads the word).
+ * pb_fisher_norm: *norm_out = float32(sqrt(sum_i F[i]^2)), the sum in float64: per-workgroup partial sums in fixed slots of ws
+ *   (pb_fisher_norm_ws_bytes() bytes, 8-byte aligned), folded by one workgroup. The order of the additions depends on n alone.
+ * pb_fisher_merge: with Fp_m = fisher[m] + minimal and k_m = coef[m] * Fp_m:
+ *     out[i] = (((0 + k_0 * model[0]) + k_1 * model[1]) + ...) / (((0 + k_0) + k_1) + ...)
+ *   in one fused pass: one 16-byte load per input vector and lane, one store. 2 <= n_models <= PB_MERGE_MAX_MODELS; coef[m] and
+ *   minimal positive and finite (then no denominator is 0); out may not alias an input. The descriptor starts zeroed. */
+typedef struct pb_fisher_desc {
+    float* out;
+    const float* model[PB_MERGE_MAX_MODELS];
+    const float* fisher[PB_MERGE_MAX_MODELS];
+    int64_t n;
+    float coef[PB_MERGE_MAX_MODELS];
+    float minimal; int32_t n_models;
+} pb_fisher_desc;
+int64_t pb_fisher_desc_bytes(void);
+int64_t pb_fisher_norm_ws_bytes(void);
+int pb_fisher_rows(const float* logits, const float* weight, float* e_out, float* dlogits, int64_t rows, int32_t C, void* stream);
+int pb_fisher_accum(float* F, const float* g, int64_t n, void* stream);
+int pb_fisher_finish(float* F, int64_t n, int64_t divisor, int32_t* flags, void* stream);
+int pb_fisher_norm(const float* F, int64_t n, void* ws, float* norm_out, void* stream);
+int pb_fisher_merge(const pb_fisher_desc* d, void* stream);
+
 /* ---- K19: set metrics for generated pieces (pb_metrics.hip; additions to ABI 10) ----------------------------------------
  * Per-piece musical features, pairwise feature distances, their moments and a Gaussian kernel density estimate: the device half of
  * pianobart_amd.metrics. Integer counts and fixed-order floating-point sums only: equal inputs give equal bytes.

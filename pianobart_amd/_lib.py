@@ -98,6 +98,12 @@ class MergeDesc(ctypes.Structure):
                 ('model_base', ctypes.c_int32), ('_pad', ctypes.c_int32)]
 
 
+class FisherDesc(ctypes.Structure):
+    """pb_fisher_desc (arrays again; tests/test_fisher_cpu.py compares the size with the compiler's)."""
+    _fields_ = [('out', ctypes.c_void_p), ('model', ctypes.c_void_p * MERGE_MAX_MODELS), ('fisher', ctypes.c_void_p * MERGE_MAX_MODELS),
+                ('n', ctypes.c_int64), ('coef', ctypes.c_float * MERGE_MAX_MODELS), ('minimal', ctypes.c_float), ('n_models', ctypes.c_int32)]
+
+
 def parse_header(path=HEADER):
     """Returns {name: (restype, [argtypes])} for every function the header declares."""
     src = re.sub(r'typedef\s+struct.*?}\s*\w+\s*;', ' ', _header_source(path), flags=re.S)

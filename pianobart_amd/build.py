@@ -19,8 +19,8 @@ FLAGS = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-ffp-contract=
 
 # flags of single sources, after FLAGS (the last -ffp-contract wins). pb_merge.hip: bit parity with the reference's CPU tensors needs every float32
 # operation rounded on its own; under -ffp-contract=fast the backend fuses a * b + c whatever the source says (`#pragma clang fp contract(off)` does not
-# reach it, and clang's __fmul_rn / __fadd_rn are plain operators)
-FILE_FLAGS = {'pb_merge.hip': ['-ffp-contract=off']}
+# reach it, and clang's __fmul_rn / __fadd_rn are plain operators). pb_fisher.hip (Fisher merging) for the same reason.
+FILE_FLAGS = {'pb_merge.hip': ['-ffp-contract=off'], 'pb_fisher.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():

@@ -133,6 +133,26 @@ class HeadAdamW:
             p.grad = None
 
 
+def prepare_inputs(x, y, device, bar_pad_word, class_num, seq, error=False):
+    """A loader batch as the classifiers take it (finetune.py:187-199): (x, y, attn, keyword arguments of the model's forward). Shared by
+    FinetuneTrainer.iteration and merge.fisher_weights, so that Fisher weights see a model's inputs exactly as its training did."""
+    x, y = x.to(device).long(), y.to(device).long()
+    if error:
+        y = torch.squeeze(y, dim=-1)
+    attn = (x[:, :, 0] != bar_pad_word).float()
+    if seq:
+        return x, y, attn, dict(input_ids_encoder=x, encoder_attention_mask=attn)
+    if class_num >= 5:                                                   # velocity: labels shifted right, class_num = the pad label
+        y_shift = torch.zeros_like(y) + class_num
+        y_shift[:, 1:] = y[:, :-1]
+        attn_shift = torch.zeros_like(attn)
+        attn_shift[:, 1:] = attn[:, :-1]
+        attn_shift[:, 0] = attn[:, 0]
+    else:
+        y_shift, attn_shift = x, attn
+    return x, y, attn, dict(input_ids_encoder=x, input_ids_decoder=y_shift, encoder_attention_mask=attn, decoder_attention_mask=attn_shift)
+
+
 class FinetuneTrainer:
     def __init__(self, pianobart, train_dataloader, valid_dataloader, test_dataloader, lr, class_num, hs, testset_shape, cpu,
                  cuda_devices=None, model=None, SeqClass=False, error=False, weight=None, data_parallel=None):
@@ -230,22 +250,8 @@ class FinetuneTrainer:
         with torch.set_grad_enabled(mode == 0):
             for x, y in training_data:
                 batch = x.shape[0]
-                x, y = x.to(self.device).long(), y.to(self.device).long()
-                if self.error:
-                    y = torch.squeeze(y, dim=-1)
-                attn = (x[:, :, 0] != self.pianobart.bar_pad_word).float()
-                if seq:
-                    y_hat = self.model(input_ids_encoder=x, encoder_attention_mask=attn)
-                else:
-                    if self.class_num >= 5:                              # velocity: labels shifted right, class_num = the pad label
-                        y_shift = torch.zeros_like(y) + self.class_num
-                        y_shift[:, 1:] = y[:, :-1]
-                        attn_shift = torch.zeros_like(attn)
-                        attn_shift[:, 1:] = attn[:, :-1]
-                        attn_shift[:, 0] = attn[:, 0]
-                    else:
-                        y_shift, attn_shift = x, attn
-                    y_hat = self.model(input_ids_encoder=x, input_ids_decoder=y_shift, encoder_attention_mask=attn, decoder_attention_mask=attn_shift)
+                x, y, attn, inputs = prepare_inputs(x, y, self.device, self.pianobart.bar_pad_word, self.class_num, seq, self.error)
+                y_hat = self.model(**inputs)
                 output = torch.from_numpy(np.argmax(y_hat.detach().cpu().numpy(), axis=-1)).to(self.device)
                 if mode == 2:
                     all_output[cnt:cnt + batch] = output.cpu()

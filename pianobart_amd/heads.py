@@ -201,6 +201,40 @@ def cross_entropy_rows(logits, target):
     return _CEFn.apply(logits, target)
 
 
+class _FisherRowsFn(torch.autograd.Function):
+    """Per-row sum_c sqrt(p_c).detach() * log p_c, the objective whose squared gradient is the empirical Fisher diagonal
+    (merging_methods.py:225-230); the backward re-runs the row kernel with the incoming per-row gradient (times `weight`) as the row weight."""
+
+    @staticmethod
+    def forward(ctx, logits, weight):
+        lc = _f32c(logits).reshape(-1, logits.shape[-1])
+        wc = None if weight is None else _f32c(weight).reshape(-1)
+        e = torch.empty(lc.shape[0], dtype=torch.float32, device=lc.device)
+        ops.fisher_rows(lc, None, e, None)
+        ctx.save_for_backward(lc, wc)
+        ctx.shape = logits.shape
+        e = e.reshape(logits.shape[:-1])
+        return e if weight is None else e * wc.reshape(e.shape)
+
+    @staticmethod
+    def backward(ctx, de):
+        lc, wc = ctx.saved_tensors
+        g = torch.empty_like(lc)
+        tmp = torch.empty(lc.shape[0], dtype=torch.float32, device=lc.device)
+        w = _f32c(de).reshape(-1)
+        ops.fisher_rows(lc, w if wc is None else w * wc, tmp, g)
+        return g.reshape(ctx.shape), None
+
+
+def fisher_expectation_rows(logits, weight=None):
+    """logits (..., C) f32 -> (...): weight * sum_c sqrt(p_c).detach() * log_softmax(logits)_c per row; weight (...) (None = 1; a row of
+    weight 0 contributes exactly 0 and receives an all-zero gradient)."""
+    if weight is not None and tuple(weight.shape) != tuple(logits.shape[:-1]):
+        from ._lib import PBError
+        raise PBError('fisher_expectation_rows: weight %s must have the shape of logits without its last axis %s' % (tuple(weight.shape), tuple(logits.shape[:-1])))
+    return _FisherRowsFn.apply(logits, weight)
+
+
 class _GatherFn(torch.autograd.Function):
     """out (..., d) = table (n, d)[ids] + bias."""
 

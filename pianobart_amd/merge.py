@@ -6,7 +6,8 @@ Every model is packed into ONE flat f32 device vector in the order of the sorted
 the host keeps the segment table. PyTorch allocates and copies; all arithmetic on parameters runs in pb_merge.hip, float32,
 each operation rounded once in the reference's order, so a merge equals the reference's CPU result bit for bit wherever the reference
 is deterministic (everything but its torch.bernoulli masks, which are replaced by a counter-based stream of our own).
-fisher_merging and regmean_merging need trainers and data and are refused by name."""
+fisher_merging takes Fisher weights that fisher_weights() (python -m pianobart_amd.fisher) computes on the device from a fine-tuned model and its
+own training data (pb_fisher.hip); without them it is refused by name, as regmean_merging (per-layer Gram matrices and inverses) always is."""
 import re
 from collections import OrderedDict, namedtuple
 
@@ -18,13 +19,20 @@ from ._lib import (PBError, MERGE_AVERAGE, MERGE_DELTA, MERGE_FINETUNED, MERGE_M
                    MERGE_MAX_MODELS, MERGE_TASK, MERGE_TIES)
 
 METHODS = ('mask_merging', 'average_merging', 'task_arithmetic', 'ties_merging')
-NEEDS_TRAINERS = ('fisher_merging', 'regmean_merging')
+FISHER = 'fisher_merging'                                  # a method of its own inputs: one Fisher vector per model (fisher_weights)
+NEEDS_TRAINERS = (FISHER, 'regmean_merging')
 _APPLY = {'average_merging': MERGE_AVERAGE, 'task_arithmetic': MERGE_TASK, 'ties_merging': MERGE_TIES}
 
 Segment = namedtuple('Segment', 'name offset numel shape')
 
 
-def _check_method(name, what):
+def _check_method(name, what, fisher=False):
+    if name == FISHER and what == 'method':
+        if fisher:
+            return
+        raise PBError("method 'fisher_merging' needs one set of Fisher weights per fine-tuned model: compute each with merge.fisher_weights(model, "
+                      "batches, ..) or `python -m pianobart_amd.fisher --ckpt ft.ckpt --task .. --dataset .. --output ft.fisher.pt` on the model's own "
+                      "training data, then pass fisher_weights=[..] (model_merge: --fisher a.fisher.pt,b.fisher.pt)")
     if name in NEEDS_TRAINERS:
         raise PBError('%s %r needs the fine-tune trainers and their data (per-example gradients / layer inputs): not part of checkpoint merging '
                       'here. Choose one of %s' % (what, name, ', '.join(METHODS if what == 'method' else sorted(_APPLY))))
@@ -47,8 +55,9 @@ class MergePlan:
 
     def __init__(self, n_models, method='mask_merging', mask_apply_method='average_merging', mask_strategy='random', use_weight_rescale=True,
                  weight_format='delta_weight', weight_mask_rate=0.8, weight_mask_rates=None, scaling_coefficient=1.0, param_value_mask_rate=0.8,
-                 seed=0, exclude=()):
-        _check_method(method, 'method')
+                 seed=0, exclude=(), fisher_weights=None, fisher_scaling_coefficients=None, normalize_fisher_weight=True, minimal_fisher_weight=1e-6,
+                 fisher_norms=None):
+        _check_method(method, 'method', fisher=fisher_weights is not None)
         if method == 'mask_merging':
             _check_method(mask_apply_method, 'mask_apply_method')
             if mask_strategy not in ('random', 'magnitude'):
@@ -72,6 +81,58 @@ class MergePlan:
         self.rates, self.lam, self.ties_rate = rates, float(scaling_coefficient), float(param_value_mask_rate)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.exclude = [exclude] if isinstance(exclude, str) else list(exclude or ())
+        self.fisher = method == FISHER
+        if self.fisher:
+            self.fisher_weights = list(fisher_weights)
+            if len(self.fisher_weights) != n_models:
+                raise PBError('fisher_weights holds %d sets of Fisher weights for %d models' % (len(self.fisher_weights), n_models))
+            self.minimal = float(minimal_fisher_weight)
+            if not (self.minimal > 0.0 and np.isfinite(np.float32(self.minimal)) and np.float32(self.minimal) > 0):
+                raise PBError('minimal_fisher_weight must be positive and finite in float32 (got %r): it keeps every denominator above 0' % (minimal_fisher_weight,))
+            self.coefficients = None if fisher_scaling_coefficients is None else [float(c) for c in fisher_scaling_coefficients]
+            if self.coefficients is not None:
+                if len(self.coefficients) != n_models:
+                    raise PBError('fisher_scaling_coefficients names %d coefficients for %d models' % (len(self.coefficients), n_models))
+                if not all(c > 0.0 and np.isfinite(c) for c in self.coefficients):
+                    raise PBError('fisher_scaling_coefficients must be positive and finite (got %r)' % (self.coefficients,))
+            self.normalize = bool(normalize_fisher_weight)
+            self.norms = None if fisher_norms is None else [float(v) for v in fisher_norms]
+            if self.norms is not None and (len(self.norms) != n_models or not all(v >= 0.0 and np.isfinite(v) for v in self.norms)):
+                raise PBError('fisher_norms must hold one finite norm >= 0 per model (got %r for %d models)' % (self.norms, n_models))
+
+
+def torch_sum_f32(x):
+    """The float32 sum of at most 8 values as the reference's `tensor.sum()` takes it on the CPU (ATen's cascade sum, 8 float lanes): a row
+    of 8 is added lane by lane from +0, left to right; a shorter row goes through four interleaved partial sums p_k = x_k + x_(k+4) + ..,
+    then the elements behind the last whole group of 4 onto p_0, then (p_0 + p_1) + p_2 + p_3. Below 4 values that is left to right."""
+    x = np.asarray(x, dtype=np.float32)
+    assert x.ndim == 1 and x.size <= 8
+    if x.size == 8:
+        s = np.float32(0.0)
+        for v in x:
+            s = np.float32(s + v)
+        return s
+    q = x.size // 4
+    p = [np.float32(0.0)] * 4
+    for i in range(q):
+        for k in range(4):
+            p[k] = np.float32(p[k] + x[4 * i + k])
+    for v in x[4 * q:]:
+        p[0] = np.float32(p[0] + v)
+    for k in range(1, 4):
+        p[0] = np.float32(p[0] + p[k])
+    return p[0]
+
+
+def fisher_coefficients(n_models, coefficients=None, normalize=True, minimal=1e-6, norms=None):
+    """The N float32 coefficients c_m of a Fisher merge, formed as the reference forms them (merging_methods.py:160-167, 254-259):
+    ones(N) / N or the given list; with `normalize` times r_m / sum(r), r_m = 1 / (norm_m + minimal)."""
+    f32 = np.float32
+    c = np.ones(n_models, dtype=f32) / f32(n_models) if coefficients is None else np.asarray(coefficients, dtype=f32)
+    if normalize:
+        r = f32(1.0) / (np.asarray(norms, dtype=f32) + f32(minimal))
+        c = c * (r / torch_sum_f32(r))
+    return c.astype(f32)
 
 
 def segment_table(shapes):
@@ -84,14 +145,31 @@ def segment_table(shapes):
     return segs
 
 
-def merge_flat(plan, pre, models, segs):
-    """The merged flat vector (a new device tensor) of the flat f32 device vectors `pre` and `models` laid out by `segs`."""
+def merge_flat(plan, pre, models, segs, fishers=None):
+    """The merged flat vector (a new device tensor) of the flat f32 device vectors `pre` and `models` laid out by `segs`. A Fisher plan
+    also takes `fishers`: one flat Fisher vector per model in the same layout (`pre` then only gives the size)."""
     N, n, dev = len(models), pre.numel(), pre.device
     if N != plan.n_models:
         raise PBError('the plan was made for %d models, got %d' % (plan.n_models, N))
     if n != sum(s.numel for s in segs):
         raise PBError('the segment table covers %d elements, the vectors hold %d' % (sum(s.numel for s in segs), n))
     out = torch.empty_like(pre)
+    if plan.fisher:
+        if fishers is None or len(fishers) != N:
+            raise PBError('a fisher_merging plan takes one flat Fisher vector per model')
+        norms = plan.norms
+        if plan.normalize and norms is None:                                    # L2 norm of each model's whole Fisher vector, on the device
+            ws, dn = ops.fisher_norm_ws(dev), torch.empty(N, dtype=torch.float32, device=dev)
+            for m in range(N):
+                ops.fisher_norm(fishers[m], ws, dn[m:m + 1])
+            norms = dn.cpu().numpy()
+            if not np.isfinite(norms).all():
+                raise PBError('the norm of a Fisher vector is not finite: refusing to merge')
+        coef = fisher_coefficients(N, plan.coefficients, plan.normalize, plan.minimal, norms)
+        if not (np.isfinite(coef).all() and (coef > 0).all()):
+            raise PBError('the Fisher coefficients %r are not positive and finite (norms %r)' % (coef.tolist(), None if norms is None else list(norms)))
+        ops.fisher_merge(ops.fisher_desc(models, fishers, out, coef, np.float32(plan.minimal)))
+        return out
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = ops.merge_kth_ws(dev)
     fmt = MERGE_FINETUNED if plan.masked and plan.format == 'finetuned_weight' else MERGE_DELTA
@@ -197,10 +275,17 @@ def merge_state_dicts(pretrained_sd, finetuned_sds, method='mask_merging', devic
 
     Merged: every float32 tensor of `pretrained_sd` whose name no `exclude` regex matches (re.match, as the reference). Names that share
     storage in `pretrained_sd` (tied tables) are one parameter, as in the reference's named_parameters(). Excluded and non-float entries
-    come back as the pre-trained ones. Keyword arguments: see MergePlan."""
+    come back as the pre-trained ones. Keyword arguments: see MergePlan.
+
+    method='fisher_merging' takes fisher_weights=[{name: f32 tensor}, ..], one dict per model as fisher_weights() returns it, and
+    fisher_scaling_coefficients / normalize_fisher_weight / minimal_fisher_weight with the reference's meaning; fisher_norms=[..]
+    overrides the device's norms of the Fisher vectors. A merged parameter that no Fisher dict names (BART's never-read `shared`
+    table: its gradient is identically 0) has Fisher weight 0 and comes out as the coefficient-weighted mean."""
     finetuned_sds = list(finetuned_sds)
     plan = MergePlan(len(finetuned_sds), method=method, **kw)
     segs, alias = state_dict_layout(pretrained_sd, plan.exclude)
+    if plan.fisher:
+        check_fisher_dicts(plan.fisher_weights, pretrained_sd, segs, alias)
     for s in segs:
         for i, sd in enumerate(finetuned_sds):
             if s.name not in sd:
@@ -219,12 +304,134 @@ def merge_state_dicts(pretrained_sd, finetuned_sds, method='mask_merging', devic
         return flat
 
     host = [pack(pretrained_sd, 'the pre-trained model')] + [pack(sd, 'fine-tuned model %d' % i) for i, sd in enumerate(finetuned_sds)]
+    fhost = [pack_fisher(fw, segs, alias, n, i) for i, fw in enumerate(plan.fisher_weights)] if plan.fisher else None
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     flats = [torch.from_numpy(h).to(dev) for h in host]
-    merged = merge_flat(plan, flats[0], flats[1:], segs).cpu()
+    fishers = [torch.from_numpy(h).to(dev) for h in fhost] if plan.fisher else None
+    merged = merge_flat(plan, flats[0], flats[1:], segs, fishers).cpu()
     out = OrderedDict((k, v.detach().cpu().clone() if torch.is_tensor(v) else v) for k, v in pretrained_sd.items())
     for s in segs:
         t = merged[s.offset:s.offset + s.numel].reshape(s.shape).clone()
         for name in alias[s.name]:
             out[name] = t
     return out
+
+
+def _fisher_entry(fw, names):
+    for name in names:
+        if name in fw:
+            return fw[name]
+    return None
+
+
+def check_fisher_dicts(fisher_weights, pretrained_sd, segs, alias):
+    """Refuses, before any device work: a Fisher dict that is empty or names something the model does not hold, dicts that name different
+    parameters, and a shape or dtype that is not the parameter's."""
+    first = None
+    for i, fw in enumerate(fisher_weights):
+        if not isinstance(fw, dict) or not fw:
+            raise PBError('Fisher weights of model %d: expected a non-empty {name: tensor} dict' % i)
+        unknown = [k for k in fw if k not in pretrained_sd]
+        if unknown:
+            raise PBError('Fisher weights of model %d name %d parameters the model does not hold (first: %s)' % (i, len(unknown), unknown[0]))
+        covered = {s.name for s in segs if _fisher_entry(fw, alias[s.name]) is not None}     # by parameter: a tied table may come under any of its names
+        if first is None:
+            first = covered
+        elif covered != first:
+            raise PBError('Fisher weights of model %d and of model 0 name different parameters (first: %s)' % (i, sorted(covered ^ first)[0]))
+        for s in segs:
+            t = _fisher_entry(fw, alias[s.name])
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or tuple(t.shape) != s.shape or t.dtype != torch.float32:
+                raise PBError('Fisher weights of model %d: %s is %s %s, the parameter %s float32' % (
+                    i, s.name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, getattr(t, 'dtype', ''), s.shape))
+
+
+def pack_fisher(fw, segs, alias, n, i):
+    """One model's Fisher dict as a flat host vector in the layout of `segs` (a parameter without an entry: 0); a negative or non-finite
+    value is refused."""
+    flat = np.zeros(n, dtype=np.float32)
+    for s in segs:
+        t = _fisher_entry(fw, alias[s.name])
+        if t is None:
+            continue
+        a = t.detach().cpu().contiguous().numpy().reshape(-1)
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise PBError('Fisher weights of model %d: %s holds a negative or non-finite value: refusing to merge' % (i, s.name))
+        flat[s.offset:s.offset + s.numel] = a
+    return flat
+
+
+def fisher_weights(model, batches, num_examples, batch_size, seq, device=None):
+    """{backbone parameter name: f32 tensor (on `device`)}: the diagonal of the empirical Fisher information of a fine-tuned classifier on its
+    own training data, as the reference's fisher_merging computes it (merging_methods.py:189-250).
+
+    model: a SequenceClassification (seq=True) or TokenClassification (seq=False) over a PianoBart of any precision; batches yields (x, y)
+    as the fine-tune loaders do; inputs are prepared as FinetuneTrainer.iteration prepares them (finetune.prepare_inputs). Per batch the
+    objective E = sum over rows and classes of sqrt(p).detach() * log_softmax(logits) is differentiated through the engine's backward into
+    its flat f32 gradient buffer, and F += grad^2 is ONE pb_fisher_accum launch over that buffer: the square of the gradient summed over the
+    batch, as in the reference. The loop ends before a batch once num_computed >= num_examples; num_computed grows by batch_size per batch
+    (a short last batch too), and F / num_computed is the result. Token tasks (an extension of ours: the reference handles (B, C) logits)
+    sum over the non-pad positions. The pass runs without dropout (every probability is 0 for its duration), takes no optimizer step and
+    leaves the weights as they were. Only parameters the engine holds get Fisher weights -- under every name the backbone's state dict
+    gives them (tied tables are one parameter) --, never a head's."""
+    return fisher_pass(model, batches, num_examples, batch_size, seq, device)[0]
+
+
+def fisher_pass(model, batches, num_examples, batch_size, seq, device=None):
+    """(fisher_weights' result, num_computed: the divisor it used)."""
+    from . import heads
+    from .finetune import prepare_inputs
+    num_examples, batch_size = int(num_examples), int(batch_size)
+    if num_examples < 1 or batch_size < 1:
+        raise PBError('fisher_weights: num_examples = %d and batch_size = %d must be positive' % (num_examples, batch_size))
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise PBError('pianobart_amd has no CPU execution path')
+    pb = model.pianobart
+    model.to(dev)
+    eng = pb._get_engine()
+    eng.bind(dev)
+    class_num = model.classifier[3].out_features - (0 if seq else 1)           # the trainer's class_num: token heads hold one more (the pad label)
+    modes = [(m, m.training) for m in model.modules()]
+    drops = [(m, m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout)]
+    p_drop = eng.p_drop
+    F = torch.zeros_like(eng.G32)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    num_computed = 0
+    try:
+        model.train()                                                       # the engine keeps its activations for a backward in training mode
+        eng.p_drop = 0.0
+        for m, _ in drops:
+            m.p = 0.0
+        with torch.enable_grad():
+            for x, y in batches:
+                if num_computed >= num_examples:
+                    break
+                x, y, attn, inputs = prepare_inputs(x, y, dev, pb.bar_pad_word, class_num, seq)
+                logits = model(**inputs)
+                e = heads.fisher_expectation_rows(logits, None if seq else attn)
+                model.zero_grad()                                           # .grad = None: the backward then writes the engine's primary buffer
+                e.sum().backward()
+                ops.fisher_accum(F, eng.G32)
+                num_computed += batch_size
+    finally:
+        model.zero_grad()
+        eng.p_drop = p_drop
+        for m, p in drops:
+            m.p = p
+        for m, t in modes:
+            m.training = t
+    if num_computed == 0:
+        raise PBError('fisher_weights: the loader gave no batch')
+    ops.fisher_finish(F, num_computed, flags)
+    if int(flags.item()):
+        raise PBError('a Fisher weight is inf or NaN (a gradient overflowed or the model holds a non-finite value)')
+    slot = {id(p): i for i, p in enumerate(eng.params)}
+    views = eng.grad_views_of(F)
+    out = OrderedDict()
+    for name, p in pb.state_dict(keep_vars=True).items():
+        if id(p) in slot:
+            out[name] = views[slot[id(p)]]
+    return out, num_computed

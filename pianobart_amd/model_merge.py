@@ -1,6 +1,7 @@
 """python -m pianobart_amd.model_merge: merge fine-tuned PianoBart backbones into one checkpoint (the reference's model_merge.py).
 
 The reference's flags keep their names and defaults; its script hard-codes mask_merging, here `--method` chooses (same default).
+`--method fisher_merging --fisher a.fisher.pt,b.fisher.pt` weights every model by the Fisher weights `python -m pianobart_amd.fisher` wrote for it.
 Checkpoints are read as this project's trainers write them ({'state_dict': ...} or a bare dict, `module.` / `pianobart.` prefixes
 stripped, head parameters dropped with a message, a file without any backbone key refused), merged on the device by
 pianobart_amd.merge, and written as {'state_dict': ...}: what PianoBart.load_state_dict and every trainer's --ckpt read."""
@@ -40,6 +41,12 @@ def get_args_merge(argv=None):
     parser.add_argument('--weight_mask_rates', type=str, default='', help='r1,r2,..: one mask rate per model (default: --weight_mask_rate for all)')
     parser.add_argument('--seed', type=int, default=0, help='seed of the random masks')
     parser.add_argument('--exclude', action='append', default=[], metavar='REGEX', help='parameter names (re.match) kept from the pre-trained model')
+    # --method fisher_merging (absent from the namespace unless given: see fisher_kwargs for the defaults)
+    S = argparse.SUPPRESS
+    parser.add_argument('--fisher', type=str, default=S, help='a.fisher.pt,b.fisher.pt: one file of pianobart_amd.fisher per model of --model_path, in its order')
+    parser.add_argument('--fisher_scaling_coefficients', type=str, default=S, help='c1,c2,..: one positive coefficient per model (default: 1/N each)')
+    parser.add_argument('--no_normalize_fisher_weight', action='store_true', default=S, help="do not scale each model by 1 / its Fisher weights' L2 norm")
+    parser.add_argument('--minimal_fisher_weight', type=float, default=S, help='added to every Fisher weight (default 1e-6)')
     return parser.parse_args(argv)
 
 
@@ -51,10 +58,31 @@ def plan_kwargs(args):
                 seed=args.seed, exclude=args.exclude)
 
 
+def fisher_kwargs(args):
+    """(the Fisher files, the Fisher keyword arguments of MergePlan without the weights themselves); the reference's defaults."""
+    files = [p for p in getattr(args, 'fisher', '').split(',') if p]
+    coef = getattr(args, 'fisher_scaling_coefficients', '')
+    return files, dict(fisher_scaling_coefficients=[float(c) for c in coef.split(',')] if coef else None,
+                       normalize_fisher_weight=not getattr(args, 'no_normalize_fisher_weight', False),
+                       minimal_fisher_weight=getattr(args, 'minimal_fisher_weight', 1e-6))
+
+
+def load_fisher_file(path):
+    f = torch.load(path, map_location='cpu', weights_only=False)
+    if not isinstance(f, dict) or not isinstance(f.get('fisher'), dict):
+        raise PBError("%s is not a file of pianobart_amd.fisher ({'fisher': {name: tensor}, ..})" % path)
+    print('   [merge] %s: Fisher weights of %d tensors over %s examples (%s, %s)' % (path, len(f['fisher']), f.get('num_computed'), f.get('task'), f.get('precision')))
+    return f['fisher']
+
+
 def model_merge(argv=None):
     args = get_args_merge(argv)
     paths = [p for p in args.model_path.split(',') if p]
     kw = plan_kwargs(args)
+    fisher_files = []
+    if args.method == 'fisher_merging':
+        fisher_files, fkw = fisher_kwargs(args)
+        kw.update(fkw, fisher_weights=fisher_files or None)         # the file names stand in for the weights until they are read
     MergePlan(len(paths), **kw)                                     # every refusal that needs no file comes first
 
     from .model import BartConfig, PianoBart
@@ -89,6 +117,8 @@ def model_merge(argv=None):
         if missing:
             raise PBError('%s lacks %d backbone keys (first: %s)' % (p, len(missing), missing[0]))
         models.append(sd)
+    if fisher_files:
+        kw['fisher_weights'] = [load_fisher_file(p) for p in fisher_files]
     merged = merge_state_dicts(pre, models, **kw)
     pianobart.load_state_dict(merged, strict=True)
     torch.save({'state_dict': pianobart.state_dict()}, args.output_path)

@@ -8,7 +8,7 @@ import os
 import torch
 
 from ._lib import (LIB, PB_BF16, PB_F32, PB_F32X3, AttnDesc, GemmDesc, PBError, GEMM_ACCUM, GEMM_C_F32, GEMM_GELU,
-                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS, MergeDesc, MERGE_MAX_MODELS, MERGE_AVERAGE,
+                   GEMM_MUL_GELU_GRAD, GEMM_ROWDOT, ATTN_CAUSAL, ATTN_GENERIC, ATTN_ONE_PASS, FisherDesc, MergeDesc, MERGE_MAX_MODELS, MERGE_AVERAGE,
                    MERGE_DELTA, MERGE_MASK_NONE)
 
 CLASS_NAMES = ('Bar', 'Position', 'Instrument', 'Pitch', 'Duration', 'Velocity', 'TimeSig', 'Tempo')   # PianoBart.classes order
@@ -408,6 +408,64 @@ def merge_sign_tally(desc):
 
 def merge_apply(desc):
     LIB.call('pb_merge_apply', ctypes.byref(desc), _stream())
+
+
+def fisher_rows(logits, weight, e_out, dlogits):
+    """pb_fisher_rows over logits (rows, C) f32: e_out[row] = sum_c sqrt(p_c) log p_c; dlogits (None: not wanted) = weight[row] * dE/dlogits
+    with sqrt(p) held constant (weight None = 1)."""
+    rows, C = logits.shape
+    for t, what in ((logits, 'logits'), (weight, 'weight'), (e_out, 'e_out'), (dlogits, 'dlogits')):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise PBError('fisher_rows: %s must be a contiguous f32 tensor' % what)
+    if e_out.numel() != rows or (weight is not None and weight.numel() != rows) or (dlogits is not None and dlogits.shape != logits.shape):
+        raise PBError('fisher_rows: e_out / weight hold one value per row, dlogits has the shape of logits')
+    LIB.call('pb_fisher_rows', _p(logits), _p(weight), _p(e_out), _p(dlogits), rows, C, _stream())
+
+
+def fisher_accum(F, g):
+    """F += g * g (two roundings) over two flat f32 tensors of one size, or equal views of them."""
+    if F.numel() != g.numel():
+        raise PBError('fisher_accum: F and g differ in size')
+    LIB.call('pb_fisher_accum', _flat_f32(F, 'F'), _flat_f32(g, 'g'), F.numel(), _stream())
+
+
+def fisher_finish(F, divisor, flags):
+    """F /= float32(divisor); flags (int32[1], zeroed by the caller) gets bit 0 where a result is not finite."""
+    if flags.dtype != torch.int32:
+        raise PBError('fisher_finish: flags is int32')
+    LIB.call('pb_fisher_finish', _flat_f32(F, 'F'), F.numel(), int(divisor), _p(flags), _stream())
+
+
+def fisher_norm_ws(device):
+    return torch.empty((LIB.query('pb_fisher_norm_ws_bytes') + 7) // 8, dtype=torch.float64, device=device)
+
+
+def fisher_norm(F, ws, norm_out):
+    """norm_out[0] = float32(sqrt(float64 sum of F^2)), in an order that depends on F.numel() alone."""
+    if norm_out.dtype != torch.float32 or ws.dtype != torch.float64:
+        raise PBError('fisher_norm: norm_out is f32, ws the float64 tensor of fisher_norm_ws')
+    LIB.call('pb_fisher_norm', _flat_f32(F, 'F'), F.numel(), _p(ws), _p(norm_out), _stream())
+
+
+def fisher_desc(models, fishers, out, coef, minimal):
+    """A pb_fisher_desc over flat f32 tensors (or equal views of them); coef: one float32 per model, minimal: float32."""
+    N = len(models)
+    if N > MERGE_MAX_MODELS:
+        raise PBError('merging takes at most %d models at a time (got %d)' % (MERGE_MAX_MODELS, N))
+    if len(fishers) != N or len(coef) != N:
+        raise PBError('fisher merge: %d models, %d Fisher vectors, %d coefficients' % (N, len(fishers), len(coef)))
+    d = FisherDesc()
+    d.out, d.n = _flat_f32(out, 'out'), out.numel()
+    for m in range(N):
+        if models[m].numel() != out.numel() or fishers[m].numel() != out.numel():
+            raise PBError('fisher merge: model %d or its Fisher vector and out differ in size' % m)
+        d.model[m], d.fisher[m], d.coef[m] = _flat_f32(models[m], 'model %d' % m), _flat_f32(fishers[m], 'fisher %d' % m), float(coef[m])
+    d.minimal, d.n_models = float(minimal), N
+    return d
+
+
+def fisher_merge(desc):
+    LIB.call('pb_fisher_merge', ctypes.byref(desc), _stream())
 
 
 FEATURE_COLS = 288                                          # the row of pb_piece_features (DESIGN.md 10)

@@ -3,6 +3,7 @@ ms per kernel family, GB/s on the bytes each family moves, the whole merge_flat 
 the same process as the yardstick of a streaming kernel on the machine.
 
     python tools/merge_bench.py [--models 4] [--out profiles/merge_kernel_stats.txt]
+    python tools/merge_bench.py --fisher [--models 4] [--out profiles/fisher_kernel_stats.txt]     the Fisher merging passes instead
 
 Each timed call runs once after one warm-up call of the same shape, between device events. Bytes are counted from the shapes:
 accum 12 n; one k-th call 4 passes x 8 n (x and base); tally (N + 1) 4 n; apply (N + 1) 4 n + 4 n. Nothing is asserted."""
@@ -33,6 +34,7 @@ def main():
     ap.add_argument('--models', type=int, default=4)
     ap.add_argument('--seq', type=int, default=1024)
     ap.add_argument('--out', default='')
+    ap.add_argument('--fisher', action='store_true', help='time the Fisher merging passes (pb_fisher.hip) against the yardstick instead')
     args = ap.parse_args()
     from pianobart_amd import ops, _lib
     from pianobart_amd.merge import MergePlan, drop_threshold, merge_flat, rescale_divisor
@@ -45,6 +47,7 @@ def main():
     pre = torch.randn(n, device=dev, generator=g) * 0.02
     models = [pre + torch.randn(n, device=dev, generator=g) * 0.002 * (m + 1) for m in range(N)]
     out = torch.empty_like(pre)
+    flags0 = torch.zeros(1, dtype=torch.int32, device=dev)
     lines = []
 
     def say(text):
@@ -66,6 +69,23 @@ def main():
 
     say('checkpoint merging, %s, n = %d parameters (%d tensors), N = %d models' % (torch.cuda.get_device_name(0), n, len(segs), N))
     row('pb_accum_f32 add (yardstick)', timed(lambda: ops.accum_f32(out, pre, add=True)), 12.0 * n)
+    if args.fisher:
+        # the four Fisher passes on the same n: accumulate 12 n bytes (F read and written, g read), finish 8 n, norm 4 n, the fused pass
+        # (2 N + 1) 4 n (N weight vectors and N Fisher vectors read, one written)
+        fishers = [(torch.randn(n, device=dev, generator=g) * 1e-3) ** 2 * (m + 1) for m in range(N)]
+        F = torch.zeros_like(pre)
+        row('pb_fisher_accum', timed(lambda: ops.fisher_accum(F, models[0])), 12.0 * n)
+        row('pb_fisher_finish', timed(lambda: ops.fisher_finish(F, 256, flags0)), 8.0 * n)
+        nws, norm = ops.fisher_norm_ws(dev), torch.zeros(1, device=dev)
+        row('pb_fisher_norm', timed(lambda: ops.fisher_norm(fishers[0], nws, norm)), 4.0 * n)
+        desc = ops.fisher_desc(models, fishers, out, [1.0 / N] * N, 1e-6)
+        row('pb_fisher_merge', timed(lambda: ops.fisher_merge(desc)), (2 * N + 1) * 4.0 * n)
+        plan = MergePlan(N, method='fisher_merging', fisher_weights=[{}] * N)
+        row('merge_flat: fisher_merging (N norms + fused pass)', timed(lambda: merge_flat(plan, pre, models, segs, fishers)))
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     ws, flags, thr = ops.merge_kth_ws(dev), torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(N, device=dev)
     k = int(n * 0.8)
     row('pb_merge_kth_abs, whole vector, k = 0.8 n', timed(lambda: ops.merge_kth_abs(models[0], pre, k, thr[0:1], flags, ws)), 4 * 8.0 * n)
