@@ -70,7 +70,7 @@ typedef struct pb_gemm_desc {
     void* slabs;                      /* workspace of splitk*M*N floats when splitk > 1 */
     float* colsum_out;                /* optional: colsum_out[n] += sum_m C[m][n] (the bias gradient of the layer that produced C's
                                          cotangent, e.g. db1 from dU): taken from the epilogue registers of the 256x256 kernel, by a
-                                         pb_colsum pass over C otherwise. Needs colsum_ws; single batch, no split-K */
+                                         pb_colsum pass over C otherwise. Needs colsum_ws; single batch, no split-K, ldc == N, N % 4 == 0 */
     float* colsum_ws;                 /* workspace of pb_gemm_colsum_ws_floats(M, N) floats */
     float* rowdot_out; int64_t ld_rowdot; /* PB_GEMM_ROWDOT (ABI 7): rowdot_out[(n / 64) * ld_rowdot + m] = sum over columns 64 (n / 64) .. + 63 of
                                          bf16(C[m][.]) * aux_in[m][.], f32 -- with C = dO (the input gradient of the attention output

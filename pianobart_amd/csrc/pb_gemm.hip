@@ -317,7 +317,8 @@ extern "C" int pb_gemm(const pb_gemm_desc* d, void* stream_) {
     PB_REQUIRE(!(d->flags & PB_GEMM_GELU) || d->aux_out, "pb_gemm: GELU epilogue needs aux_out");
     PB_REQUIRE(!(d->flags & PB_GEMM_MUL_GELU_GRAD) || d->aux_in, "pb_gemm: gelu-grad epilogue needs aux_in");
     const int nbt = (d->nb1 > 0 ? d->nb1 : 1) * (d->nb2 > 0 ? d->nb2 : 1);
-    PB_REQUIRE(!d->colsum_out || (d->colsum_ws && nbt == 1 && d->ldc == d->N), "pb_gemm: colsum_out needs colsum_ws, one batch and a dense C");
+    // (N % 4: what pb_colsum asks of the finished C -- refused here, before C is written, not behind the product)
+    PB_REQUIRE(!d->colsum_out || (d->colsum_ws && nbt == 1 && d->ldc == d->N && d->N % 4 == 0), "pb_gemm: colsum_out needs colsum_ws, one batch and a dense C with N a multiple of 4");
     if (d->dtype == PB_F32X3) return pb_gemm_x3(d, stream_);        // f32 operands as bf16 triples on the bf16 kernels (pb_gemm_x3.hip)
     if (!(d->flags & PB_GEMM_FORCE_V1)) {
         const int r2 = pb_gemm2_try(d, stream_);     // 0: done (column sums included), 2: done but the column sums are still owed, 1: declined
