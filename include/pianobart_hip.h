@@ -276,9 +276,13 @@ int pb_loss_coef(const float* counts, const float* w /*device 8*/, float* coef, 
  * A position with mask == 0 gets logp = 0, entropy = 0, rank = -1 and neither its logits nor its target are read. entropy and rank may
  * be NULL. Heads of 1 .. 1088 classes: up to 320 the register-resident row layout of K9, above it a wide form that holds one head's
  * 17 classes per lane at a time (same arithmetic and summation order); a target outside its head scores a logit of 0 as in K9.
+ * The rank of such a target follows from the same rule with that logit of 0 at the target's own index: rank = #(x > 0) +
+ * #(x == 0 at a column < target). So a target < 0 counts none of the head's zeros (+0.0 and -0.0 alike) and a target >= n all of
+ * them; a target < 0 on a head without a positive logit has rank 0 although it is no argmax.
  * pb_seq_scores: out (B,4,8) f32 = per sequence and head {sum mask*logp, sum mask*entropy, sum mask*[rank == 0], sum mask} over the S
  * positions of sequence b (rows b*S .. b*S + S - 1 of the (B*S,8) arrays); entropy / rank NULL leave their plane 0. One workgroup per
- * sequence, fixed summation order, no atomics (bit-reproducible). */
+ * sequence, fixed summation order, no atomics (bit-reproducible): per head 32 running sums, sum g over the positions g, g + 32,
+ * g + 64, ... in order, then the 32 sums added in order of g. */
 int pb_token_scores(const float* logits, const int16_t* target, const float* mask, const int32_t* seg_off /*host 9*/, float* logp,
                     float* entropy, int16_t* rank, int32_t T, int32_t V, void* stream);
 int pb_seq_scores(const float* logp, const float* entropy, const int16_t* rank, const float* mask, float* out, int32_t B, int32_t S,
