@@ -420,6 +420,34 @@ int pb_fisher_finish(float* F, int64_t n, int64_t divisor, int32_t* flags, void*
 int pb_fisher_norm(const float* F, int64_t n, void* ws, float* norm_out, void* stream);
 int pb_fisher_merge(const pb_fisher_desc* d, void* stream);
 
+/* ---- K26: RegMean merging (pb_regmean.hip; additions to ABI 10) ----------------------------------------------------------
+ * The reference's regmean_merging (model_merging_methods/merging_methods.py:266-416): per linear layer W^T = (sum_m G_m)^-1 sum_m G_m W_m^T
+ * with G_m = X_m^T X_m / rows the Gram matrix of the layer's inputs under model m. All matrices are row-major f32 with a leading dimension
+ * in elements. No float atomics: equal inputs give equal bytes. Every entry checks its arguments before the first HIP call (-2,
+ * pb_last_error names the field); 1 <= K <= 32768.
+ *
+ * pb_gram_accum: G (K, K) += X^T X for X (T, K), dtype PB_BF16 (bf16 MFMA, f32 accumulation) or PB_F32 (f32-input MFMA: an f32 fma
+ *   chain), 1 <= T <= 2^30, any K, ldx, alignment of X to its element (16-byte loads where X and ldx allow them). Only the 128 x 128 tiles
+ *   on and below the diagonal are computed; T is cut into chunks that go to different workgroups, each writes its partial tile to a fixed
+ *   slot of ws (pb_gram_ws_bytes(T, K) bytes, 16-byte aligned; 0 for sizes the entry refuses) and the slots are folded in chunk order, in
+ *   an order that depends on (T, K) alone. The new G[i][j], j <= i, is stored at (i, j) and (j, i): G comes out symmetric bit for bit
+ *   whatever its upper triangle held.
+ * pb_regmean_scale: out[i][j] = G[i][j] * (i == j ? diag : off), one multiplication per element (reduce_non_diagonal_elements with
+ *   off = float32(ratio), diag = float32(float32(1 - ratio) + float32(ratio))). out may be G (then ldo == ldg).
+ * pb_chol_factor: A (K, K) -> its lower Cholesky factor L in place, the strict upper triangle (never read) set to 0. Blocks of 64 columns:
+ *   the diagonal block by one workgroup in LDS, the panel below it by forward substitution against that block, the trailing matrix
+ *   through pb_gemm (PB_F32, alpha = -1, PB_GEMM_ACCUM). *info (device int32, zeroed by the caller) is set to 1 + j for the first column j
+ *   whose pivot is <= 0 or not finite if it is still 0, and left alone otherwise: one word may serve several calls of one stream and is
+ *   read once at the end. After such a pivot L holds inf / NaN; nothing is read or written out of bounds.
+ * pb_chol_solve: R (K, nrhs) -> Z with L L^T Z = R in place: forward then backward substitution, blocked as the factor. nrhs >= 1.
+ * pb_transpose_f32: dst (cols, rows) = src (rows, cols)^T, a copy (the (out, in) layout of a Linear.weight from the solve's (in, out)). */
+int64_t pb_gram_ws_bytes(int64_t T, int32_t K);
+int pb_gram_accum(const void* X, int64_t ldx, int32_t dtype, int64_t T, int32_t K, float* G, int64_t ldg, void* ws, void* stream);
+int pb_regmean_scale(const float* G, int64_t ldg, float* out, int64_t ldo, int32_t K, float off, float diag, void* stream);
+int pb_chol_factor(float* A, int64_t ld, int32_t K, int32_t* info, void* stream);
+int pb_chol_solve(const float* L, int64_t ldl, int32_t K, float* R, int64_t ldr, int32_t nrhs, void* stream);
+int pb_transpose_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int32_t rows, int32_t cols, void* stream);
+
 /* ---- K19: set metrics for generated pieces (pb_metrics.hip; additions to ABI 10) ----------------------------------------
  * Per-piece musical features, pairwise feature distances, their moments and a Gaussian kernel density estimate: the device half of
  * pianobart_amd.metrics. Integer counts and fixed-order floating-point sums only: equal inputs give equal bytes.

@@ -1059,6 +1059,40 @@ class Engine(GenerationMixin, ScoringMixin):
             self.g[name] = self.Gcur[s.off:s.off + s.numel].view(s.shape)
         self._alias_cross_kv(self.g)
 
+    def linear_inputs(self):
+        """[(key, X (T, K) in storage dtype, [state-dict names of the Linear weights that read X])] of the dense forward just run, straight
+        from its workspace: 4 per encoder layer, 6 per decoder layer (the cross-attention K / V projections excluded) and ONE entry for
+        the encoder output, which every decoder layer's encoder_attn.{k,v}_proj reads (dec.wkv_all). encoder_linear has no entry: its
+        input, eight concatenated embedding rows, is never materialised (the tables are folded through it, build_ptab). The views are
+        overwritten by the next forward."""
+        ws, sv = self._cur_ws, self._saved
+        if ws is None or sv is None or sv.get('pack') is not None or sv.get('sub_layer') is not None:
+            raise PBError('linear_inputs needs a dense forward_hidden with a decoder pass before it')
+        name_of = {}
+        for name, p in self.pb.state_dict(keep_vars=True).items():
+            name_of.setdefault(id(p), name)
+        names = lambda *mods: [name_of[id(m.weight)] for m in mods]
+        out = []
+        x = ws['x_enc']
+        for l in range(self.NE):
+            L, M = ws['enc'][l], self.pb.bart.encoder.layers[l]
+            sa = M.self_attn
+            out += [('enc.%d.in' % l, x, names(sa.q_proj, sa.k_proj, sa.v_proj)), ('enc.%d.ctx' % l, L['ctx'], names(sa.out_proj)),
+                    ('enc.%d.y1' % l, L['y1'], names(M.fc1)), ('enc.%d.g' % l, L['g'], names(M.fc2))]
+            x = L['y2']
+        y, cross = ws['x_dec'], []
+        for l in range(self.ND):
+            L, M = ws['dec'][l], self.pb.bart.decoder.layers[l]
+            sa, ca = M.self_attn, M.encoder_attn
+            out += [('dec.%d.in' % l, y, names(sa.q_proj, sa.k_proj, sa.v_proj)), ('dec.%d.ctx' % l, L['ctx'], names(sa.out_proj)),
+                    ('dec.%d.y1' % l, L['y1'], names(ca.q_proj)), ('dec.%d.ctxc' % l, L['ctxc'], names(ca.out_proj)),
+                    ('dec.%d.yc' % l, L['yc'], names(M.fc1)), ('dec.%d.g' % l, L['g'], names(M.fc2))]
+            cross += names(ca.k_proj, ca.v_proj)
+            y = L['y2']
+        if self.ND:
+            out.append(('enc_out', sv['enc_out'], cross))
+        return out
+
     def grad_views_of(self, buf):
         return [buf[self._elem_off(s, r):self._elem_off(s, r) + p.numel()].view(p.shape) for p, (s, r) in zip(self.params, self.param_slots)]
 

@@ -14,7 +14,8 @@ import torch
 from ._lib import PBError
 
 
-def get_args_fisher(argv=None):
+def pass_parser():
+    """The flags a data pass over one fine-tuned classifier takes (this tool and pianobart_amd.regmean)."""
     parser = argparse.ArgumentParser(description='')
     parser.add_argument('--task', choices=['melody', 'velocity', 'composer', 'emotion'], required=True)
     parser.add_argument('--dataset', type=str, choices=('asap', 'Pianist8', 'POP909', 'EMOPIA', 'GiantMIDI1k'), required=True)
@@ -32,7 +33,11 @@ def get_args_fisher(argv=None):
     parser.add_argument('--heads', type=int, default=8)
     parser.add_argument('--cuda_device', type=int, default=0)
     parser.add_argument('--precision', choices=['bf16', 'fp32', 'bf16x3'], default='bf16', help='backbone arithmetic of the pass')
-    args = parser.parse_args(argv)
+    return parser
+
+
+def get_args_fisher(argv=None):
+    args = pass_parser().parse_args(argv)
     if args.class_num is None:
         args.class_num = {'melody': 4, 'velocity': 7, 'composer': 8, 'emotion': 4}[args.task]
     if args.num_examples < 1 or args.batch_size < 1:
@@ -40,11 +45,10 @@ def get_args_fisher(argv=None):
     return args
 
 
-def fisher(argv=None):
-    args = get_args_fisher(argv)
+def load_classifier(args):
+    """(the fine-tuned classifier of --ckpt, its training split as an unshuffled loader, seq: a sequence task, the device)."""
     from torch.utils.data import DataLoader
     from .finetune import FinetuneDataset, load_data_finetune
-    from .merge import fisher_pass
     from .model import BartConfig, PianoBart, SequenceClassification, TokenClassification, checkpoint_state_dict
     from .pretrain import _load_vocab
     if not torch.cuda.is_available():
@@ -62,6 +66,13 @@ def fisher(argv=None):
     model = SequenceClassification(pianobart, args.class_num, args.hs) if seq else TokenClassification(pianobart, args.class_num + 1, args.hs)
     sd = torch.load(args.ckpt, map_location='cpu', weights_only=False)
     model.load_state_dict(checkpoint_state_dict(sd['state_dict'] if isinstance(sd, dict) and 'state_dict' in sd else sd), strict=True)
+    return model, loader, seq, device
+
+
+def fisher(argv=None):
+    args = get_args_fisher(argv)
+    from .merge import fisher_pass
+    model, loader, seq, device = load_classifier(args)
     weights, num_computed = fisher_pass(model, loader, args.num_examples, args.batch_size, seq, device)
     torch.save({'fisher': {k: v.detach().cpu().clone() for k, v in weights.items()}, 'num_computed': num_computed, 'task': args.task,
                 'precision': args.precision}, args.output)

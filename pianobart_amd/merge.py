@@ -7,7 +7,10 @@ the host keeps the segment table. PyTorch allocates and copies; all arithmetic o
 each operation rounded once in the reference's order, so a merge equals the reference's CPU result bit for bit wherever the reference
 is deterministic (everything but its torch.bernoulli masks, which are replaced by a counter-based stream of our own).
 fisher_merging takes Fisher weights that fisher_weights() (python -m pianobart_amd.fisher) computes on the device from a fine-tuned model and its
-own training data (pb_fisher.hip); without them it is refused by name, as regmean_merging (per-layer Gram matrices and inverses) always is."""
+own training data (pb_fisher.hip); without them it is refused by name. regmean_merging takes the Gram matrices of every linear layer's inputs that
+regmean_weights() (python -m pianobart_amd.regmean) accumulates from the engine's workspace, and solves W^T = (sum G_m)^-1 sum G_m W_m^T per layer by
+a Cholesky factorisation on the device (pb_regmean.hip); without them it is refused by name too."""
+import contextlib
 import re
 from collections import OrderedDict, namedtuple
 
@@ -20,13 +23,20 @@ from ._lib import (PBError, MERGE_AVERAGE, MERGE_DELTA, MERGE_FINETUNED, MERGE_M
 
 METHODS = ('mask_merging', 'average_merging', 'task_arithmetic', 'ties_merging')
 FISHER = 'fisher_merging'                                  # a method of its own inputs: one Fisher vector per model (fisher_weights)
-NEEDS_TRAINERS = (FISHER, 'regmean_merging')
+REGMEAN = 'regmean_merging'                                # and another: one {weight name: Gram matrix} dict per model (regmean_weights)
+NEEDS_TRAINERS = (FISHER, REGMEAN)
 _APPLY = {'average_merging': MERGE_AVERAGE, 'task_arithmetic': MERGE_TASK, 'ties_merging': MERGE_TIES}
 
 Segment = namedtuple('Segment', 'name offset numel shape')
 
 
-def _check_method(name, what, fisher=False):
+def _check_method(name, what, fisher=False, regmean=False):
+    if name == REGMEAN and what == 'method':
+        if regmean:
+            return
+        raise PBError("method 'regmean_merging' needs the Gram matrices of every linear layer's inputs, one set per fine-tuned model: compute each "
+                      "with merge.regmean_weights(model, batches, ..) or `python -m pianobart_amd.regmean --ckpt ft.ckpt --task .. --dataset .. --output "
+                      "ft.regmean.pt` on the model's own training data, then pass regmean_weights=[..] (model_merge: --regmean a.regmean.pt,b.regmean.pt)")
     if name == FISHER and what == 'method':
         if fisher:
             return
@@ -56,8 +66,8 @@ class MergePlan:
     def __init__(self, n_models, method='mask_merging', mask_apply_method='average_merging', mask_strategy='random', use_weight_rescale=True,
                  weight_format='delta_weight', weight_mask_rate=0.8, weight_mask_rates=None, scaling_coefficient=1.0, param_value_mask_rate=0.8,
                  seed=0, exclude=(), fisher_weights=None, fisher_scaling_coefficients=None, normalize_fisher_weight=True, minimal_fisher_weight=1e-6,
-                 fisher_norms=None):
-        _check_method(method, 'method', fisher=fisher_weights is not None)
+                 fisher_norms=None, regmean_weights=None, reduce_non_diagonal_ratio=1.0):
+        _check_method(method, 'method', fisher=fisher_weights is not None, regmean=regmean_weights is not None)
         if method == 'mask_merging':
             _check_method(mask_apply_method, 'mask_apply_method')
             if mask_strategy not in ('random', 'magnitude'):
@@ -81,6 +91,14 @@ class MergePlan:
         self.rates, self.lam, self.ties_rate = rates, float(scaling_coefficient), float(param_value_mask_rate)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.exclude = [exclude] if isinstance(exclude, str) else list(exclude or ())
+        self.regmean = method == REGMEAN
+        if self.regmean:
+            self.regmean_weights = list(regmean_weights)
+            if len(self.regmean_weights) != n_models:
+                raise PBError('regmean_weights holds %d sets of Gram matrices for %d models' % (len(self.regmean_weights), n_models))
+            self.ratio = float(reduce_non_diagonal_ratio)
+            if not 0.0 <= self.ratio <= 1.0:                                   # NaN fails both comparisons
+                raise PBError('reduce_non_diagonal_ratio must lie in [0, 1] (got %r)' % (reduce_non_diagonal_ratio,))
         self.fisher = method == FISHER
         if self.fisher:
             self.fisher_weights = list(fisher_weights)
@@ -145,15 +163,73 @@ def segment_table(shapes):
     return segs
 
 
-def merge_flat(plan, pre, models, segs, fishers=None):
+def regmean_factors(ratio):
+    """(off, diag): the float32 factors of reduce_non_diagonal_elements as the reference's float32 tensors evaluate them
+    (merging_methods.py:309-313): off = float32(ratio), diag = (1 - ratio) + ratio with every operation in float32, which is not always 1."""
+    off = torch.zeros(1, dtype=torch.float32).fill_(float(ratio))
+    diag = (torch.ones(1, dtype=torch.float32) - float(ratio)) + off
+    return float(off.item()), float(diag.item())
+
+
+def regmean_groups(regmean, segs):
+    """[[Segment, ..]]: the segments with Gram matrices, those whose matrices are ONE tensor in every model's dict (q / k / v of an attention
+    block; every decoder layer's cross-attention k / v) together: they share a factorisation and go as one stacked right-hand side."""
+    groups = OrderedDict()
+    for s in segs:
+        if s.name in regmean[0]:
+            groups.setdefault(tuple(r[s.name].data_ptr() for r in regmean), []).append(s)
+    return list(groups.values())
+
+
+def _regmean_flat(plan, pre, models, segs, regmean, out):
+    """out = the plain mean of the fine-tuned vectors (the MERGE_AVERAGE pass), then per group of weights with Gram matrices
+    S = sum_m G'_m, R (K, outs) = sum_m G'_m W_m^T, S = L L^T, L L^T Z = R, W = Z^T written over the mean. G'_m = scale(G_m)."""
+    from ._lib import PB_F32
+    N, dev = len(models), pre.device
+    ops.merge_apply(ops.merge_desc(pre, models, out, method=MERGE_AVERAGE, lam=plan.lam))
+    off, diag = regmean_factors(plan.ratio)
+    groups = regmean_groups(regmean, segs)
+    info = torch.zeros(max(1, len(groups)), dtype=torch.int32, device=dev)     # one word per factorisation, read once at the end
+    for gi, members in enumerate(groups):
+        K, outs = members[0].shape[1], [s.shape[0] for s in members]
+        nout = sum(outs)
+        S, R, Gs = (torch.zeros(K, K, dtype=torch.float32, device=dev), torch.zeros(K, nout, dtype=torch.float32, device=dev),
+                    torch.empty(K, K, dtype=torch.float32, device=dev))
+        for m in range(N):
+            ops.regmean_scale(regmean[m][members[0].name], Gs, off, diag)
+            ops.accum_f32(S, Gs)
+            o = 0
+            for s, n_out in zip(members, outs):                                 # R[:, o : o + out] += G' W^T: NT form, W is (out, K)
+                ops.gemm(Gs, models[m][s.offset:s.offset + s.numel], R, M=K, N=n_out, K=K, dtype=PB_F32, ldc=nout, c_off=o, accum=True)
+                o += n_out
+        ops.chol_factor(S, info[gi:gi + 1])
+        ops.chol_solve(S, R)
+        o = 0
+        for s, n_out in zip(members, outs):
+            ops.transpose_f32(R[:, o:o + n_out], out[s.offset:s.offset + s.numel].view(n_out, K))
+            o += n_out
+    for gi, col in enumerate(info.cpu().tolist()):
+        if col and groups:
+            raise PBError('%s: the summed Gram matrix is not positive definite (pivot of column %d of %d is <= 0 or not finite): too few rows for '
+                          'its %d inputs, or an input that is identically 0' % (', '.join(s.name for s in groups[gi]), col - 1, groups[gi][0].shape[1],
+                                                                                groups[gi][0].shape[1]))
+    return out
+
+
+def merge_flat(plan, pre, models, segs, fishers=None, regmean=None):
     """The merged flat vector (a new device tensor) of the flat f32 device vectors `pre` and `models` laid out by `segs`. A Fisher plan
-    also takes `fishers`: one flat Fisher vector per model in the same layout (`pre` then only gives the size)."""
+    also takes `fishers`: one flat Fisher vector per model in the same layout (`pre` then only gives the size); a RegMean plan `regmean`:
+    per model {segment name: (K, K) f32 device tensor} (regmean_groups tells which weights share one)."""
     N, n, dev = len(models), pre.numel(), pre.device
     if N != plan.n_models:
         raise PBError('the plan was made for %d models, got %d' % (plan.n_models, N))
     if n != sum(s.numel for s in segs):
         raise PBError('the segment table covers %d elements, the vectors hold %d' % (sum(s.numel for s in segs), n))
     out = torch.empty_like(pre)
+    if plan.regmean:
+        if regmean is None or len(regmean) != N:
+            raise PBError('a regmean_merging plan takes one {segment name: (K, K) device tensor} dict per model')
+        return _regmean_flat(plan, pre, models, segs, regmean, out)
     if plan.fisher:
         if fishers is None or len(fishers) != N:
             raise PBError('a fisher_merging plan takes one flat Fisher vector per model')
@@ -280,12 +356,20 @@ def merge_state_dicts(pretrained_sd, finetuned_sds, method='mask_merging', devic
     method='fisher_merging' takes fisher_weights=[{name: f32 tensor}, ..], one dict per model as fisher_weights() returns it, and
     fisher_scaling_coefficients / normalize_fisher_weight / minimal_fisher_weight with the reference's meaning; fisher_norms=[..]
     overrides the device's norms of the Fisher vectors. A merged parameter that no Fisher dict names (BART's never-read `shared`
-    table: its gradient is identically 0) has Fisher weight 0 and comes out as the coefficient-weighted mean."""
+    table: its gradient is identically 0) has Fisher weight 0 and comes out as the coefficient-weighted mean.
+
+    method='regmean_merging' takes regmean_weights=[{weight name: (K, K) f32 Gram matrix}, ..], one dict per model as regmean_weights()
+    returns it, and reduce_non_diagonal_ratio (default 1.0: the matrices as they are) with the reference's meaning. Every 2-D `.weight` with
+    an entry becomes (sum_m G'_m)^-1 sum_m G'_m W_m^T, transposed back; every other merged parameter is the plain mean of the fine-tuned
+    values (what method='average_merging' gives). The pre-trained model supplies names, shapes, exclusions and tied-table aliases only.
+    A summed Gram matrix that is not positive definite is a PBError that names the weight."""
     finetuned_sds = list(finetuned_sds)
     plan = MergePlan(len(finetuned_sds), method=method, **kw)
     segs, alias = state_dict_layout(pretrained_sd, plan.exclude)
     if plan.fisher:
         check_fisher_dicts(plan.fisher_weights, pretrained_sd, segs, alias)
+    if plan.regmean:
+        check_regmean_dicts(plan.regmean_weights, segs, alias)
     for s in segs:
         for i, sd in enumerate(finetuned_sds):
             if s.name not in sd:
@@ -308,7 +392,20 @@ def merge_state_dicts(pretrained_sd, finetuned_sds, method='mask_merging', devic
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     flats = [torch.from_numpy(h).to(dev) for h in host]
     fishers = [torch.from_numpy(h).to(dev) for h in fhost] if plan.fisher else None
-    merged = merge_flat(plan, flats[0], flats[1:], segs, fishers).cpu()
+    regmean = None
+    if plan.regmean:                                                            # a tensor that several names share goes to the device once and stays shared
+        on_dev, regmean = {}, []
+        for rw in plan.regmean_weights:
+            by_seg = {}
+            for s in segs:
+                t = _fisher_entry(rw, alias[s.name])
+                if t is not None:
+                    key = (t.device, t.data_ptr())
+                    if key not in on_dev:
+                        on_dev[key] = (t, t.detach().to(dev).contiguous())      # (the source is kept alive: its address is the key)
+                    by_seg[s.name] = on_dev[key][1]
+            regmean.append(by_seg)
+    merged = merge_flat(plan, flats[0], flats[1:], segs, fishers, regmean).cpu()
     out = OrderedDict((k, v.detach().cpu().clone() if torch.is_tensor(v) else v) for k, v in pretrained_sd.items())
     for s in segs:
         t = merged[s.offset:s.offset + s.numel].reshape(s.shape).clone()
@@ -363,6 +460,130 @@ def pack_fisher(fw, segs, alias, n, i):
     return flat
 
 
+@contextlib.contextmanager
+def _training_without_dropout(model, eng):
+    """The state both data passes run in: training mode (the engine then keeps every activation of the forward in its workspace) with
+    every dropout probability 0. Module modes, probabilities and the engine's p_drop come back as found, and no .grad stays set."""
+    modes = [(m, m.training) for m in model.modules()]
+    drops = [(m, m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout)]
+    p_drop = eng.p_drop
+    try:
+        model.train()
+        eng.p_drop = 0.0
+        for m, _ in drops:
+            m.p = 0.0
+        yield
+    finally:
+        model.zero_grad()
+        eng.p_drop = p_drop
+        for m, p in drops:
+            m.p = p
+        for m, t in modes:
+            m.training = t
+
+
+def check_regmean_dicts(regmean_weights, segs, alias):
+    """Refuses, before any device work: a dict that is empty or names something that is not a merged 2-D `.weight`, dicts that name different
+    parameters, an entry that is not a float32 (K, K) matrix with K the weight's in_features, and one that is not finite or not symmetric
+    to 1e-6 of its largest diagonal element."""
+    seg_of = {name: s for s in segs for name in alias[s.name]}
+    first, seen = None, {}
+    for i, rw in enumerate(regmean_weights):
+        if not isinstance(rw, dict) or not rw:
+            raise PBError('RegMean weights of model %d: expected a non-empty {weight name: (K, K) tensor} dict' % i)
+        unknown = [k for k in rw if k not in seg_of]
+        if unknown:
+            raise PBError('RegMean weights of model %d name %d entries that are no merged parameter (first: %s)' % (i, len(unknown), unknown[0]))
+        covered = {seg_of[k].name for k in rw}
+        if first is None:
+            first = covered
+        elif covered != first:
+            raise PBError('RegMean weights of model %d and of model 0 name different parameters (first: %s)' % (i, sorted(covered ^ first)[0]))
+        for k, t in rw.items():
+            s = seg_of[k]
+            if not k.endswith('.weight') or len(s.shape) != 2:
+                raise PBError('RegMean weights of model %d: %s is not the 2-D weight of a linear layer (shape %s)' % (i, k, s.shape))
+            K = s.shape[1]
+            if not torch.is_tensor(t) or tuple(t.shape) != (K, K) or t.dtype != torch.float32:
+                raise PBError('RegMean weights of model %d: %s is %s %s, expected a float32 (%d, %d) Gram matrix of the in_features of the %s weight'
+                              % (i, k, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, getattr(t, 'dtype', ''), K, K, s.shape))
+            key = (t.device, t.data_ptr())
+            if key in seen:                                                     # a matrix several names share is looked at once
+                continue
+            seen[key] = t
+            c = t.detach().cpu()
+            if not bool(torch.isfinite(c).all()):
+                raise PBError('RegMean weights of model %d: %s holds a non-finite value: refusing to merge' % (i, k))
+            if float((c - c.t()).abs().max()) > 1e-6 * float(c.diagonal().max()):
+                raise PBError('RegMean weights of model %d: %s is not symmetric to 1e-6 of its largest diagonal element: not a Gram matrix' % (i, k))
+
+
+def regmean_weights(model, batches, num_examples, seq, device=None):
+    """{name of a backbone Linear weight: (K, K) f32 Gram matrix of its inputs (on `device`)}: G = X^T X / rows over the model's own training
+    data, as the reference's regmean_merging collects it with forward hooks (merging_methods.py:330-388).
+
+    model: a SequenceClassification (seq=True) or TokenClassification (seq=False) over a PianoBart of any precision; batches yields (x, y) as
+    the fine-tune loaders do; inputs are prepared by finetune.prepare_inputs. Per batch ONE dense forward, then one pb_gram_accum per entry of
+    Engine.linear_inputs(): the workspace already holds every layer's input. All B * S rows of the padded batch count, PAD positions
+    included (the reference's hook sees x.reshape(-1, K)). The loop ends before a batch once the examples counted (+= the batch's actual
+    size) reach num_examples; every sum is divided ONCE by the rows counted (the reference keeps a running mean of per-batch means: the
+    same number in exact arithmetic, here with one rounding instead of one per batch). Names that read the same input (q / k / v; every
+    decoder layer's cross-attention k / v) hold the SAME tensor. encoder_linear.weight has no entry (its input is never materialised)
+    and is therefore averaged by the merge, as the reference averages a weight without RegMean weights; heads are never merged. Dropout,
+    module modes and parameters are left as found."""
+    return regmean_pass(model, batches, num_examples, seq, device)[0]
+
+
+def regmean_pass(model, batches, num_examples, seq, device=None):
+    """(regmean_weights' result, the rows counted: the divisor, the examples counted)."""
+    from .finetune import prepare_inputs
+    num_examples = int(num_examples)
+    if num_examples < 1:
+        raise PBError('regmean_weights: num_examples = %d must be positive' % num_examples)
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise PBError('pianobart_amd has no CPU execution path')
+    pb = model.pianobart
+    model.to(dev)
+    eng = pb._get_engine()
+    eng.bind(dev)
+    class_num = model.classifier[3].out_features - (0 if seq else 1)
+    grams, shared, ws = OrderedDict(), {}, {}
+    num_rows = num_counted = 0
+    with _training_without_dropout(model, eng), torch.no_grad():
+        for x, y in batches:
+            if num_counted >= num_examples:
+                break
+            x, y, attn, inputs = prepare_inputs(x, y, dev, pb.bar_pad_word, class_num, seq)
+            model(**inputs)
+            for key, X, names in eng.linear_inputs():
+                T, K = X.shape
+                if key not in grams:
+                    grams[key] = torch.zeros(K, K, dtype=torch.float32, device=dev)
+                    shared[key] = names
+                if (T, K) not in ws:
+                    ws[(T, K)] = ops.gram_ws(T, K, dev)
+                ops.gram_accum(grams[key], X, ws[(T, K)])
+            num_rows += x.shape[0] * x.shape[1]
+            num_counted += x.shape[0]
+    if num_counted == 0:
+        raise PBError('regmean_weights: the loader gave no batch')
+    if num_rows > 1 << 24:
+        raise PBError('regmean_weights: %d rows counted; the divisor must stay exact in float32 (at most 2^24 rows)' % num_rows)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    for G in grams.values():
+        ops.fisher_finish(G.view(-1), num_rows, flags)                          # G /= float32(rows); flags where a result is not finite
+    if int(flags.item()):
+        raise PBError('a Gram matrix holds inf or NaN (an activation overflowed or the model holds a non-finite value)')
+    out = OrderedDict()
+    for key, G in grams.items():
+        for name in shared[key]:
+            out[name] = G
+    print('   [regmean] encoder_linear.weight has no Gram matrix (its input, eight concatenated embedding rows, is never materialised): '
+          'a merge averages it')
+    return out, num_rows, num_counted
+
+
 def fisher_weights(model, batches, num_examples, batch_size, seq, device=None):
     """{backbone parameter name: f32 tensor (on `device`)}: the diagonal of the empirical Fisher information of a fine-tuned classifier on its
     own training data, as the reference's fisher_merging computes it (merging_methods.py:189-250).
@@ -394,35 +615,20 @@ def fisher_pass(model, batches, num_examples, batch_size, seq, device=None):
     eng = pb._get_engine()
     eng.bind(dev)
     class_num = model.classifier[3].out_features - (0 if seq else 1)           # the trainer's class_num: token heads hold one more (the pad label)
-    modes = [(m, m.training) for m in model.modules()]
-    drops = [(m, m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout)]
-    p_drop = eng.p_drop
     F = torch.zeros_like(eng.G32)
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     num_computed = 0
-    try:
-        model.train()                                                       # the engine keeps its activations for a backward in training mode
-        eng.p_drop = 0.0
-        for m, _ in drops:
-            m.p = 0.0
-        with torch.enable_grad():
-            for x, y in batches:
-                if num_computed >= num_examples:
-                    break
-                x, y, attn, inputs = prepare_inputs(x, y, dev, pb.bar_pad_word, class_num, seq)
-                logits = model(**inputs)
-                e = heads.fisher_expectation_rows(logits, None if seq else attn)
-                model.zero_grad()                                           # .grad = None: the backward then writes the engine's primary buffer
-                e.sum().backward()
-                ops.fisher_accum(F, eng.G32)
-                num_computed += batch_size
-    finally:
-        model.zero_grad()
-        eng.p_drop = p_drop
-        for m, p in drops:
-            m.p = p
-        for m, t in modes:
-            m.training = t
+    with _training_without_dropout(model, eng), torch.enable_grad():
+        for x, y in batches:
+            if num_computed >= num_examples:
+                break
+            x, y, attn, inputs = prepare_inputs(x, y, dev, pb.bar_pad_word, class_num, seq)
+            logits = model(**inputs)
+            e = heads.fisher_expectation_rows(logits, None if seq else attn)
+            model.zero_grad()                                               # .grad = None: the backward then writes the engine's primary buffer
+            e.sum().backward()
+            ops.fisher_accum(F, eng.G32)
+            num_computed += batch_size
     if num_computed == 0:
         raise PBError('fisher_weights: the loader gave no batch')
     ops.fisher_finish(F, num_computed, flags)

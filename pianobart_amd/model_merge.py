@@ -1,7 +1,9 @@
 """python -m pianobart_amd.model_merge: merge fine-tuned PianoBart backbones into one checkpoint (the reference's model_merge.py).
 
 The reference's flags keep their names and defaults; its script hard-codes mask_merging, here `--method` chooses (same default).
-`--method fisher_merging --fisher a.fisher.pt,b.fisher.pt` weights every model by the Fisher weights `python -m pianobart_amd.fisher` wrote for it.
+`--method fisher_merging --fisher a.fisher.pt,b.fisher.pt` weights every model by the Fisher weights `python -m pianobart_amd.fisher` wrote for it;
+`--method regmean_merging --regmean a.regmean.pt,b.regmean.pt [--reduce_non_diagonal_ratio 0.9]` solves every linear layer's least-squares
+problem from the Gram matrices `python -m pianobart_amd.regmean` wrote for each model.
 Checkpoints are read as this project's trainers write them ({'state_dict': ...} or a bare dict, `module.` / `pianobart.` prefixes
 stripped, head parameters dropped with a message, a file without any backbone key refused), merged on the device by
 pianobart_amd.merge, and written as {'state_dict': ...}: what PianoBart.load_state_dict and every trainer's --ckpt read."""
@@ -47,6 +49,9 @@ def get_args_merge(argv=None):
     parser.add_argument('--fisher_scaling_coefficients', type=str, default=S, help='c1,c2,..: one positive coefficient per model (default: 1/N each)')
     parser.add_argument('--no_normalize_fisher_weight', action='store_true', default=S, help="do not scale each model by 1 / its Fisher weights' L2 norm")
     parser.add_argument('--minimal_fisher_weight', type=float, default=S, help='added to every Fisher weight (default 1e-6)')
+    # --method regmean_merging (absent from the namespace unless given, as above)
+    parser.add_argument('--regmean', type=str, default=S, help='a.regmean.pt,b.regmean.pt: one file of pianobart_amd.regmean per model of --model_path, in its order')
+    parser.add_argument('--reduce_non_diagonal_ratio', type=float, default=S, help='off-diagonal Gram entries are multiplied by this (default 1.0)')
     return parser.parse_args(argv)
 
 
@@ -75,6 +80,15 @@ def load_fisher_file(path):
     return f['fisher']
 
 
+def load_regmean_file(path):
+    f = torch.load(path, map_location='cpu', weights_only=False)
+    if not isinstance(f, dict) or not isinstance(f.get('regmean'), dict):
+        raise PBError("%s is not a file of pianobart_amd.regmean ({'regmean': {name: tensor}, ..})" % path)
+    print('   [merge] %s: Gram matrices for %d weights over %s rows of %s examples (%s, %s)' % (path, len(f['regmean']), f.get('num_rows'), f.get('num_examples'),
+                                                                                              f.get('task'), f.get('precision')))
+    return f['regmean']
+
+
 def model_merge(argv=None):
     args = get_args_merge(argv)
     paths = [p for p in args.model_path.split(',') if p]
@@ -83,6 +97,10 @@ def model_merge(argv=None):
     if args.method == 'fisher_merging':
         fisher_files, fkw = fisher_kwargs(args)
         kw.update(fkw, fisher_weights=fisher_files or None)         # the file names stand in for the weights until they are read
+    regmean_files = []
+    if args.method == 'regmean_merging':
+        regmean_files = [p for p in getattr(args, 'regmean', '').split(',') if p]
+        kw.update(regmean_weights=regmean_files or None, reduce_non_diagonal_ratio=getattr(args, 'reduce_non_diagonal_ratio', 1.0))
     MergePlan(len(paths), **kw)                                     # every refusal that needs no file comes first
 
     from .model import BartConfig, PianoBart
@@ -119,6 +137,8 @@ def model_merge(argv=None):
         models.append(sd)
     if fisher_files:
         kw['fisher_weights'] = [load_fisher_file(p) for p in fisher_files]
+    if regmean_files:
+        kw['regmean_weights'] = [load_regmean_file(p) for p in regmean_files]
     merged = merge_state_dicts(pre, models, **kw)
     pianobart.load_state_dict(merged, strict=True)
     torch.save({'state_dict': pianobart.state_dict()}, args.output_path)

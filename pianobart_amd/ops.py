@@ -468,6 +468,69 @@ def fisher_merge(desc):
     LIB.call('pb_fisher_merge', ctypes.byref(desc), _stream())
 
 
+def _mat_f32(t, rows, cols, what):
+    """(address, leading dimension) of a 2-D f32 device tensor of `rows` x `cols` whose rows are contiguous (a column slice of a wider buffer is one)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, cols) or t.stride(1) != 1 or (rows > 1 and t.stride(0) < cols):
+        raise PBError('%s must be a (%d, %d) f32 tensor with contiguous rows (got %s %s, strides %s)' % (what, rows, cols, tuple(t.shape), t.dtype, t.stride()))
+    return _p(t), (t.stride(0) if rows > 1 else cols)
+
+
+def gram_ws(T, K, device):
+    """The workspace of one gram_accum call over (T, K) activations (reusable by the next call of that size on the same stream)."""
+    return torch.empty(max(1, LIB.query('pb_gram_ws_bytes', int(T), int(K)) // 4), dtype=torch.float32, device=device)
+
+
+def gram_accum(G, X, ws=None):
+    """G (K, K) f32 += X^T X for X (T, K) bf16 or f32 with contiguous rows; G comes out symmetric bit for bit. ws: gram_ws(T, K, device)."""
+    if X.dim() != 2 or X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+        raise PBError('gram_accum: X must be a (T, K) tensor with contiguous rows')
+    T, K = X.shape
+    g, ldg = _mat_f32(G, K, K, 'gram_accum: G')
+    if ws is None:
+        ws = gram_ws(T, K, X.device)
+    if ws.dtype != torch.float32 or ws.numel() * 4 < LIB.query('pb_gram_ws_bytes', T, K):
+        raise PBError('gram_accum: ws is smaller than pb_gram_ws_bytes(%d, %d)' % (T, K))
+    LIB.call('pb_gram_accum', _p(X), X.stride(0) if T > 1 else K, dtype_code(X.dtype), T, K, g, ldg, _p(ws), _stream())
+
+
+def regmean_scale(G, out, off, diag):
+    """out = G * (diag on the diagonal, off elsewhere); out may be G."""
+    K = G.shape[0]
+    g, ldg = _mat_f32(G, K, K, 'regmean_scale: G')
+    o, ldo = _mat_f32(out, K, K, 'regmean_scale: out')
+    LIB.call('pb_regmean_scale', g, ldg, o, ldo, K, float(off), float(diag), _stream())
+
+
+def chol_factor(A, info):
+    """A (K, K) f32 -> its lower Cholesky factor in place (strict upper triangle 0). info (int32[1], zeroed by the caller) becomes 1 + j
+    for the first pivot j that is <= 0 or not finite if it still holds 0."""
+    K = A.shape[0]
+    a, ld = _mat_f32(A, K, K, 'chol_factor: A')
+    if info.dtype != torch.int32 or info.numel() != 1:
+        raise PBError('chol_factor: info is one int32')
+    LIB.call('pb_chol_factor', a, ld, K, _p(info), _stream())
+
+
+def chol_solve(L, R):
+    """R (K, nrhs) f32 -> Z with L L^T Z = R, in place."""
+    K = L.shape[0]
+    l, ldl = _mat_f32(L, K, K, 'chol_solve: L')
+    if R.dim() != 2:
+        raise PBError('chol_solve: R must be (K, nrhs)')
+    r, ldr = _mat_f32(R, K, R.shape[1], 'chol_solve: R')
+    LIB.call('pb_chol_solve', l, ldl, K, r, ldr, R.shape[1], _stream())
+
+
+def transpose_f32(src, dst):
+    """dst (cols, rows) = src (rows, cols)^T, a copy on the device."""
+    if src.dim() != 2:
+        raise PBError('transpose_f32: src must be 2-D')
+    rows, cols = src.shape
+    s, lds = _mat_f32(src, rows, cols, 'transpose_f32: src')
+    d, ldd = _mat_f32(dst, cols, rows, 'transpose_f32: dst')
+    LIB.call('pb_transpose_f32', s, lds, d, ldd, rows, cols, _stream())
+
+
 FEATURE_COLS = 288                                          # the row of pb_piece_features (DESIGN.md 10)
 
 

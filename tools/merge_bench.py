@@ -4,6 +4,7 @@ the same process as the yardstick of a streaming kernel on the machine.
 
     python tools/merge_bench.py [--models 4] [--out profiles/merge_kernel_stats.txt]
     python tools/merge_bench.py --fisher [--models 4] [--out profiles/fisher_kernel_stats.txt]     the Fisher merging passes instead
+    python tools/merge_bench.py --regmean [--models 4] [--out profiles/regmean_kernel_stats.txt]   the RegMean kernels and merge instead
 
 Each timed call runs once after one warm-up call of the same shape, between device events. Bytes are counted from the shapes:
 accum 12 n; one k-th call 4 passes x 8 n (x and base); tally (N + 1) 4 n; apply (N + 1) 4 n + 4 n. Nothing is asserted."""
@@ -29,12 +30,77 @@ def backbone_segments(seq):
     return segment_table({n: tuple(p.shape) for n, p in m.named_parameters()})
 
 
+def regmean_groups_of(segs):
+    """{key: [names]} of the backbone's Linear weights as the Gram pass shares their inputs: q / k / v of a self-attention block, every
+    decoder layer's cross-attention k / v; encoder_linear has none."""
+    groups = {}
+    for s in segs:
+        if not s.name.endswith('.weight') or len(s.shape) != 2 or '.layers.' not in s.name or 'layer_norm' in s.name:
+            continue
+        block, leaf = s.name.rsplit('.', 2)[:2]
+        key = block + '.qkv' if leaf in ('q_proj', 'k_proj', 'v_proj') and block.endswith('self_attn') else 'cross.kv' if leaf in ('k_proj', 'v_proj') else s.name
+        groups.setdefault(key, []).append(s.name)
+    return groups
+
+
+def regmean_mode(args, dev, segs, pre, models, say, row, timed):
+    """pb_gram_accum beside the TN ops.gemm on the same X, factor + solve, and one whole merge_flat."""
+    from pianobart_amd import ops, _lib
+    from pianobart_amd.merge import MergePlan, merge_flat
+    g = torch.Generator(device=dev).manual_seed(4321)
+    T = 8192
+    for K in (768, 3072):
+        for dt, code in ((torch.bfloat16, _lib.PB_BF16), (torch.float32, _lib.PB_F32)):
+            X = (torch.randn(T, K, device=dev, generator=g) + 0.5).to(dt)
+            G, C, ws = torch.zeros(K, K, device=dev), torch.zeros(K, K, device=dev), ops.gram_ws(T, K, dev)
+            flop = 2.0 * T * K * K
+            ms = timed(lambda: ops.gram_accum(G, X, ws))
+            say('%-46s %9.3f ms   %8.1f TFLOP/s of the %.1f GFLOP of the full product' % ('pb_gram_accum (%d, %d) %s' % (T, K, str(dt)[6:]), ms, flop / ms / 1e9, flop / 1e9))
+            ms = timed(lambda: ops.gemm(X, X, C, M=K, N=K, K=T, dtype=code, a_kc=False, b_kc=False, c_f32=True, accum=True))
+            say('%-46s %9.3f ms   %8.1f TFLOP/s' % ('ops.gemm TN, same X, both triangles', ms, flop / ms / 1e9))
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    for K, nrhs in ((768, 2304), (3072, 768)):
+        X = torch.randn(2 * K, K, device=dev, generator=g) + 0.5
+        S0 = torch.zeros(K, K, device=dev)
+        ops.gram_accum(S0, X)
+        S0 /= 2 * K
+        R0 = torch.randn(K, nrhs, device=dev, generator=g)
+        S, R = S0.clone(), R0.clone()
+
+        def factor():
+            S.copy_(S0)
+            ops.chol_factor(S, info)
+
+        row('pb_chol_factor K = %d (with the copy of S)' % K, timed(factor))
+        row('pb_chol_solve K = %d, nrhs = %d' % (K, nrhs), timed(lambda: ops.chol_solve(S, R)))
+    assert int(info.item()) == 0
+    groups, N = regmean_groups_of(segs), len(models)
+    shape = {s.name: s.shape for s in segs}
+    base = {}
+    for K in (768, 3072):                                  # one Gram matrix per K and model, copied per group (a shared tensor would be ONE group)
+        for m in range(N):
+            X = (torch.randn(2 * K, K, device=dev, generator=g) + 0.5).bfloat16()
+            base[(K, m)] = torch.zeros(K, K, device=dev)
+            ops.gram_accum(base[(K, m)], X)
+            base[(K, m)] /= 2 * K
+    regmean = [dict() for _ in range(N)]
+    for names in groups.values():
+        for m in range(N):
+            G = base[(shape[names[0]][1], m)].clone()
+            for name in names:
+                regmean[m][name] = G
+    plan = MergePlan(N, method='regmean_merging', regmean_weights=[{}] * N)
+    say('%d weights in %d groups (one factorisation each)' % (sum(len(v) for v in groups.values()), len(groups)))
+    row('merge_flat: regmean_merging', timed(lambda: merge_flat(plan, pre, models, segs, regmean=regmean)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--models', type=int, default=4)
     ap.add_argument('--seq', type=int, default=1024)
     ap.add_argument('--out', default='')
     ap.add_argument('--fisher', action='store_true', help='time the Fisher merging passes (pb_fisher.hip) against the yardstick instead')
+    ap.add_argument('--regmean', action='store_true', help='time the RegMean kernels (pb_regmean.hip) and a whole regmean merge_flat instead')
     args = ap.parse_args()
     from pianobart_amd import ops, _lib
     from pianobart_amd.merge import MergePlan, drop_threshold, merge_flat, rescale_divisor
@@ -69,6 +135,12 @@ def main():
 
     say('checkpoint merging, %s, n = %d parameters (%d tensors), N = %d models' % (torch.cuda.get_device_name(0), n, len(segs), N))
     row('pb_accum_f32 add (yardstick)', timed(lambda: ops.accum_f32(out, pre, add=True)), 12.0 * n)
+    if args.regmean:
+        regmean_mode(args, dev, segs, pre, models, say, row, timed)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     if args.fisher:
         # the four Fisher passes on the same n: accumulate 12 n bytes (F read and written, g read), finish 8 n, norm 4 n, the fused pass
         # (2 N + 1) 4 n (N weight vectors and N Fisher vectors read, one written)
