@@ -594,6 +594,43 @@ int pb_texture_cols(void);
 int pb_piece_texture(const int16_t* ids16, const int32_t* start, const int32_t* pad8, const int16_t* pitch_of, const int32_t* dur_pos,
                      const int32_t* bar_pos, int32_t* out, int32_t N, int32_t S, void* stream);
 
+/* ---- K27: embedding-space set metrics (pb_embed.hip; additions to ABI 10) ------------------------------------------------------------
+ * One vector per piece from the encoder's last hidden state, float64 set moments for a Frechet distance, squared distances for rows up to
+ * 4096 wide and the k-nearest-neighbour counts of precision / recall / density / coverage (Naeem et al. 2020): the device half of
+ * pianobart_amd.embedding. No float atomics; every floating-point sum has a fixed order; integer atomics only where the
+ * result is an integer sum: equal inputs give equal bytes. Matrices are row-major with a leading dimension in elements. Every entry
+ * checks its arguments before the first HIP call (-2, pb_last_error names the field).
+ *
+ * pb_pool_rows: out[b, c] = (sum over s with mask[b, s] != 0 of H[(b S + s) ldh + c]) / count_b as f32 and count[b] = the number of such s
+ *   as int32, for H bf16 or f32 (dtype PB_BF16 / PB_F32), 1 <= B <= 65535, 1 <= S <= 65536, d >= 1, ldh >= d. mask (B, S) f32 or NULL = every row;
+ *   out (B, d) f32 with ldo >= d. The sum over s runs in f64: S is cut into 16 slices of ceil(S / 16) rows, each summed front to back,
+ *   the slices added in order; one division in f64, one rounding to f32. count_b = 0 gives a zero row. 16-byte loads where H and ldh
+ *   allow them, element loads otherwise.
+ * pb_embed_moments: mean (d) f64 = sum_n X[n] / N and C (d, d) f64 with ldc >= d, C[i][j] = sum_n (X[n][i] - mean[i]) (X[n][j] - mean[j]),
+ *   for X (N, d) f32 with ldx >= d, 2 <= N <= 2^24, 1 <= d <= 4096. Two passes over X; N is cut into at most 16 chunks of a multiple of
+ *   16 rows that depend on N alone, each chunk writes its partial column sums and its partial 64 x 64 tiles to fixed slots of ws
+ *   (pb_embed_ws_bytes(N, d) bytes, 8-byte aligned; 0 for sizes the entry refuses) and the slots are folded in chunk order. Only the
+ *   tiles on and below the diagonal are computed; C[i][j], j <= i, is stored at (i, j) and (j, i): C is symmetric bit for bit. Plain f64
+ *   fma. The caller divides by N - 1.
+ * pb_sqdist: D2[i ldd + j] = sum_f (A[i lda + f] - B[j ldb + f])^2 for A (N, d), B (M, d) f32, 1 <= d <= 4096, 1 <= N, M <= 2^20: one f32 fma
+ *   chain over f = 0 .. d - 1 per element (never |a|^2 + |b|^2 - 2ab), so equal rows give exactly 0 and the value depends on no tiling.
+ *   64 x 64 tile per workgroup, 4 x 4 per thread, slabs of 32 features staged through LDS (16-byte loads where A / B and lda / ldb allow
+ *   them). A and B may be the same buffer; D2 must not overlap them.
+ * pb_knn_radius: rad[i] = the k-th smallest of D2[i ldd + j] over 0 <= j < N, j != r0 + i, for the rows r0 .. r0 + n - 1 of a set's own
+ *   (N, N) matrix passed as the (n, N) block D2; 1 <= n, r0 >= 0, r0 + n <= N <= 2^24, 1 <= k <= min(N - 1, 64). A radix selection on the
+ *   bits: the result is a value of the input.
+ * pb_ball_counts: over D2 (n, M) with ldd, rad_ref (M), rad_gen (n): row_hits[i] += #{j : D2[i][j] < rad_ref[j]}, col_hits[j] += #{i :
+ *   D2[i][j] < rad_ref[j]}, col_hits_gen[j] += #{i : D2[i][j] < rad_gen[i]} (int32, zeroed by the caller; strict <). Integer atomics:
+ *   feeding the rows in blocks gives the one-shot counts. 1 <= n <= 2^20, 1 <= M <= 2^24. */
+int64_t pb_embed_ws_bytes(int64_t N, int32_t d);
+int pb_pool_rows(const void* H, int64_t ldh, int32_t dtype, const float* mask, float* out, int64_t ldo, int32_t* count, int32_t B, int32_t S,
+                 int32_t d, void* stream);
+int pb_embed_moments(const float* X, int64_t ldx, int64_t N, int32_t d, double* mean, double* C, int64_t ldc, void* ws, void* stream);
+int pb_sqdist(const float* A, int64_t lda, const float* B, int64_t ldb, float* D2, int64_t ldd, int32_t N, int32_t M, int32_t d, void* stream);
+int pb_knn_radius(const float* D2, int64_t ldd, int32_t n, int32_t N, int32_t r0, int32_t k, float* rad, void* stream);
+int pb_ball_counts(const float* D2, int64_t ldd, int32_t n, int32_t M, const float* rad_ref, const float* rad_gen, int32_t* row_hits,
+                   int32_t* col_hits, int32_t* col_hits_gen, void* stream);
+
 /* ---- device-side corruption for the pre-train step (distributional counterpart of gen_mask's
  * TokenMask n=0 branch, pretrain.py:276-295) and decoder shift-right (pretrain.py:132-139) ---------*/
 int pb_shift_right(const int16_t* ids, const int16_t* sos_row /*device 8*/, int16_t* out, int32_t B, int32_t S, void* stream);

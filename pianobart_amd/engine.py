@@ -20,6 +20,7 @@ from . import ops, rowpack
 
 from ._lib import LIB, PB_BF16, PB_F32, PB_F32X3, PBError
 from .generation import LN_EPS, GenerationMixin, check_prefix, check_samples, sample_seed  # noqa: F401 (the helpers stay importable from here)
+from .embedding import EmbeddingMixin
 from .scoring import ScoringMixin
 
 _WGRAD_STREAM = int(os.environ.get('PB_WGRAD_STREAM', '7'))            # second HIP stream, bits: 1 = weight-gradient GEMMs, 2 = cross-attention K/V projections, 4 = backward GEMMs as ordinary grids (0: everything on one stream, for A/B)
@@ -93,7 +94,7 @@ def _new_stream(device):
     return torch.cuda.ExternalStream(st.value, device=device)
 
 
-class Engine(GenerationMixin, ScoringMixin):
+class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
     def __init__(self, pianobart, mask_lm, precision='bf16'):
         if precision not in ('bf16', 'fp32', 'bf16x3'):
             raise PBError('precision must be "bf16", "fp32" or "bf16x3"')

@@ -222,6 +222,19 @@ class PianoBart(nn.Module):
             return SimpleNamespace(last_hidden_state=enc_h)
         return SimpleNamespace(last_hidden_state=dec_h, encoder_last_hidden_state=enc_h)
 
+    def embed(self, input_ids_encoder, encoder_attention_mask=None, return_counts=False):
+        """One vector per piece: the encoder's last hidden state mean-pooled over the rows whose mask is not 0 (None: every row), a (B, d)
+        float32 device tensor (embedding.py). One encoder-only forward without dropout and without an autograd graph, in the
+        model's own precision; the sum over the rows runs in float64 in a fixed order (pb_pool_rows). A row with no visible position gives a
+        zero vector; return_counts=True returns (emb, count) with count (B) int32 = the pooled rows of each piece."""
+        ids = torch.as_tensor(input_ids_encoder)
+        if ids.dim() != 3 or int(ids.shape[2]) != 8 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise PBError('embed: input_ids_encoder must be (B, S, 8) integers (got %s %s)' % (tuple(ids.shape), ids.dtype))
+        if ids.device.type != 'cuda':
+            raise PBError('pianobart_amd needs HIP device tensors (got %s); there is no CPU path' % ids.device)
+        emb, count = self._get_engine().embed(ops.ids_to_i16(ids), encoder_attention_mask)
+        return (emb, count) if return_counts else emb
+
     def get_rand_tok(self):
         rand = [0] * 8
         for i in range(8):
@@ -449,6 +462,10 @@ class PianoBartLM(nn.Module):
                                  samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order,
                                  allow=decoder_allow)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
+
+    def embed(self, input_ids_encoder, encoder_attention_mask=None, return_counts=False):
+        """PianoBart.embed of the backbone: one (d) float32 vector per piece."""
+        return self.pianobart.embed(input_ids_encoder, encoder_attention_mask, return_counts)
 
     def score(self, input_ids_encoder, target_ids, encoder_attention_mask=None, start=None, length=None, device_num=-1):
         """Teacher-forced scores of B pieces (scoring.py; the forward-only quantity of Ablation.py:126-166): what the model thinks of

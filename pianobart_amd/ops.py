@@ -617,6 +617,128 @@ def kde_eval(D, grid, h, upper=False, ws=None):
     return dens
 
 
+SQDIST_MAX_D = 4096                                         # the widest row of pb_sqdist and pb_embed_moments
+KNN_MAX_K = 64                                              # the largest k of pb_knn_radius
+
+
+def _rows_f32(t, what, cols=None):
+    """(address, rows, cols, leading dimension) of a 2-D f32 tensor whose rows are contiguous (a column or row slice of a wider buffer is one).
+    Checked on the host: a tensor that is not on the device is refused last, by _p."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 \
+            or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or (cols is not None and t.shape[1] != cols):
+        raise PBError('%s must be a 2-D f32 tensor%s with contiguous rows (got %s)'
+                      % (what, '' if cols is None else ' of %d columns' % cols, (tuple(t.shape), t.dtype, t.stride()) if torch.is_tensor(t) else type(t)))
+    return _p(t), t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _vec(t, dtype, n, what):
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise PBError('%s must be a contiguous %s tensor of %d entries' % (what, str(dtype).replace('torch.', ''), n))
+    return _p(t)
+
+
+def pool_rows(H, mask=None, out=None):
+    """pb_pool_rows: (out (B, d) f32, count (B) int32) with out[b] = the mean of the rows H[b, s] whose mask[b, s] != 0 (mask (B, S) f32 or
+    None = all rows) and count[b] their number. H (B, S, d) bf16 or f32 with contiguous (b, s) rows at one leading dimension (a column slice
+    of a (B, S, D) buffer is one). The sum runs in f64 in a fixed order; a row without a visible position is a zero vector."""
+    if not torch.is_tensor(H) or H.dim() != 3 or H.dtype not in (torch.float32, torch.bfloat16) or min(H.shape) < 1:
+        raise PBError('pool_rows: H must be a (B, S, d) bf16 or f32 tensor (got %s)' % ((tuple(H.shape), H.dtype) if torch.is_tensor(H) else type(H),))
+    B, S, d = H.shape
+    ldh = H.stride(1) if S > 1 else (H.stride(0) if B > 1 else d)
+    if H.stride(2) != 1 or ldh < d or (B > 1 and H.stride(0) != S * ldh):
+        raise PBError('pool_rows: the rows of H must be contiguous and evenly spaced (strides %s)' % (H.stride(),))
+    if S > 65536 or B > 65535:
+        raise PBError('pool_rows: B = %d, S = %d out of range (B <= 65535, S <= 65536)' % (B, S))
+    pm = None
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype != torch.float32 or tuple(mask.shape) != (B, S) or not mask.is_contiguous():
+            raise PBError('pool_rows: mask must be a contiguous (%d, %d) f32 tensor' % (B, S))
+        pm = _p(mask)
+    ph = _p(H)
+    if out is None:
+        out = torch.empty((B, d), dtype=torch.float32, device=H.device)
+    po, _, _, ldo = _rows_f32(out, 'pool_rows: out', d)
+    if out.shape[0] != B:
+        raise PBError('pool_rows: out holds %d rows for %d pieces' % (out.shape[0], B))
+    count = torch.empty(B, dtype=torch.int32, device=H.device)
+    LIB.call('pb_pool_rows', ph, ldh, dtype_code(H.dtype), pm, po, ldo, _p(count), B, S, d, _stream())
+    return out, count
+
+
+def embed_ws(N, d, device):
+    """The workspace of one embed_moments call over an (N, d) set (reusable by the next call of that size on the same stream)."""
+    return torch.empty(max(1, LIB.query('pb_embed_ws_bytes', int(N), int(d)) // 8), dtype=torch.float64, device=device)
+
+
+def embed_moments(X, ws=None):
+    """pb_embed_moments: (mean (d) f64, C (d, d) f64) of X (N, d) f32, N >= 2: C = sum_n (x_n - mean)(x_n - mean)^T, symmetric bit for bit;
+    the caller divides by N - 1."""
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise PBError('embed_moments: X must be an (N, d) f32 tensor')
+    N, d = X.shape
+    if N < 2:
+        raise PBError('embed_moments: N = %d; a covariance needs at least 2 rows' % N)
+    if not 1 <= d <= SQDIST_MAX_D:
+        raise PBError('embed_moments: d = %d out of range (1 .. %d)' % (d, SQDIST_MAX_D))
+    px, _, _, ldx = _rows_f32(X, 'embed_moments: X')
+    need = LIB.query('pb_embed_ws_bytes', N, d)
+    if ws is None:
+        ws = embed_ws(N, d, X.device)
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() * 8 < need:
+        raise PBError('embed_moments: ws must be a contiguous f64 tensor of at least %d bytes (embed_ws)' % need)
+    mean = torch.empty(d, dtype=torch.float64, device=X.device)
+    C = torch.empty((d, d), dtype=torch.float64, device=X.device)
+    LIB.call('pb_embed_moments', px, ldx, N, d, _p(mean), _p(C), d, _p(ws), _stream())
+    return mean, C
+
+
+def sqdist(A, B, out=None):
+    """pb_sqdist: D2 (N, M) f32 with D2[i, j] = |A[i] - B[j]|^2 for A (N, d), B (M, d) f32 with contiguous rows, 1 <= d <= 4096; one f32
+    chain of squared differences per element: equal rows give exactly 0. out: an (N, M) f32 tensor with contiguous rows."""
+    if not torch.is_tensor(A) or not torch.is_tensor(B) or A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[1]:
+        raise PBError('sqdist: A (N, d) and B (M, d) must have the same width (got %s and %s)'
+                      % (tuple(A.shape) if torch.is_tensor(A) else type(A), tuple(B.shape) if torch.is_tensor(B) else type(B)))
+    d = A.shape[1]
+    if not 1 <= d <= SQDIST_MAX_D:
+        raise PBError('sqdist: d = %d out of range (1 .. %d)' % (d, SQDIST_MAX_D))
+    pa, N, _, lda = _rows_f32(A, 'sqdist: A')
+    pb, M, _, ldb = _rows_f32(B, 'sqdist: B')
+    if out is None:
+        out = torch.empty((N, M), dtype=torch.float32, device=A.device)
+    po, n_out, _, ldd = _rows_f32(out, 'sqdist: out', M)
+    if n_out != N:
+        raise PBError('sqdist: out is %s for %d x %d rows' % (tuple(out.shape), N, M))
+    LIB.call('pb_sqdist', pa, lda, pb, ldb, po, ldd, N, M, d, _stream())
+    return out
+
+
+def knn_radius(D2, k, r0=0):
+    """pb_knn_radius: rad (n) f32, rad[i] = the k-th smallest of D2[i, j] over j != r0 + i, for the (n, N) block D2 = the rows r0 .. r0 + n - 1
+    of a set's own (N, N) squared distances. 1 <= k <= min(N - 1, 64)."""
+    if not torch.is_tensor(D2) or D2.dim() != 2:
+        raise PBError('knn_radius: D2 must be an (n, N) f32 tensor')
+    n, N = D2.shape
+    k, r0 = int(k), int(r0)
+    if N < 2 or r0 < 0 or r0 + n > N:
+        raise PBError('knn_radius: rows r0 = %d .. %d of an (N, N) matrix with N = %d' % (r0, r0 + n, N))
+    if not 1 <= k <= min(N - 1, KNN_MAX_K):
+        raise PBError('knn_radius: k = %d out of range (1 .. min(N - 1, %d) = %d)' % (k, KNN_MAX_K, min(N - 1, KNN_MAX_K)))
+    pd, _, _, ldd = _rows_f32(D2, 'knn_radius: D2')
+    rad = torch.empty(n, dtype=torch.float32, device=D2.device)
+    LIB.call('pb_knn_radius', pd, ldd, n, N, r0, k, _p(rad), _stream())
+    return rad
+
+
+def ball_counts(D2, rad_ref, rad_gen, row_hits, col_hits, col_hits_gen):
+    """pb_ball_counts: over the block D2 (n, M) of generated rows against reference columns add into the int32 counters (zeroed by the caller)
+    row_hits (n) and col_hits (M) the entries with D2[i, j] < rad_ref[j], and into col_hits_gen (M) those with D2[i, j] < rad_gen[i]."""
+    pd, n, M, ldd = _rows_f32(D2, 'ball_counts: D2')
+    args = (_vec(rad_ref, torch.float32, M, 'ball_counts: rad_ref'), _vec(rad_gen, torch.float32, n, 'ball_counts: rad_gen'),
+            _vec(row_hits, torch.int32, n, 'ball_counts: row_hits'), _vec(col_hits, torch.int32, M, 'ball_counts: col_hits'),
+            _vec(col_hits_gen, torch.int32, M, 'ball_counts: col_hits_gen'))
+    LIB.call('pb_ball_counts', pd, ldd, n, M, *args, _stream())
+
+
 RUNS_TILE = 32                                              # corpus pieces per workgroup of pb_shared_runs (pb_runs_tile; DESIGN.md 11)
 RUNS_MAX_S = 4096                                           # rows of a piece / keys of a row that pb_piece_keys and pb_shared_runs take
 NO_KEY = 0xFFFFFFFF
