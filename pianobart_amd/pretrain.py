@@ -14,7 +14,8 @@ because nn.DataParallel (pretrain.py:63-65) is exactly what this engine replaces
 ONE batch of `--batch_size` samples over the GPUs; here every rank draws its `batch_size / world` share of
 the same global batch: the shuffle + 85/15 split is drawn on rank 0 and broadcast, each epoch's order is a
 permutation seeded identically on all ranks, rank r takes every world-th sample of it (DistributedSampler),
-and the corruption / dropout streams are keyed by the rank so that no two ranks draw the same decisions.
+and the corruption / dropout streams are keyed by the rank so that no two ranks draw the same decisions. Every process initialises its
+own model from its own random state; the Pretrainer broadcasts rank 0's parameters once, so the replicas start, and stay, bit-identical.
 
 Input: the `.npy` files stay memory-mapped (pianobart_amd/data.py); concatenate, shuffle and split act on an
 index, and a batch reaches the device as int16 rows (16 bytes per token) -- what the kernels read.
@@ -232,8 +233,16 @@ class Pretrainer:
         self.rank = int(os.environ.get('RANK', 0))
         if self.world > 1:
             from .parallel import GradReducer
-            _dist_init(self.device)
+            dist = _dist_init(self.device)
             self.reducer = GradReducer(self.engine, self.world)
+            # Every rank built its own model, and torch's default generator is seeded differently in every
+            # process (the reference seeds nothing, and nn.DataParallel replicated ONE model,
+            # pretrain.py:63-65): rank 0's parameters become everyone's. The exchange sums gradients, so
+            # replicas that start apart stay apart for good. The modules alias P32 (Engine.bind); the bf16
+            # shadow follows by force.
+            self.engine.finish_updates()
+            dist.broadcast(self.engine.P32, 0)
+            self.engine.refresh_shadow(force=True)
         self._w = np.array([len(pianobart.e2w[k]) for k in pianobart.e2w], dtype=np.float64)   # e2w dict order (pretrain.py:185-189)
         self._id_limits = np.array(pianobart.n_tokens, dtype=np.int64)                      # table sizes, classes order (PianoBart.py:29-31)
         # corruption stream keyed by the rank: ranks must not draw the same positions (the dropout stream is keyed in Engine)
@@ -478,6 +487,11 @@ class _RunLog:
             with open(os.path.join(self.dir, 'log'), 'a') as outfile:
                 outfile.write(text)
 
+    def save(self, trainer, *state):
+        """trainer.save_checkpoint(*state, model.ckpt) on rank 0; the other ranks hold the same bits and write nothing."""
+        if self.rank0:
+            trainer.save_checkpoint(*state, self.filename)
+
 
 def pretrain(argv=None):
     """The pre-training driver (reference: main.py:17-100): same flags, prints, checkpoint and log artefacts; the loop itself is
@@ -528,8 +542,7 @@ def pretrain(argv=None):
         stale = 0 if is_best else stale + 1
         print('epoch: {}/{} | Train Loss: {} | Train acc: {} | Valid Loss: {} | Valid acc: {}'.format(
             epoch + 1, args.epochs, train_loss, train_acc, valid_loss, valid_acc))
-        if run.rank0:
-            trainer.save_checkpoint(epoch, best_acc, valid_acc, valid_loss, train_loss, is_best, run.filename)
+        run.save(trainer, epoch, best_acc, valid_acc, valid_loss, train_loss, is_best)
         run.write('Epoch {}: train_loss={}, train_acc={}, valid_loss={}, valid_acc={}\n'.format(epoch + 1, train_loss, train_acc, valid_loss, valid_acc))
     end_t = time.time()
     closing = f'Time cost in pretrain of PianoBart is {end_t - start_t}, start_t = {start_t}, end_t = {end_t}'

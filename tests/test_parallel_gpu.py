@@ -3,7 +3,8 @@
 With the GradReducer installed the engine (a) announces flat gradient ranges as their kernels are enqueued -- they must tile
 [0, n_total) exactly once -- (b) launches its backward GEMMs as ordinary grids instead of persistent ones, and (c) hands every
 bucket to the exchange from the stream that produced it. At world size 1 the exchange is the identity (f32 mode) or one bf16
-rounding (bf16 mode), so the step must reproduce the plain step bit for bit / to bf16 rounding."""
+rounding (bf16 mode), so the step must reproduce the plain step bit for bit / to bf16 rounding.
+Two ranks that do exchange bytes (gloo, both on one device): tests/test_parallel_two_ranks_gpu.py."""
 import os
 
 import numpy as np
