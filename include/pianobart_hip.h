@@ -657,6 +657,20 @@ int pb_corrupt_replay(const int16_t* ids, int16_t* out, float* loss_mask, const 
                       double mask_percent, const int32_t* decisions, int64_t dec_stride, const int16_t* rand_rows,
                       const int16_t* pad_row, const int16_t* mask_row, void* stream);
 int64_t pb_corrupt_replay_stride(int32_t S);
+/* Whole-piece augmentation in front of the corruption: piece b of ids (B,S,8) int16 is shifted along three axes, a = 0
+ * pitch (head 3), 1 velocity (head 5), 2 tempo (head 7), by one amount per axis; the other five heads are copied. Per axis:
+ *   coord (3, 1088) int16 device: coord[a][id] = the id's coordinate >= 0, or -1 = never touched (specials, percussion pitches)
+ *   id_at (3, 1088) int16 device: id_at[a][c] = the id of coordinate c, 0 <= c < ncoord (total: the inverse of coord)
+ *   plan  (3, 6) int32 HOST: lo, hi, blo, bhi, ncoord, thresh -- the request lo <= 0 <= hi, the coordinate bounds 0 <= blo <= bhi < ncoord
+ *         <= 1088, thresh = the apply threshold as uint32 bits (0xFFFFFFFF: always)
+ * Piece b, axis a: cmin, cmax = the extremes of coord[a][ids[b, i, head]] over the positions with a coordinate (none: s = 0); flo =
+ * max(lo, blo - cmin), fhi = min(hi, bhi - cmax); flo > 0 or fhi < 0 (the piece lies outside the bounds, or fills them): s = 0; else r =
+ * philox4x32(0, b, a, 0xA06) under the key (seed low, high), s = flo + ((uint64)r.x * (fhi - flo + 1) >> 32), and s = 0 if thresh !=
+ * 0xFFFFFFFF and r.y >= thresh. shifts[b * 3 + a] = s (int32 device); out = id_at[a][coord + s] where the id has a coordinate, else the id.
+ * So no note is clipped or wrapped. out == ids (in place) is allowed, a partial overlap is refused; 1 <= B <= 65535, 1 <= S <= 65536; ids,
+ * out and the tables 16-byte aligned. Equal inputs and seed give equal bytes. tests/augment_ref.py restates it. */
+int pb_augment(const int16_t* ids, int16_t* out, int32_t* shifts, int32_t B, int32_t S, const int16_t* coord, const int16_t* id_at,
+               const int32_t* plan, uint64_t seed, void* stream);
 
 /* ---- K14: fine-tune heads, exact f32 (model.py:128-143 SelfAttention, :165-218 SequenceClassification, :220-232 Excitation,
  * :236-272 TokenClassification; loss finetune.py:121-129). Their matrix products are pb_gemm (f32) calls.

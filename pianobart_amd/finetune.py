@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from . import augment as _augment
 from . import heads, ops
 from ._lib import LIB, PBError
 from .model import SequenceClassification, TokenClassification, checkpoint_state_dict
@@ -44,6 +45,7 @@ def get_args_finetune(argv=None):
     parser.add_argument('--weight', type=float, default=None, help='weight of regularization')
     parser.add_argument('--error_correction', action='store_true')
     parser.add_argument('--precision', choices=['bf16', 'fp32', 'bf16x3'], default='bf16', help='backbone arithmetic (not in the reference)')
+    _augment.add_arguments(parser)
     args = parser.parse_args(argv)
     if args.class_num is None:
         args.class_num = {'melody': 4, 'velocity': 7, 'composer': 8, 'emotion': 4}[args.task]
@@ -184,6 +186,10 @@ class FinetuneTrainer:
         # backbone's through the engine's bucket exchange (summed, then scaled by 1 / world in the optimizer step), the head parameters'
         # with one all-reduce of the head optimizer's flat gradient buffer. data_parallel=True installs this at world size 1 (tests).
         self.world = int(os.environ.get('WORLD_SIZE', 1))
+        self.rank = int(os.environ.get('RANK', 0))
+        # --augment: an augment.AugmentPlan (None: off) and --augment_seed. The labels do not move with the input: melody's are per position,
+        # composer's and emotion's per piece; the velocity task must not shift the velocity axis (augment.check_task, in the driver)
+        self.augment, self.augment_seed, self._train_epoch = None, 0, -1
         self.reducer = None
         if self.world > 1 or data_parallel:
             import torch.distributed as dist
@@ -239,8 +245,16 @@ class FinetuneTrainer:
         self.model.eval()
         return self.iteration(self.test_data, 2, self.SeqClass)
 
+    def augment_batch(self, x, seed):
+        """The (B, S, 8) ids of a training batch, augmented on the device (augment.apply); the shifts stay in self.last_shifts."""
+        out16, self.last_shifts = _augment.apply(ops.ids_to_i16(x.to(self.device).long()), self.augment, seed)
+        return out16.long()
+
     def iteration(self, training_data, mode, seq):
         total_acc, total_cnt, total_loss = 0.0, 0, 0.0
+        aug_index = 0
+        if mode == 0:
+            self._train_epoch += 1                                           # training epochs so far: part of a batch's augmentation seed
         self.model.train(mode == 0)
         sampler = getattr(training_data, 'sampler', None)
         if mode == 0 and hasattr(sampler, 'set_epoch'):                      # rank-sharded training set: a new permutation per epoch
@@ -250,6 +264,9 @@ class FinetuneTrainer:
         with torch.set_grad_enabled(mode == 0):
             for x, y in training_data:
                 batch = x.shape[0]
+                if mode == 0 and self.augment is not None:                   # training batches only
+                    x = self.augment_batch(x, _augment.batch_seed(self.augment_seed, self.rank, self._train_epoch, aug_index))
+                    aug_index += 1
                 x, y, attn, inputs = prepare_inputs(x, y, self.device, self.pianobart.bar_pad_word, self.class_num, seq, self.error)
                 y_hat = self.model(**inputs)
                 output = torch.from_numpy(np.argmax(y_hat.detach().cpu().numpy(), axis=-1)).to(self.device)
@@ -348,6 +365,7 @@ def finetune(argv=None):
     args = get_args_finetune(argv)
     print('Loading Dictionary')
     e2w, w2e = _load_vocab(args.dict_file)
+    plan = _augment.from_args(args, e2w, task=args.task)                       # refused here, before any data is loaded
     print('\nLoading Dataset')
     (train_loader, valid_loader, test_loader), test_shape = _finetune_loaders(args)
     print('\nBuilding BART model')
@@ -362,6 +380,7 @@ def finetune(argv=None):
     print('\nCreating Finetune Trainer')
     trainer = FinetuneTrainer(pianobart, train_loader, valid_loader, test_loader, args.lr, args.class_num, args.hs, test_shape, args.cpu,
                               args.cuda_devices[:1], None, args.task in ('composer', 'emotion'), args.error_correction, args.weight)
+    trainer.augment, trainer.augment_seed = plan, args.augment_seed
     print('\nTraining Start')
     save_dir = os.path.join('result/finetune/', args.task + '_' + args.name)
     os.makedirs(save_dir, exist_ok=True)

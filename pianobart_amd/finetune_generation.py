@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import torch
 
+from . import augment as _augment
 from . import ops
 from ._lib import PBError
 from .model import PianoBartLM, checkpoint_state_dict
@@ -50,6 +51,7 @@ def get_args_generation(argv=None):
     parser.add_argument('--precision', choices=['bf16', 'fp32', 'bf16x3'], default='bf16', help='backbone arithmetic (not in the reference)')
     parser.add_argument('--accum_steps', type=_positive_int, default=1,
                         help='gradient accumulation: one optimizer step over this many consecutive training batches (not in the reference)')
+    _augment.add_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -84,6 +86,8 @@ class GenerationTrainer:
         self.lr = lr
         self.accum_steps = 1                                                 # --accum_steps: training batches per optimizer step
         self.world = int(os.environ.get('WORLD_SIZE', 1))
+        self.rank = int(os.environ.get('RANK', 0))
+        self.augment, self.augment_seed, self._train_epoch = None, 0, -1     # --augment: an augment.AugmentPlan (None: off), --augment_seed
         self.reducer = None
         if self.world > 1:                                                   # one process per GPU, same exchange as the pre-train step
             import torch.distributed as dist
@@ -109,8 +113,18 @@ class GenerationTrainer:
         self.model.eval()
         return self.iteration(self.test_data, 2)
 
+    def augment_pair(self, x16, y16, seed):
+        """The prompt x16 and the continuation y16 are ONE piece: they are augmented as the (B, 2S, 8) rows [x, y], so both halves carry the
+        same shifts, clamped by the extremes of the whole. Returns (x16, y16, shifts)."""
+        S = x16.shape[1]
+        both, shifts = _augment.apply(torch.cat([x16, y16], dim=1), self.augment, seed)
+        return both[:, :S].contiguous(), both[:, S:].contiguous(), shifts
+
     def iteration(self, training_data, mode):
         eng, pad = self.engine, int(self.pianobart.bar_pad_word)
+        aug_index = 0
+        if mode == 0:
+            self._train_epoch += 1                                           # training epochs so far: part of a batch's augmentation seed
         total_acc, total_loss = np.zeros(8), 0.0
         all_output, cnt = (torch.empty(self.testset_shape) if mode == 2 else None), 0
         sampler = getattr(training_data, 'sampler', None)
@@ -129,6 +143,9 @@ class GenerationTrainer:
                 x, y = x.to(self.device).long(), y.to(self.device).long()
                 B, S = x.shape[:2]
                 x16, y16 = ops.ids_to_i16(x), ops.ids_to_i16(y)
+                if mode == 0 and self.augment is not None:                   # training batches only
+                    x16, y16, self.last_shifts = self.augment_pair(x16, y16, _augment.batch_seed(self.augment_seed, self.rank, self._train_epoch, aug_index))
+                    aug_index += 1
                 attn_enc = (x16[:, :, 0] != pad).float()
                 loss_mask = attn_enc[:, :, None].expand(B, S, 8).contiguous()   # y_shift = x: the decoder mask is the encoder's
                 micro.append((x16, y16, attn_enc, loss_mask))
@@ -221,6 +238,7 @@ def finetune_generation(argv=None):
     print("\nCreating Finetune Trainer")
     trainer = GenerationTrainer(pianobart, loaders[0], loaders[1], loaders[2], args.lr, y_test.shape, args.cpu, args.cuda_devices, model)
     trainer.accum_steps = args.accum_steps
+    trainer.augment, trainer.augment_seed = _augment.from_args(args, e2w), args.augment_seed
     print("\nTraining Start")
     save_dir = os.path.join('result/finetune/generation_' + args.name)
     os.makedirs(save_dir, exist_ok=True)

@@ -1063,6 +1063,13 @@ def corrupt_replay(ids16, out16, loss_mask, choice, mask_percent, decisions, ran
              decisions.shape[1], _p(rand_rows), pr, mr, _stream())
 
 
+def augment(ids16, out16, shifts, coord, id_at, plan18, seed):
+    """pb_augment (include/pianobart_hip.h): ids16 / out16 (B,S,8) int16 device (out16 may be ids16), shifts (B,3) int32 device, coord / id_at
+    (3, HEAD_MAX) int16 device, plan18 a HOST ctypes int32[18] (augment.AugmentPlan builds the three). Refusals raise PBError."""
+    B, S = ids16.shape[:2]
+    LIB.call('pb_augment', _p(ids16), _p(out16), _p(shifts), B, S, _p(coord), _p(id_at), plan18, ctypes.c_uint64(seed), _stream())
+
+
 def key_extent(key_mask, kmax):
     B, Sk = key_mask.shape
     LIB.call('pb_key_extent', _p(key_mask), _p(kmax), B, Sk, _stream())

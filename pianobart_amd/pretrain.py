@@ -30,6 +30,7 @@ import time
 import numpy as np
 import torch
 
+from . import augment as _augment
 from . import ops
 from ._lib import PBError
 from .data import BalancedDistributedSampler, MidiDataset, OctupleShards, sequence_lengths
@@ -68,6 +69,7 @@ def get_args_pretrain(argv=None):
     parser.add_argument('--quiet', action='store_true', help='do not print the two per-step Loss/Acc lines')
     parser.add_argument('--accum_steps', type=_positive_int, default=1,
                         help='gradient accumulation: one optimizer step over this many consecutive loader batches (global loss normalisation)')
+    _augment.add_arguments(parser)
     parser.add_argument('--resume', type=str, default='', help='continue from a checkpoint THIS driver wrote: weights, LM heads, AdamW moments and step, epoch, best_acc')
     return parser.parse_args(argv)
 
@@ -248,6 +250,8 @@ class Pretrainer:
         # corruption stream keyed by the rank: ranks must not draw the same positions (the dropout stream is keyed in Engine)
         self._step_seed = (0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * self.rank) & 0xFFFFFFFFFFFFFFFF
         self._epoch = 0
+        self.augment, self.augment_seed = None, 0               # --augment: an augment.AugmentPlan (None: off) and --augment_seed
+        self._train_epoch = 0                                   # the epoch of the running train() call: part of a batch's augmentation seed
 
     # ---- reference API ------------------------------------------------------------------------------
     def train(self):
@@ -255,6 +259,7 @@ class Pretrainer:
         sampler = getattr(self.train_data, 'sampler', None)
         if hasattr(sampler, 'set_epoch'):                     # DistributedSampler: a new, rank-consistent permutation every epoch
             sampler.set_epoch(self._epoch)
+        self._train_epoch = self._epoch
         self._epoch += 1
         return self.iteration(self.train_data, self.max_seq_len)
 
@@ -324,8 +329,10 @@ class Pretrainer:
         ops.corrupt(ids16, out, lm, ch, None, float(self.mask_percent), self._step_seed, pb.pad_word_np, pb.mask_word_np, pb.n_tokens)
         return out, lm, ch
 
-    def prepare_batch(self, ori_seq_batch):
-        """pretrain.py:125-153 on the device: corrupted encoder ids, shift-right decoder ids, loss mask, attention masks."""
+    def prepare_batch(self, ori_seq_batch, augment_seed=None):
+        """pretrain.py:125-153 on the device: corrupted encoder ids, shift-right decoder ids, loss mask, attention masks. augment_seed (a
+        training batch under --augment; None: the rows stay as they are): the target is augmented behind the id check, and the encoder ids,
+        the decoder ids and the loss mask all derive from the augmented rows; the shifts stay in self.last_shifts."""
         if ori_seq_batch.device.type == 'cpu':                             # nn.Embedding's IndexError (PianoBart.py:15-16), on the loader's host copy
             a = ori_seq_batch.numpy()
             if a.size and (a.min() < 0 or (a.reshape(-1, 8).max(0) >= self._id_limits).any()):
@@ -336,6 +343,8 @@ class Pretrainer:
             tgt16 = self.engine.note_ids(tgt16, owned=tgt16.data_ptr() != ori_seq_batch.data_ptr())   # (a caller's int16 tensor is checked on a copy) without draining the stream (Engine._raise_if_bad_ids); the corrupted and the
             self.engine._queue_id_verdict()                                # shifted ids derive from these and from in-range specials / random tokens
         B, S = tgt16.shape[:2]
+        if augment_seed is not None and self.augment is not None:
+            tgt16, self.last_shifts = _augment.apply(tgt16, self.augment, augment_seed)
         enc16, loss_mask, _ = self._corrupt(tgt16)
         dec16 = torch.empty_like(tgt16)
         ops.shift_right(tgt16, self.engine.sos16, dec16, B, S)
@@ -380,12 +389,22 @@ class Pretrainer:
         if K < 1:
             raise PBError('accum_steps must be >= 1 (got %r)' % (self.accum_steps,))
 
+        aug_index = 0                                           # loader batches of this epoch so far: the last part of a batch's augmentation seed
+
+        def prepare(batch):
+            nonlocal aug_index
+            if not train or self.augment is None:               # validation, and anything with train=False, is never augmented
+                return self.prepare_batch(batch)
+            seed = _augment.batch_seed(self.augment_seed, self.rank, self._train_epoch, aug_index)
+            aug_index += 1
+            return self.prepare_batch(batch, augment_seed=seed)
+
         def stage(group):
             """The batches of one optimizer step, prepared on the side stream; with more than one, the sum of their loss-mask counts too (the
             heads are normalised by the counts of the WHOLE step, which every micro-batch must know before its backward)."""
             prep.wait_stream(main)                                      # everything the previous batches were given (their buffers may be recycled)
             with torch.cuda.stream(prep):
-                micro = [self.prepare_batch(batch) for batch in group]
+                micro = [prepare(batch) for batch in group]
                 total = None
                 if len(micro) > 1:
                     total = eng.mask_counts(micro[0][3])
@@ -519,6 +538,7 @@ def pretrain(argv=None):
                          args.cpu, args.cuda_devices)
     trainer.quiet = args.quiet
     trainer.accum_steps = args.accum_steps
+    trainer.augment, trainer.augment_seed = _augment.from_args(args, e2w), args.augment_seed
     print("\nTraining Start")
     run = _RunLog(args.name, rank == 0)
     print("   save model at {}".format(run.filename))
