@@ -11,7 +11,14 @@
     order at a few units of 2^-24. K on both sides of every 64-column block edge, K = 768 (two 512-column pieces of the trailing update).
   * a zero row and column: info = 1 + j; through merge_state_dicts a PBError that names the weight.
   * the whole merge of a 1 + 1 layer model against tests/regmean_ref.py in float64, held to 4 times the float32 recipe's own error.
-  * the pass against float64 forward hooks on the oracle's classifier; the command lines end to end."""
+  * the pass against float64 forward hooks on the oracle's classifier; the command lines end to end.
+  * the reference's own recorded regmean_merging results on a toy classifier (tests/golden/g17_regmean.npz, read through the helpers of
+    tests/test_regmean_cpu.py): merge_state_dicts per case and N, every solved weight within 4 times the recorded output's own distance from
+    float64 (at least one float32 ulp), every averaged parameter equal to the recording bit for bit; q / k as one shared Gram tensor and as
+    two copies; pb_gram_accum over the recorded activations, batch by batch and in one call, f32 and bf16, held to 4 times the recorded
+    matrix's own figure; a 2-D-input layer cut to fewer rows than inputs is refused by name. Two deviations from the reference stay as they
+    are: a sum that is not positive definite is refused where the reference inverts whatever it is given, and the pass gives
+    encoder_linear.weight no Gram matrix (merge.regmean_pass prints it) -- the toy has no such layer, every Linear of it is solved."""
 import copy
 import os
 
@@ -19,6 +26,7 @@ import pytest
 import torch
 
 from tests import regmean_ref as R
+from tests.test_regmean_cpu import CASE_IDS, GOLDEN_CASES, MARGIN, ULP, gram_figure, golden, golden_activations, golden_truth, rel_error
 
 gpu = pytest.mark.gpu
 TS = [1, 2, 33, 63, 64, 65, 255, 256, 257, 1000]
@@ -473,3 +481,100 @@ def test_regmean_and_model_merge_command_lines(tmp_path, capsys):
     assert all(bool(torch.isfinite(v).all()) for v in merged.values() if v.is_floating_point())
     with pytest.raises(PBError, match=r'regmean_merging.*pianobart_amd\.regmean'):
         model_merge(mflags + ['--method', 'regmean_merging'])
+
+
+# ---- the reference's recorded results ---------------------------------------------------------------------------------------------------------
+def _merge_recorded(case, N, grams=None):
+    from pianobart_amd import merge as M
+    g = golden()
+    c = g.cases[(case, N)]
+    grams = g.grams[:N] if grams is None else grams
+    grams = [{k: v for k, v in G.items() if k in c.kept} for G in grams]   # an excluded weight is not merged: its matrix is not handed over
+    return M.merge_state_dicts(g.pre, g.fts[:N], method='regmean_merging', regmean_weights=grams, reduce_non_diagonal_ratio=c.ratio, exclude=c.exclude)
+
+
+def _check_against_recording(case, N, got, tag='device'):
+    g = golden()
+    c = g.cases[(case, N)]
+    assert list(got) == list(g.pre)
+    for name in g.pre:
+        if name not in c.kept:
+            assert got[name].numpy().tobytes() == g.pre[name].numpy().tobytes(), name
+        elif name in g.solved:
+            W64, e_rec = golden_truth(case, N, name)
+            e_dev = rel_error(got[name], W64)
+            print('%-5s N=%d %-12s K %3d: %s %.3g, recorded reference %.3g (bound %.3g)' % (case, N, name, W64.shape[1], tag, e_dev, e_rec, MARGIN * max(e_rec, ULP)))
+            assert e_dev <= MARGIN * max(e_rec, ULP), (case, N, name, e_dev, e_rec)
+        else:
+            assert got[name].numpy().tobytes() == c.out[name].numpy().tobytes(), name
+
+
+@gpu
+@pytest.mark.parametrize('case,N', GOLDEN_CASES, ids=CASE_IDS)
+def test_merge_matches_the_recorded_reference(case, N):
+    _need_gpu()
+    _check_against_recording(case, N, _merge_recorded(case, N))
+
+
+@gpu
+@pytest.mark.parametrize('case,N', [('r1', 2), ('r09', 3), ('r09x', 3)], ids=['r1-2', 'r09-3', 'r09x-3'])
+def test_shared_and_copied_gram_matrices_give_the_same_bytes(case, N):
+    """q and k read one input. As ONE tensor per model regmean_groups makes them one factorisation with stacked right-hand sides (128 columns;
+    with q excluded a group of one); as two equal copies two factorisations."""
+    _need_gpu()
+    from pianobart_amd import merge as M
+    g = golden()
+    segs = [s for s in g.segs if s.name in g.cases[(case, N)].kept]
+    shared = g.grams[:N]
+    copied = [dict(G, **{'k.weight': G['k.weight'].clone()}) for G in shared]
+    kept = lambda grams: [{k: v for k, v in G.items() if k in g.cases[(case, N)].kept} for G in grams]
+    assert len(M.regmean_groups(kept(copied), segs)) == len(M.regmean_groups(kept(shared), segs)) + ('q.weight' in g.cases[(case, N)].kept) == 5 - (case == 'r09x')
+    a, b = _merge_recorded(case, N, shared), _merge_recorded(case, N, copied)
+    for name in a:
+        assert a[name].numpy().tobytes() == b[name].numpy().tobytes(), name
+    _check_against_recording(case, N, a, 'shared')
+    _check_against_recording(case, N, b, 'copied')
+
+
+@gpu
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+def test_gram_accum_on_the_recorded_activations(dtype):
+    """G = (sum over the batches of X^T X) / rows as the pass forms it (pb_gram_accum per batch, one pb_fisher_finish), batch by batch as the
+    hook saw them (40- and 30-row calls, or 8 and 6) and in one call (350 rows: two chunks of T), against X^T X / rows in float64 of the values
+    the kernel was given. The header promises an order that depends on (T, K) alone, not that two batches equal their concatenation for
+    real values: both results are held to 4 times the recorded matrix's own figure (at least one float32 ulp)."""
+    _need_gpu()
+    from pianobart_amd import ops
+    for module, G_rec, batches in golden_activations():
+        given = [b.to(dtype) for b in batches]
+        fig_rec, _ = gram_figure(G_rec, batches)
+        bound = MARGIN * max(fig_rec, ULP)
+        rows, K = sum(b.shape[0] for b in batches), G_rec.shape[0]
+        for how, calls in (('batch-wise', given), ('one call', [torch.cat(given)])):
+            G = torch.zeros(K, K, device='cuda')
+            for x in calls:
+                ops.gram_accum(G, x.cuda())
+            flags = torch.zeros(1, dtype=torch.int32, device='cuda')
+            ops.fisher_finish(G.view(-1), rows, flags)
+            assert int(flags.item()) == 0 and torch.equal(G, G.t())
+            fig, _ = gram_figure(G.cpu(), given)
+            print('%-5s K %3d %-5s %-10s: device %.3g, recorded reference %.3g (bound %.3g)' % (module, K, str(dtype)[6:], how, fig, fig_rec, bound))
+            assert fig <= bound, (module, how, fig, fig_rec)
+
+
+@gpu
+def test_too_few_rows_for_a_2d_input_layer_are_refused_by_name():
+    """head sees one row per example. Its Gram matrices cut to 6 rows per model (12 in all for 16 inputs) sum to a singular matrix: the
+    reference returns finite garbage, merge_state_dicts a PBError that names the weight."""
+    _need_gpu()
+    from pianobart_amd._lib import PBError
+    g = golden()
+    (_, _, batches), = [a for a in golden_activations() if a[0] == 'head']
+    X = torch.cat(batches).double()
+    assert X.shape[1] == 16
+    grams = [dict(G) for G in g.grams[:2]]
+    for m in range(2):
+        x = X[6 * m:6 * m + 6]
+        grams[m]['head.weight'] = (x.t() @ x / 6).float()
+    with pytest.raises(PBError, match=r'head\.weight.*not positive definite'):
+        _merge_recorded('r1', 2, grams)
