@@ -265,6 +265,32 @@ int pb_mask_count(const float* loss_mask, float* counts, float* partials /* >= p
  * w_i = weight_i * n_tok_i with the denominator sum(n_tok), i.e. scale = sum_w / sum(n_tok)) */
 int pb_loss_coef(const float* counts, const float* w /*device 8*/, float* coef, float scale, void* stream);
 
+/* ---- K28: K9 with soft targets: knowledge distillation and label smoothing (pb_distill.hip; additions to ABI 10) ----
+ * Everything of pb_ce_fwd_bwd (logits, target, loss_mask, seg_off, coef, dlogits in dtype or NULL, argmax_out or NULL, T, V) plus
+ *   teacher  (T_t,V) f32  the teacher's logits in the same layout, or NULL (then alpha must be 0 and plane 5 stays 0)
+ *   t_row    (T) int32    the teacher row that student row t reads, or NULL: row t reads row t (then T_t >= T). A row number outside
+ *                         0 .. T_t - 1 is not read: that row's teacher logits count as NaN
+ *   alpha in [0,1], tau > 0 and finite, eps in [0,1): host scalars
+ * Per row t and head i of n classes, z = the student's logits of the head, u = the teacher's of row t_row[t], y = target, m = loss mask,
+ * p = softmax(z), p_tau = softmax(z / tau), q = softmax(u / tau), each softmax on its own maximum:
+ *   hard   = -log p[y]                                   (a target outside its head scores a logit of 0 and has no one-hot column)
+ *   hard_e = (1 - eps) hard - (eps / n) sum_c log p[c]
+ *   kl     = sum_c q[c] (log q[c] - log p_tau[c])        (a class with q == 0 counts as 0), as
+ *            sum_c q[c] ((u[c] - max u) - (z[c] - max z)) / tau + log sum_c e^((z[c] - max z) / tau) - log sum_c e^((u[c] - max u) / tau)
+ *   loss   = (1 - alpha) hard_e + alpha tau^2 kl
+ *   dlogits[t, off_i + c] = coef[i] m ((1 - alpha) (p[c] - (1 - eps) [c == y] - eps / n) + alpha tau (p_tau[c] - q[c]))
+ * (d kl / dz = (p_tau - q) / tau, so the soft part carries tau, not tau^2). coef[i] * m multiplies: a head without any loss position has
+ * coef = inf and NaN gradients exactly where K9 has them. argmax is the first maximum.
+ * sums (5,8) f32 += {sum loss*m, sum m, sum correct*m, sum hard*m, sum kl*m}; the second and third are exact counts. Per-workgroup
+ * partials (partials: >= pb_distill_partials_floats() floats) are added in a fixed order: equal inputs give equal bytes.
+ * alpha = 0, eps = 0 and teacher NULL compute K9's quantities. Heads of at most 320 classes run a register-resident form (one wave64
+ * holds the student's and the teacher's row), others (up to 1088 classes) one head at a time; both use the same arithmetic. */
+int pb_distill_fwd_bwd(const float* logits, const float* teacher, const int32_t* t_row, const int16_t* target, const float* loss_mask,
+                       const int32_t* seg_off /*host 9*/, float* sums, float* partials, const float* coef, void* dlogits,
+                       int16_t* argmax_out, int32_t T, int32_t T_t, int32_t V, int32_t dtype, float alpha, float tau, float eps,
+                       void* stream);
+int64_t pb_distill_partials_floats(void);
+
 /* ---- K16: teacher-forced scoring (pb_score.hip; additions to ABI 9) ---------------------------------
  * The forward-only quantity of Ablation.py:126-166 (a teacher-forced decoder pass evaluated against the piece), per token instead of
  * K9's 24 batch-wide sums. logits (T,V) f32 and seg_off as for pb_ce_fwd_bwd; target (T,8) int16; mask (T) f32 of 0 / 1, one value per

@@ -147,6 +147,9 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         # gradient accumulation (loss_and_grads(micro=(i, K))): the f32 sum of the micro-batches before the last one (allocated by the first
         # K > 1 step), the (i, K) of the backward in flight, and the (i, K) the next call must continue
         self.G_acc, self._micro, self._micro_prev = None, None, None
+        # distillation / label smoothing (loss_and_grads(distill=..., smooth=...)): planes 4 and 5 (hard CE, KL) of the last such call as a (16,)
+        # device tensor, None after a plain call; the (40,) sums and the kernel's partial sums are allocated by the first such call
+        self.last_distill_sums, self._dsums, self._dpartials = None, None, None
 
     # ------------------------------------------------------------------ flat parameter layout
     def _layout(self):
@@ -1231,7 +1234,7 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
 
     # ------------------------------------------------------------------ fused pre-train step (bench / Pretrainer)
     def loss_and_grads(self, enc16, dec16, tgt16, loss_mask, emask, dmask, train=True, count_hook=None, head_w=None, w_scale=1.0,
-                       argmax_out=None, ids_checked=False, micro=None):
+                       argmax_out=None, ids_checked=False, micro=None, distill=None, smooth=0.0):
         """Forward + fused CE/argmax/acc + full backward. Returns the (24,) device tensor of sums
         {sum ce*m, sum m, sum correct*m} x 8 heads. `count_hook(counts)` may all-reduce the 8 mask counts (DP).
         ids_checked: the caller vouches that every id lies inside its embedding table (ids generated on the device, or a host batch it
@@ -1242,9 +1245,15 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         runs the same forward and backward into G32; the first K - 1 are summed into G_acc, the last one adds G_acc to G32 (range by range in front
         of grad_hook, which the earlier ones do not call), so that optimizer_step sees one summed gradient. The 8 heads are normalised by their mask
         counts and meet in the backbone, so the K gradients cannot be rescaled afterwards: the caller passes the counts of the WHOLE step to
-        every micro-batch through count_hook (mask_counts). None and (0, 1) are the step without accumulation."""
+        every micro-batch through count_hook (mask_counts). None and (0, 1) are the step without accumulation.
+        distill (an object with .teacher, a frozen Engine with LM heads over the same vocabulary layout, .alpha and .tau) and / or smooth (label
+        smoothing eps): the loss becomes (1 - alpha) * smoothed CE + alpha * tau^2 * KL(teacher || student) at temperature tau, per head, through
+        pb_distill_fwd_bwd instead of pb_ce_fwd_bwd (DESIGN.md 5 "Distillation"). The teacher computes its logits for the same (unpacked) batch,
+        teacher_logits; the student's packed rows find their teacher rows through the row map they were packed with. Plane 0 of the returned
+        sums is then the mixed objective; the hard-CE and KL sums stay in self.last_distill_sums ((16,) device tensor; None after a plain call)."""
         B, S = enc16.shape[:2]
         T = B * S
+        soft = self._check_distill(distill, smooth, S)
         micro = self._check_micro(micro, train)
         self._raise_if_bad_ids()
         if not ids_checked:
@@ -1256,6 +1265,13 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         self._tables_ready = False
         pack = self._pack_batch(enc16, dec16, tgt16, loss_mask, emask, dmask) if (_PACK_ROWS and argmax_out is None) else None
         self._raise_if_bad_ids()
+        t_logits = t_row = None
+        if soft and distill is not None:
+            # the teacher reads the whole batch (the ids range-checked above), dense: packed student row r finds its teacher row b * S + s in the
+            # row map it was gathered with
+            t_logits = distill.teacher.teacher_logits(enc16, dec16, emask, dmask)
+            if pack is not None:
+                t_row = pack.sub.src if pack.sub is not None else pack.src_d
         if pack is not None:
             enc16, dec16, tgt, lm = pack.enc16, pack.dec16, pack.tgt16, pack.loss_mask
             if pack.sub is not None:                                   # the last decoder layer hands over the rows with a loss term only
@@ -1269,13 +1285,24 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         logits = self.heads_forward(dec_h)
         ws = self._cur_ws
         sums, counts, coef = self.scal[0:24], self.scal[24:32], self.scal[32:40]
+        if soft:
+            if self._dsums is None or self._dsums.device != self.device:
+                self._dsums = torch.zeros(40, dtype=torch.float32, device=self.device)
+                self._dpartials = torch.empty(int(LIB.query('pb_distill_partials_floats')), dtype=torch.float32, device=self.device)
+            sums = self._dsums
+        self.last_distill_sums = sums[24:40] if soft else None
         ops.fill_f32(sums, 0.0)
         ops.mask_count(lm, counts, self.partials)
         if count_hook is not None:
             count_hook(counts)
         ops.loss_coef(counts, self.loss_w if head_w is None else head_w, coef, w_scale)
         dlogits = ws['dlogits'][:logits.shape[0]] if train else None
-        ops.ce_fwd_bwd(logits, tgt, lm, sums, self.partials, coef, dlogits, argmax_out, layout=self.lay)
+        if soft:
+            ops.distill_fwd_bwd(logits, t_logits, t_row, tgt, lm, sums, self._dpartials, coef, dlogits, argmax_out,
+                                distill.alpha if distill is not None else 0.0, distill.tau if distill is not None else 1.0, smooth, layout=self.lay)
+            sums = sums[0:24]
+        else:
+            ops.ce_fwd_bwd(logits, tgt, lm, sums, self.partials, coef, dlogits, argmax_out, layout=self.lay)
         if train:
             self._micro = micro
             try:
@@ -1297,6 +1324,48 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                         ops.accum_f32(self.G32, self.G_acc, add=True)
                     self._micro_prev = None
         return sums
+
+    def _check_distill(self, distill, smooth, S):
+        """True when the step runs the soft-target loss kernel. Everything that can be refused is refused here, before any device work."""
+        try:
+            ok = 0.0 <= float(smooth) < 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise PBError('smooth (label smoothing) must lie in [0, 1) (got %r)' % (smooth,))
+        if distill is None:
+            return float(smooth) != 0.0
+        teacher, alpha, tau = getattr(distill, 'teacher', None), getattr(distill, 'alpha', None), getattr(distill, 'tau', None)
+        if not isinstance(teacher, Engine):
+            raise PBError('distill.teacher must be an Engine (got %s)' % type(teacher).__name__)
+        if not (isinstance(alpha, (int, float)) and 0.0 <= alpha <= 1.0):
+            raise PBError('distill.alpha must lie in [0, 1] (got %r)' % (alpha,))
+        if not (isinstance(tau, (int, float)) and 0.0 < tau < float('inf')):
+            raise PBError('distill.tau (the temperature) must be finite and > 0 (got %r)' % (tau,))
+        if teacher is self:
+            raise PBError('distill.teacher is the student engine itself: the teacher needs a workspace of its own (copy the model)')
+        if teacher.mlm is None:
+            raise PBError('the teacher engine has no LM heads: there are no logits to distill')
+        if teacher.lay.vocab != self.lay.vocab or tuple(teacher.lay.sizes) != tuple(self.lay.sizes):
+            raise PBError('the teacher layout has V = %d columns %s, the student layout V = %d %s: distillation needs the same dictionary'
+                          % (teacher.lay.vocab, list(teacher.lay.sizes), self.lay.vocab, list(self.lay.sizes)))
+        if teacher.Smax < S:
+            raise PBError('the teacher window (max_position_embeddings %d) is shorter than the sequence length S = %d' % (teacher.Smax, S))
+        tdev = teacher.device if teacher.device is not None else teacher._param_map()[0][0].device
+        if tdev != self.device:
+            raise PBError('the teacher is on another device (%s) than the student (%s)' % (tdev, self.device))
+        return True
+
+    def teacher_logits(self, enc16, dec16, emask, dmask):
+        """This engine as a distillation teacher: the LM-head logits of one batch, enc16 / dec16 (B, S, 8) int16 ids that the caller has
+        range-checked, masks (B, S) f32. An inference forward over all B * S rows (no dropout, no row packing) followed by the head GEMM; no
+        gradient buffer is touched. Returns a dense (B * S, V) f32 view of this engine's own workspace, valid until its next call."""
+        if self.mlm is None:
+            raise PBError('the teacher engine has no LM heads: there are no logits to distill')
+        if self.device is None:
+            self.bind(enc16.device)
+        dec_h, _ = self.forward_hidden(enc16, dec16, emask, dmask, False, 0, pack=None)
+        return self.heads_forward(dec_h)
 
     def _check_micro(self, micro, train):
         """(i, K) of an accumulated step, or None for the step without accumulation (micro=None or (0, 1))."""

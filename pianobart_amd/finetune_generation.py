@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import augment as _augment
+from . import distill as _distill
 from . import ops
 from ._lib import PBError
 from .model import PianoBartLM, checkpoint_state_dict
@@ -52,6 +53,7 @@ def get_args_generation(argv=None):
     parser.add_argument('--accum_steps', type=_positive_int, default=1,
                         help='gradient accumulation: one optimizer step over this many consecutive training batches (not in the reference)')
     _augment.add_arguments(parser)
+    _distill.add_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -88,6 +90,7 @@ class GenerationTrainer:
         self.world = int(os.environ.get('WORLD_SIZE', 1))
         self.rank = int(os.environ.get('RANK', 0))
         self.augment, self.augment_seed, self._train_epoch = None, 0, -1     # --augment: an augment.AugmentPlan (None: off), --augment_seed
+        self.distill, self.label_smoothing = None, 0.0                       # --distill_from / --label_smoothing: training steps only
         self.reducer = None
         if self.world > 1:                                                   # one process per GPU, same exchange as the pre-train step
             import torch.distributed as dist
@@ -159,8 +162,12 @@ class GenerationTrainer:
             B, S = micro[-1][0].shape[:2]
             am = torch.empty(B * S, 8, dtype=torch.int16, device=self.device) if mode == 2 else None
             step_sums = torch.empty(24, dtype=torch.float32, device=self.device) if n_micro > 1 else None
+            soft_kw = _distill.step_kwargs(self.distill, self.label_smoothing) if mode == 0 else {}      # validation and test stay plain cross-entropy
+            extra = torch.empty(16, dtype=torch.float32, device=self.device) if soft_kw else None
             sums = run_micro_batches(eng, self.reducer, [(x16, x16, y16, lm, am_enc, am_enc) for x16, y16, am_enc, lm in micro], total, step_sums,
-                                     train=(mode == 0), head_w=self._hw, w_scale=self._scale, argmax_out=am)
+                                     extra_sums=extra, train=(mode == 0), head_w=self._hw, w_scale=self._scale, argmax_out=am, **soft_kw)
+            if soft_kw:
+                sums = torch.cat([sums, extra])                        # the hard-CE and KL sums travel with the 24 (reducer, host read)
             if mode == 0:
                 if self.reducer:
                     self.reducer.all_reduce_grads()
@@ -174,7 +181,8 @@ class GenerationTrainer:
             if mode == 2:
                 all_output[cnt:cnt + B] = am.view(B, S, 8).float().cpu()
                 cnt += B
-            sys.stdout.write('Loss: {:06f} | loss: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}\n'.format(loss, *losses))
+            more = _distill.progress_suffix(s[24:40], s[8:16], self._wnp * self._ntok) if len(s) == 40 else ''     # a distilled / smoothed step: hard CE and KL
+            sys.stdout.write('Loss: {:06f} | loss: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}{}\n'.format(loss, *losses, more))
             sys.stdout.write('Acc: {:06f} | acc: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}\n'.format(np.average(accs), *accs))
             sys.stdout.write('FAD(BAR) Similarity: n/a , FAD Similarity n/a \n')            # `shapesimilarity` is not installed: not measured
             total_acc += accs
@@ -239,6 +247,7 @@ def finetune_generation(argv=None):
     trainer = GenerationTrainer(pianobart, loaders[0], loaders[1], loaders[2], args.lr, y_test.shape, args.cpu, args.cuda_devices, model)
     trainer.accum_steps = args.accum_steps
     trainer.augment, trainer.augment_seed = _augment.from_args(args, e2w), args.augment_seed
+    trainer.distill, trainer.label_smoothing = _distill.from_args(args, e2w, w2e, trainer.device)     # every rank loads its own frozen teacher
     print("\nTraining Start")
     save_dir = os.path.join('result/finetune/generation_' + args.name)
     os.makedirs(save_dir, exist_ok=True)

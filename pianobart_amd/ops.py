@@ -298,6 +298,19 @@ def ce_fwd_bwd(logits, target16, loss_mask, sums, partials, coef, dlogits, argma
              _p(argmax_out), T, V, dtype_code(dlogits.dtype) if dlogits is not None else PB_F32, _stream())
 
 
+def distill_fwd_bwd(logits, teacher, t_row, target16, loss_mask, sums, partials, coef, dlogits, argmax_out, alpha, tau, eps, layout=None):
+    """pb_distill_fwd_bwd: ce_fwd_bwd with soft targets. teacher (T_t, V) f32 or None; t_row (T,) int32 (the teacher row of every student
+    row) or None; sums (40,) f32 = (5, 8) {loss, m, correct, hard CE, KL}, accumulated into; partials >= pb_distill_partials_floats()."""
+    T, V = logits.shape
+    if teacher is not None and (teacher.dim() != 2 or teacher.shape[1] != V or teacher.dtype != torch.float32 or not teacher.is_contiguous()):
+        raise PBError('distill_fwd_bwd: teacher logits must be a contiguous (T_t, %d) float32 tensor (got %s %s)' % (V, tuple(teacher.shape), teacher.dtype))
+    if t_row is not None and (t_row.dtype != torch.int32 or t_row.numel() < T):
+        raise PBError('distill_fwd_bwd: t_row must hold %d int32 row numbers (got %d of %s)' % (T, t_row.numel(), t_row.dtype))
+    LIB.call('pb_distill_fwd_bwd', _p(logits), _p(teacher), _p(t_row), _p(target16), _p(loss_mask), _off9(layout, False), _p(sums), _p(partials),
+             _p(coef), _p(dlogits), _p(argmax_out), T, teacher.shape[0] if teacher is not None else 0, V,
+             dtype_code(dlogits.dtype) if dlogits is not None else PB_F32, float(alpha), float(tau), float(eps), _stream())
+
+
 def token_scores(logits, target16, mask, logp, entropy=None, rank=None, layout=None):
     """pb_token_scores: logits (T, V) f32, target16 (T, 8) int16, mask (T,) f32 of 0 / 1 -> logp / entropy (T, 8) f32, rank (T, 8) int16
     (entropy and rank may be None)."""

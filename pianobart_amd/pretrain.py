@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import augment as _augment
+from . import distill as _distill
 from . import ops
 from ._lib import PBError
 from .data import BalancedDistributedSampler, MidiDataset, OctupleShards, sequence_lengths
@@ -70,6 +71,7 @@ def get_args_pretrain(argv=None):
     parser.add_argument('--accum_steps', type=_positive_int, default=1,
                         help='gradient accumulation: one optimizer step over this many consecutive loader batches (global loss normalisation)')
     _augment.add_arguments(parser)
+    _distill.add_arguments(parser)
     parser.add_argument('--resume', type=str, default='', help='continue from a checkpoint THIS driver wrote: weights, LM heads, AdamW moments and step, epoch, best_acc')
     return parser.parse_args(argv)
 
@@ -175,12 +177,14 @@ def group_batches(batches, k):
         yield group
 
 
-def run_micro_batches(eng, reducer, micro, total, step_sums, before=None, **kw):
+def run_micro_batches(eng, reducer, micro, total, step_sums, before=None, extra_sums=None, **kw):
     """The Engine.loss_and_grads calls of ONE optimizer step over the batches `micro` (argument tuples enc16, dec16, tgt16, loss_mask, emask,
     dmask); returns the step's (24,) sums. One batch: the call without accumulation, the reducer's count exchange inside it. Several:
     `total` holds the summed Engine.mask_counts of all of them; it is all-reduced ONCE, every micro-batch receives it through count_hook
     (the heads are normalised by the counts of the whole step), micro-batch i runs as micro=(i, len(micro)), and the 24 sums, which the
-    engine overwrites in every call, are added up in `step_sums`, a (24,) buffer of the caller's. before(i) runs in front of call i."""
+    engine overwrites in every call, are added up in `step_sums`, a (24,) buffer of the caller's. before(i) runs in front of call i.
+    extra_sums (a (16,) buffer of the caller's, for steps with distill= / smooth= among kw): receives the step's hard-CE and KL sums
+    (Engine.last_distill_sums), added up over the micro-batches the same way."""
     n = len(micro)
     if n == 1:
         count_hook = reducer.reduce_counts if reducer else None
@@ -194,6 +198,8 @@ def run_micro_batches(eng, reducer, micro, total, step_sums, before=None, **kw):
         sums = eng.loss_and_grads(*tensors, count_hook=count_hook, micro=(i, n) if n > 1 else None, **kw)
         if n > 1:
             ops.accum_f32(step_sums, sums, add=i > 0)
+        if extra_sums is not None and eng.last_distill_sums is not None:
+            ops.accum_f32(extra_sums, eng.last_distill_sums, add=i > 0)
     return sums if n == 1 else step_sums
 
 
@@ -252,6 +258,9 @@ class Pretrainer:
         self._epoch = 0
         self.augment, self.augment_seed = None, 0               # --augment: an augment.AugmentPlan (None: off) and --augment_seed
         self._train_epoch = 0                                   # the epoch of the running train() call: part of a batch's augmentation seed
+        # --distill_from / --label_smoothing: a distill.Distill (None: off) and the smoothing eps of the TRAINING steps; validation stays
+        # plain cross-entropy. The teacher is frozen and is neither reduced nor saved
+        self.distill, self.label_smoothing = None, 0.0
 
     # ---- reference API ------------------------------------------------------------------------------
     def train(self):
@@ -369,7 +378,8 @@ class Pretrainer:
             accs = s[16:24] / s[8:16]
             total_loss = float((losses * self._w).sum() / self._w.sum())
             if not self.quiet:
-                sys.stdout.write('Loss: {:06f} | loss: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}\n'.format(total_loss, *losses))
+                more = _distill.progress_suffix(s[24:40], s[8:16], self._w) if len(s) == 40 else ''      # a distilled / smoothed step: hard CE and KL
+                sys.stdout.write('Loss: {:06f} | loss: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}{}\n'.format(total_loss, *losses, more))
                 sys.stdout.write('Acc: {:06f} | acc: {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}, {:03f}\n'.format(np.average(accs), *accs))
             total_acc += accs
             total_losses += total_loss
@@ -382,7 +392,7 @@ class Pretrainer:
         main = torch.cuda.current_stream(self.device)
         if getattr(self, '_prep_stream', None) is None:
             self._prep_stream = torch.cuda.Stream(device=self.device)
-            self._sum_pins = [torch.empty(24, dtype=torch.float32).pin_memory() for _ in range(3)]
+            self._sum_pins = [torch.empty(40, dtype=torch.float32).pin_memory() for _ in range(3)]    # 24 sums (+ 16 of a distilled step)
         prep = self._prep_stream
 
         K = int(self.accum_steps) if train else 1               # validation ignores --accum_steps
@@ -429,12 +439,15 @@ class Pretrainer:
 
         def enqueue_read(sums, k):
             """24 floats device -> pinned host behind an event on the launch stream; nothing waits here."""
-            pin = self._sum_pins[k % len(self._sum_pins)]
+            pin = self._sum_pins[k % len(self._sum_pins)][:sums.numel()]
             pin.copy_(sums, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(main)
             return pin, ev
 
+        soft_kw = _distill.step_kwargs(self.distill, self.label_smoothing) if train else {}
+        if soft_kw and getattr(self, '_extra_sums', None) is None:
+            self._extra_sums = torch.empty(16, dtype=torch.float32, device=self.device)
         eng._pack_prefetch.clear()                                      # requests of an epoch that ended early (an exception between stage and step)
         it = group_batches(training_data, K)
         first = next(it, None)
@@ -457,13 +470,15 @@ class Pretrainer:
                     announce(after)
 
             sums = run_micro_batches(eng, self.reducer, micro, total, getattr(self, '_step_sums', None), before=before,
-                                     train=train, ids_checked=True)      # prepare_batch validated the host batch
+                                     extra_sums=self._extra_sums if soft_kw else None, train=train, ids_checked=True, **soft_kw)      # prepare_batch validated the host batch
+            if soft_kw:
+                sums = torch.cat([sums, self._extra_sums])              # 40 sums travel to the log lines (and through the reducer) together
             if train:
                 if self.reducer:
                     self.reducer.all_reduce_grads()
                 eng.optimizer_step(lr=self.lr)
             if self.reducer:
-                if n_micro == 1:
+                if n_micro == 1 and not soft_kw:
                     sums = sums.clone()                                 # the engine reuses its scalar buffer in the next step
                 self.reducer.reduce_sums(sums)
             cur = enqueue_read(sums, k)
@@ -539,6 +554,7 @@ def pretrain(argv=None):
     trainer.quiet = args.quiet
     trainer.accum_steps = args.accum_steps
     trainer.augment, trainer.augment_seed = _augment.from_args(args, e2w), args.augment_seed
+    trainer.distill, trainer.label_smoothing = _distill.from_args(args, e2w, w2e, trainer.device)     # every rank loads its own frozen teacher
     print("\nTraining Start")
     run = _RunLog(args.name, rank == 0)
     print("   save model at {}".format(run.filename))
