@@ -939,7 +939,29 @@ int pb_nucleus_rows(const float* probs, int32_t width, const int32_t* n, const f
  *                                   pb_batch_decoder_admit of `row` stores, in the same small kernel as the row's position, limit, stop
  *                                   bar, bar floor and done = 0. An admit without a staged value stores -1: a slot never inherits its
  *                                   previous occupant's mask. Host state only, no device work. Refused (< 0, pb_last_error, nothing
- *                                   changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1, an index outside the table. */
+ *                                   changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1, an index outside the table.
+ * Bar schedules (an addition to ABI 10): a row may carry a bar schedule, one entry per ordinary bar id k = 0 .. pad[0] - 1: the index (in
+ * pb_batch_decoder_allow's table) of the mask that heads 1 .. 7 take in a token whose bar -- head 0's id after forcing -- is k, or -1 = the
+ * row's own mask. Head 0 is sampled as without a schedule (the row's own mask and bar floor); a token whose bar is special ends the row and is
+ * never written: the device leaves its heads 1 .. 7 under the mask it sampled them with first (the sampler starts heads 1 .. 7 from
+ * the entry of the decoder input's bar and samples them a second time only where the token's own bar names another mask). The caller stores in an entry the mask it wants IN FORCE (already intersected with the
+ * row's own mask, special ids set). Draws, temperatures, nucleus rule, given heads, stop test and logged logits are untouched; on a
+ * time-ordered row head 1's second pass starts from the quotients the bar's mask left.
+ *   pb_batch_decoder_schedule       in pb_batch_decoder_allow's window and after it (the masks every schedule points to go up with the rows'
+ *                                   masks in that ONE call): table = (n_sched, nbar) host ints, nbar = pad[0]; row_sched = (B) host ints, the
+ *                                   index of row b's schedule, -1 = none (what sampler_init sets for every row). The table is copied to
+ *                                   device memory the decoder owns; the indices are stored beside the rows' mask indices in decoder-stream
+ *                                   order; pb_batch_decoder_start keeps them. Same kernels, kernarg layouts and launches per step. Refused
+ *                                   (< 0, pb_last_error, nothing changed): a null argument, before sampler_init, after a step was issued or
+ *                                   captured, n_sched < 1, nbar != pad[0], an entry outside -1 .. n_masks - 1, a row index outside -1 ..
+ *                                   n_sched - 1. While a schedule is in place pb_batch_decoder_allow is refused (the entries point into its
+ *                                   table); a later sampler_init clears both.
+ *   pb_batch_decoder_admit_schedule refill: stages the schedule index (-1 .. n_sched - 1 of the table pb_batch_decoder_schedule uploaded, which
+ *                                   therefore holds the schedules of ALL rows of the call from the start) that the next
+ *                                   pb_batch_decoder_admit of `row` stores, with the row's mask index. An admit without a staged value
+ *                                   stores -1: a slot never inherits its previous occupant's schedule. Host state only. Refused (< 0,
+ *                                   pb_last_error, nothing changed): not a dynamic decoder, before sampler_init, row outside 0 .. B - 1, an
+ *                                   index outside the table. */
 #define PB_DECODE_BATCH_MAX 16
 typedef struct pb_decode_batch {
     pb_decode_plan plan;
@@ -972,6 +994,8 @@ int pb_batch_decoder_admit_order(void* dec, int32_t row, int32_t floor);
 int pb_batch_decoder_sampler_form(void* dec);
 int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t n_masks, int32_t words, const int32_t* row_mask);
 int pb_batch_decoder_admit_allow(void* dec, int32_t row, int32_t mask_index);
+int pb_batch_decoder_schedule(void* dec, const int32_t* table, int32_t n_sched, int32_t nbar, const int32_t* row_sched);
+int pb_batch_decoder_admit_schedule(void* dec, int32_t row, int32_t sched_index);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

@@ -65,11 +65,17 @@ struct BState {
     // uint32 words in device memory the decoder owns, bit c & 31 of word c >> 5 = vocabulary column c), -1 = every class is allowed
     // (pb_batch_decoder_allow, pb_batch_decoder_admit_allow). The two per-row rules sit side by side: the sampler reads them with ONE
     // 8-byte load, so a free row's requests are those of a sampler that knew the bar floor alone
-    struct RowRule { int order, allow; };
+    // ... and rule[b].sched >= 0 = the row follows bar schedule sched of the table stab ((n_sched, nbar) ints in device memory the decoder
+    // owns, nbar = pad[0]: entry k = the index in amask of the mask heads 1 .. 7 take in a token of bar k, -1 = the row's own mask), -1 =
+    // no schedule (pb_batch_decoder_schedule, pb_batch_decoder_admit_schedule). With it the rules are ONE 16-byte load; `reserved` pads
+    // the record to that size and is kept at -1
+    struct alignas(16) RowRule { int order, allow, sched, reserved; };
     RowRule rule[BMAX];
     int opad[2];
     int awords;
     const uint32_t* amask;
+    int nbar;
+    const int* stab;
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -1262,6 +1268,17 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // the host masks its own copy. The bit of class c of head h is bit off[h] + c of the row's mask -- the heads' offsets are no multiples
 // of 32, so the word is indexed by column. Block-uniform on the row's index and no template parameter, for order[b]'s reasons: a free
 // row pays one compare and 4 more bytes in the load that brings its bar floor, a masked row K loads of words its wave shares.
+// Bar schedules (pb_batch_decoder_schedule), both forms and both widths: a row with rule[b].sched >= 0 takes the mask of heads 1 .. 7
+// from the bar of the token it is sampling, b0 = head 0's id after forcing -- which exists only behind the barrier that publishes
+// htok[0]. Waves 1 .. 7 therefore sample under a GUESS first: the entry of the decoder input's bar (tok_dev[b * 8], which the ordered path
+// reads too; entry 0 where that bar is special, the SOS row). Behind the barrier the entry of b0 is read (b0 special: the guess stands,
+// the row ends); if it names another mask, waves 1 .. 7 run the three stages again with it and the draws they had -- the quotients
+// re-formed from the logits row, which this kernel never writes (the rank counting in between takes all 512 threads, as in the first pass). The result does not depend on the guess; the guess makes the second pass
+// rare (the first token of a bar whose mask differs from the previous bar's). Wave 0 keeps the row's own mask: the schedule never
+// touches head 0. The schedule pass needs b0 != the input's bar (equal bars have equal entries), head 1's time-ordered pass needs b0 ==
+// it, and with a special input bar (the only case where the guess is not the input bar's entry) low1 is 0: a position pays at most ONE
+// second pass. Block-uniform like the other rules (BState, tok_dev, the force table, htok[0] behind a barrier): a row without a schedule
+// pays one compare and 8 more bytes in the rule load.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1409,8 +1426,8 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     // time-ordered row (order[b] >= 0, block-uniform): low0 = the first bar head 0 may sample; low1 > 0 = the first position head 1 may
     // sample IF the token's bar stays prev0 (0: head 1 is free whatever the bar). prev = the row's decoder input, read here, in front of
     // the first barrier; the last stage overwrites it behind the last one.
-    const BState::RowRule rule = a.st->rule[b];                  // one 8-byte load: the bar floor and the allow mask (below) of the row
-    const int ord = rule.order, alw = rule.allow;
+    const BState::RowRule rule = a.st->rule[b];                  // one 16-byte load: the bar floor, the allow mask and the bar schedule (below) of the row
+    const int ord = rule.order, alw = rule.allow, sch = rule.sched;
     int low0 = 0, low1 = 0, prev0 = -1;
     if (ord >= 0) {
         const int p0 = a.tok_dev[b * 8 + 0], p1 = a.tok_dev[b * 8 + 1];
@@ -1418,11 +1435,22 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         low0 = max(ord, bar ? p0 : 0);
         if (bar && p1 < a.st->opad[1]) { low1 = p1; prev0 = p0; }
     }
+    // bar schedule (rule[b].sched >= 0, block-uniform): guess = the mask of the decoder input's bar, for waves 1 .. 7. An entry of -1
+    // means the row's own mask, so what is compared behind the barrier is the index the waves actually used. The row's entries are
+    // stab[sch * nbar .. + nbar - 1]; nbar = pad[0] and the bar indexed is < opad[0] = pad[0] (checked by pb_batch_decoder_schedule).
+    const int* srow = a.st->stab + (size_t)max(sch, 0) * a.st->nbar;     // formed for every row, read by a scheduled one (amask's remark, below)
+    int guess = alw;
+    if (sch >= 0) {
+        const int p0 = a.tok_dev[b * 8 + 0];
+        const int g = srow[(unsigned)p0 < (unsigned)a.st->opad[0] ? p0 : 0];
+        if (g >= 0) guess = g;
+    }
     // allowed classes (rule[b].allow >= 0, block-uniform): the row's mask, one bit per vocabulary column
     // The address is formed whether the row has a mask or not (index 0 for a free row; never read then): with a branch of its own here
     // the compiler requests pos[b] a scalar-load round trip later than it did, which every free row would pay (1 us per launch, measured).
-    const bool masked = alw >= 0;
-    const uint32_t* amask = a.st->amask + (size_t)max(alw, 0) * a.st->awords;
+    const int mine = h == 0 ? alw : guess;                       // wave-uniform: head 0 never sees the schedule
+    const bool masked = mine >= 0;
+    const uint32_t* amask = a.st->amask + (size_t)max(mine, 0) * a.st->awords;
     const float* logits = a.logits + (size_t)b * a.vocab;
     float* log_logits = a.log_logits + ((size_t)b * a.S + pos) * a.vocab;
     const int n = a.n[h], off = a.off[h];
@@ -1495,6 +1523,62 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         if (lane == 0) htok[h] = id;
     }
     __syncthreads();
+    // Bar schedule: the mask of heads 1 .. 7 is that of bar b0, head 0's id AFTER forcing. Where it is not the guessed one, waves 1 .. 7
+    // sample again (the kernel's comment); every condition is block-uniform, so the barriers below are reached by all 512 threads or by
+    // none. The quotients come from the logits row again (the first pass left -inf where its mask bit); no bar floor: that is head 0's.
+    // Head 1's time-ordered pass below then starts from these quotients, and cannot follow a pass taken here (b0 == prev0 there).
+    if (sch >= 0) {
+        int b0 = htok[0];
+        if constexpr (FORCED) { if (f0 >= 0) b0 = f0; }
+        int want = guess;
+        if ((unsigned)b0 < (unsigned)a.st->opad[0]) { const int s = srow[b0]; want = s >= 0 ? s : alw; }
+        if (want != guess) {
+            if (h != 0) {
+                unsigned allowed = ~0u;
+                if (want >= 0) {
+                    const uint32_t* wmask = a.st->amask + (size_t)want * a.st->awords;
+                    allowed = 0u;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const int col = min(off + lane + 64 * k, a.vocab - 1);
+                        allowed |= ((wmask[col >> 5] >> (col & 31)) & 1u) << k;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int c = lane + 64 * k;
+                    const bool in = c < n;
+                    const float lg = in ? logits[off + c] : 0.f;
+                    y[k] = (in && ((allowed >> k) & 1u)) ? lg / T : -INFINITY;
+                }
+                smp_softmax(y, n, lane, pn[h]);
+            }
+            __syncthreads();
+            {
+                // the first pass's rank counting again, one thread per (head, class) over all 512 threads: a wave that ranked its own head
+                // class by class took 4x the whole first pass (measured). Head 0's probabilities did not change: its classes keep their
+                // thread and write nothing.
+                int tot = 0;
+                if constexpr (WIDE) { for (int q = 0; q < 8; ++q) tot += a.p[q] < 1.0f ? a.n[q] : 0; }
+                for (int c0 = t; WIDE ? c0 < tot : c0 == t; c0 += 512) {
+                    int hh = -1, c = c0;
+                    for (int q = 0; q < 8; ++q) {
+                        if (a.p[q] < 1.0f) {
+                            if (hh < 0 && c < a.n[q]) hh = q;
+                            if (hh < 0) c -= a.n[q];
+                        }
+                    }
+                    if (hh >= 1) smp_rank<W>(pn[hh], c, sp[hh], si[hh]);
+                }
+            }
+            __syncthreads();
+            if (h != 0) {
+                const int id = smp_pick<K>(ph, n, lane, u_draw, pn[h], sp[h], si[h]);
+                if (lane == 0) htok[h] = id;
+            }
+            __syncthreads();
+        }
+    }
     // Time-ordered row, head 1: its mask depends on head 0's id AFTER forcing (b0 == prev0: the token stays in the bar of its
     // predecessor), which exists only now. Wave 1 therefore samples a second time behind the barrier that published htok[0]. The other
     // way -- both variants in the first pass, one selected here -- would give the masked variant a ninth wave or a second round of wave 1 at
@@ -1560,12 +1644,19 @@ __global__ __launch_bounds__(64) void dec_allow_kernel(BState* __restrict__ st, 
     if (t < BMAX) st->rule[t].allow = g.allow[t];
     if (t == 0) { st->awords = g.words; st->amask = g.table; }
 }
+struct SchedArgs { int sched[BMAX]; int nbar; const int* table; };
+__global__ __launch_bounds__(64) void dec_sched_kernel(BState* __restrict__ st, const SchedArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) st->rule[t].sched = g.sched[t];
+    if (t == 0) { st->nbar = g.nbar; st->stab = g.table; }
+}
 struct AdmitArgs {
     BState* st; int16_t* tok_dev;
     int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
     int stop;                                // the new occupant's stop bar (pad[0]: none)
     int order;                               // ... and its bar floor of time-ordered sampling (-1: a free row)
     int allow;                               // ... and the index of its allow mask in the decoder's table (-1: every class allowed)
+    int sched;                               // ... and the index of its bar schedule in the decoder's table (-1: none)
     int16_t tok[8];
 };
 __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
@@ -1574,7 +1665,7 @@ __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
     if (t == 0) {
         a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
         a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop;
-        a.st->rule[b].order = a.order; a.st->rule[b].allow = a.allow;
+        a.st->rule[b].order = a.order; a.st->rule[b].allow = a.allow; a.st->rule[b].sched = a.sched; a.st->rule[b].reserved = -1;
     }
 }
 
@@ -1625,6 +1716,10 @@ struct Decoder {
     int admit_allow[BMAX] = {};            // pb_batch_decoder_admit_allow: the index the row's next admit stores (-1: none staged -> a free row)
     uint32_t* allow_dev = nullptr;         // pb_batch_decoder_allow: (n_allow, allow.words) masks, one bit per vocabulary column
     int n_allow = 0;                       // masks in allow_dev; 0 behind sampler_init until pb_batch_decoder_allow
+    SchedArgs sched{};                     // host mirror of the rows' schedule indices in BState (-1: no schedule) and of the table's address
+    int admit_sched[BMAX] = {};            // pb_batch_decoder_admit_schedule: the index the row's next admit stores (-1: none staged -> no schedule)
+    int* sched_dev = nullptr;              // pb_batch_decoder_schedule: (n_sched, sched.nbar) indices into allow_dev's masks, -1 = the row's own mask
+    int n_sched = 0;                       // schedules in sched_dev; 0 behind sampler_init until pb_batch_decoder_schedule
     hipEvent_t ev_fence = nullptr;
     char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
     size_t stage_bytes = 0;
@@ -1894,6 +1989,7 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     if (D->u_dev) (void)hipFree(D->u_dev);
     if (D->force_dev) (void)hipFree(D->force_dev);
     if (D->allow_dev) (void)hipFree(D->allow_dev);
+    if (D->sched_dev) (void)hipFree(D->sched_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
     for (int i = 0; i < N_STAGE; ++i) if (D->stage_ev[i]) (void)hipEventDestroy(D->stage_ev[i]);
@@ -2030,7 +2126,7 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     PB_CHECK_HIP(hipMemcpyAsync(D->u_dev, u, sizeof(double) * B * S * 8, hipMemcpyHostToDevice, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->limit, limit, BMAX, D->stream));    // every row; pb_batch_decoder_start may set them one by one
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->stop, pad8[0], BMAX, D->stream));   // no row stops at a bar until pb_batch_decoder_stop says so
-    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->rule, -1, 2 * BMAX, D->stream));    // every row is sampled freely, from every class, until pb_batch_decoder_order / _allow say otherwise
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)D->st->rule, -1, 4 * BMAX, D->stream));    // every row is sampled freely, from every class, in every bar, until pb_batch_decoder_order / _allow / _schedule say otherwise
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[0], pad8[0], 1, D->stream));
     PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->opad[1], pad8[1], 1, D->stream));
     PB_CHECK_HIP(hipStreamSynchronize(D->stream));                     // `u` may be pageable: the copy is done when we return
@@ -2038,6 +2134,8 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     for (int b = 0; b < BMAX; ++b) { D->stop.stop[b] = pad8[0]; D->admit_stop[b] = -1; D->order.order[b] = -1; D->admit_order[b] = -1; }
     for (int b = 0; b < BMAX; ++b) { D->allow.allow[b] = -1; D->admit_allow[b] = -1; }
     D->n_allow = 0;                                                     // the previous run's table (if any) stays allocated and unread: no row points into it
+    for (int b = 0; b < BMAX; ++b) { D->sched.sched[b] = -1; D->admit_sched[b] = -1; }
+    D->n_sched = 0;                                                     // likewise
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
     D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
@@ -2128,6 +2226,7 @@ extern "C" int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t 
     PB_REQUIRE(D && masks && row_mask, "pb_batch_decoder_allow: null argument");
     PB_REQUIRE(D->sampler, "pb_batch_decoder_allow: pb_batch_decoder_sampler_init first");
     PB_REQUIRE(!D->issued, "pb_batch_decoder_allow: a step was already issued; the rows' allow masks are set before the run's first step");
+    PB_REQUIRE(!D->n_sched, "pb_batch_decoder_allow: a bar schedule points into the table in place; upload the masks before pb_batch_decoder_schedule");
     PB_REQUIRE(n_masks > 0 && n_masks <= 65536, "pb_batch_decoder_allow: %d masks (1 .. 65536)", n_masks);
     PB_REQUIRE(words == (D->sa.vocab + 31) / 32, "pb_batch_decoder_allow: %d words per mask for %d vocabulary columns (%d)", words, D->sa.vocab,
                (D->sa.vocab + 31) / 32);
@@ -2158,6 +2257,49 @@ extern "C" int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t 
     if (D->allow_dev) (void)hipFree(D->allow_dev);               // the previous table: no row has pointed into it since sampler_init (hipFree drains the device)
     D->allow_dev = tab; D->n_allow = n_masks;
     D->allow = g;
+    return 0;
+}
+
+// Bar schedules (see the header): the table of distinct schedules goes up once, into memory the decoder owns, and one index per row is
+// stored beside the rows' allow masks in decoder-stream order by a small kernel. Its entries index the masks pb_batch_decoder_allow
+// uploaded, so that call comes first. Everything is checked on the host before anything changes.
+extern "C" int pb_batch_decoder_schedule(void* dec, const int32_t* table, int32_t n_sched, int32_t nbar, const int32_t* row_sched) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && table && row_sched, "pb_batch_decoder_schedule: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_schedule: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_schedule: a step was already issued; the rows' bar schedules are set before the run's first step");
+    PB_REQUIRE(n_sched > 0 && n_sched <= 65536, "pb_batch_decoder_schedule: %d schedules (1 .. 65536)", n_sched);
+    PB_REQUIRE(nbar == D->sa.pad[0], "pb_batch_decoder_schedule: %d entries per schedule for %d ordinary bar ids (pad[0])", nbar, D->sa.pad[0]);
+    for (size_t i = 0; i < (size_t)n_sched * (size_t)nbar; ++i)
+        PB_REQUIRE(table[i] >= -1 && table[i] < D->n_allow, "pb_batch_decoder_schedule: schedule %d, bar %d: mask index %d outside -1..%d (-1 = the row's own "
+                   "mask; the table is pb_batch_decoder_allow's)", (int)(i / nbar), (int)(i % nbar), table[i], D->n_allow - 1);
+    for (int b = 0; b < D->B; ++b)
+        PB_REQUIRE(row_sched[b] >= -1 && row_sched[b] < n_sched, "pb_batch_decoder_schedule: row %d: schedule index %d outside -1..%d (-1 = no schedule)", b,
+                   row_sched[b], n_sched - 1);
+    const size_t bytes = sizeof(int) * (size_t)n_sched * (size_t)nbar;
+    int* tab = nullptr;
+    if (hipMalloc(&tab, bytes) != hipSuccess) {
+        pb_set_error("pb_batch_decoder_schedule: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    if (hipMemcpyAsync(tab, table, bytes, hipMemcpyHostToDevice, D->stream) != hipSuccess ||
+        hipStreamSynchronize(D->stream) != hipSuccess) {         // `table` may be pageable: the copy is done when we return
+        pb_set_error("pb_batch_decoder_schedule: upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(tab);
+        return -1;
+    }
+    SchedArgs g = D->sched;
+    for (int b = 0; b < D->B; ++b) g.sched[b] = row_sched[b];
+    g.nbar = nbar; g.table = tab;
+    hipLaunchKernelGGL(dec_sched_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
+    if (hipGetLastError() != hipSuccess) {
+        pb_set_error("pb_batch_decoder_schedule: launch failed");
+        (void)hipFree(tab);
+        return -1;
+    }
+    if (D->sched_dev) (void)hipFree(D->sched_dev);               // the previous table: no row has pointed into it since sampler_init (hipFree drains the device)
+    D->sched_dev = tab; D->n_sched = n_sched;
+    D->sched = g;
     return 0;
 }
 
@@ -2235,9 +2377,12 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
         h.stop[b] = D->stop.stop[b];                                  // as sampler_init / pb_batch_decoder_stop left it (unread without a sampler)
         h.rule[b].order = D->sampler ? D->order.order[b] : -1;        // ... / pb_batch_decoder_order
         h.rule[b].allow = D->sampler ? D->allow.allow[b] : -1;        // ... / pb_batch_decoder_allow
+        h.rule[b].sched = D->sampler ? D->sched.sched[b] : -1;        // ... / pb_batch_decoder_schedule
+        h.rule[b].reserved = -1;
     }
     h.opad[0] = D->sa.pad[0]; h.opad[1] = D->sa.pad[1];
     h.awords = D->allow.words; h.amask = D->n_allow ? D->allow_dev : nullptr;
+    h.nbar = D->sched.nbar; h.stab = D->n_sched ? D->sched_dev : nullptr;
     for (int b = 0; b < B; ++b) {
         PB_REQUIRE(last_pos[b] >= -1 && last_pos[b] < S, "pb_batch_decoder_start: row %d at position %d (S = %d)", b, last_pos[b], S);
         PB_REQUIRE(!limit || (limit[b] >= 0 && limit[b] <= S), "pb_batch_decoder_start: row %d limit %d outside 0..%d", b, limit[b], S);
@@ -2336,6 +2481,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     a.stop = D->admit_stop[row] >= 0 ? D->admit_stop[row] : D->sa.pad[0];    // never the previous occupant's
     a.order = D->admit_order[row];                                           // -1 unless staged: nor its bar floor
     a.allow = D->admit_allow[row];                                           // ... nor its allow mask
+    a.sched = D->admit_sched[row];                                           // ... nor its bar schedule
     for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
@@ -2356,6 +2502,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     D->stop.stop[row] = a.stop; D->admit_stop[row] = -1;
     D->order.order[row] = a.order; D->admit_order[row] = -1;
     D->allow.allow[row] = a.allow; D->admit_allow[row] = -1;
+    D->sched.sched[row] = a.sched; D->admit_sched[row] = -1;
     D->live[row] = true;
     return 0;
 }
@@ -2394,6 +2541,19 @@ extern "C" int pb_batch_decoder_admit_allow(void* dec, int32_t row, int32_t mask
     PB_REQUIRE(mask_index >= -1 && mask_index < D->n_allow, "pb_batch_decoder_admit_allow: row %d: mask index %d outside -1..%d (-1 = every class allowed; the "
                "table is pb_batch_decoder_allow's)", row, mask_index, D->n_allow - 1);
     D->admit_allow[row] = mask_index;
+    return 0;
+}
+
+// The bar schedule (an index into pb_batch_decoder_schedule's table) of the prompt the next pb_batch_decoder_admit puts into `row` (see the
+// header). Host state only: the store is the admit's.
+extern "C" int pb_batch_decoder_admit_schedule(void* dec, int32_t row, int32_t sched_index) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit_schedule: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_admit_schedule: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit_schedule: row %d of %d", row, D->B);
+    PB_REQUIRE(sched_index >= -1 && sched_index < D->n_sched, "pb_batch_decoder_admit_schedule: row %d: schedule index %d outside -1..%d (-1 = no schedule; the "
+               "table is pb_batch_decoder_schedule's)", row, sched_index, D->n_sched - 1);
+    D->admit_sched[row] = sched_index;
     return 0;
 }
 

@@ -25,7 +25,8 @@ class Args:
     def __init__(self, dict_file=_VOCAB, ckpt='./PianoBART_Giant.ckpt', input='./Data/POP909/POP909/001/001.mid', output='./output.mid',
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
                  precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False,
-                 key=None, pitch_range=None, instruments=None, tempo=None, max_duration=None, velocity=None):
+                 key=None, pitch_range=None, instruments=None, tempo=None, max_duration=None, velocity=None, chords=None, bars_per_chord=1,
+                 chord_start=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
@@ -36,6 +37,8 @@ class Args:
         self.ordered = ordered              # time-ordered sampling: no sampled (bar, position) goes back (eval_generation --ordered)
         # allowed classes (eval_generation --key / --pitch_range / --instruments / --tempo / --max_duration / --velocity): one mask for the piece
         self.key, self.pitch_range, self.instruments, self.tempo, self.max_duration, self.velocity = key, pitch_range, instruments, tempo, max_duration, velocity
+        # a bar schedule (eval_generation --chords / --bars_per_chord / --chord_start): the pitches follow a chord progression bar by bar
+        self.chords, self.bars_per_chord, self.chord_start = chords, bars_per_chord, chord_start
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -71,6 +74,8 @@ def get_args(argv=None):
                     '--infill LO:HI and 0 otherwise')
     from .generation import add_allow_flags
     add_allow_flags(ap)
+    from .generation import add_schedule_flags
+    add_schedule_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -182,6 +187,9 @@ def demo(args=None):
     from .generation import allow_from_args
     amask = allow_from_args(args, e2w)       # --key / --pitch_range / ..: what the free heads may sample (None: no flag)
     allow = [amask] if amask is not None else None
+    from .generation import schedule_from_args
+    bar = schedule_from_args(args, e2w, prefix[0, :ks[0]] if ks is not None and ks[0] else None)     # --chords: the first chord behind the prime
+    bar = dict(decoder_bar_allow=[bar]) if bar is not None else {}
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
@@ -189,10 +197,10 @@ def demo(args=None):
             from .generation import sample_seed
             y = model.generate_batch(octuple, attn_encoder, seeds=[sample_seed(seed, j, 0, 1) for j in range(samples)], device_num=device_num,
                                      decoder_prefix=prefix, prefix_len=ks, samples_per_prompt=samples,
-                                     decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
+                                     decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow, **bar)
         else:
             y = model(input_ids_encoder=octuple, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                      decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
+                      decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow, **bar)
     if plan is not None:                     # the rows behind the region go back behind the new ones
         from .generation import infill_splice
         spliced = [infill_splice(row, plan['suffix'], args.max_seq_len, pianobart.bar_pad_word) for row in y.cpu()]

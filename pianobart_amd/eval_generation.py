@@ -49,6 +49,14 @@ checks generation.is_allowed on every output row behind its prime (kept attribut
 fails. Combines with --prime, --keep, --bars, --infill, --ordered, --samples, --refill, --score and --pick; not with --score_dataset. Without
 the flags the output files are byte-identical to a run of a version without them.
 
+Bar schedules (--chords C:maj,G:maj,A:min,F:maj [--bars_per_chord N] [--chord_start B]): the pitches a free head may sample change with the
+bar -- bar B takes the tones of the first chord, bar B + N those of the second, .., the progression repeated to the end of the piece
+(PianoBartLM.generate_batch's decoder_bar_allow; generation.chord_schedule; DESIGN.md section 1, "Bar schedules"). B defaults to 0, and
+with --prime to the bar after the one each piece's prime ends in, so every piece gets its own schedule. The tool checks
+generation.follows_schedule on every output row behind its prime and raises PBError where it fails. Combines with the allow flags (the
+masks intersect) and everything they combine with; not with --score_dataset. Without the flags the output files are byte-identical to a
+run of a version without them.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -67,7 +75,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import add_allow_flags, allow_flags_given, allow_from_args, check_refill, infill_plan, is_allowed, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
+from .generation import add_allow_flags, add_schedule_flags, follows_schedule, schedule_from_args, allow_flags_given, allow_from_args, check_refill, infill_plan, is_allowed, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -118,6 +126,7 @@ def get_args(argv=None):
     ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
                     '--infill LO:HI and 0 otherwise')
     add_allow_flags(ap)
+    add_schedule_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -202,6 +211,8 @@ def check_args(args):
         raise PBError('--score_dataset generates nothing: it takes no --ordered')
     if allow_flags_given(args) and getattr(args, 'score_dataset', False):
         raise PBError('--score_dataset generates nothing: it takes no --%s' % allow_flags_given(args)[0])
+    if getattr(args, 'chords', None) is not None and getattr(args, 'score_dataset', False):
+        raise PBError('--score_dataset generates nothing: it takes no --chords')
     if getattr(args, 'keep', None) is not None:
         parse_keep(args.keep)
         if getattr(args, 'prime', None) is None:
@@ -296,9 +307,18 @@ def eval_generation(args=None):
             if not is_allowed(y[r], amask, start=k, forced=forced[p] if forced is not None else None, layout=model.pianobart.layout):
                 raise PBError('--%s: output row %d leaves the allowed classes behind its prime of %d rows' % (allow_flags_given(args)[0], r, k))
 
+    schedule_from_args(args, e2w)                        # --chords: the flags' own refusals, before any device work
+
+    def scheduled(y, ks, forced, own, bar):
+        """--chords: every output row of y (row r belongs to piece own[r] of the call) follows its piece's schedule behind its prime."""
+        for r, p in enumerate(own if bar is not None else []):
+            k = ks[p] if ks is not None else 0
+            if not follows_schedule(y[r], bar[p], start=k, forced=forced[p] if forced is not None else None, layout=model.pianobart.layout):
+                raise PBError('--chords: output row %d leaves its bar schedule behind its prime of %d rows' % (r, k))
+
     def inputs(x):
         """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars,
-        (--infill) the plans and (--ordered) the bar floors."""
+        (--infill) the plans, (--ordered) the bar floors, (the allow flags) the masks and (--chords) the bar schedules."""
         prefix = ks = forced = stops = plans = None
         order = [floor] * len(x) if floor is not None else None
         allow = [amask] * len(x) if amask is not None else None
@@ -315,7 +335,10 @@ def eval_generation(args=None):
             x, prefix = prime_inputs(x, ks, pad_word)
         if bars is not None:
             stops = [stop_after_bars(prefix[b, :ks[b]] if ks is not None else None, bars, bar_pad) for b in range(len(x))]
-        return x, prefix, ks, forced, stops, plans, order, allow
+        bar = None
+        if getattr(args, 'chords', None) is not None:        # one schedule per piece: its first chord sits behind the piece's own prime
+            bar = [schedule_from_args(args, e2w, prefix[b, :ks[b]] if ks is not None and ks[b] else None) for b in range(len(x))]
+        return x, prefix, ks, forced, stops, plans, order, allow, bar
 
     def splice(y, plans, own):
         """--infill: row r of y (numpy) spliced with the suffix of its piece own[r]; counts the truncated ones."""
@@ -357,14 +380,15 @@ def eval_generation(args=None):
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
-            x, prefix, ks, forced, stops, plans, order, allow = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow, bar = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
                                      device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
-                                     decoder_order=order, decoder_allow=allow,
+                                     decoder_order=order, decoder_allow=allow, **(dict(decoder_bar_allow=bar) if bar is not None else {}),
                                      samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
             own = [i - c0 for i, _ in chunk]
             allowed(y, ks, forced, own)
+            scheduled(y, ks, forced, own, bar)
             if do_score:
                 sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
             y = y.float().cpu().numpy()
@@ -378,17 +402,20 @@ def eval_generation(args=None):
         gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
         for c0 in range(0, N if samples == 1 else 0, gen_rows):
             c1 = min(N, c0 + gen_rows)
-            x, prefix, ks, forced, stops, plans, order, allow = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow, bar = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
                 y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
-                          decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow)
+                          decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow,
+                          **(dict(decoder_bar_allow=bar) if bar is not None else {}))
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
                                          decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops, decoder_order=order,
-                                         decoder_allow=allow, refill=(refill or True) if refill is not None else False)
+                                         decoder_allow=allow, refill=(refill or True) if refill is not None else False,
+                                         **(dict(decoder_bar_allow=bar) if bar is not None else {}))
             allowed(y, ks, forced, list(range(c1 - c0)))
+            scheduled(y, ks, forced, list(range(c1 - c0)), bar)
             output[c0:c1] = y.float().cpu().numpy() if plans is None else splice(y.float().cpu().numpy(), plans, list(range(c1 - c0)))
             for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):
                 s1 = min(c1 - c0, s0 + args.batch_size)

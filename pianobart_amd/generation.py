@@ -473,6 +473,240 @@ def is_allowed(rows, mask, start=0, forced=None, layout=None):
     return bool(ok.all())
 
 
+def _unpack_bits(packed, vocab):
+    """(n, V) bool rows of a table packed as check_allow packs it."""
+    return np.unpackbits(np.ascontiguousarray(packed).astype('<u4').view(np.uint8), axis=1, bitorder='little')[:, :vocab].astype(bool)
+
+
+def _pack_bits(masks, V):
+    words = (V + 31) // 32
+    bits = np.zeros((len(masks), words * 32), dtype=np.uint8)
+    bits[:, :V] = np.stack(masks)
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder='little')).view('<u4').astype(np.uint32).reshape(len(masks), words)
+
+
+def _schedule_entries(sched, nbar, who):
+    """One bar schedule in either argument form -> {bar: mask or None}, the bars checked."""
+    if isinstance(sched, dict):
+        items = list(sched.items())
+    else:
+        try:
+            items = list(enumerate(sched))
+        except TypeError:
+            raise PBError('%s = %r is neither None, a dict {bar: mask} nor a sequence of masks' % (who, sched))
+        if len(items) > nbar:
+            raise PBError('%s has %d entries: a schedule holds at most one per ordinary bar id 0 .. %d' % (who, len(items), nbar - 1))
+    out = {}
+    for k, m in items:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < nbar:
+            raise PBError('%s: bar %r is not an ordinary bar id 0 .. %d' % (who, k, nbar - 1))
+        out[int(k)] = m
+    return out
+
+
+def check_bar_allow(bar_allow, allow, P, layout=None, owner=None):
+    """The argument rules of bar schedules, on the host before any device work. bar_allow: one schedule per prompt -- a list of P entries,
+    each None (no schedule), a dict {bar id: (V,) bool mask} or a sequence of at most pad[0] masks / None indexed by bar id; for P = 1 one
+    schedule by itself will do. allow: the call's `allow` argument as check_allow takes it (the rows' own masks). Every bar mask is
+    intersected with its prompt's row mask and gets the special ids of every head set; a (row mask, bar mask) pair that leaves a head
+    without an ordinary class raises PBError naming the prompt, the bar and the head. An entry that removes nothing beyond the row mask
+    is no entry. owner (row -> prompt, check_samples): the indices are expanded to one per output row.
+    Returns None where no schedule is in force (bar_allow None, or no entry that removes a class: the caller runs what it ran before,
+    check_allow included), else (masks, index, table, sched): masks = the distinct masks of rows AND bars packed as check_allow packs
+    them, (n, ceil(V / 32)) uint32; index = one int per row, the row's own mask or -1 = free; table = the distinct schedules, (n_sched,
+    pad[0]) int32, entry k = the mask in force for heads 1 .. 7 of a token of bar k or -1 = the row's own; sched = one int per row, the
+    row's schedule or -1 = none. (masks, index) is check_allow's result for the call, with the bars' masks appended to the table."""
+    if bar_allow is None:
+        return None
+    lay = layout if layout is not None else ops.DEFAULT_LAYOUT
+    V, nbar = int(lay.vocab), int(lay.pad8[0])
+    is_mask = lambda m: isinstance(m, (np.ndarray, torch.Tensor)) and m.ndim == 1
+    if isinstance(bar_allow, dict) or (P == 1 and isinstance(bar_allow, (list, tuple)) and any(is_mask(m) for m in bar_allow)):
+        bar_allow = [bar_allow]
+    if not isinstance(bar_allow, (list, tuple)):
+        raise PBError('bar_allow must be a list of %d schedules, one per prompt (got %r)' % (P, type(bar_allow).__name__))
+    if len(bar_allow) != P:
+        raise PBError('bar_allow has %d entries for %d prompt(s)' % (len(bar_allow), P))
+    base = check_allow(allow, P, lay)                        # the rows' own masks: the argument rules and refusals of the call without a schedule
+    rows = list(_unpack_bits(base[0], V)) if base is not None else []
+    index = list(base[1]) if base is not None else [-1] * P
+    keys = {m.tobytes(): i for i, m in enumerate(rows)}
+    masks = list(rows)
+    skeys, table, sched = {}, [], []
+    for p, sc in enumerate(bar_allow):
+        if sc is None:
+            sched.append(-1)
+            continue
+        own = rows[index[p]] if index[p] >= 0 else np.ones(V, dtype=bool)
+        line = np.full(nbar, -1, dtype=np.int32)
+        for k, m in sorted(_schedule_entries(sc, nbar, 'bar_allow[%d]' % p).items()):
+            if m is None:
+                continue
+            try:
+                m = _as_numpy(m)
+            except Exception:
+                raise PBError('bar_allow[%d], bar %d: %r is neither None nor a bool mask' % (p, k, m))
+            if m.dtype != np.bool_:
+                raise PBError('bar_allow[%d], bar %d: the mask must be bool (got %s)' % (p, k, m.dtype))
+            if m.shape != (V,):
+                raise PBError('bar_allow[%d], bar %d: mask of shape %s, expected (%d,), one bool per vocabulary column' % (p, k, tuple(m.shape), V))
+            m = m & own
+            for h in range(8):
+                o, n, pad = lay.seg_off[h], lay.sizes[h], lay.pad8[h]
+                if h and not m[o:o + pad].any():                 # head 0 never sees the schedule
+                    raise PBError('bar_allow[%d]: the row mask and the mask of bar %d leave head %d (%s) without an ordinary class'
+                                  % (p, k, h, ops.CLASS_NAMES[h]))
+                m[o + pad:o + n] = True
+            m[lay.seg_off[0]:lay.seg_off[1]] = own[lay.seg_off[0]:lay.seg_off[1]]     # ... so its columns stay the row's: one canonical form per effect
+            if (m == own).all():
+                continue
+            key = m.tobytes()
+            if key not in keys:
+                keys[key] = len(masks)
+                masks.append(m)
+            line[k] = keys[key]
+        if (line < 0).all():
+            sched.append(-1)
+            continue
+        key = line.tobytes()
+        if key not in skeys:
+            skeys[key] = len(table)
+            table.append(line)
+        sched.append(skeys[key])
+    if not table:
+        return None
+    if owner is not None:
+        index, sched = [index[p] for p in owner], [sched[p] for p in owner]
+    return _pack_bits(masks, V), index, np.ascontiguousarray(np.stack(table), dtype=np.int32), sched
+
+
+def unpack_schedule(plan, vocab):
+    """The schedules of check_bar_allow's result as the host's decode loops take them: per ROW None, or a list of pad[0] entries, entry k
+    = the (vocab,) torch.bool mask in force for heads 1 .. 7 of a token of bar k, None = the row's own mask."""
+    if plan is None:
+        return None
+    ms = [torch.from_numpy(np.ascontiguousarray(b)) for b in _unpack_bits(plan[0], vocab)]
+    lines = [[ms[e] if e >= 0 else None for e in line] for line in plan[2]]
+    return [lines[i] if i >= 0 else None for i in plan[3]]
+
+
+def _slice_schedule(plan, a, b):
+    """check_bar_allow's result for the rows a .. b - 1 (both tables stay whole); None where none of them has a schedule."""
+    if plan is None or all(i < 0 for i in plan[3][a:b]):
+        return None
+    return plan[0], list(plan[1][a:b]), plan[2], list(plan[3][a:b])
+
+
+def scheduled_token(frow, sample, allow, sched, floor, prev, pad):
+    """The token of ONE position under the bar-schedule contract, for every decode path: allowed_token (and through it ordered_token and
+    forced_token) with the path's sample() told the row's schedule and head 0's given id. sched: the row's entry of unpack_schedule (None:
+    no schedule -- allowed_token(frow, sample, allow, floor, prev, pad), nothing else). sample(sched=(masks_by_bar, given0)[, allow=..,
+    order=..]) is the path's own sampling of the position: head 0 as ever, heads 1 .. 7 from the mask of bar b0 = given0 if >= 0 else the
+    sampled bar (PianoBartLM.sample_row). Given heads are written as given; the draws are forced_token's."""
+    if sched is None:
+        return allowed_token(frow, sample, allow, floor, prev, pad)
+    given0 = int(frow[0]) if frow is not None else -1
+    return allowed_token(frow, lambda **kw: sample(sched=(sched, given0), **kw), allow, floor, prev, pad)
+
+
+def follows_schedule(rows, schedule, start=0, forced=None, layout=None):
+    """Whether every emitted, non-given head 1 .. 7 of the rows from `start` on is inside the mask its row's bar has in `schedule` (host,
+    numpy). rows (S, 8) Octuple ids; the emitted rows are those in front of the first row whose bar id is special. schedule: a dict {bar:
+    (V,) bools} or a sequence of masks / None by bar id (check_bar_allow's forms, the masks as given: is_allowed tests the row's own);
+    a bar without an entry tests nothing, special ids count as allowed. forced (S, 8) or None: a given head (>= 0) is not tested."""
+    lay = layout if layout is not None else ops.DEFAULT_LAYOUT
+    x = _as_numpy(rows).astype(np.int64)
+    special = np.flatnonzero(x[:, 0] >= lay.pad8[0])
+    e = int(special[0]) if len(special) else len(x)
+    ent = {k: _as_numpy(m).astype(bool) for k, m in _schedule_entries(schedule, int(lay.pad8[0]), 'schedule').items() if m is not None}
+    off, pad, top = np.asarray(lay.seg_off[:8], dtype=np.int64), np.asarray(lay.pad8, dtype=np.int64), np.asarray(lay.sizes) - 1
+    fr = _as_numpy(forced) if forced is not None else None
+    for i in range(start, e):
+        m = ent.get(int(x[i, 0]))
+        if m is None:
+            continue
+        ok = m[np.clip(x[i], 0, top) + off] | (x[i] >= pad)
+        if fr is not None:
+            ok |= fr[i] >= 0
+        if not ok[1:].all():
+            return False
+    return True
+
+
+_CHORDS = {'maj': (0, 4, 7), 'min': (0, 3, 7), 'dim': (0, 3, 6), 'aug': (0, 4, 8), '7': (0, 4, 7, 10), 'maj7': (0, 4, 7, 11), 'min7': (0, 3, 7, 10),
+           'sus2': (0, 2, 7), 'sus4': (0, 5, 7)}
+
+
+def chord_mask(e2w, chord):
+    """One (V,) bool mask (a bar's entry of a schedule, or an allow mask) that keeps the melodic 'Pitch k' whose pitch class is a tone of the
+    chord and removes the 'Pitch percussion k' classes; every other head stays free. chord = 'ROOT:QUALITY': roots C, C#, Db, D, .. B
+    (allow_mask's tonics), qualities maj, min, dim, aug, 7, maj7, min7, sus2, sus4. e2w: the dictionary's event -> word half (PianoBart.e2w).
+    PBError: a string of another form, an unknown root or quality (the known ones listed), or a dictionary without such a pitch."""
+    try:
+        root, quality = str(chord).split(':')
+    except ValueError:
+        raise PBError('chord_mask: %r is not ROOT:QUALITY (C:maj, A:min7, ..)' % (chord,))
+    if root not in _TONICS:
+        raise PBError('chord_mask: unknown root %r (%s)' % (root, ', '.join(_TONICS)))
+    if quality not in _CHORDS:
+        raise PBError('chord_mask: unknown quality %r (%s)' % (quality, ', '.join(_CHORDS)))
+    lay, cls = ops.Layout.from_dict(e2w), ops.CLASS_NAMES[3]
+    pcs = {(_TONICS[root] + d) % 12 for d in _CHORDS[quality]}
+    ids = [int(i) for w, i in e2w[cls].items() if int(i) < lay.pad8[3] and w[len(cls) + 1:].isdigit() and int(w[len(cls) + 1:]) % 12 in pcs]
+    if not ids:
+        raise PBError('chord_mask: the dictionary has no melodic pitch on a tone of %s' % chord)
+    return allow_mask(e2w, heads={3: ids})
+
+
+def chord_schedule(e2w, chords, bars_per_chord=1, start_bar=0, repeat=True, n_bars=None):
+    """A bar schedule (check_bar_allow's sequence form: pad[0] entries, a chord_mask or None) from a chord progression: bar start_bar +
+    j takes chord (j // bars_per_chord) of `chords`, for j = 0 .. n_bars - 1 (None: up to the dictionary's last bar id). repeat: the
+    progression starts over when it ends; otherwise the bars behind it have no entry. Bars in front of start_bar have none."""
+    chords = [chords] if isinstance(chords, str) else list(chords)
+    if not chords:
+        raise PBError('chord_schedule: no chord named')
+    for name, v, lo in (('bars_per_chord', bars_per_chord, 1), ('start_bar', start_bar, 0)) + ((('n_bars', n_bars, 0),) if n_bars is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise PBError('chord_schedule: %s must be an integer >= %d (got %r)' % (name, lo, v))
+    nbar = int(ops.Layout.from_dict(e2w).pad8[0])
+    ms = {}
+    out = [None] * nbar
+    for k in range(int(start_bar), nbar if n_bars is None else min(nbar, int(start_bar) + int(n_bars))):
+        c = (k - int(start_bar)) // int(bars_per_chord)
+        if c >= len(chords) and not repeat:
+            break
+        name = chords[c % len(chords)]
+        if name not in ms:
+            ms[name] = chord_mask(e2w, name)
+        out[k] = ms[name]
+    return out
+
+
+def add_schedule_flags(ap):
+    """The command-line form of chord_schedule, shared by eval_generation, demo and tools/decode_batch_bench.py."""
+    ap.add_argument('--chords', type=str, default=None, metavar='ROOT:QUALITY[,...]', help='bar schedule: the pitches of bar after bar follow this chord '
+                    'progression (C:maj,G:maj,A:min,F:maj), repeated to the end of the piece')
+    ap.add_argument('--bars_per_chord', type=int, default=1, metavar='N', help='--chords: every chord holds for N bars')
+    ap.add_argument('--chord_start', type=int, default=None, metavar='B', help='--chords: the bar of the first chord (default: 0, or with --prime the bar '
+                    'after the one each piece\'s prime ends in)')
+
+
+def schedule_from_args(args, e2w, prime=None):
+    """The bar schedule the flags of add_schedule_flags describe for ONE piece, built from the dictionary e2w; None where --chords is not
+    given. prime: the piece's prime rows (k, 8) or None -- without --chord_start the first chord sits in the bar after the one the prime
+    ends in (bar 0 for an unprimed piece). PBError for flags that are not of their form, and chord_schedule's."""
+    chords = getattr(args, 'chords', None)
+    if chords is None:
+        if getattr(args, 'chord_start', None) is not None or getattr(args, 'bars_per_chord', 1) != 1:
+            raise PBError('--chord_start and --bars_per_chord need --chords')
+        return None
+    names = [t.strip() for t in str(chords).split(',') if t.strip()]
+    start = getattr(args, 'chord_start', None)
+    if start is None:
+        start = int(_as_numpy(prime)[-1, 0]) + 1 if prime is not None and len(prime) else 0
+    return chord_schedule(e2w, names, bars_per_chord=getattr(args, 'bars_per_chord', 1), start_bar=int(start))
+
+
 def stop_vector(pad_cpu, s):
     """The 8 thresholds of ONE row's stop test, for every decode path: the reference's `(current_output >= pad).any()` (model.py:47)
     becomes `(current_output >= stop_vector(pad, s)).any()` -- pad with its head 0 lowered to the row's stop bar s, so the one comparison
@@ -679,7 +913,8 @@ class GenerationMixin:
         return dict(sampler_form='wide') if self.last_sampler_form == 'wide' else {}
 
     # ------------------------------------------------------------------ generate (model.py:28-66)
-    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None, allow=None):
+    def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None, allow=None,
+                 bar_allow=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -711,7 +946,11 @@ class GenerationMixin:
         in place of every logit whose bit is 0 (allowed_token; DESIGN.md section 1, "Allowed classes"). The mask is constant over the
         positions; the special ids stay reachable; forcing, the stop test, the draws and what is written are unchanged; an ordered row
         loses the classes either rule removes. `sample_row` must then take the keyword `allow`. None, or True everywhere: the call
-        without the argument."""
+        without the argument.
+        bar_allow (one bar schedule, or a sequence of one; check_bar_allow): allowed classes that change with the bar -- head 0 as without
+        it; heads 1 .. 7 of a token whose bar after forcing is b0 are sampled from `allow AND bar_allow[b0]` where b0 is ordinary and
+        has an entry (scheduled_token; DESIGN.md section 1, "Bar schedules"). `sample_row` must then take the keyword `sched`. None, or
+        no entry that removes a class: the call without the argument; last_decode gains `scheduled` only when a schedule is in force."""
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
@@ -720,16 +959,18 @@ class GenerationMixin:
         sb = stop[0] if stop is not None else None
         order = check_order([order] if isinstance(order, (int, np.integer)) and not isinstance(order, bool) else order, 1, order_max=int(self.pb.pad_word_np[0]) - 1)
         ob = order[0] if order is not None else None
-        allow = check_allow(allow, 1, self.lay if allow is not None else None)
+        plan = check_bar_allow(bar_allow, allow, 1, self.lay)
+        allow = plan[:2] if plan is not None else check_allow(allow, 1, self.lay if allow is not None else None)
         ab = unpack_allow(allow, self.lay.vocab)[0] if allow is not None else None
+        sc = unpack_schedule(plan, self.lay.vocab)[0] if plan is not None else None
         fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -740,11 +981,11 @@ class GenerationMixin:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                     info = self._decode_device_sampled(run.dec, 1, S, lambda b, row, **kw: sample_row(row, **kw), [np.random.get_state()], sampler,
                                                        res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop,
-                                                       order=order, allow=allow)
+                                                       order=order, allow=allow, sched=plan)
                     info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0], ended=info['ended'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob, ab)
-                self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()))
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob, ab, sc)
+                self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()), **(dict(scheduled=True) if sc is not None else {}))
                 if not with_ended:
                     del self.last_decode['ended']
             else:
@@ -760,7 +1001,7 @@ class GenerationMixin:
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
-                    tok = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ab, ob, prev, pad_cpu)
+                    tok = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ab, sc, ob, prev, pad_cpu)
                     if (tok >= sv).any():
                         break
                     res_cpu[0, i] = prev = tok
@@ -932,11 +1173,12 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None, allow=None):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None, allow=None, sched=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
         k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
-        (ordered_token; prev is tok_np, the decoder's input). allow: the row's (V,) bool mask or None (allowed_token)."""
+        (ordered_token; prev is tok_np, the decoder's input). allow: the row's (V,) bool mask or None (allowed_token). sched: the row's
+        schedule (unpack_schedule) or None (scheduled_token)."""
         import ctypes
         sv, ended = stop_vector(pad_cpu, stop), 'limit'
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
@@ -950,7 +1192,7 @@ class GenerationMixin:
         for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
-            tok = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), allow, order, tok_np, pad_cpu)
+            tok = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), allow, sched, order, tok_np, pad_cpu)
             if (tok >= sv).any():
                 ended = end_reason(tok, pad_cpu)
                 break
@@ -963,7 +1205,7 @@ class GenerationMixin:
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
     def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
-                       refill=False, stop=None, order=None, allow=None):
+                       refill=False, stop=None, order=None, allow=None, bar_allow=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -1002,7 +1244,12 @@ class GenerationMixin:
         allow ((B, V) bools, or a list of B masks / None; check_allow): allowed classes, row b under `generate`'s contract with allow[b];
         None = a free row, so one batch may mix both. With samples it describes the P prompts, like the prefix. The fused decoder's device
         sampler tests the same bits (pb_batch_decoder_allow uploads the distinct masks once; a refilled slot gets its row's mask index
-        with the hand-over, pb_batch_decoder_admit_allow). None, or True everywhere: the call without the argument."""
+        with the hand-over, pb_batch_decoder_admit_allow). None, or True everywhere: the call without the argument.
+        bar_allow (a list of B bar schedules / None; check_bar_allow): row b under `generate`'s contract with bar_allow[b]; None = no
+        schedule, so one batch may mix scheduled, masked and free rows. With samples it describes the P prompts. The device sampler
+        picks the mask of heads 1 .. 7 by the bar it sampled (pb_batch_decoder_schedule uploads the distinct schedules once, their
+        masks travel in pb_batch_decoder_allow's table; a refilled slot gets its row's index with the hand-over,
+        pb_batch_decoder_admit_schedule). None, or no entry that removes a class: the call without the argument."""
         def done(out, with_ended=stop is not None):      # every path below records `ended`; a call without `stop` keeps the record it had
             if not with_ended and self.last_decode is not None:
                 self.last_decode.pop('ended', None)
@@ -1015,7 +1262,8 @@ class GenerationMixin:
         pad0 = int(self.pb.pad_word_np[0])
         stop = check_stop(stop, P, pad0, owner if samples is not None else None)         # one entry per output row
         order = check_order(order, P, owner if samples is not None else None, order_max=pad0 - 1)            # ... and here
-        allow = check_allow(allow, P, self.lay if allow is not None else None, owner if samples is not None else None)   # ... and here: (distinct masks, one index per row)
+        plan = check_bar_allow(bar_allow, allow, P, self.lay, owner if samples is not None else None)    # ... and here: None, or both tables and both indices per row
+        allow = plan[:2] if plan is not None else check_allow(allow, P, self.lay if allow is not None else None, owner if samples is not None else None)   # (distinct masks, one index per row)
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
         self._await_updates(2)
@@ -1024,10 +1272,10 @@ class GenerationMixin:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order, allow))
-            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order, allow))
+                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order, allow, plan))
+            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order, allow, plan))
         if slots and R > slots:
-            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order, allow)
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order, allow, plan)
             if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
                 return done(out)
         outs, ended = [], []
@@ -1038,39 +1286,43 @@ class GenerationMixin:
             od = order[c0:c0 + len(own)] if order is not None else None
             od = od if od is not None and any(v != -1 for v in od) else None       # ... and one without an ordered row
             al = _slice_allow(allow, c0, c0 + len(own))                           # ... and one without a masked row
+            pl = _slice_schedule(plan, c0, c0 + len(own))                         # ... and one without a scheduled row
+            al = pl[:2] if pl is not None else al                                 # (a scheduled chunk uploads the table even if its rows' own masks are free)
             p0, p1 = own[0], own[-1] + 1                 # prompt-major rows: the chunk's prompts are a range
             outs.append(self._generate_batch_chunk(enc_ids[p0:p1], emask[p0:p1] if emask is not None else None, sample_row,
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
                                                    groups=[p - p0 for p in own] if samples is not None else None,
                                                    forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st, order=od,
-                                                   allow=al))
+                                                   allow=al, sched=pl))
             ended += (self.last_decode or {}).get('ended') or [None] * len(own)
         if len(outs) > 1 and self.last_decode is not None:                # last_decode describes the last chunk; `ended` covers every row
             self.last_decode['ended'] = ended
         return done(torch.cat(outs, 0))
 
     def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None, order=None,
-                                 allow=None):
+                                 allow=None, sched=None):
         """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt. stop: one
-        entry per ROW (check_stop expands it), or None; order likewise (check_order), and allow's indices (check_allow)."""
+        entry per ROW (check_stop expands it), or None; order likewise (check_order), and allow's indices (check_allow) and sched's
+        (check_bar_allow)."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
                                          max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
-                                         forced[idx.numpy()] if forced is not None else None, stop, order, allow)
+                                         forced[idx.numpy()] if forced is not None else None, stop, order, allow, sched)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
     def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None, order=None,
-                             allow=None):
+                             allow=None, sched=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
         caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
         checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None; order: one bar floor per row
-        (check_order) or None; allow: check_allow's result with one index per row, or None."""
+        (check_order) or None; allow: check_allow's result with one index per row, or None; sched: check_bar_allow's result likewise, or None."""
         saved = np.random.get_state()
         outs, ended, pad0 = [], [], int(self.pb.pad_word_np[0])
         masks = unpack_allow(allow, self.lay.vocab)
+        scheds = unpack_schedule(sched, self.lay.vocab)
         try:
             for b in range(int(enc_ids.shape[0])):
                 np.random.set_state(rngs[b].get_state())
@@ -1079,33 +1331,35 @@ class GenerationMixin:
                                           max_new=max_new, sampler=sampler, prefix=pre, forced=forced[b:b + 1] if forced is not None else None,
                                           stop=stop[b] if stop is not None else pad0,         # 256: no stop, and the row's `ended`
                                           order=order[b] if order is not None else None,
-                                          allow=masks[b].numpy() if masks is not None and masks[b] is not None else None))
+                                          allow=masks[b].numpy() if masks is not None and masks[b] is not None else None,
+                                          bar_allow=[scheds[b]] if scheds is not None and scheds[b] is not None else None))
                 ended.append((self.last_decode or {}).get('ended'))
                 rngs[b].set_state(np.random.get_state())
         finally:
             np.random.set_state(saved)
-        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended)
+        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended, **(dict(scheduled=True) if sched is not None else {}))
         return torch.cat(outs, 0)
 
     def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None, order=None,
-                              allow=None):
+                              allow=None, sched=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
         loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None;
-        order: one bar floor per ROW, or None; allow: check_allow's result with one index per ROW, or None."""
+        order: one bar floor per ROW, or None; allow: check_allow's result with one index per ROW, or None; sched: check_bar_allow's
+        result likewise, or None."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order, allow)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order, allow, sched)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
             info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row, **kw: sample_row(row, rngs[b], **kw), [r.get_state() for r in rngs],
                                                sampler, run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
                                                forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop,
-                                               order=order, allow=allow)
+                                               order=order, allow=allow, sched=sched)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None, allow=None):
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None, allow=None, sched=None):
         """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
         waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
         in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
@@ -1119,7 +1373,8 @@ class GenerationMixin:
         stages nothing and its slot gets pad[0], never the previous occupant's value. order (R bar floors or None) travels the same way
         (pb_batch_decoder_order, pb_batch_decoder_admit_order; a free row stages nothing and its slot gets -1), and so does allow (check_allow's
         result for the R rows: the table of ALL rows' masks goes up at the start, pb_batch_decoder_allow, and a later row's index is staged,
-        pb_batch_decoder_admit_allow). Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        pb_batch_decoder_admit_allow), and sched (check_bar_allow's result: pb_batch_decoder_schedule, pb_batch_decoder_admit_schedule; a
+        successor without a schedule stages nothing and its slot gets -1). Returns the (R, S, 8) result, or None -- before any encoder work -- where
         pb_batch_decoder_create declines the shape."""
         R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
@@ -1135,12 +1390,12 @@ class GenerationMixin:
                 return None
             try:
                 return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
-                                        pad_cpu, stop, order, allow).to(dev)
+                                        pad_cpu, stop, order, allow, sched).to(dev)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
     def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None, order=None,
-                    allow=None):
+                    allow=None, bars=None):
         """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
         import ctypes
         from collections import deque
@@ -1216,7 +1471,11 @@ class GenerationMixin:
         if allow is not None:                                              # the masks of ALL rows: a later row's index points into this table
             LIB.call('pb_batch_decoder_allow', dec, allow[0].ctypes.data, allow[0].shape[0], allow[0].shape[1],
                      np.asarray(allow[1][:n], dtype=np.int32).ctypes.data)
+        if bars is not None:                                              # ... and the schedules of ALL rows, behind the masks they point to
+            rs = np.asarray(bars[3][:n], dtype=np.int32)                   # held until the call returns
+            LIB.call('pb_batch_decoder_schedule', dec, bars[2].ctypes.data, bars[2].shape[0], bars[2].shape[1], rs.ctypes.data)
         masks = unpack_allow(allow, vocab)
+        scheds = unpack_schedule(bars, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
@@ -1270,6 +1529,8 @@ class GenerationMixin:
                     LIB.call('pb_batch_decoder_admit_order', dec, s, order[r])
                 if allow is not None and allow[1][r] != -1:                # likewise; a free successor of a masked row gets -1
                     LIB.call('pb_batch_decoder_admit_allow', dec, s, allow[1][r])
+                if bars is not None and bars[3][r] != -1:                # likewise; a successor without a schedule gets -1
+                    LIB.call('pb_batch_decoder_admit_schedule', dec, s, bars[3][r])
                 LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
                          fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
                 counts['admissions'] += 1
@@ -1298,8 +1559,8 @@ class GenerationMixin:
 
         def verify(s, r, a, e):                    # positions a .. e-1 of row r in slot s, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(a, e):
-                tok = allowed_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
-                                    masks[r] if masks is not None else None, order[r] if order is not None else None,
+                tok = scheduled_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
+                                    masks[r] if masks is not None else None, scheds[r] if scheds is not None else None, order[r] if order is not None else None,
                                     res_cpu[r, i - 1] if i else sos, pad_cpu)
                 tokens[r] += 1
                 if (tok >= svs[r]).any():
@@ -1347,14 +1608,14 @@ class GenerationMixin:
         assert sched.done(), (sched.finished, R)
         self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                                 tokens=tokens, rewinds=rewinds, steps=stat['steps'], row_steps=stat['row_steps'], loop_ms=(time.perf_counter() - t_loop) * 1e3,
-                                host_ms=stat['host_s'] * 1e3, device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, refill=n, slices=NS,
+                                host_ms=stat['host_s'] * 1e3, device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, refill=n, slices=NS, **(dict(scheduled=True) if bars is not None else {}),
                                 admissions=counts['admissions'], row_slot=row_slot, encoder_passes=counts['encoder_passes'], s_enc=s_enc, batched=True, batch=n,
                                 prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms, ended=ended,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
         return res_cpu
 
     def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None,
-                               order=None, allow=None):
+                               order=None, allow=None, sched=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -1382,7 +1643,10 @@ class GenerationMixin:
         bites; one that applies it differs from the host as rarely as the unordered sampler does.
         allow (check_allow's result with B indices) or None: the distinct masks and the rows' indices go to the device sampler
         (pb_batch_decoder_allow: it tests the class's bit where it forms the quotient) and the host samples every position through
-        allowed_token with the row's mask; the logged logits rows are the raw ones."""
+        allowed_token with the row's mask; the logged logits rows are the raw ones.
+        sched (check_bar_allow's result with B indices; allow is then its first two members) or None: the distinct schedules and the rows'
+        indices go to the device sampler behind the masks (pb_batch_decoder_schedule: it picks the mask of heads 1 .. 7 by the bar of the
+        token it samples) and the host samples every position through scheduled_token with the row's schedule."""
         import contextlib
         import ctypes
         from collections import deque
@@ -1413,7 +1677,11 @@ class GenerationMixin:
         if allow is not None:
             LIB.call('pb_batch_decoder_allow', dec, allow[0].ctypes.data, allow[0].shape[0], allow[0].shape[1],
                      np.asarray(allow[1], dtype=np.int32).ctypes.data)
+        if sched is not None:
+            rs = np.asarray(sched[3], dtype=np.int32)                      # held until the call returns
+            LIB.call('pb_batch_decoder_schedule', dec, sched[2].ctypes.data, sched[2].shape[0], sched[2].shape[1], rs.ctypes.data)
         masks = unpack_allow(allow, vocab)
+        scheds = unpack_schedule(sched, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
         lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
         LIB.call('pb_batch_decoder_logs', dec, ctypes.byref(lp), ctypes.byref(tp))
@@ -1448,8 +1716,8 @@ class GenerationMixin:
 
         def verify(b, s, e):                       # positions s .. e-1 of row b, in order: None, ('stop', i) or ('seek', i, ids)
             for i in range(s, e):
-                tok = allowed_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
-                                    masks[b] if masks is not None else None, order[b] if order is not None else None,
+                tok = scheduled_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
+                                    masks[b] if masks is not None else None, scheds[b] if scheds is not None else None, order[b] if order is not None else None,
                                     res_cpu[b, i - 1] if i else sos, pad_cpu)
                 tokens[b] += 1
                 if (tok >= svs[b]).any():
@@ -1489,15 +1757,16 @@ class GenerationMixin:
                             sp[b][0] = sp[b][1] = i + 1
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
-                    device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, ended=ended)
+                    device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, ended=ended,
+                    **(dict(scheduled=True) if sched is not None else {}))
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
         rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
         fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads.
         stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None (ordered_token; prev is `cur`, the step's input).
-        allow: the row's (V,) bool mask or None (allowed_token)."""
+        allow: the row's (V,) bool mask or None (allowed_token). sched: the row's schedule (unpack_schedule) or None (scheduled_token)."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
@@ -1549,7 +1818,7 @@ class GenerationMixin:
                 frow = fr[i] if fr is not None else None
                 if frow is None or (frow < 0).any():
                     ops.gemm(h, self.w['head.w'], logits, M=1, N=self.lay.vocab, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
-                tok = allowed_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), allow, order,
+                tok = scheduled_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), allow, sched, order,
                                     cur.reshape(8).cpu() if order is not None else None, pad_cpu)
                 if (tok >= sv).any():
                     break
@@ -1557,11 +1826,12 @@ class GenerationMixin:
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
         cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
-        (ordered_token; prev is decoder input i, which the loop wrote at i - 1). allow: the row's (V,) bool mask or None (allowed_token)."""
+        (ordered_token; prev is decoder input i, which the loop wrote at i - 1). allow: the row's (V,) bool mask or None (allowed_token).
+        sched: the row's schedule (unpack_schedule) or None (scheduled_token)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -1584,7 +1854,7 @@ class GenerationMixin:
                 dec16 = ops.ids_to_i16(dec)
                 dec_h, _ = self.forward_hidden(enc16, dec16, em, dmask, False, 0, reuse_encoder=(i > k))
                 logits = self.heads_forward(dec_h)
-                cur = allowed_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), allow, order,
+                cur = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), allow, sched, order,
                                     dec[0, i].cpu() if order is not None else None, pad_cpu)
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)

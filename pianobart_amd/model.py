@@ -363,7 +363,7 @@ class PianoBartLM(nn.Module):
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
                 decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None,
-                decoder_order=None, decoder_allow=None):
+                decoder_order=None, decoder_allow=None, decoder_bar_allow=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
         position k on (Engine.generate's `prefix`).
         decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
@@ -389,7 +389,14 @@ class PianoBartLM(nn.Module):
         mask is constant over the positions; the six special ids of every head are always reachable (generation.check_allow sets them);
         given heads are written as given; the draws, the stop test and decoder_prefix are untouched; with decoder_order the row loses the
         classes either rule removes. generation.allow_mask builds a mask from the dictionary's names (key, pitch range, instruments, ..).
-        None, or True everywhere: the call without the argument. DESIGN.md section 1, "Allowed classes"."""
+        None, or True everywhere: the call without the argument. DESIGN.md section 1, "Allowed classes".
+        decoder_bar_allow (a bar schedule, or a sequence of one; generate=True only): a dict {bar id: (V,) bool mask} or a sequence of at
+        most pad[0] masks / None indexed by bar id -- allowed classes that change with the bar. Head 0 (the bar) is sampled as without
+        it; with b0 = head 0's id after forcing, heads 1 .. 7 of the token are sampled from `decoder_allow AND schedule[b0]` where b0 is
+        an ordinary bar with an entry, else from decoder_allow alone. The special ids stay reachable; given heads, the draws, the stop
+        test and the prefix are untouched; on an ordered row head 1's second pass starts from the bar's quotients.
+        generation.chord_schedule builds one from chord names ('C:maj', 'G:maj', ..). None, no entry, or entries True everywhere: the
+        call without the argument. DESIGN.md section 1, "Bar schedules"."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
@@ -402,6 +409,8 @@ class PianoBartLM(nn.Module):
                 raise PBError('decoder_order constrains what a generated piece samples: it needs generate=True')
             if decoder_allow is not None:
                 raise PBError('decoder_allow constrains what a generated piece samples: it needs generate=True')
+            if decoder_bar_allow is not None:
+                raise PBError('decoder_bar_allow constrains what a generated piece samples: it needs generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             off = self.pianobart.layout.seg_off
@@ -410,13 +419,14 @@ class PianoBartLM(nn.Module):
             print("ERROR")
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
-                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order, allow=decoder_allow)
+                           prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order, allow=decoder_allow,
+                           bar_allow=decoder_bar_allow)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
                        decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False,
-                       decoder_stop=None, decoder_order=None, decoder_allow=None):
+                       decoder_stop=None, decoder_order=None, decoder_allow=None, decoder_bar_allow=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -442,7 +452,11 @@ class PianoBartLM(nn.Module):
         decoder_allow ((B, V) bools, or a list of B entries, each a (V,) mask or None = free): prompt b under forward(generate=True,
         decoder_allow=...)'s contract with its own mask, so one batch may mix masked and free rows. With samples_per_prompt it describes
         the P prompts. The fused decoder's device sampler tests the same bits, so a masked batch keeps the batched decode's launches per
-        step and its rewind rate."""
+        step and its rewind rate.
+        decoder_bar_allow (a list of B entries, each a bar schedule -- forward(generate=True, decoder_bar_allow=...)'s dict or sequence --
+        or None): prompt b under that contract with its own schedule, so one batch may mix scheduled, masked and free rows. With
+        samples_per_prompt it describes the P prompts. The device sampler picks the mask of heads 1 .. 7 by the bar it sampled, so a
+        scheduled batch keeps the batched decode's launches per step and its rewind rate."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -460,7 +474,7 @@ class PianoBartLM(nn.Module):
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
                                  samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order,
-                                 allow=decoder_allow)
+                                 allow=decoder_allow, bar_allow=decoder_bar_allow)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def embed(self, input_ids_encoder, encoder_attention_mask=None, return_counts=False):
@@ -492,7 +506,7 @@ class PianoBartLM(nn.Module):
     SAMPLE_T =[1.2, 1.2, 5, 1, 2, 5, 5, 1.2]
     SAMPLE_P = [1, 1, 1, 0.9, 0.9, 1, 1, 0.9]
 
-    def sample_row(self, row_logits, rng=None, order=None, allow=None):
+    def sample_row(self, row_logits, rng=None, order=None, allow=None, sched=None):
         """row_logits: (vocab,) f32 CPU tensor of one position (1280 for the default dictionary); returns the 8 sampled ids (model.py:68-78). sampling()'s own tensor ops
         on the host row -- the division by the temperature (one call with a per-element temperature vector: the same quotients) and a
         1-D softmax per head -- then nucleus() for all 8 heads in one native call (pb_nucleus_rows: numpy's arithmetic order and
@@ -507,7 +521,13 @@ class PianoBartLM(nn.Module):
         allow = a (vocab,) bool tensor or array, True = the class may be sampled (generation.allowed_token), or None: the quotients of
         the other columns are set to -inf in front of the 8 softmaxes (probability exactly 0), beside the ordered sample's own mask; head
         1's second pass starts from the masked quotients. The native call and the tie rule are unchanged; without `allow` so is the
-        arithmetic."""
+        arithmetic.
+        sched = (masks_by_bar, given0) (generation.scheduled_token), or None: the bar schedule. masks_by_bar[k] is the (vocab,) bool mask
+        in force for heads 1 .. 7 of a token of bar k (already intersected with `allow`, special ids set), or None = `allow` alone. The
+        position is sampled as without it; then, with b0 = head 0's id after forcing (given0 if >= 0, else the id just sampled), where b0
+        is an ordinary bar with a mask the raw quotients of heads 1 .. 7 are masked with it, softmaxed again and pb_nucleus_rows runs
+        again with the same u: out[0] is kept, heads 1 .. 7 are replaced. The ordered head-1 pass then starts from those quotients. One
+        random_sample(8) either way; without `sched` the arithmetic and the native call are unchanged."""
         lay = getattr(getattr(self, 'pianobart', None), 'layout', None) or ops.DEFAULT_LAYOUT      # called on the class itself: the default dictionary
         tab = _sample_tables(lay)
         off = lay.seg_off
@@ -528,6 +548,19 @@ class PianoBartLM(nn.Module):
             for j in range(8):
                 if tie[0] >> j & 1:
                     out[j] = _nucleus_with_draw(pn[j, :tab['n'][j]], self.SAMPLE_P[j], u[j])
+        if sched is not None:
+            b0 = int(sched[1]) if sched[1] >= 0 else int(out[0])
+            m = sched[0][b0] if b0 < len(sched[0]) else None         # a special bar id has no entry: the row ends
+            if m is not None:
+                # heads 1 .. 7 again under bar b0's mask (a subset of `allow`, so masking the quotients in place is masking the raw ones);
+                # head 0's row of `probs` is untouched, so its id comes out as it did and is kept anyway
+                y[off[1]:].masked_fill_(~torch.as_tensor(m)[off[1]:], -np.inf)
+                for j in range(1, 8):
+                    torch.softmax(y[off[j]:off[j + 1]], dim=-1, out=probs[j, :tab['n'][j]])
+                again = out.copy()
+                LIB.call('pb_nucleus_rows', probs.data_ptr(), probs.shape[1], tab['n_p'], tab['p_p'], u.ctypes.data, 8, again.ctypes.data, tie.ctypes.data)
+                for j in range(1, 8):
+                    out[j] = _nucleus_with_draw(probs.numpy()[j, :tab['n'][j]], self.SAMPLE_P[j], u[j]) if tie[0] >> j & 1 else again[j]
         if order is not None and order[2] > 0 and (order[3] if order[3] >= 0 else int(out[0])) == order[1]:
             # the token stays in its predecessor's bar: head 1 again, from the masked quotients, with the draw it had (the other rows of
             # `probs` are untouched, so their ids come out as they did)
