@@ -1018,6 +1018,33 @@ int pb_event_record(void* ev, void* stream);
 int pb_stream_wait_event(void* stream, void* ev);
 int32_t pb_defer_desc_bytes(void);
 
+/* ---- K27: LoRA, low-rank adapters on the attention projections (pb_lora.hip; additions to ABI 10) ------------------------
+ * y = x W^T + b + s (x A^T) B^T with A (r, K), B (N, r), s = alpha / r (DESIGN.md 5 "LoRA"). The activations X / Y are rows of the storage
+ * dtype (PB_BF16 or PB_F32) with a leading dimension ld and a column offset, both in elements (the q / k / v slice of a (T, 3d) buffer is
+ * ld = 3d, offset 0 / d / 2d); they are read or written once, with 16-byte vectors where the slice's address and ld allow them. The adapter
+ * matrices, T and all sums are f32 (f32-input MFMA: an f32 fma chain). r is a multiple of 4 in 4 .. 64; 0 <= M <= 2^24 and M = 0 returns 0
+ * without a launch. No atomics: equal inputs give equal bytes. Every entry checks its arguments before the first HIP call (-2,
+ * pb_last_error names the argument).
+ *
+ * pb_lora_down:  T (M, r) = alpha * X (M, K) * W^T. w_kr = 0: W is (r, K); 1: W is (K, r). pb_lora_down_rows() rows per workgroup.
+ * pb_lora_up:    Y (M, N) += alpha * T (M, r) * W, a read-modify-write in Y's dtype (one rounding). w_nr = 0: W is (r, N); 1: W is (N, r).
+ *                Nothing outside columns y_off .. y_off + N - 1 of rows 0 .. M - 1 is written. pb_lora_up_rows() rows per workgroup.
+ * pb_lora_wgrad: G = alpha * T (M, r)^T * X (M, C), overwritten. g_cr = 0: G is (r, C); 1: G is (C, r). M is cut into
+ *                pb_lora_wgrad_chunk(M, r) rows per wave, each wave writes its partial to its slot of ws (pb_lora_wgrad_ws_floats(M, r, C) floats,
+ *                16-byte aligned; 0 for sizes the entry refuses) and the slots are added in slot order.
+ * pb_lora_merge: W (N, K) += alpha * B (N, r) A (r, K), all f32 with dense rows: an fma chain over r per element and one fma onto W. */
+int pb_lora_down_rows(void);
+int pb_lora_up_rows(void);
+int64_t pb_lora_wgrad_chunk(int64_t M, int32_t r);
+int64_t pb_lora_wgrad_ws_floats(int64_t M, int32_t r, int32_t C);
+int pb_lora_down(const void* X, int64_t ldx, int64_t x_off, int32_t dtype, const float* W, int32_t w_kr, float* T, int64_t M, int32_t K, int32_t r,
+                 float alpha, void* stream);
+int pb_lora_up(void* Y, int64_t ldy, int64_t y_off, int32_t dtype, const float* T, const float* W, int32_t w_nr, int64_t M, int32_t N, int32_t r,
+               float alpha, void* stream);
+int pb_lora_wgrad(const float* T, const void* X, int64_t ldx, int64_t x_off, int32_t dtype, float* G, int32_t g_cr, int64_t M, int32_t C, int32_t r,
+                  float alpha, float* ws, void* stream);
+int pb_lora_merge(float* W, const float* B, const float* A, int64_t N, int32_t K, int32_t r, float alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ class Args:
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
                  precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False,
                  key=None, pitch_range=None, instruments=None, tempo=None, max_duration=None, velocity=None, chords=None, bars_per_chord=1,
-                 chord_start=None):
+                 chord_start=None, lora=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
@@ -39,6 +39,7 @@ class Args:
         self.key, self.pitch_range, self.instruments, self.tempo, self.max_duration, self.velocity = key, pitch_range, instruments, tempo, max_duration, velocity
         # a bar schedule (eval_generation --chords / --bars_per_chord / --chord_start): the pitches follow a chord progression bar by bar
         self.chords, self.bars_per_chord, self.chord_start = chords, bars_per_chord, chord_start
+        self.lora = lora                    # None or the path of an adapter file: merged into the checkpoint's weights before generation (eval_generation --lora)
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
 
@@ -72,6 +73,8 @@ def get_args(argv=None):
                     'or one MASK row for the whole region (span)')
     ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
                     '--infill LO:HI and 0 otherwise')
+    ap.add_argument('--lora', type=str, default=None, metavar='PATH', help='an adapter file (finetune_generation --lora_rank): loaded on top of --ckpt '
+                    'and merged into the weights before generation')
     from .generation import add_allow_flags
     add_allow_flags(ap)
     from .generation import add_schedule_flags
@@ -167,6 +170,11 @@ def demo(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
+    if getattr(args, 'lora', None):
+        from . import lora as _lora
+        print("   Merging adapters from", args.lora.split('/')[-1])
+        _lora.load(args.lora, model, with_optimizer=False)
+        model._get_engine().merge_lora()
     octuple, prefix, ks, forced, stops, plan = octuple.long(), None, None, None, None, None
     if region is not None:                   # the rows in front of the region prime the decoder, the encoder sees the region as MASK
         from .generation import infill_plan

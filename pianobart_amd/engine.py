@@ -150,6 +150,41 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         # distillation / label smoothing (loss_and_grads(distill=..., smooth=...)): planes 4 and 5 (hard CE, KL) of the last such call as a (16,)
         # device tensor, None after a plain call; the (40,) sums and the kernel's partial sums are allocated by the first such call
         self.last_distill_sums, self._dsums, self._dpartials = None, None, None
+        # LoRA (attach_lora; DESIGN.md 5 "LoRA"): the lora.LoraState of the attached adapters, None without them (every launch is then what it was);
+        # wgrad_launches counts the backbone weight-gradient GEMMs _wgrad has issued (none while adapters are attached)
+        self.lora, self.wgrad_launches = None, 0
+
+    # ------------------------------------------------------------------ LoRA
+    def attach_lora(self, cfg, seed=0, train_heads=True):
+        """Freeze the backbone and give every projection named by cfg.targets a trainable rank-r adapter (A ~ U(-1/sqrt(K), 1/sqrt(K)) from a
+        torch.Generator seeded with `seed`, B = 0). train_heads: the LM heads keep training beside the adapters. Everything that can be refused is
+        refused before any device work."""
+        from .lora import LoraConfig, LoraState
+        if not isinstance(cfg, LoraConfig):
+            raise PBError('attach_lora needs a lora.LoraConfig (got %s)' % type(cfg).__name__)
+        cfg.check(self.d)
+        if self.lora is not None:
+            raise PBError('LoRA adapters are already attached to this engine (attaching a second time); merge_lora() or detach_lora() first')
+        if int(os.environ.get('WORLD_SIZE', 1)) > 1 or self.grad_hook is not None:
+            raise PBError('LoRA does not run data parallel (WORLD_SIZE = %s): the reducer buckets the flat backbone gradient' % os.environ.get('WORLD_SIZE', 1))
+        if self.device is None:
+            self.bind(self._param_map()[0][0].device)
+        self.finish_updates()
+        self.lora = LoraState(self, cfg, seed, train_heads)
+        return self.lora
+
+    def detach_lora(self):
+        """Drop the adapters (and their moments) without folding them in: the backbone is what it was before attach_lora."""
+        self.lora = None
+
+    def merge_lora(self):
+        """W += s B A for every site, in the f32 masters (pb_lora_merge); the bf16 shadow and its transposed copies follow, the adapters are dropped:
+        a plain model again, for the fused decoder, generate_batch, scoring, the metrics and model_merge."""
+        if self.lora is None:
+            raise PBError('merge_lora: no LoRA adapters are attached')
+        self.lora.merge(self)
+        self.lora = None
+        self.refresh_shadow(force=True)
 
     # ------------------------------------------------------------------ flat parameter layout
     def _layout(self):
@@ -538,6 +573,8 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
             if l == 2:
                 self._await_updates(1)
             self._linear(x, pf + 'wqkv', pf + 'bqkv', L['qkv'], T, 3 * d, d)
+            if self.lora is not None:
+                self.lora.forward(self, pf + 'qkv', x, L['qkv'], T)
             self._attn_fwd((L['qkv'], 0, 3 * d), (L['qkv'], d, 3 * d), (L['qkv'], 2 * d, 3 * d), (L['ctx'], 0, d), emask, False, B, S, S, L['attn'],
                            rows=r_enc)
             self._linear(L['ctx'], pf + 'wo', pf + 'bo', L['a1'], T, d, d)
@@ -573,6 +610,9 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         def kv_project(l0, l1):
             ops.gemm(enc_out, self.w['dec.wkv_all'], ws['kvc_all'], M=Te, N=(l1 - l0) * 2 * d, K=d, dtype=self.gcode, bias=self.wf['dec.bkv_all'][l0 * 2 * d:],
                      ldc=kvld, b_off=l0 * 2 * d * d, c_off=l0 * 2 * d, dbg=_FWD_GEMM_FLAGS)
+            if self.lora is not None:                      # the ck / cv adapter terms follow their GEMM on its stream, in front of kv_ready
+                for l in range(l0, l1):
+                    self.lora.forward(self, 'dec.%d.ckv' % l, enc_out, ws['kvc_all'], Te)
         kv_ready = None
         if (_WGRAD_STREAM & 2) and self._side_stream() is not None and self.ND:
             self._event().wait_on(self._side)
@@ -590,6 +630,8 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         for l in range(self.ND):
             L, pf = ws['dec'][l], 'dec.%d.' % l
             self._linear(y, pf + 'wqkv', pf + 'bqkv', L['qkv'], T, 3 * d, d)
+            if self.lora is not None:
+                self.lora.forward(self, pf + 'qkv', y, L['qkv'], T)
             self._attn_fwd((L['qkv'], 0, 3 * d), (L['qkv'], d, 3 * d), (L['qkv'], 2 * d, 3 * d), (L['ctx'], 0, d), dmask, True, B, S, S, L['attn'],
                            rows=r_dec)
             self._linear(L['ctx'], pf + 'wo', pf + 'bo', L['a1'], T, d, d)
@@ -605,6 +647,8 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                 Lq['attnc'] = L['attnc']
                 sub_layer = Lq
             self._linear(y1, pf + 'wq_c', pf + 'bq_c', Lq['qc'], Tq, d, d)
+            if self.lora is not None:
+                self.lora.forward(self, pf + 'cq', y1, Lq['qc'], Tq)
             if kv_ready is not None and (l == 0 or l == kv_cut):
                 kv_ready[l].wait_on(torch.cuda.current_stream())
             kx, vx = kv_of(l)
@@ -629,6 +673,10 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
     # ------------------------------------------------------------------ backward
     def _wgrad(self, dy, x, gname, M, N, T, ldy=None, ldx=None, dy_off=0, x_off=0, g_off=0):
         """G[gname] (M,N) = dy(T,M)^T @ x(T,N)  (TN GEMM into the f32 gradient buffer)."""
+        if self.lora is not None and (gname != 'head.w' or not self.lora.train_heads):
+            return            # frozen backbone: no weight gradient but the LM heads' (when they train beside the adapters)
+        if gname != 'head.w':
+            self.wgrad_launches += 1
         nsplit, slabs, big = 1, None, False
         if (self.code == PB_BF16 or self.x3) and T % 64 == 0:
             big = M >= 256 and N >= 256 and (M * N > 768 * 768 or _WG_DXD_256)     # 256x256 tiles, one block per CU (768x768: 128x128 tiles measured 712 vs 636 TF)
@@ -890,10 +938,15 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                     ops.colsum(dkv_all[:, l * 2 * d:(l + 1) * 2 * d], g[pf + 'bkv_c'], self.partials, Te, 2 * d, ld=kvld)
                 self._wgrad(dq_d, y1, pf + 'wq_c', d, d, Tq)
                 self._dgrad(dq_d, pf + 'wq_c', g1q, Tq, d, d, True)
+                if self.lora is not None:
+                    self.lora.backward(self, pf + 'cq', dq_d, y1, g1q, Tq)
                 if l == 0:
                     # the key / value side of every layer's cross-attention, in one go: nothing before the encoder's backward reads it
                     self._wgrad(dkv_all, sv['enc_out'], 'dec.wkv_all', kvld, d, Te)
                     self._dgrad(dkv_all, 'dec.wkv_all', genc, Te, d, kvld, False)
+                    if self.lora is not None:
+                        for lk in range(self.ND):
+                            self.lora.backward(self, 'dec.%d.ckv' % lk, dkv_all, sv['enc_out'], genc, Te)
                 if Tq != Td:
                     # the gradient wrt y1 lives on the loss rows: spread it over the decoder rows (zeros elsewhere) in the buffer `cur` has left
                     full = gy if g1.data_ptr() != gy.data_ptr() else galt
@@ -912,11 +965,15 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                     ops.colsum(dqkv_d, bq, self.partials, Td, 3 * d)
                 self._wgrad(dqkv_d, x_in, pf + 'wqkv', 3 * d, d, Td)
                 self._dgrad(dqkv_d, pf + 'wqkv', g2, Td, d, 3 * d, True)
+                if self.lora is not None:
+                    self.lora.backward(self, pf + 'qkv', dqkv_d, x_in, g2, Td)
                 cur = g2
                 self._ready(pf + 'wqkv', pf + 'w2')
             if self.ND:
                 self._ready('dec.wkv_all')
-            if sv.get('alt'):
+            if self.lora is not None:
+                pass                                                      # frozen backbone: nothing below the first decoder layer takes a gradient
+            elif sv.get('alt'):
                 gpre = cur
                 if p > 0.0:
                     gpre = gy if cur is not gy else galt
@@ -960,10 +1017,17 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                 ops.colsum(dqkv_e, bq, self.partials, Te, 3 * d)
             self._wgrad(dqkv_e, x_in, pf + 'wqkv', 3 * d, d, Te)
             self._dgrad(dqkv_e, pf + 'wqkv', g2, Te, d, 3 * d, True)
+            if self.lora is not None:
+                self.lora.backward(self, pf + 'qkv', dqkv_e, x_in, g2, Te)
             cur = g2
             self._ready(pf + 'wqkv', pf + 'w2')
         # the layers have left their last bias / LayerNorm-parameter partial sums: the one launch that reduces them all runs on the second
         # stream, beside the embedding gradients
+        if self.lora is not None:
+            # frozen backbone: the Octuple tables, the merge Linear and the position tables take no gradient
+            ops.defer_flush()
+            self._join_side()
+            return
         side_tail = (_WGRAD_STREAM & 1) and self._side_stream() is not None and self.grad_hook is None
         if side_tail:
             self._event().wait_on(self._side)
@@ -1211,11 +1275,17 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
         self._seed = (self._seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
         return self._seed
 
+    def _refuse_lora_autograd(self):
+        if self.lora is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.params):
+            raise PBError('a training forward through the autograd module path while LoRA adapters are attached: its backward returns backbone gradients '
+                          'that no longer exist; train with loss_and_grads / optimizer_step, or run the forward under torch.no_grad()')
+
     def module_forward_logits(self, enc_ids, dec_ids, emask, dmask, training):
         if self.mlm is None:
             raise PBError('engine has no LM heads')
         if enc_ids.device.type != 'cuda':
             raise PBError('pianobart_amd needs HIP device tensors (got %s); there is no CPU path' % enc_ids.device)
+        self._refuse_lora_autograd()
         self.bind(enc_ids.device)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params)
         out = _LMFn.apply(self, enc_ids, dec_ids, emask, dmask, training, need_grad, *self.params)
@@ -1225,6 +1295,7 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
     def module_forward_hidden(self, enc_ids, dec_ids, emask, dmask, training, dec_embeds=None):
         if enc_ids.device.type != 'cuda':
             raise PBError('pianobart_amd needs HIP device tensors (got %s); there is no CPU path' % enc_ids.device)
+        self._refuse_lora_autograd()
         self.bind(enc_ids.device)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params)
         n_backbone = len(self.params) - (16 if self.mlm is not None else 0)
@@ -1379,6 +1450,8 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
                 raise PBError('micro must be None or (i, K) with integers 0 <= i < K (got %r)' % (micro,))
             i, K = int(i), int(K)
             if K > 1:
+                if self.lora is not None:
+                    raise PBError('micro=(%d, %d): gradient accumulation does not combine with LoRA adapters (it sums the flat backbone gradient)' % (i, K))
                 if not train:
                     raise PBError('micro=(%d, %d): gradient accumulation belongs to training steps (train=False computes no gradient)' % (i, K))
                 if i > 0 and self._micro_prev != (i - 1, K):
@@ -1413,6 +1486,11 @@ class Engine(GenerationMixin, ScoringMixin, EmbeddingMixin):
     def optimizer_step(self, lr=2e-5, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, max_norm=3.0, gscale=1.0):
         """clip_grad_norm_(3.0) + HF AdamW on the flat buffers, refreshing the bf16 shadow (pretrain.py:195-196)."""
         self._raise_if_bad_ids(wait=True)
+        if self.lora is not None:
+            # adapters attached: the update covers the adapter buffer and (train_heads) the head ranges only; pipeline_updates is ignored and no
+            # backbone moment is allocated (DESIGN.md 5 "LoRA")
+            self.step_count += 1
+            return self.lora.step(self, lr, betas, eps, weight_decay, max_norm, gscale)
         if self.opt_m is None:
             self.opt_m = torch.zeros_like(self.P32)
             self.opt_v = torch.zeros_like(self.P32)

@@ -125,6 +125,8 @@ def get_args(argv=None):
                     'or one MASK row for the whole region (span)')
     ap.add_argument('--ordered', action='store_true', help='time-ordered sampling: no sampled (bar, position) goes back; the bar floor is LO under '
                     '--infill LO:HI and 0 otherwise')
+    ap.add_argument('--lora', type=str, default=None, metavar='PATH', help='an adapter file (finetune_generation --lora_rank): loaded on top of --ckpt '
+                    'and merged into the weights before anything runs')
     add_allow_flags(ap)
     add_schedule_flags(ap)
     return ap.parse_args(argv)
@@ -291,6 +293,11 @@ def eval_generation(args=None):
     device = torch.device('cuda', device_num)
     print("Use GPU", device)
     model = model.to(device).eval()
+    if getattr(args, 'lora', None):
+        from . import lora as _lora
+        print("   Merging adapters from", args.lora.split('/')[-1])
+        _lora.load(args.lora, model, with_optimizer=False)
+        model._get_engine().merge_lora()
     bar_pad = model.pianobart.bar_pad_word
     prime = parse_prime(getattr(args, 'prime', None))
     samples = getattr(args, 'samples', 1)

@@ -20,6 +20,7 @@ import torch
 
 from . import augment as _augment
 from . import distill as _distill
+from . import lora as _lora
 from . import ops
 from ._lib import PBError
 from .model import PianoBartLM, checkpoint_state_dict
@@ -54,6 +55,7 @@ def get_args_generation(argv=None):
                         help='gradient accumulation: one optimizer step over this many consecutive training batches (not in the reference)')
     _augment.add_arguments(parser)
     _distill.add_arguments(parser)
+    _lora.add_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -91,6 +93,7 @@ class GenerationTrainer:
         self.rank = int(os.environ.get('RANK', 0))
         self.augment, self.augment_seed, self._train_epoch = None, 0, -1     # --augment: an augment.AugmentPlan (None: off), --augment_seed
         self.distill, self.label_smoothing = None, 0.0                       # --distill_from / --label_smoothing: training steps only
+        self.lora = None                                                     # --lora_rank: the attached lora.LoraState (attach_lora below), None = the whole model trains
         self.reducer = None
         if self.world > 1:                                                   # one process per GPU, same exchange as the pre-train step
             import torch.distributed as dist
@@ -192,9 +195,25 @@ class GenerationTrainer:
         out = (round(total_loss / n, 4), [round(float(a) / n, 4) for a in total_acc], None, None)           # FAD(BAR), FAD: not measured
         return out + (all_output,) if mode == 2 else out
 
+    def attach_lora(self, cfg, seed=0, train_heads=True):
+        """--lora_rank: freeze the backbone and train adapters (and, unless told otherwise, the fresh LM heads) from here on."""
+        if self.reducer is not None or self.world > 1:
+            raise PBError('--lora_rank does not combine with a multi-rank launch: the reducer buckets the flat backbone gradient')
+        if int(self.accum_steps) > 1:
+            raise PBError('--lora_rank does not combine with --accum_steps %d' % self.accum_steps)
+        self.lora = self.engine.attach_lora(cfg, seed=seed, train_heads=train_heads)
+        return self.lora
+
     def save_checkpoint(self, epoch, train_acc, valid_acc, valid_loss, train_loss, is_best, filename):
-        """finetune_generation.py:276-290: whole-model state_dict (pianobart.* + mask_lm.*)."""
+        """finetune_generation.py:276-290: whole-model state_dict (pianobart.* + mask_lm.*). With adapters attached (--lora_rank) the adapter file
+        model.lora.pt (and model_best.lora.pt) is written instead: A / B, the heads, their moments; never a backbone tensor."""
         eng = self.engine
+        if eng.lora is not None:
+            root = filename[:-len('.ckpt')] if filename.endswith('.ckpt') else filename
+            _lora.save(root + '.lora.pt', self.model)
+            if is_best:
+                shutil.copyfile(root + '.lora.pt', root + '_best.lora.pt')
+            return
         state = {'epoch': epoch + 1, 'state_dict': {k: v.detach().cpu() for k, v in self.model.state_dict().items()}, 'valid_acc': valid_acc,
                  'valid_loss': valid_loss, 'train_loss': train_loss, 'train_acc': train_acc,
                  'optimizer': dict(eng.optimizer_state(self.model), lr=self.lr)}            # moments keyed by parameter name
@@ -214,6 +233,7 @@ def finetune_generation(argv=None):
     for seed_fn in (torch.manual_seed, np.random.seed, random.seed):
         seed_fn(2023)
     args = get_args_generation(argv)
+    lora_cfg = _lora.from_args(args)                                          # --accum_steps > 1 and a multi-rank launch are refused by name here
     print("Loading Dictionary")
     if args.dict_file.endswith('.json'):
         import json
@@ -246,6 +266,8 @@ def finetune_generation(argv=None):
     print("\nCreating Finetune Trainer")
     trainer = GenerationTrainer(pianobart, loaders[0], loaders[1], loaders[2], args.lr, y_test.shape, args.cpu, args.cuda_devices, model)
     trainer.accum_steps = args.accum_steps
+    if lora_cfg is not None:
+        trainer.attach_lora(lora_cfg, seed=args.lora_seed, train_heads=not args.lora_freeze_heads)
     trainer.augment, trainer.augment_seed = _augment.from_args(args, e2w), args.augment_seed
     trainer.distill, trainer.label_smoothing = _distill.from_args(args, e2w, w2e, trainer.device)     # every rank loads its own frozen teacher
     print("\nTraining Start")

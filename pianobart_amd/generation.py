@@ -903,6 +903,13 @@ def sampler_form_for(sizes, p):
     return 'wide' if max(int(n) for n in sizes) > 272 or ranked > 512 else 'narrow'
 
 
+def _refuse_unmerged_lora(eng, what):
+    """The fused decoder reads the backbone's weights alone: with LoRA adapters attached (Engine.attach_lora) it would generate from the base
+    model. Fold them in first. Reads the instance's own `lora` entry only, so it comes in front of every argument check without touching the engine."""
+    if vars(eng).get('lora') is not None:
+        raise PBError('%s: LoRA adapters are attached and not merged; call merge_lora() first (the decode kernels read the backbone weights only)' % what)
+
+
 class GenerationMixin:
     last_sampler_form = None            # 'narrow' / 'wide': the device sampler of the last device-sampled decode (None: there was none yet)
 
@@ -951,6 +958,7 @@ class GenerationMixin:
         it; heads 1 .. 7 of a token whose bar after forcing is b0 are sampled from `allow AND bar_allow[b0]` where b0 is ordinary and
         has an entry (scheduled_token; DESIGN.md section 1, "Bar schedules"). `sample_row` must then take the keyword `sched`. None, or
         no entry that removes a class: the call without the argument; last_decode gains `scheduled` only when a schedule is in force."""
+        _refuse_unmerged_lora(self, 'generate')
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
         ks, rows = check_prefix(prefix, None, 1, S, self.pb.pad_word_np)
@@ -1035,6 +1043,7 @@ class GenerationMixin:
         the shape, and creates none at PB_DECODE_GRAPH=-1. Otherwise a declined shape is yielded at once, before any encoder work, with
         run.dec None (the caller's fallback). Yields the run: dec, bp, bufs, B, S, G, groups, s_enc / starts (per row), pad_cpu, res_cpu
         ((B, S, 8) PAD with the prefixes in place), prefill_ms() and setup_ms."""
+        _refuse_unmerged_lora(self, 'the fused decoder')
         G, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         shared = groups is not None
         groups = list(groups) if shared else list(range(G))
@@ -1128,6 +1137,7 @@ class GenerationMixin:
         scratch rows, (B, vocab) logits and the split records. G: the cross cache holds G <= B slices, one per distinct prompt
         (pb_batch_decoder_share_cross maps the rows onto them)."""
         from ._lib import DecodeBatch
+        _refuse_unmerged_lora(self, 'the fused decoder')
         d, X, ff, wf = self.d, self.xdt, self.fd, self.wf
         e = lambda *shape, dt=X: torch.empty(*shape, dtype=dt, device=dev)
         bufs = dict(kvc=[e(B if G is None else G, S, 2 * d) for _ in range(self.ND)], kvs=[torch.zeros(B, S, 2 * d, dtype=X, device=dev) for _ in range(self.ND)],
@@ -1254,6 +1264,7 @@ class GenerationMixin:
             if not with_ended and self.last_decode is not None:
                 self.last_decode.pop('ended', None)
             return out
+        _refuse_unmerged_lora(self, 'generate_batch')
         P = int(enc_ids.shape[0])
         slots = check_refill(refill, samples, self.BATCH_MAX)
         owner = check_samples(samples, P, len(rngs)) if samples is not None else list(range(P))        # row -> prompt

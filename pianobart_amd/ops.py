@@ -1136,3 +1136,66 @@ def defer_flush():
 def l2_penalty(p, g, weight, scratch, loss_acc):
     """finetune.py:241-243 for one parameter tensor: loss_acc += weight * ||p||, g += weight * p / ||p|| (g may be None)."""
     LIB.call('pb_l2_penalty', _p(p), _p(g), p.numel(), float(weight), _p(scratch), _p(loss_acc), _stream())
+
+
+# ---- K27: LoRA (pb_lora.hip) -------------------------------------------------------------------------------------------------------------
+def _lora_rows(t, M, width, off, what):
+    """(address, leading dimension) of the (M, width) slice at column `off` of the row-major activation buffer `t` (bf16 or f32)."""
+    if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise PBError('%s must be a 2-D tensor with contiguous rows (got %s, strides %s)' % (what, tuple(t.shape), t.stride()))
+    if M > t.shape[0] or off < 0 or off + width > t.shape[1]:
+        raise PBError('%s: rows 0 .. %d, columns %d .. %d lie outside the %s tensor' % (what, M - 1, off, off + width - 1, tuple(t.shape)))
+    return _p(t), (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _lora_small(t, shape, what):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise PBError('%s must be a contiguous f32 tensor of shape %s (got %s %s)' % (what, tuple(shape), tuple(t.shape), t.dtype))
+    return _p(t)
+
+
+def lora_down(X, W, T, M, K, alpha=1.0, x_off=0, w_kr=False):
+    """T (M, r) f32 = alpha * X[:M, x_off : x_off + K] @ W^T. W is (r, K), or (K, r) with w_kr. X: bf16 or f32 rows of any leading dimension."""
+    r = T.shape[1]
+    x, ldx = _lora_rows(X, M, K, x_off, 'lora_down: X')
+    w = _lora_small(W, (K, r) if w_kr else (r, K), 'lora_down: W')
+    if T.dtype != torch.float32 or T.dim() != 2 or not T.is_contiguous() or T.shape[0] < M:
+        raise PBError('lora_down: T must be a contiguous (>= M, r) f32 tensor')
+    LIB.call('pb_lora_down', x, ldx, x_off, dtype_code(X.dtype), w, int(w_kr), _p(T), M, K, r, float(alpha), _stream())
+
+
+def lora_up(Y, T, W, M, N, alpha=1.0, y_off=0, w_nr=False):
+    """Y[:M, y_off : y_off + N] += alpha * T[:M] @ W in Y's dtype. W is (r, N), or (N, r) with w_nr."""
+    r = T.shape[1]
+    y, ldy = _lora_rows(Y, M, N, y_off, 'lora_up: Y')
+    w = _lora_small(W, (N, r) if w_nr else (r, N), 'lora_up: W')
+    if T.dtype != torch.float32 or T.dim() != 2 or not T.is_contiguous() or T.shape[0] < M:
+        raise PBError('lora_up: T must be a contiguous (>= M, r) f32 tensor')
+    LIB.call('pb_lora_up', y, ldy, y_off, dtype_code(Y.dtype), _p(T), w, int(w_nr), M, N, r, float(alpha), _stream())
+
+
+def lora_wgrad_ws(M, r, C, device):
+    """The workspace of one lora_wgrad call (reusable by the next call of that size on the same stream)."""
+    return torch.empty(max(4, int(LIB.query('pb_lora_wgrad_ws_floats', int(M), int(r), int(C)))), dtype=torch.float32, device=device)
+
+
+def lora_wgrad(T, X, G, M, C, alpha=1.0, x_off=0, g_cr=False, ws=None):
+    """G = alpha * T[:M]^T @ X[:M, x_off : x_off + C], overwritten. G is (r, C), or (C, r) with g_cr. Bitwise reproducible."""
+    r = T.shape[1]
+    x, ldx = _lora_rows(X, M, C, x_off, 'lora_wgrad: X')
+    g = _lora_small(G, (C, r) if g_cr else (r, C), 'lora_wgrad: G')
+    if T.dtype != torch.float32 or T.dim() != 2 or not T.is_contiguous() or T.shape[0] < M:
+        raise PBError('lora_wgrad: T must be a contiguous (>= M, r) f32 tensor')
+    if ws is None:
+        ws = lora_wgrad_ws(M, r, C, X.device)
+    if ws.dtype != torch.float32 or ws.numel() < LIB.query('pb_lora_wgrad_ws_floats', M, r, C):
+        raise PBError('lora_wgrad: ws is smaller than pb_lora_wgrad_ws_floats(%d, %d, %d)' % (M, r, C))
+    LIB.call('pb_lora_wgrad', _p(T), x, ldx, x_off, dtype_code(X.dtype), g, int(g_cr), M, C, r, float(alpha), _p(ws), _stream())
+
+
+def lora_merge(W, B, A, alpha):
+    """W (N, K) f32 += alpha * B (N, r) @ A (r, K), in place (W may be a row range of a flat-buffer slot)."""
+    N, K = W.shape
+    r = A.shape[0]
+    w = _lora_small(W, (N, K), 'lora_merge: W')
+    LIB.call('pb_lora_merge', w, _lora_small(B, (N, r), 'lora_merge: B'), _lora_small(A, (r, K), 'lora_merge: A'), N, K, r, float(alpha), _stream())
