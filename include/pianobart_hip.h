@@ -996,6 +996,32 @@ int pb_batch_decoder_allow(void* dec, const uint32_t* masks, int32_t n_masks, in
 int pb_batch_decoder_admit_allow(void* dec, int32_t row, int32_t mask_index);
 int pb_batch_decoder_schedule(void* dec, const int32_t* table, int32_t n_sched, int32_t nbar, const int32_t* row_sched);
 int pb_batch_decoder_admit_schedule(void* dec, int32_t row, int32_t sched_index);
+/* Anchored notes (an addition to ABI 10): a row may carry a list of anchors, complete tokens A[0 .. n) of 8 ordinary ids in non-decreasing
+ * (bar, position) order, and a counter k of those written (0 at start and admit). Every position is sampled as without them -- the
+ * candidate c, under the row's floor, mask, schedule and draws -- and the sampler's last stage decides: if k < n and (c ends the row: c[0]
+ * >= the row's stop bar or a special id in any head; or (c[0], c[1]) >= (A[k][0], A[k][1])) the 8 ids written are A[k], k becomes k + 1
+ * and the row is NOT done; else c is written and the done test is what it was. Both forms and both widths of the sampler, the kernels
+ * without the force table; the caller makes an anchored row time-ordered (pb_batch_decoder_order, floor >= 0).
+ *   pb_batch_decoder_anchor         between sampler_init and start, behind pb_batch_decoder_stop / _order: rows = (n_rows, 8) host ids, the
+ *                                   anchors of ALL rows of the call, copied to device memory the decoder owns; row_base / row_cnt = (B) host
+ *                                   ints, row b's anchors are rows row_base[b] .. + row_cnt[b] - 1 (count 0 = none). Stored in
+ *                                   decoder-stream order; pb_batch_decoder_start keeps them and sets the counters to 0. Same kernels, kernarg
+ *                                   layouts and launches per step. Refused (< 0, pb_last_error, nothing changed): a null argument, before
+ *                                   sampler_init, after a step was issued or captured, a decoder with a force table (and pb_batch_decoder_force
+ *                                   is refused behind it), n_rows < 1, a slice outside the table, more anchors than S, an id outside 0 ..
+ *                                   pad[h] - 1, a row's anchors out of (bar, position) order, a bar below the row's floor or >= its stop bar.
+ *   pb_batch_decoder_admit_anchor   refill: stages the slice of that table the next pb_batch_decoder_admit of `row` stores, with a counter
+ *                                   of 0; behind the row's admit_stop / admit_order. An admit without a staged value stores none: a slot
+ *                                   never inherits its previous occupant's anchors. Host state only. Refused: not a dynamic decoder, before
+ *                                   sampler_init, row outside 0 .. B - 1, a slice outside the table, order or bars as above.
+ *   pb_batch_decoder_seek_anchor    with the pb_batch_decoder_seek that rewinds `row`: sets its counter to `placed`, the number of anchors
+ *                                   the host has written up to the position sought, in decoder-stream order. Refused: before sampler_init,
+ *                                   row outside 0 .. B - 1, placed outside 0 .. the row's count.
+ *   pb_batch_decoder_anchors_placed drains what is enqueued and reads the B counters into out (0 for a row without anchors). */
+int pb_batch_decoder_anchor(void* dec, const int16_t* rows, int32_t n_rows, const int32_t* row_base, const int32_t* row_cnt);
+int pb_batch_decoder_admit_anchor(void* dec, int32_t row, int32_t base, int32_t cnt);
+int pb_batch_decoder_seek_anchor(void* dec, int32_t row, int32_t placed);
+int pb_batch_decoder_anchors_placed(void* dec, int32_t* out);
 
 /* ---- K15: deferred parameter-gradient reductions -----------------------------------------------------------------------
  * The bias / LayerNorm-parameter gradients of one backward pass (the `db = grad.sum(0)` of every nn.Linear and nn.LayerNorm autograd

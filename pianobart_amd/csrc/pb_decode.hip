@@ -11,6 +11,8 @@
 //   * pb_decode_step a native host function that issues the 8*ND + 2 launches of one token (embed -> ND x [q|k|v (+LN2 of the
 //                    layer below), self-attn, out, q_c (+LN1), cross-attn, out_c, fc1+GELU (+LNc), fc2] -> heads (+LN2))
 //                    without Python between; the post-LNs ride in the prologue of the GEMV that consumes them.
+#include <vector>
+
 #include "pb_common.h"
 #include "pb_api_internal.h"
 
@@ -67,8 +69,13 @@ struct BState {
     // 8-byte load, so a free row's requests are those of a sampler that knew the bar floor alone
     // ... and rule[b].sched >= 0 = the row follows bar schedule sched of the table stab ((n_sched, nbar) ints in device memory the decoder
     // owns, nbar = pad[0]: entry k = the index in amask of the mask heads 1 .. 7 take in a token of bar k, -1 = the row's own mask), -1 =
-    // no schedule (pb_batch_decoder_schedule, pb_batch_decoder_admit_schedule). With it the rules are ONE 16-byte load; `reserved` pads
-    // the record to that size and is kept at -1
+    // no schedule (pb_batch_decoder_schedule, pb_batch_decoder_admit_schedule). With it the rules are ONE 16-byte load; `reserved` padded
+    // the record to that size
+    // ... and rule[b].reserved >= 0 = the row carries anchors (pb_batch_decoder_anchor, pb_batch_decoder_admit_anchor): its value is the
+    // row's base in the anchor table atab ((n, 8) int16 ordinary ids, 16 bytes a row, in device memory the decoder owns), acnt[b] the
+    // number of its anchors and aplaced[b] the counter k of those written so far -- the one field of a row's rules that the SAMPLER
+    // writes, so a rewind restores it (pb_batch_decoder_seek_anchor). -1 = no anchors: the 16-byte rule load is all a free row makes.
+    // apad = the first special id of every head: the single-row sampler's kernargs hold none, and an anchored row tests all 8
     struct alignas(16) RowRule { int order, allow, sched, reserved; };
     RowRule rule[BMAX];
     int opad[2];
@@ -76,6 +83,10 @@ struct BState {
     const uint32_t* amask;
     int nbar;
     const int* stab;
+    int acnt[BMAX];
+    int aplaced[BMAX];
+    int apad[8];
+    const int16_t* atab;
 };
 
 // ROWS (the fused decoder's row form, B > 1 rows of x / res / y / ln_out / split records, bf16): the workgroup keeps its weight fragments
@@ -1279,6 +1290,14 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int16_t* __restric
 // it, and with a special input bar (the only case where the guess is not the input bar's entry) low1 is 0: a position pays at most ONE
 // second pass. Block-uniform like the other rules (BState, tok_dev, the force table, htok[0] behind a barrier): a row without a schedule
 // pays one compare and 8 more bytes in the rule load.
+// Anchored notes (pb_batch_decoder_anchor), both forms and both widths, the instantiations WITHOUT the force table: a row with
+// rule[b].reserved >= 0 carries a list of complete tokens A[0 .. n) in (bar, position) order and a counter k of those written. The
+// position is sampled as ever -- the candidate c -- and the last stage decides: if k < n and (c ends the row, or c's (bar, position) >=
+// A[k]'s) the 8 ids written are A[k], k becomes k + 1 and the row lives; else c is written and the done test is the one it was. The
+// counter and A[k] (one 16-byte row) are requested at the top of the kernel beside done[b] / pos[b]; the comparison sits behind the last
+// barrier, where htok[0] and htok[1] are final, in the 8 threads that write, each of which forms the whole decision from htok (LDS) and
+// block-uniform values -- no barrier is added. k is device state the SAMPLER advances: a rewind sets it (pb_batch_decoder_seek_anchor).
+// A row without anchors pays one compare on the slot of the rule load that was padding.
 struct SampleCommon {
     const float* logits;                  // (B, vocab) f32 rows of the positions just decoded
     const double* u;                      // (B, S, 8) uniform draws, device
@@ -1428,6 +1447,19 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
     // the first barrier; the last stage overwrites it behind the last one.
     const BState::RowRule rule = a.st->rule[b];                  // one 16-byte load: the bar floor, the allow mask and the bar schedule (below) of the row
     const int ord = rule.order, alw = rule.allow, sch = rule.sched;
+    // anchored row (rule[b].reserved >= 0, block-uniform; never with the force table): the counter, the count and the anchor the counter
+    // names are requested here; the last stage compares and writes. ak == an: every anchor is placed and the row samples on (the row
+    // read is then the last one, unused). A row's count is >= 1 wherever its base is >= 0 (pb_batch_decoder_anchor stores -1 for 0).
+    [[maybe_unused]] const int anc = rule.reserved;
+    [[maybe_unused]] int ak = 0, an = 0, astop = stop0;
+    [[maybe_unused]] uint4 arow = {0u, 0u, 0u, 0u};
+    if constexpr (!FORCED) {
+        if (anc >= 0) {
+            ak = a.st->aplaced[b]; an = a.st->acnt[b];
+            if constexpr (!ROWS) astop = a.st->stop[b];          // the single-row form has no done test of its own: the anchor rule needs the bar
+            arow = *reinterpret_cast<const uint4*>(a.st->atab + (size_t)(anc + max(min(ak, an - 1), 0)) * 8);     // 16 bytes, 16-byte aligned
+        }
+    }
     int low0 = 0, low1 = 0, prev0 = -1;
     if (ord >= 0) {
         const int p0 = a.tok_dev[b * 8 + 0], p1 = a.tok_dev[b * 8 + 1];
@@ -1615,9 +1647,35 @@ __global__ __launch_bounds__(512) void dec_sample_kernel(const typename SampleKe
         int id = htok[t];
         if constexpr (FORCED) { if (f >= 0) id = f; }
         if (a.fault_period > 0 && (!ROWS || b == a.fault_row) && t == 0 && (pos % a.fault_period) == a.fault_period - 1) id = (id + 1) % a.n[0];
+        // Anchored row with an anchor left: each of the 8 writing threads forms the whole decision from the candidate in htok (final: behind
+        // the last barrier; head 0 as the fault hook left it) and block-uniform values, so all 8 agree without another barrier. The
+        // candidate ends the row (the done test below, over all 8 heads) or its time has reached the anchor's: the anchor is written, all
+        // 8 heads as given, the counter advances and the row lives. Thread 0 alone stores the counter, which every thread read at the top.
+        [[maybe_unused]] bool placed = false;
+        if constexpr (!FORCED) {
+            if (anc >= 0 && ak < an) {
+                int c0 = htok[0];
+                const int c1 = htok[1];
+                if (a.fault_period > 0 && (!ROWS || b == a.fault_row) && (pos % a.fault_period) == a.fault_period - 1) c0 = (c0 + 1) % a.n[0];
+                bool ends = c0 >= astop;
+#pragma unroll
+                for (int q = 1; q < 8; ++q) {
+                    int padq;
+                    if constexpr (ROWS) padq = a.pad[q]; else padq = a.st->apad[q];
+                    ends = ends || htok[q] >= padq;
+                }
+                const int a0 = (int16_t)(arow.x & 0xffffu), a1 = (int16_t)(arow.x >> 16);
+                if (ends || c0 > a0 || (c0 == a0 && c1 >= a1)) {
+                    const unsigned w = t < 2 ? arow.x : (t < 4 ? arow.y : (t < 6 ? arow.z : arow.w));
+                    id = (int16_t)((t & 1) ? (w >> 16) : (w & 0xffffu));
+                    placed = true;
+                    if (t == 0) a.st->aplaced[b] = ak + 1;
+                }
+            }
+        }
         a.tok_dev[b * 8 + t] = (int16_t)id;
         a.log_tok[((size_t)b * a.S + pos) * 8 + t] = (int16_t)id;
-        if constexpr (ROWS) { if (id >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }    // the device stops the row here; the host confirms or rewinds it
+        if constexpr (ROWS) { if (!placed && id >= (t == 0 ? stop0 : a.pad[t])) a.st->done[b] = 1; }    // the device stops the row here; the host confirms or rewinds it
     }
 }
 
@@ -1650,6 +1708,13 @@ __global__ __launch_bounds__(64) void dec_sched_kernel(BState* __restrict__ st, 
     if (t < BMAX) st->rule[t].sched = g.sched[t];
     if (t == 0) { st->nbar = g.nbar; st->stab = g.table; }
 }
+struct AnchorArgs { int base[BMAX], cnt[BMAX]; int pad[8]; const int16_t* table; };
+__global__ __launch_bounds__(64) void dec_anchor_kernel(BState* __restrict__ st, const AnchorArgs g) {
+    const int t = threadIdx.x;
+    if (t < BMAX) { st->rule[t].reserved = g.cnt[t] > 0 ? g.base[t] : -1; st->acnt[t] = g.cnt[t]; st->aplaced[t] = 0; }
+    if (t < 8) st->apad[t] = g.pad[t];
+    if (t == 0) st->atab = g.table;
+}
 struct AdmitArgs {
     BState* st; int16_t* tok_dev;
     int row, s_enc, ck, slice, pos, limit;   // row < B <= BMAX (checked by pb_batch_decoder_admit)
@@ -1657,6 +1722,7 @@ struct AdmitArgs {
     int order;                               // ... and its bar floor of time-ordered sampling (-1: a free row)
     int allow;                               // ... and the index of its allow mask in the decoder's table (-1: every class allowed)
     int sched;                               // ... and the index of its bar schedule in the decoder's table (-1: none)
+    int anchor, n_anchor;                    // ... and its anchors: base in the decoder's table and count (-1, 0: none); the counter starts at 0
     int16_t tok[8];
 };
 __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
@@ -1665,7 +1731,8 @@ __global__ __launch_bounds__(64) void dec_admit_kernel(const AdmitArgs a) {
     if (t == 0) {
         a.st->s_enc[b] = a.s_enc; a.st->ck[b] = a.ck; a.st->kv_row[b] = a.slice;
         a.st->pos[b] = a.pos; a.st->limit[b] = a.limit; a.st->done[b] = 0; a.st->stop[b] = a.stop;
-        a.st->rule[b].order = a.order; a.st->rule[b].allow = a.allow; a.st->rule[b].sched = a.sched; a.st->rule[b].reserved = -1;
+        a.st->rule[b].order = a.order; a.st->rule[b].allow = a.allow; a.st->rule[b].sched = a.sched;
+        a.st->rule[b].reserved = a.n_anchor > 0 ? a.anchor : -1; a.st->acnt[b] = a.n_anchor; a.st->aplaced[b] = 0;
     }
 }
 
@@ -1720,6 +1787,11 @@ struct Decoder {
     int admit_sched[BMAX] = {};            // pb_batch_decoder_admit_schedule: the index the row's next admit stores (-1: none staged -> no schedule)
     int* sched_dev = nullptr;              // pb_batch_decoder_schedule: (n_sched, sched.nbar) indices into allow_dev's masks, -1 = the row's own mask
     int n_sched = 0;                       // schedules in sched_dev; 0 behind sampler_init until pb_batch_decoder_schedule
+    AnchorArgs anchor{};                   // host mirror of the rows' anchor bases and counts in BState (count 0: none) and of the table's address
+    int admit_anchor[BMAX] = {}, admit_nanchor[BMAX] = {};     // pb_batch_decoder_admit_anchor: what the row's next admit stores (count 0: none staged -> no anchors)
+    int16_t* anchor_dev = nullptr;         // pb_batch_decoder_anchor: (n_anchor, 8) ordinary ids, the anchors of ALL rows of the call
+    std::vector<int16_t> anchor_host;      // ... and the host's copy, for pb_batch_decoder_admit_anchor's checks
+    int n_anchor = 0;                      // rows in anchor_dev; 0 behind sampler_init until pb_batch_decoder_anchor
     hipEvent_t ev_fence = nullptr;
     char* stage = nullptr;                 // pinned: N_STAGE entries of {u (S, 8) f64 | forced (S, 8) i16 | mask (S) f32}
     size_t stage_bytes = 0;
@@ -1990,6 +2062,7 @@ extern "C" int pb_batch_decoder_destroy(void* dec) {
     if (D->force_dev) (void)hipFree(D->force_dev);
     if (D->allow_dev) (void)hipFree(D->allow_dev);
     if (D->sched_dev) (void)hipFree(D->sched_dev);
+    if (D->anchor_dev) (void)hipFree(D->anchor_dev);
     if (D->log_logits) (void)hipHostFree(D->log_logits);
     if (D->log_tok) (void)hipHostFree(D->log_tok);
     for (int i = 0; i < N_STAGE; ++i) if (D->stage_ev[i]) (void)hipEventDestroy(D->stage_ev[i]);
@@ -2136,6 +2209,8 @@ extern "C" int pb_batch_decoder_sampler_init(void* dec, const float* temps8, con
     D->n_allow = 0;                                                     // the previous run's table (if any) stays allocated and unread: no row points into it
     for (int b = 0; b < BMAX; ++b) { D->sched.sched[b] = -1; D->admit_sched[b] = -1; }
     D->n_sched = 0;                                                     // likewise
+    for (int b = 0; b < BMAX; ++b) { D->anchor.base[b] = -1; D->anchor.cnt[b] = 0; D->admit_anchor[b] = -1; D->admit_nanchor[b] = 0; }
+    D->n_anchor = 0;                                                    // likewise (the memset of `rule` above cleared the rows' slots)
     D->sa.logits = D->bp.plan.logits; D->sa.u = D->u_dev; D->sa.st = D->st; D->sa.tok_dev = D->tok_dev;
     D->sa.log_logits = D->log_logits; D->sa.log_tok = D->log_tok; D->sa.vocab = (int)vocab; D->sa.S = (int)S;
     D->sa.fault_row = fault_row; D->sa.fault_period = (D->B == 1 && fault_row != 0) ? 0 : fault_period;    // the single-row sampler corrupts row 0
@@ -2158,6 +2233,7 @@ extern "C" int pb_batch_decoder_force(void* dec, const int16_t* forced) {
     PB_REQUIRE(D && forced, "pb_batch_decoder_force: null argument");
     PB_REQUIRE(D->sampler, "pb_batch_decoder_force: pb_batch_decoder_sampler_init first");
     PB_REQUIRE(!D->issued, "pb_batch_decoder_force: a step was already issued; the sampler kernel is fixed for this decoder");
+    PB_REQUIRE(!D->n_anchor, "pb_batch_decoder_force: the decoder carries anchors (pb_batch_decoder_anchor): position-indexed and time-indexed givens do not combine");
     const size_t n = (size_t)D->B * (size_t)D->bp.plan.S * 8;
     for (size_t k = 0; k < n; ++k) {
         const int v = forced[k], h = (int)(k & 7);
@@ -2190,9 +2266,12 @@ extern "C" int pb_batch_decoder_stop(void* dec, const int32_t* stop_bar) {
     for (int b = 0; b < D->B; ++b)
         PB_REQUIRE(stop_bar[b] >= 0 && stop_bar[b] <= D->sa.pad[0], "pb_batch_decoder_stop: row %d: bar %d outside 0..%d (%d = no stop)", b, stop_bar[b],
                    D->sa.pad[0], D->sa.pad[0]);
-    if (D->B == 1) return 0;                                           // the single-row kernels have no done flag: the host ends the run
     StopArgs g = D->stop;
     for (int b = 0; b < D->B; ++b) g.stop[b] = stop_bar[b];
+    if (D->B == 1) {                                                   // the single-row kernels have no done flag: the host ends the run. No device work;
+        D->stop = g;                                                   // the mirror keeps the bar for an anchored row's rule (pb_batch_decoder_anchor, _start)
+        return 0;
+    }
     hipLaunchKernelGGL(dec_stop_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
     PB_LAUNCH_CHECK();
     D->stop = g;
@@ -2378,8 +2457,12 @@ extern "C" int pb_batch_decoder_start(void* dec, const int32_t* last_pos, const 
         h.rule[b].order = D->sampler ? D->order.order[b] : -1;        // ... / pb_batch_decoder_order
         h.rule[b].allow = D->sampler ? D->allow.allow[b] : -1;        // ... / pb_batch_decoder_allow
         h.rule[b].sched = D->sampler ? D->sched.sched[b] : -1;        // ... / pb_batch_decoder_schedule
-        h.rule[b].reserved = -1;
+        const bool anchored = D->sampler && D->n_anchor && D->anchor.cnt[b] > 0;
+        h.rule[b].reserved = anchored ? D->anchor.base[b] : -1;      // ... / pb_batch_decoder_anchor
+        h.acnt[b] = anchored ? D->anchor.cnt[b] : 0; h.aplaced[b] = 0; // a start is the row's first position: no anchor placed
     }
+    for (int k = 0; k < 8; ++k) h.apad[k] = D->sa.pad[k];
+    h.atab = D->n_anchor ? D->anchor_dev : nullptr;
     h.opad[0] = D->sa.pad[0]; h.opad[1] = D->sa.pad[1];
     h.awords = D->allow.words; h.amask = D->n_allow ? D->allow_dev : nullptr;
     h.nbar = D->sched.nbar; h.stab = D->n_sched ? D->sched_dev : nullptr;
@@ -2482,6 +2565,8 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     a.order = D->admit_order[row];                                           // -1 unless staged: nor its bar floor
     a.allow = D->admit_allow[row];                                           // ... nor its allow mask
     a.sched = D->admit_sched[row];                                           // ... nor its bar schedule
+    a.anchor = D->admit_nanchor[row] > 0 ? D->admit_anchor[row] : -1;        // ... nor its anchors
+    a.n_anchor = D->admit_nanchor[row];
     for (int h = 0; h < 8; ++h) a.tok[h] = next_tok8[h];
     PB_CHECK_HIP(hipEventRecord(D->ev, (hipStream_t)caller_stream));
     PB_CHECK_HIP(hipStreamWaitEvent(D->stream, D->ev, 0));
@@ -2503,6 +2588,7 @@ extern "C" int pb_batch_decoder_admit(void* dec, int32_t row, int32_t slice, int
     D->order.order[row] = a.order; D->admit_order[row] = -1;
     D->allow.allow[row] = a.allow; D->admit_allow[row] = -1;
     D->sched.sched[row] = a.sched; D->admit_sched[row] = -1;
+    D->anchor.base[row] = a.anchor; D->anchor.cnt[row] = a.n_anchor; D->admit_anchor[row] = -1; D->admit_nanchor[row] = 0;
     D->live[row] = true;
     return 0;
 }
@@ -2554,6 +2640,113 @@ extern "C" int pb_batch_decoder_admit_schedule(void* dec, int32_t row, int32_t s
     PB_REQUIRE(sched_index >= -1 && sched_index < D->n_sched, "pb_batch_decoder_admit_schedule: row %d: schedule index %d outside -1..%d (-1 = no schedule; the "
                "table is pb_batch_decoder_schedule's)", row, sched_index, D->n_sched - 1);
     D->admit_sched[row] = sched_index;
+    return 0;
+}
+
+// Anchored notes (see the header). anchor_check: `cnt` rows of 8 ids at `a` are ordinary ids in non-decreasing (bar, position) order
+// with every bar in floor .. stop - 1; the message names `who`.
+static int anchor_check(const Decoder* D, const int16_t* a, int cnt, int floor, int stop, const char* who, int row) {
+    for (int i = 0; i < cnt; ++i) {
+        for (int h = 0; h < 8; ++h)
+            PB_REQUIRE(a[i * 8 + h] >= 0 && a[i * 8 + h] < D->sa.pad[h], "%s: row %d, anchor %d, head %d: id %d is not an ordinary id 0..%d", who, row, i, h,
+                       (int)a[i * 8 + h], D->sa.pad[h] - 1);
+        PB_REQUIRE(i == 0 || a[i * 8] > a[i * 8 - 8] || (a[i * 8] == a[i * 8 - 8] && a[i * 8 + 1] >= a[i * 8 - 7]),
+                   "%s: row %d, anchor %d at (bar %d, position %d) lies in front of anchor %d at (%d, %d): anchors come in time order", who, row, i,
+                   (int)a[i * 8], (int)a[i * 8 + 1], i - 1, (int)a[i * 8 - 8], (int)a[i * 8 - 7]);
+        PB_REQUIRE(a[i * 8] >= floor && a[i * 8] < stop, "%s: row %d, anchor %d: bar %d outside the row's bars %d..%d (its floor and its stop bar)", who, row, i,
+                   (int)a[i * 8], floor, stop - 1);
+    }
+    return 0;
+}
+
+// The table of the anchors of ALL rows of the call goes up once, into memory the decoder owns; each row's base and count are stored, with
+// a counter of 0, in decoder-stream order by a small kernel that takes them by kernarg. Behind pb_batch_decoder_stop / _order (the rows'
+// bars are checked against them). Everything is checked on the host before anything changes. It reaches the single-row sampler too.
+extern "C" int pb_batch_decoder_anchor(void* dec, const int16_t* rows, int32_t n_rows, const int32_t* row_base, const int32_t* row_cnt) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && rows && row_base && row_cnt, "pb_batch_decoder_anchor: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_anchor: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(!D->issued, "pb_batch_decoder_anchor: a step was already issued; the rows' anchors are set before the run's first step");
+    PB_REQUIRE(!D->force_dev, "pb_batch_decoder_anchor: the decoder has a force table (pb_batch_decoder_force): position-indexed and time-indexed givens do "
+               "not combine");
+    PB_REQUIRE(n_rows > 0 && n_rows <= (1 << 20), "pb_batch_decoder_anchor: %d anchor rows (1 .. %d)", n_rows, 1 << 20);
+    for (int b = 0; b < D->B; ++b) {
+        PB_REQUIRE(row_cnt[b] >= 0 && row_base[b] >= 0 && (long long)row_base[b] + row_cnt[b] <= n_rows,
+                   "pb_batch_decoder_anchor: row %d: anchors %d .. %d + %d outside the table's %d rows", b, row_base[b], row_base[b], row_cnt[b], n_rows);
+        PB_REQUIRE(row_cnt[b] <= D->bp.plan.S, "pb_batch_decoder_anchor: row %d: %d anchors for a window of %d positions", b, row_cnt[b], D->bp.plan.S);
+    }
+    for (int i = 0; i < n_rows; ++i)
+        for (int h = 0; h < 8; ++h)
+            PB_REQUIRE(rows[i * 8 + h] >= 0 && rows[i * 8 + h] < D->sa.pad[h], "pb_batch_decoder_anchor: table row %d, head %d: id %d is not an ordinary id 0..%d", i,
+                       h, (int)rows[i * 8 + h], D->sa.pad[h] - 1);
+    for (int b = 0; b < D->B; ++b)
+        if (anchor_check(D, rows + (size_t)row_base[b] * 8, row_cnt[b], D->order.order[b] > 0 ? D->order.order[b] : 0, D->stop.stop[b], "pb_batch_decoder_anchor", b))
+            return -1;
+    const size_t bytes = sizeof(int16_t) * 8 * (size_t)n_rows;
+    int16_t* tab = nullptr;
+    if (hipMalloc(&tab, bytes) != hipSuccess) {
+        pb_set_error("pb_batch_decoder_anchor: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    if (hipMemcpyAsync(tab, rows, bytes, hipMemcpyHostToDevice, D->stream) != hipSuccess ||
+        hipStreamSynchronize(D->stream) != hipSuccess) {         // `rows` may be pageable: the copy is done when we return
+        pb_set_error("pb_batch_decoder_anchor: upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(tab);
+        return -1;
+    }
+    AnchorArgs g = D->anchor;
+    for (int b = 0; b < D->B; ++b) { g.base[b] = row_cnt[b] > 0 ? row_base[b] : -1; g.cnt[b] = row_cnt[b]; }
+    for (int h = 0; h < 8; ++h) g.pad[h] = D->sa.pad[h];
+    g.table = tab;
+    hipLaunchKernelGGL(dec_anchor_kernel, dim3(1), dim3(64), 0, D->stream, D->st, g);
+    if (hipGetLastError() != hipSuccess) {
+        pb_set_error("pb_batch_decoder_anchor: launch failed");
+        (void)hipFree(tab);
+        return -1;
+    }
+    if (D->anchor_dev) (void)hipFree(D->anchor_dev);             // the previous table: no row has pointed into it since sampler_init (hipFree drains the device)
+    D->anchor_dev = tab; D->n_anchor = n_rows;
+    D->anchor_host.assign(rows, rows + (size_t)n_rows * 8);
+    D->anchor = g;
+    return 0;
+}
+
+// The anchors (rows base .. base + cnt - 1 of pb_batch_decoder_anchor's table) of the prompt the next pb_batch_decoder_admit puts into
+// `row` (see the header); behind the row's pb_batch_decoder_admit_stop / _admit_order, against which the bars are checked. Host state only.
+extern "C" int pb_batch_decoder_admit_anchor(void* dec, int32_t row, int32_t base, int32_t cnt) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->dynamic, "pb_batch_decoder_admit_anchor: not a dynamic decoder (pb_batch_decoder_dynamic)");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_admit_anchor: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_admit_anchor: row %d of %d", row, D->B);
+    PB_REQUIRE(cnt >= 0 && base >= 0 && (long long)base + cnt <= D->n_anchor && cnt <= D->bp.plan.S,
+               "pb_batch_decoder_admit_anchor: row %d: anchors %d .. %d + %d outside the table's %d rows (the table is pb_batch_decoder_anchor's)", row, base, base,
+               cnt, D->n_anchor);
+    if (cnt && anchor_check(D, D->anchor_host.data() + (size_t)base * 8, cnt, D->admit_order[row] > 0 ? D->admit_order[row] : 0,
+                            D->admit_stop[row] >= 0 ? D->admit_stop[row] : D->sa.pad[0], "pb_batch_decoder_admit_anchor", row)) return -1;
+    D->admit_anchor[row] = cnt > 0 ? base : -1; D->admit_nanchor[row] = cnt;
+    return 0;
+}
+
+// The counter of a rewound row: with the pb_batch_decoder_seek that moved it back, the number of anchors the HOST has placed up to the
+// position it seeks to. In decoder-stream order behind that seek's stores; the steps enqueued next read it.
+extern "C" int pb_batch_decoder_seek_anchor(void* dec, int32_t row, int32_t placed) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && D->sampler, "pb_batch_decoder_seek_anchor: pb_batch_decoder_sampler_init first");
+    PB_REQUIRE(row >= 0 && row < D->B, "pb_batch_decoder_seek_anchor: row %d of %d", row, D->B);
+    PB_REQUIRE(placed >= 0 && placed <= D->anchor.cnt[row], "pb_batch_decoder_seek_anchor: row %d: %d anchors placed of %d", row, placed, D->anchor.cnt[row]);
+    PB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)&D->st->aplaced[row], placed, 1, D->stream));
+    return 0;
+}
+
+// The rows' counters after draining what is enqueued: out = B host ints.
+extern "C" int pb_batch_decoder_anchors_placed(void* dec, int32_t* out) {
+    Decoder* D = (Decoder*)dec;
+    PB_REQUIRE(D && out, "pb_batch_decoder_anchors_placed: null argument");
+    PB_REQUIRE(D->sampler, "pb_batch_decoder_anchors_placed: pb_batch_decoder_sampler_init first");
+    PB_CHECK_HIP(hipStreamSynchronize(D->stream));
+    int got[BMAX];
+    PB_CHECK_HIP(hipMemcpy(got, D->st->aplaced, sizeof(int) * BMAX, hipMemcpyDeviceToHost));
+    for (int b = 0; b < D->B; ++b) out[b] = D->anchor.cnt[b] > 0 ? got[b] : 0;
     return 0;
 }
 

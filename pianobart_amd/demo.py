@@ -26,7 +26,7 @@ class Args:
                  num_workers=5, max_seq_len=1024, hs=1024, layers=8, ffn_dims=2048, heads=8, nopretrain=False, cpu=False, cuda_devices=[0],
                  precision='bf16', prime=None, samples=1, seed=None, keep=None, bars=None, infill=None, infill_mode='rows', ordered=False,
                  key=None, pitch_range=None, instruments=None, tempo=None, max_duration=None, velocity=None, chords=None, bars_per_chord=1,
-                 chord_start=None, lora=None):
+                 chord_start=None, lora=None, accompany=None):
         self.dict_file, self.ckpt, self.input, self.output, self.num_workers = dict_file, ckpt, input, output, num_workers
         self.max_seq_len, self.hs, self.layers, self.ffn_dims, self.heads = max_seq_len, hs, layers, ffn_dims, heads
         self.nopretrain, self.cpu, self.cuda_devices, self.precision = nopretrain, cpu, cuda_devices, precision
@@ -39,6 +39,7 @@ class Args:
         self.key, self.pitch_range, self.instruments, self.tempo, self.max_duration, self.velocity = key, pitch_range, instruments, tempo, max_duration, velocity
         # a bar schedule (eval_generation --chords / --bars_per_chord / --chord_start): the pitches follow a chord progression bar by bar
         self.chords, self.bars_per_chord, self.chord_start = chords, bars_per_chord, chord_start
+        self.accompany = accompany          # None, 'skyline' or 'bass': keep that line of the piece behind the prime, write the notes around it (needs prime)
         self.lora = lora                    # None or the path of an adapter file: merged into the checkpoint's weights before generation (eval_generation --lora)
         self.samples, self.seed = samples, seed     # n continuations of the piece (n > 1 needs a seed): sample j from RandomState(seed + j)
 
@@ -79,6 +80,8 @@ def get_args(argv=None):
     add_allow_flags(ap)
     from .generation import add_schedule_flags
     add_schedule_flags(ap)
+    from .generation import add_anchor_flags
+    add_anchor_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -143,6 +146,8 @@ def demo(args=None):
     keep = check_keep_args(getattr(args, 'keep', None), getattr(args, 'prime', None))
     bars = getattr(args, 'bars', None)
     region = check_bar_args(bars, getattr(args, 'infill', None), getattr(args, 'prime', None), getattr(args, 'keep', None), getattr(args, 'seed', None))
+    from .generation import check_anchor_flags
+    check_anchor_flags(args)                 # --accompany: needs --prime, not with --keep / --infill
     if args.cpu or not torch.cuda.is_available():
         raise PBError('pianobart_amd has no CPU execution path: demo() needs an MI355X')
     if args.cuda_devices is not None and len(args.cuda_devices) > 1:
@@ -175,7 +180,7 @@ def demo(args=None):
         print("   Merging adapters from", args.lora.split('/')[-1])
         _lora.load(args.lora, model, with_optimizer=False)
         model._get_engine().merge_lora()
-    octuple, prefix, ks, forced, stops, plan = octuple.long(), None, None, None, None, None
+    octuple, prefix, ks, forced, stops, plan, anc = octuple.long(), None, None, None, None, None, None
     if region is not None:                   # the rows in front of the region prime the decoder, the encoder sees the region as MASK
         from .generation import infill_plan
         plan = infill_plan(octuple[0], region[0], region[1], pianobart.mask_word_np, pianobart.pad_word_np, getattr(args, 'infill_mode', 'rows'))
@@ -187,17 +192,23 @@ def demo(args=None):
         if keep is not None:                 # the kept attributes of the piece's rows behind the prime are given, the others sampled
             from .generation import keep_mask
             forced = keep_mask(octuple, keep, ks, pianobart.bar_pad_word)
+        from .generation import anchors_from_args
+        anc = anchors_from_args(args, octuple[0], ks[0], e2w)     # --accompany: the piece's skyline / bass line behind the prime (None: no flag)
         octuple, prefix = prime_inputs(octuple, ks, pianobart.pad_word_np)
     if bars is not None:                     # the row finishes the bar its prime ends in and writes `bars` whole new bars
         from .generation import stop_after_bars
         stops = [stop_after_bars(prefix[0, :ks[0]] if ks is not None else None, bars, pianobart.bar_pad_word)]
-    order = [region[0] if region is not None else 0] if getattr(args, 'ordered', False) else None      # the bar floor: the region's first bar, else 0
+    elif anc is not None and len(anc):       # --accompany without --bars: the row stops at the bar after its last anchor
+        stops = [min(int(anc[-1, 0]) + 1, int(pianobart.bar_pad_word))]
+    order = [region[0] if region is not None else 0] if getattr(args, 'ordered', False) or anc is not None else None      # the bar floor: the region's first bar, else 0
     from .generation import allow_from_args
     amask = allow_from_args(args, e2w)       # --key / --pitch_range / ..: what the free heads may sample (None: no flag)
     allow = [amask] if amask is not None else None
     from .generation import schedule_from_args
     bar = schedule_from_args(args, e2w, prefix[0, :ks[0]] if ks is not None and ks[0] else None)     # --chords: the first chord behind the prime
     bar = dict(decoder_bar_allow=[bar]) if bar is not None else {}
+    if anc is not None:
+        bar['decoder_anchors'] = [anc]
     octuple = octuple.to(device)
     attn_encoder = (octuple[:, :, 0] != pianobart.bar_pad_word).float()
     with torch.no_grad():
@@ -219,6 +230,12 @@ def demo(args=None):
             for j, row in enumerate(y):
                 if not is_time_ordered(row, start=plan['k'], floor=order[0]):
                     raise PBError('--ordered --infill: sample %d is not in time order behind its prime of %d rows' % (j, plan['k']))
+    if anc is not None:
+        from .generation import follows_anchors
+        for j, row in enumerate(y.cpu()):
+            ok, placed = follows_anchors(row, anc, start=ks[0])
+            if not ok:
+                raise PBError('--accompany: sample %d holds %d of its %d anchors in time order behind its prime of %d rows' % (j, placed, len(anc), ks[0]))
     for j, path in enumerate(sample_paths(args.output, samples)):
         if Octuple2Midi(y[j:j + 1], path):
             print(f"Saved to {path}")

@@ -57,6 +57,13 @@ generation.follows_schedule on every output row behind its prime and raises PBEr
 masks intersect) and everything they combine with; not with --score_dataset. Without the flags the output files are byte-identical to a
 run of a version without them.
 
+Anchored generation (--prime N|half --accompany skyline|bass): of each piece's own rows behind the prime, the highest (skyline) or lowest
+(bass) melodic note of every (bar, position) is kept where it falls in time and the model writes the notes around them
+(generation.anchor_rows -> PianoBartLM.generate_batch's decoder_anchors; DESIGN.md section 1, "Anchored notes"). --ordered is implied; the
+row stops at the bar after its last anchor unless --bars is given. The tool checks generation.follows_anchors on every output row behind
+its prime and raises PBError where it fails. Combines with --bars, the allow flags, --chords, --samples, --refill, --score and --pick; not
+with --keep, --infill or --score_dataset. Without the flag the output files are byte-identical to a run of a version without it.
+
 Scoring (PianoBartLM.score: one teacher-forced pass per generate call, after it; the generation file is byte-identical with and without):
   * --score writes a second float32 file, (N, 9) or (N, n, 9) with --samples n: per output row the 8 per-head sums of the log-probability
     of its sampled events (start = the prime length under --prime, so forced rows are not scored) and the number of scored positions.
@@ -75,7 +82,7 @@ import numpy as np
 import torch
 
 from ._lib import PBError
-from .generation import add_allow_flags, add_schedule_flags, follows_schedule, schedule_from_args, allow_flags_given, allow_from_args, check_refill, infill_plan, is_allowed, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
+from .generation import add_anchor_flags, anchors_from_args, check_anchor_flags, follows_anchors, add_allow_flags, add_schedule_flags, follows_schedule, schedule_from_args, allow_flags_given, allow_from_args, check_refill, infill_plan, is_allowed, infill_splice, is_time_ordered, keep_mask, parse_keep, sample_seed, stop_after_bars
 from .scoring import pick_best
 from .model import BartConfig, PianoBart, PianoBartLM, checkpoint_state_dict
 
@@ -129,6 +136,7 @@ def get_args(argv=None):
                     'and merged into the weights before anything runs')
     add_allow_flags(ap)
     add_schedule_flags(ap)
+    add_anchor_flags(ap)
     return ap.parse_args(argv)
 
 
@@ -215,6 +223,9 @@ def check_args(args):
         raise PBError('--score_dataset generates nothing: it takes no --%s' % allow_flags_given(args)[0])
     if getattr(args, 'chords', None) is not None and getattr(args, 'score_dataset', False):
         raise PBError('--score_dataset generates nothing: it takes no --chords')
+    check_anchor_flags(args)                                 # --accompany: needs --prime, not with --keep / --infill
+    if getattr(args, 'accompany', None) is not None and getattr(args, 'score_dataset', False):
+        raise PBError('--score_dataset generates nothing: it takes no --accompany')
     if getattr(args, 'keep', None) is not None:
         parse_keep(args.keep)
         if getattr(args, 'prime', None) is None:
@@ -304,7 +315,8 @@ def eval_generation(args=None):
     keep = parse_keep(args.keep) if getattr(args, 'keep', None) is not None else None
     bars, infill, truncated = getattr(args, 'bars', None), parse_infill(getattr(args, 'infill', None), bar_pad), 0
     pad_word = model.pianobart.pad_word_np
-    floor = (infill[0] if infill is not None else 0) if getattr(args, 'ordered', False) else None       # --ordered: every row's bar floor
+    accompany = getattr(args, 'accompany', None)
+    floor = (infill[0] if infill is not None else 0) if getattr(args, 'ordered', False) or accompany is not None else None       # --ordered (implied by --accompany): every row's bar floor
     amask = allow_from_args(args, e2w)                   # --key / --pitch_range / ..: the one allow mask of every row (None: no flag)
 
     def allowed(y, ks, forced, own):
@@ -323,10 +335,18 @@ def eval_generation(args=None):
             if not follows_schedule(y[r], bar[p], start=k, forced=forced[p] if forced is not None else None, layout=model.pianobart.layout):
                 raise PBError('--chords: output row %d leaves its bar schedule behind its prime of %d rows' % (r, k))
 
+    def anchored(y, ks, own, anc):
+        """--accompany: every output row of y (row r belongs to piece own[r] of the call) holds its piece's anchors, in time order."""
+        for r, p in enumerate(own if anc is not None else []):
+            ok, placed = follows_anchors(y[r], anc[p], start=ks[p], layout=model.pianobart.layout)
+            if not ok:
+                raise PBError('--accompany: output row %d holds %d of its %d anchors in time order behind its prime of %d rows' % (r, placed, len(anc[p]), ks[p]))
+
     def inputs(x):
         """What one generate call gets for the pieces x (B, S, 8): the encoder input, decoder prefix, prefix lengths, forced table, stop bars,
-        (--infill) the plans, (--ordered) the bar floors, (the allow flags) the masks and (--chords) the bar schedules."""
-        prefix = ks = forced = stops = plans = None
+        (--infill) the plans, (--ordered) the bar floors, (the allow flags) the masks, (--chords) the bar schedules and (--accompany) the
+        anchors."""
+        prefix = ks = forced = stops = plans = anc = None
         order = [floor] * len(x) if floor is not None else None
         allow = [amask] * len(x) if amask is not None else None
         if infill is not None:
@@ -339,13 +359,17 @@ def eval_generation(args=None):
         elif prime is not None:                       # the Ablation.py:132-139 split: first k_b rows primed, the encoder sees them only
             ks = prime_lengths(x.numpy(), prime, bar_pad, pad_word)
             forced = keep_mask(x, keep, ks, bar_pad) if keep is not None else None     # from the piece's rows, before prime_inputs pads them
+            if accompany is not None:                 # likewise: each piece's skyline / bass line behind its prime
+                anc = [anchors_from_args(args, x[b], ks[b], e2w) for b in range(len(x))]
             x, prefix = prime_inputs(x, ks, pad_word)
         if bars is not None:
             stops = [stop_after_bars(prefix[b, :ks[b]] if ks is not None else None, bars, bar_pad) for b in range(len(x))]
+        elif anc is not None:                         # --accompany without --bars: the row stops at the bar after its last anchor
+            stops = [min(int(a[-1, 0]) + 1, int(bar_pad)) if len(a) else int(bar_pad) for a in anc]
         bar = None
         if getattr(args, 'chords', None) is not None:        # one schedule per piece: its first chord sits behind the piece's own prime
             bar = [schedule_from_args(args, e2w, prefix[b, :ks[b]] if ks is not None and ks[b] else None) for b in range(len(x))]
-        return x, prefix, ks, forced, stops, plans, order, allow, bar
+        return x, prefix, ks, forced, stops, plans, order, allow, bar, anc
 
     def splice(y, plans, own):
         """--infill: row r of y (numpy) spliced with the suffix of its piece own[r]; counts the truncated ones."""
@@ -387,15 +411,17 @@ def eval_generation(args=None):
         for r0 in range(0, len(rows), args.batch_size):     # --samples n > 1: --batch_size rows per call, the samples of a prompt grouped
             chunk = rows[r0:r0 + args.batch_size]
             c0, c1 = chunk[0][0], chunk[-1][0] + 1
-            x, prefix, ks, forced, stops, plans, order, allow, bar = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow, bar, anc = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             y = model.generate_batch(x, (x[:, :, 0] != bar_pad).float(), seeds=[sample_seed(args.seed, j, i, N) for i, j in chunk],
                                      device_num=device_num, decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops,
                                      decoder_order=order, decoder_allow=allow, **(dict(decoder_bar_allow=bar) if bar is not None else {}),
+                                     **(dict(decoder_anchors=anc) if anc is not None else {}),
                                      samples_per_prompt=[sum(1 for i, _ in chunk if i == p) for p in range(c0, c1)])
             own = [i - c0 for i, _ in chunk]
             allowed(y, ks, forced, own)
             scheduled(y, ks, forced, own, bar)
+            anchored(y, ks, own, anc)
             if do_score:
                 sc, _ = score_rows(x[torch.as_tensor(own, device=device)], y, [ks[p] for p in own] if ks is not None else None)
             y = y.float().cpu().numpy()
@@ -409,20 +435,21 @@ def eval_generation(args=None):
         gen_rows = max(N, 1) if refill is not None else args.batch_size          # --refill: every prompt in one call, scored in --batch_size batches
         for c0 in range(0, N if samples == 1 else 0, gen_rows):
             c1 = min(N, c0 + gen_rows)
-            x, prefix, ks, forced, stops, plans, order, allow, bar = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
+            x, prefix, ks, forced, stops, plans, order, allow, bar, anc = inputs(torch.as_tensor(np.asarray(data[c0:c1])).long())
             x = x.to(device)
             attn_encoder = (x[:, :, 0] != bar_pad).float()
             if args.seed is None:
                 y = model(input_ids_encoder=x, encoder_attention_mask=attn_encoder, generate=True, device_num=device_num, decoder_prefix=prefix,
                           decoder_forced=forced, decoder_stop=stops, decoder_order=order, decoder_allow=allow,
-                          **(dict(decoder_bar_allow=bar) if bar is not None else {}))
+                          **(dict(decoder_bar_allow=bar) if bar is not None else {}), **(dict(decoder_anchors=anc) if anc is not None else {}))
             else:
                 y = model.generate_batch(x, attn_encoder, seeds=[args.seed + i for i in range(c0, c1)], device_num=device_num,
                                          decoder_prefix=prefix, prefix_len=ks, decoder_forced=forced, decoder_stop=stops, decoder_order=order,
                                          decoder_allow=allow, refill=(refill or True) if refill is not None else False,
-                                         **(dict(decoder_bar_allow=bar) if bar is not None else {}))
+                                         **(dict(decoder_bar_allow=bar) if bar is not None else {}), **(dict(decoder_anchors=anc) if anc is not None else {}))
             allowed(y, ks, forced, list(range(c1 - c0)))
             scheduled(y, ks, forced, list(range(c1 - c0)), bar)
+            anchored(y, ks, list(range(c1 - c0)), anc)
             output[c0:c1] = y.float().cpu().numpy() if plans is None else splice(y.float().cpu().numpy(), plans, list(range(c1 - c0)))
             for s0 in range(0, c1 - c0 if do_score else 0, args.batch_size):
                 s1 = min(c1 - c0, s0 + args.batch_size)

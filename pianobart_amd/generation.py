@@ -733,6 +733,201 @@ def stop_after_bars(prefix_rows, n, pad0):
     return min(q + 1 + int(n), int(pad0))
 
 
+def _anchor_list(a, who):
+    """One anchor list in any argument form -> (n, 8) int64 numpy (n may be 0)."""
+    try:
+        x = _as_numpy(a)
+    except Exception:
+        raise PBError('%s = %r is neither None nor an (n, 8) array of Octuple ids' % (who, a))
+    if x.size == 0:
+        return np.zeros((0, 8), dtype=np.int64)
+    if x.ndim != 2 or x.shape[1] != 8:
+        raise PBError('%s of shape %s: expected (n, 8), complete Octuple rows' % (who, tuple(x.shape)))
+    if x.dtype == np.bool_ or not np.issubdtype(x.dtype, np.integer):
+        raise PBError('%s: anchor ids must be integers (got %s)' % (who, x.dtype))
+    return x.astype(np.int64)
+
+
+def check_anchors(anchors, P, S, pad, ks=None, rows=None, stop=None, order=None, forced=None, max_new=None, owner=None):
+    """The argument rules of anchored generation, on the host before any device work ("Anchored notes"). anchors: one
+    anchor list per prompt -- a list of P entries, each None / empty (a free prompt) or (n, 8) complete Octuple rows of ordinary ids,
+    non-decreasing in (bar, position); for P = 1 one (n, 8) array by itself will do. pad: the first special id per head. ks / rows: the
+    prefix lengths and rows of check_prefix; stop / order: check_stop's / check_order's results, one entry per ROW (owner: row -> prompt,
+    check_samples) or None; forced: check_forced's result; max_new: the call's. Raises PBError naming the prompt and the rule for: an id
+    that is negative or >= pad[h]; anchors out of (bar, position) order; a bar below the row's floor max(order, 0) or >= its stop bar; an
+    anchor in front of the last row of the prefix; more anchors than positions left in the window; anchors together with forced tokens.
+    Returns None where no prompt has an anchor (the caller runs what it ran before), else (lists, order): lists = one entry per ROW, an
+    (n, 8) int64 tensor or None; order = one bar floor per ROW with every anchored row at max(order, 0) -- anchors imply time order."""
+    if anchors is None:
+        return None
+    pad = np.asarray(pad, dtype=np.int64).reshape(8)
+    if P == 1 and not (isinstance(anchors, (list, tuple)) and len(anchors) == 1 and (anchors[0] is None or np.ndim(_as_numpy(anchors[0])) == 2)):
+        anchors = [anchors]
+    if not isinstance(anchors, (list, tuple)):
+        raise PBError('anchors must be a list of %d anchor lists, one per prompt (got %r)' % (P, type(anchors).__name__))
+    if len(anchors) != P:
+        raise PBError('anchors has %d entries for %d prompt(s)' % (len(anchors), P))
+    lists = [None if a is None else _anchor_list(a, 'anchors[%d]' % p) for p, a in enumerate(anchors)]
+    lists = [a if a is not None and len(a) else None for a in lists]
+    if all(a is None for a in lists):
+        return None
+    if forced is not None:
+        raise PBError('anchors do not combine with forced tokens in one call: position-indexed and time-indexed givens do not combine')
+    owner = list(range(P)) if owner is None else list(owner)
+    first = {p: r for r, p in reversed(list(enumerate(owner)))}           # a prompt's rows share its stop and floor
+    for p, a in enumerate(lists):
+        if a is None:
+            continue
+        bad = np.argwhere((a < 0) | (a >= pad))
+        if len(bad):
+            i, h = int(bad[0, 0]), int(bad[0, 1])
+            raise PBError('anchors of prompt %d, anchor %d, head %d: id %d is not an ordinary event (0 <= id < %d)' % (p, i, h, int(a[i, h]), int(pad[h])))
+        t = a[:, 0] * (int(pad[1]) + 1) + a[:, 1]
+        if (np.diff(t) < 0).any():
+            i = int(np.flatnonzero(np.diff(t) < 0)[0]) + 1
+            raise PBError('anchors of prompt %d: anchor %d at (bar %d, position %d) lies in front of anchor %d at (%d, %d): anchors come in (bar, position) order'
+                          % (p, i, int(a[i, 0]), int(a[i, 1]), i - 1, int(a[i - 1, 0]), int(a[i - 1, 1])))
+        r = first.get(p)
+        floor = max(int(order[r]), 0) if order is not None and r is not None else 0
+        sb = int(stop[r]) if stop is not None and r is not None else int(pad[0])
+        out = np.flatnonzero((a[:, 0] < floor) | (a[:, 0] >= sb))
+        if len(out):
+            i = int(out[0])
+            raise PBError('anchors of prompt %d: anchor %d sits in bar %d, outside the bars %d .. %d the row may write (its floor and its stop bar)'
+                          % (p, i, int(a[i, 0]), floor, sb - 1))
+        k = int(ks[p]) if ks is not None else 0
+        if k:
+            q = _as_numpy(rows[p][k - 1]).astype(np.int64)
+            if (int(a[0, 0]), int(a[0, 1])) < (int(q[0]), int(q[1])):
+                raise PBError('anchors of prompt %d: anchor 0 at (bar %d, position %d) lies in front of the last row of the prefix at (%d, %d)'
+                              % (p, int(a[0, 0]), int(a[0, 1]), int(q[0]), int(q[1])))
+        left = (S if max_new is None else max(0, min(S, k + int(max_new)))) - k
+        if len(a) > left:
+            raise PBError('anchors of prompt %d: %d anchors for the %d positions left in the window (S = %d, prefix %d%s)'
+                          % (p, len(a), left, S, k, '' if max_new is None else ', max_new %d' % int(max_new)))
+    out = [torch.from_numpy(lists[p]) if lists[p] is not None else None for p in owner]
+    floors = [int(v) for v in order] if order is not None else [-1] * len(owner)
+    return out, [max(f, 0) if a is not None else f for f, a in zip(floors, out)]
+
+
+def anchored_token(sample, anchors, k, stop_vector, pad):
+    """The token of ONE position under the anchored-notes contract, for every decode path -- the single definition of the rule. sample: the
+    candidate, the 8 ids the position sampled as it would without anchors (scheduled_token's result); anchors: the row's (n, 8) int64
+    tensor or None; k: the anchors written so far; stop_vector: the row's 8 stop thresholds (stop_vector()); pad: the first special id per
+    head. Returns (token, k'): while k < n, a candidate that ends the row (any head >= its threshold) or whose (bar, position) has reached
+    A[k]'s gives way to A[k], all 8 heads, and k' = k + 1 -- the candidate is discarded, its draws stay consumed, and the caller's stop
+    test cannot trip on an anchor (its ids are ordinary and its bar is below the stop bar: check_anchors). Otherwise (sample, k)."""
+    if anchors is None or k >= len(anchors):
+        return sample, k
+    a = anchors[k]
+    ends = bool((sample >= stop_vector).any()) or bool((sample >= pad).any())
+    if ends or (int(sample[0]), int(sample[1])) >= (int(a[0]), int(a[1])):
+        return a.clone(), k + 1
+    return sample, k
+
+
+def follows_anchors(rows, anchors, start=0, layout=None):
+    """Whether a generated row kept its anchors (host, numpy). rows (S, 8) Octuple ids; the emitted rows are those in front of the first row
+    whose bar id is special. anchors (n, 8). Returns (ok, placed): placed = how many anchors, in order, occur as whole rows among the
+    emitted rows from `start` on (a subsequence match, each anchor at the first row that equals it behind its predecessor); ok = all n
+    do and the (bar, position) pairs of rows start - 1, start, .. are non-decreasing (is_time_ordered's test)."""
+    lay = layout if layout is not None else ops.DEFAULT_LAYOUT
+    x = _as_numpy(rows).astype(np.int64)
+    a = _anchor_list(anchors, 'anchors') if anchors is not None else np.zeros((0, 8), dtype=np.int64)
+    special = np.flatnonzero(x[:, 0] >= lay.pad8[0])
+    e = int(special[0]) if len(special) else len(x)
+    placed = 0
+    for i in range(start, e):
+        if placed < len(a) and np.array_equal(x[i], a[placed]):
+            placed += 1
+    lo = max(start - 1, 0)
+    t = x[lo:e, 0] * (int(lay.pad8[1]) + 1) + x[lo:e, 1]
+    ordered = start >= e or not (np.diff(t) < 0).any()
+    return bool(placed == len(a) and ordered), placed
+
+
+def anchor_rows(piece, which, e2w=None):
+    """The rows of a piece to keep as anchors (host, numpy). piece (n, 8) Octuple ids (the rows in front of the first special bar id count);
+    which: 'skyline' = of every (bar, position) the melodic note of highest pitch, 'bass' = the lowest -- percussion notes never -- or a
+    boolean selector over the piece's rows. e2w: the dictionary's event -> word half (PianoBart.e2w): a pitch word 'Pitch k' is melodic
+    with value k, 'Pitch percussion k' is not; None: the default dictionary, where ids 0 .. 127 are the melodic pitches. Returns the
+    selected rows (m, 8) int64 in (bar, position) order (a stable sort: rows of one time keep the piece's order)."""
+    x = _as_numpy(piece)
+    if x.ndim != 2 or x.shape[1] != 8:
+        raise PBError('anchor_rows: piece of shape %s, expected (n, 8)' % (tuple(x.shape),))
+    x = x.astype(np.int64)
+    lay = ops.Layout.from_dict(e2w) if e2w is not None else ops.DEFAULT_LAYOUT
+    special = np.flatnonzero((x >= np.asarray(lay.pad8, dtype=np.int64)).any(1))
+    x = x[:int(special[0])] if len(special) else x
+    if not isinstance(which, str):
+        sel = _as_numpy(which)
+        if sel.dtype != np.bool_ or sel.ndim != 1 or len(sel) < len(x):
+            raise PBError('anchor_rows: a row selector must be a bool vector over the piece\'s rows (got %s of shape %s)' % (sel.dtype, tuple(sel.shape)))
+        keep = x[sel[:len(x)]]
+    else:
+        if which not in ('skyline', 'bass'):
+            raise PBError('anchor_rows: %r is neither "skyline", "bass" nor a bool row selector' % (which,))
+        if e2w is None:
+            value = {i: i for i in range(128)}
+        else:
+            cls = ops.CLASS_NAMES[3]
+            value = {int(i): int(w[len(cls) + 1:]) for w, i in e2w[cls].items() if w[len(cls) + 1:].isdigit()}
+        best = {}
+        for i, r in enumerate(x):
+            v = value.get(int(r[3]))
+            if v is None:
+                continue
+            key = (int(r[0]), int(r[1]))
+            if key not in best or (v > best[key][0] if which == 'skyline' else v < best[key][0]):
+                best[key] = (v, i)
+        keep = x[sorted(i for _, i in best.values())]
+    return keep[np.argsort(keep[:, 0] * (int(lay.pad8[1]) + 1) + keep[:, 1], kind='stable')] if len(keep) else keep.reshape(0, 8)
+
+
+def add_anchor_flags(ap):
+    """The command-line form of anchor_rows, shared by eval_generation, demo and tools/decode_batch_bench.py."""
+    ap.add_argument('--accompany', type=str, default=None, choices=('skyline', 'bass'), help='anchored generation (needs --prime): keep the highest '
+                    '(skyline) or lowest (bass) melodic note of every (bar, position) of each piece behind its prime where it falls in time and let '
+                    'the model write the notes around them; implies --ordered; not with --keep or --infill')
+
+
+def check_anchor_flags(args):
+    """The flag rules of --accompany: PBError where it comes without --prime or together with --keep / --infill."""
+    if getattr(args, 'accompany', None) is None:
+        return
+    if getattr(args, 'prime', None) is None:
+        raise PBError('--accompany needs --prime N|half: the anchors are the piece\'s own rows behind the prime')
+    for other in ('keep', 'infill'):
+        if getattr(args, other, None):
+            raise PBError('--accompany does not combine with --%s: position-indexed and time-indexed givens do not combine' % other)
+
+
+def anchors_from_args(args, piece, k, e2w=None):
+    """The anchors of ONE piece under --accompany: anchor_rows of its rows behind the prime of k rows; None without the flag."""
+    which = getattr(args, 'accompany', None)
+    if which is None:
+        return None
+    return anchor_rows(_as_numpy(piece)[int(k):], which, e2w)
+
+
+def _anchor_table(lists):
+    """The device form of check_anchors' lists: (table (n, 8) int16 of every row's anchors, base, cnt), the last two int32, one per row."""
+    base, cnt, parts = [], [], []
+    for a in lists:
+        base.append(sum(cnt))
+        cnt.append(0 if a is None else len(a))
+        if a is not None:
+            parts.append(a.numpy().astype(np.int16))
+    return np.ascontiguousarray(np.concatenate(parts)), np.asarray(base, dtype=np.int32), np.asarray(cnt, dtype=np.int32)
+
+
+def _slice_anchors(lists, a, b):
+    """check_anchors' lists for the rows a .. b - 1; None where none of them has an anchor."""
+    if lists is None or all(v is None for v in lists[a:b]):
+        return None
+    return list(lists[a:b])
+
+
 def infill_plan(piece, lo, hi, mask_word, pad_word, mode='rows'):
     """The plan of "rewrite bars lo .. hi-1 of this piece and leave the rest alone", host only. piece (S, 8) Octuple ids: ordinary rows with
     non-decreasing bar ids (ValueError otherwise: the piece has no region), then usually an EOS row, then PAD; 0 <= lo < hi <= pad_word[0].
@@ -921,7 +1116,7 @@ class GenerationMixin:
 
     # ------------------------------------------------------------------ generate (model.py:28-66)
     def generate(self, enc_ids, emask, sample_row, use_cache=True, max_new=None, sampler=None, prefix=None, forced=None, stop=None, order=None, allow=None,
-                 bar_allow=None):
+                 bar_allow=None, anchors=None):
         """Autoregressive decode with the reference's control flow (SOS start, host-side nucleus sampling, early stop on
         any special token). The reference re-runs encoder AND decoder over all S positions for every generated position
         (model.py:42-45); here the encoder runs once, the cross-attention K/V of every decoder layer are projected once,
@@ -957,7 +1152,12 @@ class GenerationMixin:
         bar_allow (one bar schedule, or a sequence of one; check_bar_allow): allowed classes that change with the bar -- head 0 as without
         it; heads 1 .. 7 of a token whose bar after forcing is b0 are sampled from `allow AND bar_allow[b0]` where b0 is ordinary and
         has an entry (scheduled_token; DESIGN.md section 1, "Bar schedules"). `sample_row` must then take the keyword `sched`. None, or
-        no entry that removes a class: the call without the argument; last_decode gains `scheduled` only when a schedule is in force."""
+        no entry that removes a class: the call without the argument; last_decode gains `scheduled` only when a schedule is in force.
+        anchors ((n, 8) complete Octuple rows in (bar, position) order, or a sequence of one; check_anchors): anchored notes -- every
+        position is sampled as without them and anchored_token decides what is written: while anchors remain, a candidate that would end
+        the row or whose (bar, position) has reached the next anchor's gives way to that anchor ("Anchored notes").
+        The row is time-ordered with floor max(order, 0). Not with `forced`. None, or an empty list: the call without the argument;
+        last_decode gains `anchors_placed` only when anchors were given."""
         _refuse_unmerged_lora(self, 'generate')
         S = int(enc_ids.shape[1])
         with_ended = stop is not None
@@ -974,11 +1174,16 @@ class GenerationMixin:
         fr = forced[0] if forced is not None else None
         k = ks[0]
         pre = rows[0, :k] if k else None
+        anc = check_anchors(anchors, 1, S, self.pb.pad_word_np, ks, rows, stop, order, forced, max_new)
+        if anc is not None:                                  # anchors imply time order
+            order = anc[1]
+            ob = order[0]
+        an = anc[0][0] if anc is not None else None
         self._await_updates(2)
         if not use_cache:
-            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc)
+            return self._generate_nocache(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc, an)
         if self.hd not in (32, 64, 96, 128):                 # pb_attn_decode's row-chunk layouts; other head sizes use the training kernels
-            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc)
+            return self._generate_pyloop(enc_ids, emask, sample_row, k, pre, fr, sb, ob, ab, sc, an)
         # One hipGraph replay per token where the fused decoder covers the shape (pb_batch_decoder_create's rule) at B = 1: it keeps the
         # position in device memory; PB_DECODE_GRAPH=0 issues the same launches directly, PB_DECODE_GRAPH=-1 keeps the round-2 loop below (A/B)
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, round2=True) as run:
@@ -989,10 +1194,10 @@ class GenerationMixin:
                     fault = int(getattr(self, 'decode_fault_period', 0) or 0)    # tests: the device's choice is corrupted at every fault-th position
                     info = self._decode_device_sampled(run.dec, 1, S, lambda b, row, **kw: sample_row(row, **kw), [np.random.get_state()], sampler,
                                                        res_cpu, pad_cpu, max_new, (0, fault), inline_verify=True, starts=[k], forced=forced, stop=stop,
-                                                       order=order, allow=allow, sched=plan)
+                                                       order=order, allow=allow, sched=plan, anchors=anc[0] if anc is not None else None)
                     info.update(tokens=info['tokens'][0], rewinds=info['rewinds'][0], ended=info['ended'][0])
                 else:
-                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob, ab, sc)
+                    info = self._decode_host_sampled(run.dec, S, sample_row, res_cpu, pad_cpu, max_new, k, fr, sb, ob, ab, sc, an)
                 self.last_decode = dict(info, s_enc=run.s_enc[0], prefix=k, prefill_ms=float(run.prefill_ms()), **(dict(scheduled=True) if sc is not None else {}))
                 if not with_ended:
                     del self.last_decode['ended']
@@ -1006,10 +1211,12 @@ class GenerationMixin:
                 logit_pin = torch.empty(self.lay.vocab, dtype=torch.float32).pin_memory()
                 sv = stop_vector(pad_cpu, sb)
                 prev = pre[k - 1] if k else torch.from_numpy(self.pb.sos_word_np)
+                ak = 0                                                          # anchors written (anchored_token)
                 for i in range(k, S):
                     LIB.call('pb_decode_step', pref, i, stream)
                     logit_pin.copy_(run.bufs['logits'][0])                      # D2H on the current stream, returns when the row has landed
                     tok = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_pin, **kw), ab, sc, ob, prev, pad_cpu)
+                    tok, ak = anchored_token(tok, an, ak, sv, pad_cpu)
                     if (tok >= sv).any():
                         break
                     res_cpu[0, i] = prev = tok
@@ -1183,12 +1390,12 @@ class GenerationMixin:
             raise PBError('pb_batch_decoder_create failed (%d): %s' % (rc, LIB.load().pb_last_error().decode()))
         return dec if rc == 0 else None
 
-    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None, allow=None, sched=None):
+    def _decode_host_sampled(self, dec, S, sample_row, res_cpu, pad_cpu, max_new, k=0, fr=None, stop=None, order=None, allow=None, sched=None, anchors=None):
         """One host round trip per token through the B = 1 decoder (pb_batch_decoder_step): tokens in, logits rows out, sample_row between.
         k > 0 (primed): the decoder starts behind the prefix (pb_batch_decoder_start), fed its last row, which res_cpu[0, k - 1] holds.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
         (ordered_token; prev is tok_np, the decoder's input). allow: the row's (V,) bool mask or None (allowed_token). sched: the row's
-        schedule (unpack_schedule) or None (scheduled_token)."""
+        schedule (unpack_schedule) or None (scheduled_token). anchors: the row's (n, 8) anchors or None (anchored_token)."""
         import ctypes
         sv, ended = stop_vector(pad_cpu, stop), 'limit'
         tok_np = np.ascontiguousarray((res_cpu[0, k - 1].numpy() if k else np.asarray(self.pb.sos_word_np)).astype(np.int16))
@@ -1197,25 +1404,26 @@ class GenerationMixin:
             LIB.call('pb_batch_decoder_start', dec, last.ctypes.data, tok_np.ctypes.data, None)
         logit_cpu = torch.empty(self.lay.vocab, dtype=torch.float32)
         tok_p, log_p = ctypes.c_void_p(tok_np.ctypes.data), ctypes.c_void_p(logit_cpu.data_ptr())
-        n = 0
+        n = ak = 0
         t_loop = time.perf_counter()
         for i in range(k, S if max_new is None else min(S, k + max_new)):
             LIB.call('pb_batch_decoder_step', dec, tok_p, log_p)
             n += 1
             tok = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logit_cpu, **kw), allow, sched, order, tok_np, pad_cpu)
+            tok, ak = anchored_token(tok, anchors, ak, sv, pad_cpu)
             if (tok >= sv).any():
                 ended = end_reason(tok, pad_cpu)
                 break
             res_cpu[0, i] = tok
             tok_np[:] = tok.numpy()
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
-                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, ended=ended)
+                    tokens=n, loop_ms=(time.perf_counter() - t_loop) * 1e3, ended=ended, **(dict(anchors_placed=[ak]) if anchors is not None else {}))
 
     # ---- batched generation ----------------------------------------------------------------------------------------------------
     BATCH_MAX = 16                         # rows per batched decoder (PB_DECODE_BATCH_MAX); larger batches go in chunks
 
     def generate_batch(self, enc_ids, emask, sample_row, rngs, max_new=None, sampler=None, prefix=None, prefix_len=None, samples=None, forced=None,
-                       refill=False, stop=None, order=None, allow=None, bar_allow=None):
+                       refill=False, stop=None, order=None, allow=None, bar_allow=None, anchors=None):
         """B prompts at once, each with its own numpy RandomState. For every prompt b the result row equals the batch-1 `generate` of that
         prompt run with the global RNG set to rngs[b]'s state, token for token, and rngs[b] ends where the global RNG would end (the
         contract of tests/test_generate_batch_gpu.py). sample_row(row_logits, rng) is model.py:68-107 drawing its 8 uniforms from `rng`
@@ -1259,7 +1467,12 @@ class GenerationMixin:
         schedule, so one batch may mix scheduled, masked and free rows. With samples it describes the P prompts. The device sampler
         picks the mask of heads 1 .. 7 by the bar it sampled (pb_batch_decoder_schedule uploads the distinct schedules once, their
         masks travel in pb_batch_decoder_allow's table; a refilled slot gets its row's index with the hand-over,
-        pb_batch_decoder_admit_schedule). None, or no entry that removes a class: the call without the argument."""
+        pb_batch_decoder_admit_schedule). None, or no entry that removes a class: the call without the argument.
+        anchors (a list of B anchor lists / None; check_anchors): anchored notes, row b under `generate`'s contract with anchors[b]; None
+        or empty = a free prompt, so one batch may mix both. With samples it describes the P prompts. The device sampler applies the rule
+        and keeps each row's counter (pb_batch_decoder_anchor uploads all anchors once; a refilled slot gets its row's slice with the
+        hand-over, pb_batch_decoder_admit_anchor; a rewind restores the counter, pb_batch_decoder_seek_anchor). Not with `forced`. None,
+        or no anchor in any list: the call without the argument; last_decode gains `anchors_placed`, one count per row, otherwise."""
         def done(out, with_ended=stop is not None):      # every path below records `ended`; a call without `stop` keeps the record it had
             if not with_ended and self.last_decode is not None:
                 self.last_decode.pop('ended', None)
@@ -1277,19 +1490,22 @@ class GenerationMixin:
         allow = plan[:2] if plan is not None else check_allow(allow, P, self.lay if allow is not None else None, owner if samples is not None else None)   # (distinct masks, one index per row)
         if len(rngs) != len(owner):
             raise PBError('generate_batch: %d generators for %d prompts' % (len(rngs), P))
+        anc = check_anchors(anchors, P, int(enc_ids.shape[1]), self.pb.pad_word_np, ks, rows, stop, order, forced, max_new, owner if samples is not None else None)
+        if anc is not None:                              # one list per output row; anchors imply time order
+            anc, order = anc
         self._await_updates(2)
         R = len(owner)
         if R == 0:
             return torch.from_numpy(self.pb.pad_word_np).to(enc_ids.device).repeat(0, enc_ids.shape[1], 1)
         if not self._batch_decoder_covers(sampler):
             if samples is None:
-                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order, allow, plan))
-            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order, allow, plan))
+                return done(self._generate_batch_loop(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, stop, order, allow, plan, anc))
+            return done(self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced, stop, order, allow, plan, anc))
         if slots and R > slots:
-            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order, allow, plan)
+            out = self._generate_batch_refill(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, slots, stop, order, allow, plan, anc)
             if out is not None:                          # None: the fused decoder declines the shape -- the chunks' per-prompt loops, as ever
                 return done(out)
-        outs, ended = [], []
+        outs, ended, got = [], [], []
         for c0 in range(0, R, self.BATCH_MAX):
             own = owner[c0:c0 + self.BATCH_MAX]
             st = stop[c0:c0 + len(own)] if stop is not None else None
@@ -1304,34 +1520,39 @@ class GenerationMixin:
                                                    rngs[c0:c0 + len(own)], max_new, sampler, ks[p0:p1], rows[p0:p1] if rows is not None else None,
                                                    groups=[p - p0 for p in own] if samples is not None else None,
                                                    forced=forced[p0:p1] if forced is not None and (forced[p0:p1] != -1).any() else None, stop=st, order=od,
-                                                   allow=al, sched=pl))
+                                                   allow=al, sched=pl, anchors=_slice_anchors(anc, c0, c0 + len(own))))
             ended += (self.last_decode or {}).get('ended') or [None] * len(own)
+            got += (self.last_decode or {}).get('anchors_placed') or [0] * len(own)
         if len(outs) > 1 and self.last_decode is not None:                # last_decode describes the last chunk; `ended` covers every row
             self.last_decode['ended'] = ended
+        if anc is not None and self.last_decode is not None:              # ... and so does `anchors_placed`, where anchors were given
+            self.last_decode['anchors_placed'] = got
         return done(torch.cat(outs, 0))
 
     def _generate_batch_expanded(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, owner, forced=None, stop=None, order=None,
-                                 allow=None, sched=None):
+                                 allow=None, sched=None, anchors=None):
         """The per-prompt loop over the rows of `owner` (row -> prompt): every row runs the batch-1 `generate` of its prompt. stop: one
         entry per ROW (check_stop expands it), or None; order likewise (check_order), and allow's indices (check_allow) and sched's
-        (check_bar_allow)."""
+        (check_bar_allow) and anchors' lists (check_anchors)."""
         idx = torch.as_tensor(owner, dtype=torch.long)
         return self._generate_batch_loop(enc_ids[idx.to(enc_ids.device)], emask[idx.to(emask.device)] if emask is not None else None, sample_row, rngs,
                                          max_new, sampler, [ks[p] for p in owner], rows[idx] if rows is not None else None,
-                                         forced[idx.numpy()] if forced is not None else None, stop, order, allow, sched)
+                                         forced[idx.numpy()] if forced is not None else None, stop, order, allow, sched, anchors)
 
     def _batch_decoder_covers(self, sampler):
         """The switches under which generate_batch tries the fused decoder; whether it covers the shape is pb_batch_decoder_create's rule."""
         return sampler is not None and _DECODE_SPEC and _DECODE_GRAPH >= 0
 
     def _generate_batch_loop(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks=None, rows=None, forced=None, stop=None, order=None,
-                             allow=None, sched=None):
+                             allow=None, sched=None, anchors=None):
         """The per-prompt loop: each row's generator state is swapped into the global RNG for its batch-1 `generate` and copied back; the
         caller's global state is restored afterwards. ks / rows: the prefix lengths and rows of check_prefix (None: unprimed); forced: one
         checked table per row (check_forced) or None; stop: one stop bar per row (check_stop) or None; order: one bar floor per row
-        (check_order) or None; allow: check_allow's result with one index per row, or None; sched: check_bar_allow's result likewise, or None."""
+        (check_order) or None; allow: check_allow's result with one index per row, or None; sched: check_bar_allow's result likewise, or None;
+        anchors: check_anchors' lists, one entry per row, or None."""
         saved = np.random.get_state()
         outs, ended, pad0 = [], [], int(self.pb.pad_word_np[0])
+        got = []
         masks = unpack_allow(allow, self.lay.vocab)
         scheds = unpack_schedule(sched, self.lay.vocab)
         try:
@@ -1343,34 +1564,39 @@ class GenerationMixin:
                                           stop=stop[b] if stop is not None else pad0,         # 256: no stop, and the row's `ended`
                                           order=order[b] if order is not None else None,
                                           allow=masks[b].numpy() if masks is not None and masks[b] is not None else None,
-                                          bar_allow=[scheds[b]] if scheds is not None and scheds[b] is not None else None))
+                                          bar_allow=[scheds[b]] if scheds is not None and scheds[b] is not None else None,
+                                          anchors=[anchors[b]] if anchors is not None and anchors[b] is not None else None))
                 ended.append((self.last_decode or {}).get('ended'))
+                got += (self.last_decode or {}).get('anchors_placed') or [0]
                 rngs[b].set_state(np.random.get_state())
         finally:
             np.random.set_state(saved)
-        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended, **(dict(scheduled=True) if sched is not None else {}))
+        self.last_decode = dict(batched=False, batch=int(enc_ids.shape[0]), ended=ended, **(dict(scheduled=True) if sched is not None else {}),
+                                **(dict(anchors_placed=got) if anchors is not None else {}))
         return torch.cat(outs, 0)
 
     def _generate_batch_chunk(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, groups=None, forced=None, stop=None, order=None,
-                              allow=None, sched=None):
+                              allow=None, sched=None, anchors=None):
         """<= BATCH_MAX rows through one fused decoder: the set-up of _decoder_run (groups as there), then the device-ahead / host-behind
         loop with per-row draws, per-row verification and per-row rewinds (_decode_device_sampled). stop: one stop bar per ROW, or None;
         order: one bar floor per ROW, or None; allow: check_allow's result with one index per ROW, or None; sched: check_bar_allow's
-        result likewise, or None."""
+        result likewise, or None; anchors: check_anchors' lists, one entry per ROW, or None."""
         with torch.no_grad(), self._decoder_run(enc_ids, emask, ks, rows, groups) as run:
             if run.dec is None:                                            # not covered: the per-prompt loop
-                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order, allow, sched)
+                return self._generate_batch_expanded(enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, run.groups, forced, stop, order, allow, sched,
+                                                     anchors)
             fault = getattr(self, 'decode_fault_row', None) or (-1, 0)     # tests: the device's choice of one row corrupted
             info = self._decode_device_sampled(run.dec, run.B, run.S, lambda b, row, **kw: sample_row(row, rngs[b], **kw), [r.get_state() for r in rngs],
                                                sampler, run.res_cpu, run.pad_cpu, max_new, fault, inline_verify=False, starts=run.starts,
                                                forced=np.ascontiguousarray(forced[np.asarray(run.groups)]) if forced is not None else None, stop=stop,
-                                               order=order, allow=allow, sched=sched)
+                                               order=order, allow=allow, sched=sched, anchors=anchors)
         self.last_decode = dict(info, s_enc=run.s_enc, batched=True, batch=run.B, prefix=run.starts, prefill_ms=run.prefill_ms(), groups=run.groups,
                                 encoder_passes=run.G, prefill_passes=sum(1 for k in ks if 0 < k < run.S), setup_ms=run.setup_ms,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in run.bufs['kvc']))
         return run.res_cpu.to(enc_ids.device)
 
-    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None, allow=None, sched=None):
+    def _generate_batch_refill(self, enc_ids, emask, sample_row, rngs, max_new, sampler, ks, rows, forced, n, stop=None, order=None, allow=None, sched=None,
+                               anchors=None):
         """R > n rows through ONE fused decoder of n slots (pb_batch_decoder_dynamic): a slot whose row has stopped is handed to the next
         waiting prompt (pb_batch_decoder_admit) while the other slots decode on. refill.RefillSchedule keeps the books: rows are admitted
         in row order into the lowest free slot, and the cross K|V caches hold n + E slices so that the next prompts' batch-1 encoder
@@ -1385,7 +1611,9 @@ class GenerationMixin:
         (pb_batch_decoder_order, pb_batch_decoder_admit_order; a free row stages nothing and its slot gets -1), and so does allow (check_allow's
         result for the R rows: the table of ALL rows' masks goes up at the start, pb_batch_decoder_allow, and a later row's index is staged,
         pb_batch_decoder_admit_allow), and sched (check_bar_allow's result: pb_batch_decoder_schedule, pb_batch_decoder_admit_schedule; a
-        successor without a schedule stages nothing and its slot gets -1). Returns the (R, S, 8) result, or None -- before any encoder work -- where
+        successor without a schedule stages nothing and its slot gets -1), and anchors (check_anchors' R lists: the table of ALL rows'
+        anchors goes up at the start, pb_batch_decoder_anchor, a later row's slice is staged, pb_batch_decoder_admit_anchor, and the
+        host's counter of a rewound row goes back with pb_batch_decoder_seek_anchor). Returns the (R, S, 8) result, or None -- before any encoder work -- where
         pb_batch_decoder_create declines the shape."""
         R, S, dev = int(enc_ids.shape[0]), int(enc_ids.shape[1]), enc_ids.device
         pad_cpu = torch.from_numpy(self.pb.pad_word_np)
@@ -1401,12 +1629,12 @@ class GenerationMixin:
                 return None
             try:
                 return self._refill_run(dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup,
-                                        pad_cpu, stop, order, allow, sched).to(dev)
+                                        pad_cpu, stop, order, allow, sched, anchors).to(dev)
             finally:
                 LIB.call('pb_batch_decoder_destroy', dec)
 
     def _refill_run(self, dec, bufs, enc16, em, s_enc, sample_row, rngs, max_new, sampler, ks, rows, forced, n, NS, t_setup, pad_cpu, stop=None, order=None,
-                    allow=None, bars=None):
+                    allow=None, bars=None, anchors=None):
         """The body of _generate_batch_refill on a created decoder (destroyed by the caller). Returns res_cpu."""
         import ctypes
         from collections import deque
@@ -1485,6 +1713,11 @@ class GenerationMixin:
         if bars is not None:                                              # ... and the schedules of ALL rows, behind the masks they point to
             rs = np.asarray(bars[3][:n], dtype=np.int32)                   # held until the call returns
             LIB.call('pb_batch_decoder_schedule', dec, bars[2].ctypes.data, bars[2].shape[0], bars[2].shape[1], rs.ctypes.data)
+        if anchors is not None:                                            # ... and the anchors of ALL rows; the first n rows' slices with them
+            atab, abase, acnt = _anchor_table(anchors)
+            LIB.call('pb_batch_decoder_anchor', dec, atab.ctypes.data, atab.shape[0], np.ascontiguousarray(abase[:n]).ctypes.data,
+                     np.ascontiguousarray(acnt[:n]).ctypes.data)
+        placed = [0] * R                           # anchors the HOST has written, per row
         masks = unpack_allow(allow, vocab)
         scheds = unpack_schedule(bars, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
@@ -1542,6 +1775,8 @@ class GenerationMixin:
                     LIB.call('pb_batch_decoder_admit_allow', dec, s, allow[1][r])
                 if bars is not None and bars[3][r] != -1:                # likewise; a successor without a schedule gets -1
                     LIB.call('pb_batch_decoder_admit_schedule', dec, s, bars[3][r])
+                if anchors is not None and anchors[r] is not None:         # likewise, behind its stop bar and floor; a free successor gets none
+                    LIB.call('pb_batch_decoder_admit_anchor', dec, s, int(abase[r]), int(acnt[r]))
                 LIB.call('pb_batch_decoder_admit', dec, s, c, s_enc[r], ks[r] - 1, tok.ctypes.data, lim[r], u.ctypes.data,
                          fr.ctypes.data if fr is not None else None, em_host[r].ctypes.data if em_host is not None else None, stream())
                 counts['admissions'] += 1
@@ -1573,6 +1808,8 @@ class GenerationMixin:
                 tok = scheduled_token(forced[r, i] if forced is not None else None, lambda **kw: sample_row(log_logits[s, i], rngs[r], **kw),
                                     masks[r] if masks is not None else None, scheds[r] if scheds is not None else None, order[r] if order is not None else None,
                                     res_cpu[r, i - 1] if i else sos, pad_cpu)
+                if anchors is not None:
+                    tok, placed[r] = anchored_token(tok, anchors[r], placed[r], svs[r], pad_cpu)
                 tokens[r] += 1
                 if (tok >= svs[r]).any():
                     ended[r] = end_reason(tok, pad_cpu)
@@ -1610,6 +1847,8 @@ class GenerationMixin:
                         i = out[1]
                         rewinds[r] += 1
                         LIB.call('pb_batch_decoder_seek', dec, s, i, out[2].ctypes.data)
+                        if anchors is not None and anchors[r] is not None:  # the device's counter ran ahead with the discarded positions
+                            LIB.call('pb_batch_decoder_seek_anchor', dec, s, placed[r])
                         nxt[s] = i + 1
                         for _, sp in runs:
                             if sp[s] is not None and sp[s][0] == r:
@@ -1620,13 +1859,14 @@ class GenerationMixin:
         self.last_decode = dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                                 tokens=tokens, rewinds=rewinds, steps=stat['steps'], row_steps=stat['row_steps'], loop_ms=(time.perf_counter() - t_loop) * 1e3,
                                 host_ms=stat['host_s'] * 1e3, device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, refill=n, slices=NS, **(dict(scheduled=True) if bars is not None else {}),
+                                **(dict(anchors_placed=placed) if anchors is not None else {}),
                                 admissions=counts['admissions'], row_slot=row_slot, encoder_passes=counts['encoder_passes'], s_enc=s_enc, batched=True, batch=n,
                                 prefix=list(ks), prefill_ms=sum(t() for t in timers), prefill_passes=sum(primed), setup_ms=setup_ms, ended=ended,
                                 cross_cache_bytes=sum(t.numel() * t.element_size() for t in bufs['kvc']))
         return res_cpu
 
     def _decode_device_sampled(self, dec, B, S, sample, states, sampler, res_cpu, pad_cpu, max_new, fault, inline_verify, starts=None, forced=None, stop=None,
-                               order=None, allow=None, sched=None):
+                               order=None, allow=None, sched=None, anchors=None):
         """The decode loop without a host round trip per token (round 6), for B rows. The 8 uniform draws of a position do not depend on its
         logits (np.random.choice inside nucleus(), model.py:97), so each row's S x 8 are drawn AHEAD from a copy of its generator state
         (`states`: the global RNG's for `generate`, rngs[b]'s for `generate_batch`) and uploaded; the device then samples every position
@@ -1657,7 +1897,12 @@ class GenerationMixin:
         allowed_token with the row's mask; the logged logits rows are the raw ones.
         sched (check_bar_allow's result with B indices; allow is then its first two members) or None: the distinct schedules and the rows'
         indices go to the device sampler behind the masks (pb_batch_decoder_schedule: it picks the mask of heads 1 .. 7 by the bar of the
-        token it samples) and the host samples every position through scheduled_token with the row's schedule."""
+        token it samples) and the host samples every position through scheduled_token with the row's schedule.
+        anchors (check_anchors' lists, B entries; order then holds a floor >= 0 for every anchored row) or None: the table of all anchors
+        and each row's slice go to the device sampler last (pb_batch_decoder_anchor: its last stage applies the rule and advances the
+        row's counter on the device) and the host passes every candidate through anchored_token with a counter of its own per row. The
+        counter is state the device moved while running ahead, so a rewind restores it from the host's (pb_batch_decoder_seek_anchor
+        behind pb_batch_decoder_seek). Returns `anchors_placed` per row then."""
         import contextlib
         import ctypes
         from collections import deque
@@ -1691,6 +1936,10 @@ class GenerationMixin:
         if sched is not None:
             rs = np.asarray(sched[3], dtype=np.int32)                      # held until the call returns
             LIB.call('pb_batch_decoder_schedule', dec, sched[2].ctypes.data, sched[2].shape[0], sched[2].shape[1], rs.ctypes.data)
+        if anchors is not None:                                            # behind the stop bars and floors it is checked against
+            atab, abase, acnt = _anchor_table(anchors)                     # held until the call returns
+            LIB.call('pb_batch_decoder_anchor', dec, atab.ctypes.data, atab.shape[0], abase.ctypes.data, acnt.ctypes.data)
+        placed = [0] * B                           # anchors the HOST has written, per row
         masks = unpack_allow(allow, vocab)
         scheds = unpack_schedule(sched, vocab)
         sos = torch.from_numpy(self.pb.sos_word_np)
@@ -1730,6 +1979,8 @@ class GenerationMixin:
                 tok = scheduled_token(forced[b, i] if forced is not None else None, lambda **kw: sample(b, log_logits[b, i], **kw),
                                     masks[b] if masks is not None else None, scheds[b] if scheds is not None else None, order[b] if order is not None else None,
                                     res_cpu[b, i - 1] if i else sos, pad_cpu)
+                if anchors is not None:
+                    tok, placed[b] = anchored_token(tok, anchors[b], placed[b], svs[b], pad_cpu)
                 tokens[b] += 1
                 if (tok >= svs[b]).any():
                     ended[b] = end_reason(tok, pad_cpu)
@@ -1763,21 +2014,24 @@ class GenerationMixin:
                         i = r[1]
                         rewinds[b] += 1
                         LIB.call('pb_batch_decoder_seek', dec, b, i, r[2].ctypes.data)
+                        if anchors is not None and anchors[b] is not None:  # the device's counter ran ahead with the discarded positions
+                            LIB.call('pb_batch_decoder_seek_anchor', dec, b, placed[b])
                         nxt[b] = i + 1
                         for _, sp in runs:
                             sp[b][0] = sp[b][1] = i + 1
         return dict(launches_per_token=int(LIB.query('pb_batch_decoder_launches', dec)), graph=bool(LIB.query('pb_batch_decoder_graph', dec)),
                     tokens=tokens, rewinds=rewinds, steps=steps, loop_ms=(time.perf_counter() - t_loop) * 1e3, host_ms=host_s * 1e3,
                     device_sampler=True, **self._note_sampler_form(dec), tokens_per_graph_replay=K, ended=ended,
-                    **(dict(scheduled=True) if sched is not None else {}))
+                    **(dict(scheduled=True) if sched is not None else {}), **(dict(anchors_placed=placed) if anchors is not None else {}))
 
-    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None):
+    def _generate_pyloop(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None, anchors=None):
         """KV-cached decode sequenced from Python with the training kernels (M = 1 GEMMs, flash attention with one query):
         kept as a cross-check of the native pb_decode_step path. k / pre (primed): positions 0 .. k-1 are stepped through with the prefix
         rows as their tokens (their K|V land in the cache one step at a time, independently of _prefill) and sample nothing.
         fr (S, 8): the row's forced table (forced_token); a position with all 8 heads given skips the LM heads.
         stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None (ordered_token; prev is `cur`, the step's input).
-        allow: the row's (V,) bool mask or None (allowed_token). sched: the row's schedule (unpack_schedule) or None (scheduled_token)."""
+        allow: the row's (V,) bool mask or None (allowed_token). sched: the row's schedule (unpack_schedule) or None (scheduled_token).
+        anchors: the row's (n, 8) anchors or None (anchored_token)."""
         pb, d, H, X = self.pb, self.d, self.H, self.xdt
         S, dev = enc_ids.shape[1], enc_ids.device
         pad = torch.from_numpy(pb.pad_word_np).to(dev)
@@ -1800,6 +2054,7 @@ class GenerationMixin:
             logits = f(1, self.lay.vocab)
             save = dict(lse=f(1, H, 1)) if self.use_flash else dict(P=e(1, H, 1, S))
             cur = torch.tensor(pb.sos_word_np, device=dev).reshape(1, 1, 8)
+            ak = 0
             for i in range(S):
                 tok16 = ops.ids_to_i16(cur)
                 ops.embed_ln_fwd(tok16.reshape(1, 8), self.ptab, wf['lin.b'], wf['dec.pos'][i:], wf['dec.lne.w'], wf['dec.lne.b'], x,
@@ -1831,18 +2086,19 @@ class GenerationMixin:
                     ops.gemm(h, self.w['head.w'], logits, M=1, N=self.lay.vocab, K=d, dtype=self.gcode, bias=wf['head.b'], c_f32=True)
                 tok = scheduled_token(frow, lambda **kw: sample_row(logits[0].cpu(), **kw), allow, sched, order,
                                     cur.reshape(8).cpu() if order is not None else None, pad_cpu)
+                tok, ak = anchored_token(tok, anchors, ak, sv, pad_cpu)
                 if (tok >= sv).any():
                     break
                 result[:, i, :] = tok.to(dev)
                 cur = tok.to(dev).reshape(1, 1, 8)
         return result
 
-    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None):
+    def _generate_nocache(self, enc_ids, emask, sample_row, k=0, pre=None, fr=None, stop=None, order=None, allow=None, sched=None, anchors=None):
         """The reference's schedule minus the redundant encoder re-runs: full decoder pass per position (kept as the
         cross-check of the cached path). k / pre (primed): decoder inputs 1 .. k and their mask hold the prefix, the loop starts at k.
         fr (S, 8): the row's forced table (forced_token). stop: the row's stop bar or None (stop_vector). order: the row's bar floor or None
         (ordered_token; prev is decoder input i, which the loop wrote at i - 1). allow: the row's (V,) bool mask or None (allowed_token).
-        sched: the row's schedule (unpack_schedule) or None (scheduled_token)."""
+        sched: the row's schedule (unpack_schedule) or None (scheduled_token). anchors: the row's (n, 8) anchors or None (anchored_token)."""
         pb = self.pb
         S = enc_ids.shape[1]
         dev = enc_ids.device
@@ -1860,6 +2116,7 @@ class GenerationMixin:
         pad_cpu = torch.from_numpy(pb.pad_word_np)
         sv = stop_vector(pad_cpu, stop)
         em, enc16 = self._prompt_inputs(enc_ids, emask)
+        ak = 0
         with torch.no_grad():
             for i in range(k, S):
                 dec16 = ops.ids_to_i16(dec)
@@ -1867,6 +2124,7 @@ class GenerationMixin:
                 logits = self.heads_forward(dec_h)
                 cur = scheduled_token(fr[i] if fr is not None else None, lambda **kw: sample_row(logits[i].float().cpu(), **kw), allow, sched, order,
                                     dec[0, i].cpu() if order is not None else None, pad_cpu)
+                cur, ak = anchored_token(cur, anchors, ak, sv, pad_cpu)
                 if i != S - 1:
                     dec[:, i + 1, :] = cur.to(dev)
                     dmask[:, i + 1] += 1

@@ -363,7 +363,7 @@ class PianoBartLM(nn.Module):
 
     def forward(self, input_ids_encoder, input_ids_decoder=None, encoder_attention_mask=None,
                 decoder_attention_mask=None, generate=False, device_num=-1, *, decoder_prefix=None, decoder_forced=None, decoder_stop=None,
-                decoder_order=None, decoder_allow=None, decoder_bar_allow=None):
+                decoder_order=None, decoder_allow=None, decoder_bar_allow=None, decoder_anchors=None):
         """decoder_prefix (1, k, 8) (generate=True only): primed generation -- the first k decoder events are given and the loop samples from
         position k on (Engine.generate's `prefix`).
         decoder_forced (1, S, 8) integers in model column order (generate=True only): forced tokens -- -1 leaves a head free, v >= 0 says
@@ -396,7 +396,15 @@ class PianoBartLM(nn.Module):
         an ordinary bar with an entry, else from decoder_allow alone. The special ids stay reachable; given heads, the draws, the stop
         test and the prefix are untouched; on an ordered row head 1's second pass starts from the bar's quotients.
         generation.chord_schedule builds one from chord names ('C:maj', 'G:maj', ..). None, no entry, or entries True everywhere: the
-        call without the argument. DESIGN.md section 1, "Bar schedules"."""
+        call without the argument. DESIGN.md section 1, "Bar schedules".
+        decoder_anchors (one (n, 8) array of complete Octuple rows, or a sequence of one; generate=True only): anchored notes -- the rows
+        are kept wherever they fall in time and the model writes the notes around them ("harmonise this melody", "keep the bass line").
+        Ordinary ids, non-decreasing in (bar, position). Every position is sampled as without them (the candidate); while anchors remain,
+        a candidate that would end the row or whose (bar, position) has reached the next anchor's gives way to that anchor, all 8 heads as
+        given (on a tie the anchor goes first; the candidate's draws stay consumed), so every anchor is written in order unless the
+        window ends first, and the row cannot end while one remains. The row is time-ordered with floor max(decoder_order, 0). Not with
+        decoder_forced. generation.anchor_rows picks a piece's skyline or bass line. None, or an empty list: the call without the
+        argument. DESIGN.md section 1, "Anchored notes"."""
         eng = self._get_engine()
         if not generate:
             if decoder_prefix is not None:
@@ -411,6 +419,8 @@ class PianoBartLM(nn.Module):
                 raise PBError('decoder_allow constrains what a generated piece samples: it needs generate=True')
             if decoder_bar_allow is not None:
                 raise PBError('decoder_bar_allow constrains what a generated piece samples: it needs generate=True')
+            if decoder_anchors is not None:
+                raise PBError('decoder_anchors are notes a generated piece keeps: they need generate=True')
             logits = eng.module_forward_logits(input_ids_encoder, input_ids_decoder, encoder_attention_mask,
                                                decoder_attention_mask, self.training)
             off = self.pianobart.layout.seg_off
@@ -420,13 +430,13 @@ class PianoBartLM(nn.Module):
             exit(-1)
         out = eng.generate(input_ids_encoder, encoder_attention_mask, self.sample_row, sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P),
                            prefix=decoder_prefix, forced=decoder_forced, stop=decoder_stop, order=decoder_order, allow=decoder_allow,
-                           bar_allow=decoder_bar_allow)
+                           bar_allow=decoder_bar_allow, anchors=decoder_anchors)
         # model.py:33-36: the result lives on `cuda:device_num`, or on the CPU for device_num == -1
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def generate_batch(self, input_ids_encoder, encoder_attention_mask=None, seeds=None, rngs=None, max_new=None, device_num=-1, *,
                        decoder_prefix=None, prefix_len=None, samples_per_prompt=None, decoder_forced=None, refill=False,
-                       decoder_stop=None, decoder_order=None, decoder_allow=None, decoder_bar_allow=None):
+                       decoder_stop=None, decoder_order=None, decoder_allow=None, decoder_bar_allow=None, decoder_anchors=None):
         """Generation for B prompts at once (forward(generate=True) keeps the reference's batch-1 rule). Prompt b samples from its own
         numpy RandomState: rngs[b] (advanced in place) or RandomState(seeds[b]); one of the two is required. Row b of the (B, S, 8)
         result is what forward(generate=True) returns for prompt b alone after np.random.set_state(<that generator's state>); the global
@@ -456,7 +466,10 @@ class PianoBartLM(nn.Module):
         decoder_bar_allow (a list of B entries, each a bar schedule -- forward(generate=True, decoder_bar_allow=...)'s dict or sequence --
         or None): prompt b under that contract with its own schedule, so one batch may mix scheduled, masked and free rows. With
         samples_per_prompt it describes the P prompts. The device sampler picks the mask of heads 1 .. 7 by the bar it sampled, so a
-        scheduled batch keeps the batched decode's launches per step and its rewind rate."""
+        scheduled batch keeps the batched decode's launches per step and its rewind rate.
+        decoder_anchors (a list of B entries, each an (n, 8) anchor list or None = a free prompt): prompt b under forward(generate=True,
+        decoder_anchors=...)'s contract with its own anchors, so one batch may mix anchored and free rows. With samples_per_prompt it
+        describes the P prompts. The device sampler applies the rule itself and keeps each row's counter, which a rewind restores."""
         B = int(input_ids_encoder.shape[0])
         if (rngs is None) == (seeds is None):
             raise PBError('generate_batch: give either seeds or rngs (one generator per prompt)')
@@ -474,7 +487,7 @@ class PianoBartLM(nn.Module):
         out = eng.generate_batch(input_ids_encoder, encoder_attention_mask, self.sample_row, rngs, max_new=max_new,
                                  sampler=dict(T=self.SAMPLE_T, P=self.SAMPLE_P), prefix=decoder_prefix, prefix_len=prefix_len,
                                  samples=samples_per_prompt, forced=decoder_forced, refill=refill, stop=decoder_stop, order=decoder_order,
-                                 allow=decoder_allow, bar_allow=decoder_bar_allow)
+                                 allow=decoder_allow, bar_allow=decoder_bar_allow, anchors=decoder_anchors)
         return out.cpu() if device_num == -1 else out.to(torch.device('cuda', device_num))
 
     def embed(self, input_ids_encoder, encoder_attention_mask=None, return_counts=False):

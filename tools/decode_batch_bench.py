@@ -5,7 +5,7 @@ verification ms per step and an HBM-bytes estimate per step (decoder + LM-head w
 encoder rows and its self K/V cache at the mean position); plus the batch-1 Engine.generate rate measured in the same process.
 
     python tools/decode_batch_bench.py [--steps 256] [--batches 1 4 8 16] [--prime K] [--keep ATTR[,ATTR...]] [--bars N] [--ordered]
-                                        [--key TONIC:MODE] [--pitch_range LO:HI] [--chords ROOT:QUALITY[,...]]
+                                        [--key TONIC:MODE] [--pitch_range LO:HI] [--chords ROOT:QUALITY[,...]] [--accompany skyline|bass]
 
 --keep pitch,velocity: forced tokens -- the named attributes of synthetic pieces are given at every position (generation.keep_mask) and the
 model samples the others, at the largest B of --batches: ms per step and rewinds per row, beside the unforced run of the same process.
@@ -21,6 +21,11 @@ Compare with a run of the same command without the flags.
 --chords C:maj,G:maj,A:min,F:maj [--bars_per_chord N] [--chord_start B]: a bar schedule -- every row of the plain --batches runs (and of the
 batch-1 run) follows the chord progression bar by bar (generation.chord_schedule), so the step is timed with scheduled rows; the line then
 names the schedule ("chords") and the rewinds per row. Compare with a run of the same command without the flags.
+
+--accompany skyline|bass: anchored generation -- every row of the plain --batches runs (and of the batch-1 run) keeps that line of a
+synthetic piece of its own (generation.anchor_rows, at most --steps / 2 anchors a row) and writes the notes around it, so the step is timed
+with anchored rows; the line then names the anchors ("accompany"), the anchors placed and the rewinds per row. Compare with a run of the
+same command without the flag.
 
 --samples n: n samples of ONE prompt instead. Three runs alternate in this process, --reps times: "grouped" (samples=n: one encoder pass,
 one (1, S, 2d) cross cache per layer, the grouped cross-attention kernel), "indirect" (the same with PB_DECODE_CROSS_GROUPED=0: the per-row
@@ -80,6 +85,8 @@ def main(argv=None):
     ap.add_argument('--pitch_range', type=str, default=None, metavar='LO:HI', help='... melodic pitches LO <= k < HI')
     from pianobart_amd.generation import add_schedule_flags
     add_schedule_flags(ap)                      # --chords / --bars_per_chord / --chord_start: the plain --batches runs with a bar schedule on every row
+    ap.add_argument('--accompany', type=str, default=None, choices=('skyline', 'bass'), help='the plain --batches runs with anchors on every row: that line of '
+                    'a synthetic piece per row, at most --steps / 2 anchors')
     ap.add_argument('--sizes', type=int, nargs=8, default=None, metavar='N', help='the 8 head sizes of another dictionary (PianoBart.classes order), e.g. '
                     '1030 134 135 518 300 38 260 55: a head over 272 classes selects the wide device sampler. Plain --batches runs only')
     ap.add_argument('--bars_log', type=str, default=os.path.join(ROOT, 'profiles', 'bar_stop_b16.jsonl'), help='--bars: the file the lines are appended to')
@@ -311,10 +318,16 @@ def main(argv=None):
     allow_of = lambda B: [amask] * B if amask is not None else None
     from pianobart_amd.generation import schedule_from_args
     bar = schedule_from_args(args, e2w)         # --chords: one bar schedule for every row of the plain runs (None: no schedule)
-    bar_of = lambda B: dict(bar_allow=[bar] * B) if bar is not None else {}
+    lines = None                                # --accompany: one anchor list per row of the plain runs (None: no anchors)
+    if args.accompany is not None:
+        from pianobart_amd.generation import anchor_rows
+        pieces = (synth_octuple_batch(Bmax, S, seed=13, min_len=S) if args.sizes is None else synth_batch(sizes, Bmax, S, seed=13, min_len=S))[5].numpy()
+        lines = [anchor_rows(p, args.accompany, e2w)[:max(1, steps // 2)] for p in pieces]
+    bar_of = lambda B, n=steps: dict(**(dict(bar_allow=[bar] * B) if bar is not None else {}),
+                                     **(dict(anchors=[a[:max(1, n // 2)] for a in lines[:B]]) if lines is not None else {}))
     # batch 1 through Engine.generate (the device-sampled batch-1 decoder), same process
     np.random.seed(0)
-    eng.generate(enc[:1], emask[:1], model.sample_row, max_new=16, sampler=sampler, allow=amask, **bar_of(1))
+    eng.generate(enc[:1], emask[:1], model.sample_row, max_new=16, sampler=sampler, allow=amask, **bar_of(1, 16))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     eng.generate(enc[:1], emask[:1], model.sample_row, max_new=steps, sampler=sampler, allow=amask, **bar_of(1))
@@ -325,7 +338,7 @@ def main(argv=None):
     res = {}
     for B in args.batches:
         rngs = [np.random.RandomState(b) for b in range(B)]
-        eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=16, sampler=sampler, allow=allow_of(B), **bar_of(B))     # warm-up (capture, pinned logs)
+        eng.generate_batch(enc[:B], emask[:B], model.sample_row, rngs, max_new=16, sampler=sampler, allow=allow_of(B), **bar_of(B, 16))     # warm-up (capture, pinned logs)
         torch.cuda.synchronize()
         rngs = [np.random.RandomState(b) for b in range(B)]
         t0 = time.perf_counter()
@@ -338,8 +351,10 @@ def main(argv=None):
                            loop_ms=info['loop_ms'], launches_per_step=info['launches_per_token'], graph=info['graph'],
                            rewinds=sum(info['rewinds']), host_ms_per_step=info['host_ms'] / max(1, info['steps']), steps=info['steps'],
                            tokens=ntok, hbm_bytes_per_step=w_bytes + kv_bytes(B))
-        if bar is not None:
+        if bar is not None or lines is not None:
             res[str(B)]['rewinds_per_row'] = [int(v) for v in info['rewinds']]
+        if lines is not None:
+            res[str(B)]['anchors_placed'] = [int(v) for v in info['anchors_placed']]
     best = max(res.values(), key=lambda r: r['tokens_per_s'])['tokens_per_s']
     out = {"metric": "batched generate tokens/s (KV-cached decode, %dL/%dd, S=%d, %d positions per row)" % (L, d, S, steps),
            "batch1_generate_tokens_per_s": b1, "batch1_info": b1_info, "by_batch": res,
@@ -348,6 +363,8 @@ def main(argv=None):
         out['allow'] = dict(key=args.key, pitch_range=args.pitch_range, allowed_columns=int(amask.sum()), vocab=int(amask.size))
     if bar is not None:
         out['chords'] = dict(chords=args.chords, bars_per_chord=args.bars_per_chord, chord_start=args.chord_start, scheduled=bool(b1_info.get('scheduled')))
+    if lines is not None:
+        out['accompany'] = dict(which=args.accompany, anchors_per_row=[len(a[:max(1, steps // 2)]) for a in lines[:max(args.batches)]])
     if args.prime:
         # primed generation: the first K rows of each prompt's own piece given to the decoder, the encoder sees those rows only
         # (Ablation.py:132-139); --steps positions sampled after them. prefill_ms = the teacher-forced decoder pass that fills the
